@@ -512,10 +512,16 @@ def cpu_quota():
         return None
 
 
+CPU_PROCS_AT_ONCE = 4        # + this process: every worker opens the GPU (torch.optim's step asks torch.cuda.is_available(),
+                             # which initialises the HIP runtime), and a shared MI355X node ends a job that holds the GPU in
+                             # more than 6 processes at once
+
+
 def cpu_baseline(workload, seconds=12.0):
     """Reference-cadence CPU port timed on the host cores BEFORE this process touches the GPU (fork is safe then):
-    (1) one single-thread process alone, (2) P single-thread processes at once, P = physical cores (bounded by memory:
-    each worker holds its own torch state) -- the whole-node CPU number of SURVEY.md 8d.  `value` is the whole-node figure."""
+    (1) one single-thread process alone, (2) min(P, CPU_PROCS_AT_ONCE) single-thread processes at once, P = physical
+    cores (bounded by memory: each worker holds its own torch state), their mean rate scaled to P -- the whole-node CPU
+    number of SURVEY.md 8d.  `value` is the whole-node figure."""
     import multiprocessing as mp
     ctx = mp.get_context("fork")
     chunk = 4 if workload.startswith("evopf") else 100
@@ -540,21 +546,24 @@ def cpu_baseline(workload, seconds=12.0):
     if P_mem < P:
         cap_note = " (%d physical cores visible, capped by available memory)" % phys
         P = P_mem
-    barrier = ctx.Barrier(P)
-    procs = [ctx.Process(target=_cpu_worker, args=(workload, seconds, chunk, barrier, q)) for _ in range(P)]
+    K = min(P, CPU_PROCS_AT_ONCE)
+    barrier = ctx.Barrier(K)
+    procs = [ctx.Process(target=_cpu_worker, args=(workload, seconds, chunk, barrier, q)) for _ in range(K)]
     for pr in procs:
         pr.start()
     res = [q.get() for _ in procs]
     for pr in procs:
         pr.join()
-    node = sum(d / t for d, t in res)
+    per_process = sum(d / t for d, t in res) / K
+    node = per_process * P
     kind = "shipped trainer host loop on tests/oracle_backend.py (oracle/evopf.py kernels), torch-CPU MLPs" \
         if workload.startswith("evopf") else "oracle/rpo_loop.py OracleRPO"
     return dict(value=node, unit="env-steps/s", cores=P, kind="port", single_core_value=solo,
-                per_process_under_load=node / P,
+                per_process_under_load=per_process, processes_at_once=K,
                 sample="%s, %s, 1 env per process, rollout + one batch-256 update per env step, 1 thread per process: "
-                       "1 process alone %.1f s (%d steps) and %d processes at once%s %.1f s each (%d steps in total)"
-                       % (kind, DESCRIBE[workload], dt1, done1, P, cap_note, seconds, sum(d for d, _ in res)))
+                       "1 process alone %.1f s (%d steps) and %d processes at once %.1f s each (%d steps in total), their "
+                       "mean rate x %d cores%s"
+                       % (kind, DESCRIBE[workload], dt1, done1, K, seconds, sum(d for d, _ in res), P, cap_note))
 
 
 # ------------------------------------------------------------------------------------------------ launch of N ranks
@@ -603,30 +612,47 @@ def timed_run(tr, steps, warmup, world, device):
             tr.run_steps(500)
             fence()
             log("debug window %d: %.4f ms/iter" % (w, (time.perf_counter() - tw) / 500 * 1e3))
-    def region():
-        fence()
-        t0 = time.perf_counter()
-        tr.run_steps(steps)
-        fence()
-        dt = time.perf_counter() - t0
-        if world > 1:
-            tmax = torch.tensor([dt], device=device, dtype=torch.float64)
-            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-            dt = float(tmax.item())
-        return dt
-    # The timed region is EXACTLY `steps` steps between two fences (max over ranks); a short one (the driver's --steps 20 is
-    # 0.84 ms) is a single sample of a noisy quantity, so the region is repeated until >= MIN_TIMED_S have been timed in total
-    # (the count follows from the first region, which every rank sees as the same max-reduced number) and the MEDIAN region
-    # is reported, with the spread next to it.
-    regions = [region()]
-    reps = int(min(MAX_REGIONS, max(1, np.ceil(MIN_TIMED_S / regions[0]))))
-    for _ in range(reps - 1):
-        tr.run_steps((-tr._t) % pf)                             # (every region starts on a window boundary, untimed)
-        regions.append(region())
-    return regions
+    # The timed region is EXACTLY `steps` steps between two fences (max over ranks), timed once: `--steps` is the number of
+    # steps measured, and the trainer's state after them does not depend on the clock (--dump-outputs).  A short region is a
+    # single sample of a noisy quantity; ask for more steps to average over more.
+    fence()
+    t0 = time.perf_counter()
+    tr.run_steps(steps)
+    fence()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        tmax = torch.tensor([dt], device=device, dtype=torch.float64)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        dt = float(tmax.item())
+    return [dt]
 
 
-MIN_TIMED_S, MAX_REGIONS = 0.05, 400
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(tr, out_dir):
+    """--dump-outputs: what the timed steps handed back in the last of them, one .npy per array -- the transitions the
+    fused step scattered into the replay ring (`transition_<column>`, one row per env), the observations the next step
+    starts from (`obs`), the parameters after the update (`params`: the flat buffer, critic | shared | actor | multipliers)
+    and the target networks, all float32, and the last losses (`loss_<name>`, float64).  Every input comes from the seeds
+    of make_trainer, so two builds run with the same arguments can be compared array for array."""
+    torch.cuda.synchronize()
+    buf, ag = tr.buffer, tr.agent
+    n = buf.n_envs
+    first = (buf.pointer - n) % (buf.capacity * n)              # the ring slot of the last vector step
+    rows = buf.rows[first:first + n]
+    arrays = {"transition_" + k: rows[:, lo:hi] for k, (lo, hi) in buf.cols.items()}
+    arrays.update(obs=tr.vec.obs, params=ag.flat.data, critic_target=ag.critic_target_flat)
+    if ag.actor_target_flat is not None:
+        arrays["actor_target"] = ag.actor_target_flat
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    arrays.update(("loss_" + k, np.float64(float(v))) for k, v in tr.last_losses.items())
+    total = sum(np.asarray(v).nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    log("dumped %d arrays (%d bytes) of step %d to %s" % (len(arrays), total, tr._t, out_dir))
 
 
 def region_stats(regions, steps):
@@ -747,6 +773,9 @@ def main():
     ap.add_argument("--tuning", default="", metavar="KEY=VALUE[,...]",
                     help="A/B aid: library kernel-variant switches (rpo_tuning / ops.TUNE) set before the trainer is built; the "
                          "line reports them under config.tuning")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what their last step computed (transitions, observations, parameters, "
+                         "losses of --workload's trainer; rank 0) as DIR/<name>.npy, to compare two builds on identical inputs")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -807,6 +836,8 @@ def main():
     spin_up(device)
     tr = prepared_trainer(n_total, device, args.workload)
     timing = region_stats(timed_run(tr, args.steps, args.warmup, world, device), args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
     elapsed = timing["median"]
     value = n_total * args.steps / elapsed
     # the violation rate needs a window of its own: over a few dozen vector steps it is noise (measured 0.325 over
@@ -825,8 +856,8 @@ def main():
         "ms_per_step": timing["ms_per_step"], "ms_per_step_min": timing["ms_per_step_min"],
         "ms_per_step_max": timing["ms_per_step_max"], "timed_regions": timing["timed_regions"],
         "timed_total_ms": timing["timed_total_ms"],
-        "timing_note": "value = steps x envs / MEDIAN of `timed_regions` regions of exactly `steps` steps each (barrier + "
-                       "synchronize on both sides, max over ranks), repeated until >= %d ms were timed" % int(MIN_TIMED_S * 1e3),
+        "timing_note": "value = steps x envs / the time of ONE region of exactly `steps` steps (barrier + synchronize on both "
+                       "sides, max over ranks)",
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": ("CartSafe-v0 RPODDPG, %d vectorised envs per MI355X, scripts/cart_exp.py "

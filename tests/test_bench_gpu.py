@@ -118,6 +118,32 @@ def test_scale_preflight_over_gloo_on_one_gpu():
         json.dump(v, f, indent=1)
 
 
+@pytest.mark.timeout(900, method="thread")
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR`: what the last of exactly `--steps` timed steps computed -- its transitions, the
+    observations, parameters and targets after the update, the losses -- as float32 / float64 .npy files of at most 64 MB,
+    the same from two runs with the same arguments (every input comes from fixed seeds)."""
+    import numpy as np
+    args = ["--steps", "24", "--warmup", "4", "--no-extras", "--no-cpu-baseline", "--no-clinic"]
+    runs = []
+    for i in range(2):
+        d = os.path.join(str(tmp_path), "run%d" % i)
+        rc, out, err = _run_bench({}, args + ["--dump-outputs", d], budget=400)
+        assert rc == 0, err[-4000:]
+        r = json.loads(out.strip().splitlines()[-1])
+        assert r["steps"] == 24 and r["timed_regions"] == 1
+        runs.append({f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = runs
+    assert sorted(a) == sorted(b)
+    assert {"params", "critic_target", "obs", "transition_state", "transition_action", "transition_next_state", "loss_critic"} <= set(a)
+    assert a["transition_state"].shape == (4096, 6) and a["obs"].shape == (4096, 6)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), (k, a[k].dtype)
+        assert np.isfinite(a[k]).all(), k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6, err_msg=k)
+
+
 def test_lanes_sweep_rows_carry_both_rooflines():
     """bench.py's `lanes_sweep`: whole iterations -- rollout only, rollout + the batch-256 update -- with
     env-steps/s and the fractions of the f32 MFMA peak and of the HBM roofline.  Here at two small sizes (the bench runs 4096 /

@@ -200,6 +200,24 @@ def test_bench_timing_and_regime_helpers():
     assert bench.hbm_regime(1.07e9, 9000.0)["frac_of_achievable"] == 1.0
 
 
+def test_bench_cpu_leg_runs_at_most_cpu_procs_at_once_workers():
+    """bench.py's CPU leg forks single-thread workers, and each of them opens the GPU (torch.optim's step calls
+    torch.cuda.is_available()): on a node with many cores at most CPU_PROCS_AT_ONCE run at once, and the whole-node figure
+    is their mean rate scaled to the cores.  In a fresh child process, which has not touched the GPU before it forks."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, bench; bench.physical_cores = lambda: 64; bench.cpu_quota = lambda: None; "
+            "print(json.dumps(dict(bench.cpu_baseline('cart_ddpg', seconds=0.5), limit=bench.CPU_PROCS_AT_ONCE)))")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    assert res["limit"] <= 5                                     # + the bench process itself: 6 processes at most
+    assert res["processes_at_once"] == min(res["cores"], res["limit"])
+    assert res["per_process_under_load"] > 0 and abs(res["value"] - res["cores"] * res["per_process_under_load"]) < 1e-9 * res["value"]
+
+
 def test_evopf_static_order_is_refused_for_another_network():
     """The EVOPF solver's static elimination order has case14's branch pattern compiled in (csrc/evopf_dev.h: kAdjMask): a
     constant table whose Ybus has an entry outside that pattern -- or RPO_EVOPF_PIVOT=dynamic -- selects partial pivoting
