@@ -436,7 +436,10 @@ typedef struct {
      * backward kernels then splits the batch over up to 256 slices -- every slice accumulates its share of every parameter
      * gradient into its own copy of the network's gradient span inside this buffer (one owner per element, fixed order) and a
      * second launch adds the slices in order: the batch reductions use the width of the chip instead of ~50 workgroups
-     * (36 ms -> ~2 ms at 2^20 rows), still bitwise reproducible.  Needs >= 2 x (the span of the gradient tensors, in floats). */
+     * (36 ms -> ~2 ms at 2^20 rows), still bitwise reproducible.  Needs >= 2 x (the span of the gradient tensors, in floats).
+     * Must be 16-byte aligned (it is zeroed with float4 stores): rpo_mlp_backward / _pair (whenever param_grads is set) and
+     * rpo_ddpg_actor_backward / rpo_sac_actor_backward (the actor's scratch) refuse another address with RPO_ERR_ARG before
+     * any launch. */
     float* splitk_scratch; long long splitk_floats;
 } rpo_mlp_grad;
 #define RPO_SPLITK_FROM 16384

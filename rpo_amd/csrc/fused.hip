@@ -1076,6 +1076,7 @@ int rpo_ddpg_actor_backward(int env, const rpo_mlp* actor_host, const rpo_mlp_gr
     MlpGrad ag{actor_grad_host->Ws, actor_grad_host->bs, actor_grad_host->Wa, actor_grad_host->ba, actor_grad_host->W0,
                actor_grad_host->b0, actor_grad_host->W1, actor_grad_host->b1, actor_grad_host->W1b, actor_grad_host->b1b};
     if (!ag.Ws || !ag.bs || !ag.W0 || !ag.b0 || !ag.W1 || !ag.b1) return RPO_ERR_NULL;
+    if ((reinterpret_cast<uintptr_t>(actor_grad_host->splitk_scratch) & 15u) != 0) return RPO_ERR_ARG;   // (as rpo_mlp_backward)
     // the critic only propagates (d/d action, and dx0 for a shared embedding): no parameter gradients of its own
     p.critic = BwdArgs{critic, none, batch_size, batch, row, actions, 2, critic_x0, critic_h1, dq, critic_dh,
                        critic_dx0, da, 0, 0, nullptr};
@@ -1176,6 +1177,7 @@ int rpo_sac_actor_backward(int env, const rpo_mlp* actor_host, const rpo_mlp_gra
     MlpGrad ag{actor_grad_host->Ws, actor_grad_host->bs, actor_grad_host->Wa, actor_grad_host->ba, actor_grad_host->W0,
                actor_grad_host->b0, actor_grad_host->W1, actor_grad_host->b1, actor_grad_host->W1b, actor_grad_host->b1b};
     if (!ag.Ws || !ag.bs || !ag.W0 || !ag.b0 || !ag.W1 || !ag.b1 || !ag.W1b || !ag.b1b) return RPO_ERR_NULL;
+    if ((reinterpret_cast<uintptr_t>(actor_grad_host->splitk_scratch) & 15u) != 0) return RPO_ERR_ARG;   // (as rpo_mlp_backward)
     p.critic1 = BwdArgs{q1, none, batch_size, batch, row, actions, 2, critic1_x0, critic1_h1, dq1, critic1_dh, critic1_dx0, da1,
                         0, 0, nullptr};
     p.critic2 = BwdArgs{q2, none, batch_size, batch, row, actions, 2, critic2_x0, critic2_h1, dq2, critic2_dh, critic2_dx0, da2,

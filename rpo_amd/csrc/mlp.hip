@@ -311,6 +311,8 @@ static int make_bwd_args(BwdArgs& args, const rpo_mlp* net_host, const rpo_mlp_g
         if (!first_layer_state_only && (!g.W0 || !g.b0 || !g.W1 || !g.b1 || (net.A > 0 && (!g.Wa || !g.ba))))
             return RPO_ERR_NULL;
         if (!first_layer_state_only && net.n_out > 1 && (!g.W1b || !g.b1b)) return RPO_ERR_NULL;
+        // the split-K scratch is zeroed by a float4 kernel (splitk_zero): a misaligned buffer is refused, not memset
+        if ((reinterpret_cast<uintptr_t>(grad_host->splitk_scratch) & 15u) != 0) return RPO_ERR_ARG;
     }
     args = BwdArgs{net, g, n, s, s_stride, a, a_stride, x0, h1, dout, dh, dx0, da, param_grads, first_layer_state_only,
                    gradmax, t};

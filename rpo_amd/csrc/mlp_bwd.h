@@ -761,9 +761,12 @@ __global__ __launch_bounds__(RPO_BLOCK) void splitk_zero_kernel(float4* __restri
     for (long long i = (long long)blockIdx.x * RPO_BLOCK + threadIdx.x; i < n4; i += (long long)gridDim.x * RPO_BLOCK)
         p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
+// A scratch that is not 16-byte aligned is refused (RPO_ERR_ARG; rpo_mlp_backward / _pair check it up front): falling back to
+// hipMemsetAsync would put a memset node back into a captured window.
 static inline int splitk_zero(const SplitK& k, hipStream_t stream) {
     const size_t floats = (size_t)k.Z * (size_t)k.stride;        // (stride is a multiple of 4 floats; the scratch is 16-byte aligned)
-    if (RPO_SPLITK_ZERO && (reinterpret_cast<uintptr_t>(k.scratch) & 15u) == 0) {
+    if (RPO_SPLITK_ZERO) {
+        if ((reinterpret_cast<uintptr_t>(k.scratch) & 15u) != 0) return RPO_ERR_ARG;
         long long n4 = (long long)(floats / 4), blocks = (n4 + RPO_BLOCK - 1) / RPO_BLOCK;
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(splitk_zero_kernel<0>, dim3((unsigned)blocks), dim3(RPO_BLOCK), 0, stream, reinterpret_cast<float4*>(k.scratch), n4);

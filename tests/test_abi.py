@@ -2,6 +2,7 @@
 import ctypes
 import os
 import subprocess
+import sys
 
 import pytest
 
@@ -127,3 +128,57 @@ def test_every_entry_point_survives_null_arguments():
     was = lib.rpo_tuning(_lib.CONST["RPO_TUNE_BWD_ONEPASS"], -1)
     assert lib.rpo_tuning(_lib.CONST["RPO_TUNE_BWD_ONEPASS"], 0) == was and lib.rpo_tuning(_lib.CONST["RPO_TUNE_BWD_ONEPASS"], was) == 0
     assert lib.rpo_tuning(_lib.CONST["RPO_TUNE_BWD_ONEPASS"], -1) == was
+
+
+
+_MISALIGNED_CHILD = r"""
+import ctypes, sys
+import torch
+from rpo_amd import _lib, ops
+if torch.cuda.device_count() != 0:                # (host addresses stand in for device pointers: never where a GPU is visible)
+    sys.exit(3)
+lib = _lib.load()
+S, A, E, H, n = 6, 2, 128, 256, 20000
+buf = (ctypes.c_float * (1 << 16))()
+base = (ctypes.addressof(buf) + 15) // 16 * 16
+p = [base + 4096 * i for i in range(10)]        # (distinct, 16-byte aligned host addresses; nothing is dereferenced)
+critic = ops._MlpStruct(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], None, None, S, A, E, H, 1, 0, 1)
+actor = ops._MlpStruct(p[0], p[1], None, None, p[4], p[5], p[6], p[7], None, None, S, 0, E, H, 1, 0, 1)
+gactor = ops._MlpStruct(p[0], p[1], None, None, p[4], p[5], p[6], p[7], p[8], p[9], S, 0, E, H, 2, 0, 1)
+bad = ops._MlpGradStruct(*p[:8], p[8], p[9], base + 4, 1 << 24)
+good = ops._MlpGradStruct(*p[:8], p[8], p[9], base + 16, 1 << 24)
+r = ctypes.c_void_p(base)
+res = {}
+one = (n, r, 16, r, 16, r, r, r, r, r, None)
+pair = (n, r, 16, r, 16, r, r, r, r, r, None, r, r, r, r, r, None)
+# default switches, and the rows pass + split-K weights pass, whose rows kernel is launched BEFORE the scratch is zeroed: only
+# a refusal in the argument validation answers RPO_ERR_ARG there -- a launch on this GPU-less process answers a HIP error
+for key, tune in (("default", {}), ("two_pass", dict(bwd_stream=0, bwd_onepass=0))):
+    with ops.tuning(**tune):
+        res["backward_" + key] = lib.rpo_mlp_backward(ctypes.byref(critic), ctypes.byref(bad), *one, 1, 0, None, None, None)
+        res["pair_" + key] = lib.rpo_mlp_backward_pair(ctypes.byref(critic), ctypes.byref(bad), ctypes.byref(critic),
+                                                       ctypes.byref(bad), *pair, 1, 0, None, None, None, None)
+        res["pair_second_" + key] = lib.rpo_mlp_backward_pair(ctypes.byref(critic), ctypes.byref(good), ctypes.byref(critic),
+                                                              ctypes.byref(bad), *pair, 1, 0, None, None, None, None)
+# the fused actor backward entry points (their weights pass is launched after the actor kernel)
+res["ddpg_actor"] = lib.rpo_ddpg_actor_backward(0, ctypes.byref(actor), ctypes.byref(bad), ctypes.byref(critic), 0, r, n, r, r, r,
+                                                r, r, 1.0, 1.0, 0.0, -1.0, 1.0, 1.0, 0.0, r, r, 1, r, r, r, r, r, r, r, r, r,
+                                                r, r, r, r, None, None)
+res["sac_actor"] = lib.rpo_sac_actor_backward(0, ctypes.byref(gactor), ctypes.byref(bad), ctypes.byref(critic), ctypes.byref(critic),
+                                              0, r, n, r, r, r, r, r, r, r, 0.1, -1.0, 1.0, 1.0, 0.0, r, 1, r, r, r, r, r, r, r,
+                                              r, r, r, r, r, r, r, r, r, r, r, None, None)
+print(res)
+sys.exit(0 if all(v == _lib.CONST["RPO_ERR_ARG"] for v in res.values()) else 1)
+"""
+
+
+def test_misaligned_splitk_scratch_is_refused_before_any_launch():
+    """rpo_mlp_grad.splitk_scratch must be 16-byte aligned (it is zeroed with float4 stores; a hipMemsetAsync fallback would put
+    a memset node into a captured window).  rpo_mlp_backward, rpo_mlp_backward_pair (either network) and the fused
+    rpo_ddpg_actor_backward / rpo_sac_actor_backward answer RPO_ERR_ARG in their argument validation, before any launch.
+    Host buffers stand in for the device pointers, so the calls run in a child process that sees no GPU: a launch there
+    fails with a HIP error instead of touching memory, and that error is what a missing up-front check would return."""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _MISALIGNED_CHILD], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr[-3000:]

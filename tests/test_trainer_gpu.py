@@ -421,16 +421,18 @@ def test_wide_rollout_tiles_are_bitwise_identical(hip, monkeypatch):
     np.testing.assert_allclose(hip.reduce_stats(a.vec.stats[:12]).cpu().numpy(),
                                hip.reduce_stats(b.vec.stats[:12]).cpu().numpy(), rtol=1e-5, atol=1e-9)
     # generic forward: n >= 12288 takes the streaming kernel (weights in LDS, round 5; 12 or 16 waves per workgroup) or, with
-    # the switch off, the 64-row tiles of rounds 3-4; a 4096-row slice of the same input the 16-row tiles: the same bits
+    # the switch off, the 64-row tiles of rounds 3-4; every 4096-row slice of the same input the 16-row tiles: the same bits,
+    # on all 16 384 rows
     f = a.fused
     s = torch.randn(16384, 6, device=dev)
-    out_n = torch.empty(4096, 1, device=dev)
-    f.forward("actor", s[:4096], None, out_n)
+    out_n = torch.full((16384, 1), float("nan"), device=dev)
+    for r0 in range(0, 16384, 4096):
+        f.forward("actor", s[r0:r0 + 4096], None, out_n[r0:r0 + 4096])
     for kw in (dict(fwd_stream=1, fwd_stream_waves=12), dict(fwd_stream=1, fwd_stream_waves=16), dict(fwd_stream=0)):
-        out_w = torch.empty(16384, 1, device=dev)
+        out_w = torch.full((16384, 1), float("nan"), device=dev)
         with hip.tuning(**kw):
             f.forward("actor", s, None, out_w)
-        assert torch.equal(out_w[:4096], out_n), kw
+        assert torch.equal(out_w, out_n), kw
 
 
 @pytest.mark.parametrize("sel,n_envs", [(3, 1000), (3, 16 * 16 * 256 * 2 + 37), (4, 1000), (4, 64 * 16 * 256 + 16 * 3 + 5)],
