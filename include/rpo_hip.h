@@ -136,6 +136,23 @@ extern "C" {
 #define RPO_STAT_PROJ_ITERS 9    /* sum over envs of GRG iterations taken by the rollout projection       */
 #define RPO_STAT_TERMINATED 10   /* episodes ended by the env's own termination test (not the TimeLimit)   */
 
+/* Per-episode accumulators of a policy evaluation (rpo_<env>_evaluate, rpo_eval_accumulate): float[n, RPO_EVAL_LEN], one
+ * row per episode, written by the launch at step 0 (nothing needs clearing).  Slots 0..6 are floats; slot 7 holds the int32
+ * word RPO_EVAL_ALIVE | RPO_EVAL_NONFINITE | length << RPO_EVAL_LEN_SHIFT. */
+#define RPO_EVAL_LEN 8
+#define RPO_EVAL_RET 0           /* sum of the rewards of the episode's steps */
+#define RPO_EVAL_MEAN_INEQ 1     /* running mean m + (x - m) / (i + 1) of the step's max inequality violation */
+#define RPO_EVAL_MEAN_EQ 2       /* the same of the step's max |equality residual| */
+#define RPO_EVAL_MAX_INEQ 3      /* maxima over the episode's steps (NaN-propagating like torch.maximum) */
+#define RPO_EVAL_MAX_EQ 4
+#define RPO_EVAL_VIOL_STEPS 5    /* steps whose max inequality violation exceeds viol_thresh */
+#define RPO_EVAL_PROJ_ITERS 6    /* GRG iterations summed over the episode */
+#define RPO_EVAL_WORD 7
+#define RPO_EVAL_ALIVE 1         /* the episode has not ended: the next step updates the row */
+#define RPO_EVAL_NONFINITE 2     /* a live step produced a non-finite reward or violation */
+#define RPO_EVAL_LEN_SHIFT 2     /* steps taken (the step that ended the episode included) */
+#define RPO_EVAL_LANE_STEPS 4194304  /* lane-steps per evaluate launch the host aims at: steps = clamp(this / n, 1, horizon) */
+
 /* noise_mode of the *_act_project entry points (agent/ddpg_pa.py:101-112, rpo_ddpg.py:98-106) */
 #define RPO_NOISE_NONE 0      /* deterministic: ap used as is, not clipped          (take_action(deterministic=True)) */
 #define RPO_NOISE_EXPLICIT 1  /* ap += eps * noise[i], then clip to the box         (tests: noise injected)           */
@@ -809,6 +826,36 @@ int rpo_pendulum_rollout(const rpo_mlp* actor_host, int gauss, float scale, floa
                          float eps_start, float eps_end, float eps_decay, float box_lo, float box_hi, int max_steps,
                          float corr_lr, float corr_eps, float corr_momentum, int max_episode_steps, int auto_reset,
                          float viol_thresh, unsigned long long seed, unsigned env_id_base, int defer_clock, void* stream);
+
+/* Policy evaluation (RPOTrainerBase.evaluate, rpo_amd/algo/evaluation.py): env steps [t0, t0 + steps) of n_envs independent
+ * episodes with eval()'s policy (rpo_ddpg.py:224-226, rpo_sac.py:238-240), in one launch that loops over the steps inside
+ * each workgroup: actor MLP -> tanh box (gauss = 0) | mean head clip(scale * tanh(mean) + base, box_lo, box_hi) (gauss = 1)
+ * -> complete_partial -> grad_steps (max_steps iterations, no noise) -> env step + violations + TimeLimit (no auto-reset, no
+ * replay row, no statistics row) -> the lane's accumulator row acc [n_envs, RPO_EVAL_LEN] (t0 == 0 writes it from scratch).
+ * A lane whose episode has ended is not stepped again; a workgroup whose lanes have all ended returns.  The host enqueues
+ * the launches back to back, t0 = 0, steps, 2 * steps, ...
+ * == per step: rpo_mlp_forward (+ rpo_gauss_head(deterministic)) + rpo_<env>_act_project(RPO_NOISE_NONE, iters) +
+ *    rpo_<env>_step(auto_reset 0, cap_steps 1) + rpo_eval_accumulate, bit for bit.
+ * The actor: embed width E = 128, hidden 256 (RPO_ERR_ARG otherwise).
+ * CartSafe-v0: state [n,6] is the observation.  SpringPendulum-v0: internal [n,4] and obs [n,5] (the observations the
+ * actor and the projection read; rewritten by every step).  ctrl (may be NULL): receives ctrl[RPO_CTRL_NONFINITE] like the
+ * step kernels'; ctrl[RPO_CTRL_T] is neither read nor advanced. */
+int rpo_cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                          float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0,
+                          int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                          float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                          float viol_thresh, void* stream);
+int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                          float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                          float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                          float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, void* stream);
+
+/* The stepwise form of the same statistics (any env): step `step` of n episodes from the transition rows rpo_<env>_step
+ * wrote (rows [n, row_stride], the column layout of the env's replay rows: reward, done, eq_viol [eq_num], ineq_viol
+ * [ineq_num] at the given columns) and the projection's iteration counts iters [n] (may be NULL: 0) into acc
+ * [n, RPO_EVAL_LEN]; step == 0 writes the rows from scratch. */
+int rpo_eval_accumulate(int n, const float* rows, int row_stride, int reward_col, int done_col, int eq_col, int eq_num,
+                        int ineq_col, int ineq_num, const int* iters, int step, float viol_thresh, float* acc, void* stream);
 
 /* Forward half of the critic update (rpo_ddpg.py:165-174, 327-337): ReplayBuffer.sample (Philox draw, or idx_in when
  * given) -> batch_out [B,24]; pi_targ(s') -> Complete + Proj -> Q_targ(s', a') = qn_out; Q(s, a) = q_out with the

@@ -263,9 +263,11 @@ def _env_int(name, default):
 #:                  projection on one workgroup per row tile (0: one launch per stage, one-workgroup projection)
 #:   branch         second captured branch of the generic-launch windows (EVOPF-v0): rollout t+1 beside update t, and the
 #:                  actor-only prefix of the policy step beside the critic update (0: serial windows)
+#:   fused_eval     evaluate(): actor -> head -> Complete -> GRG -> env step -> per-episode statistics as a few launches that
+#:                  loop over the env steps (0: the stepwise path, one _eval_action + step + rpo_eval_accumulate per step)
 #:   force_dist     (default 0) data-parallel code path over a one-rank process group
 SCHEDULE_DEFAULTS = dict(fused_mlp=1, fused_rollout=1, fused_critic=1, fused_actor=1, split=1, ride=1, front=1, branch=1,
-                         force_dist=0)
+                         fused_eval=1, force_dist=0)
 
 
 def parse_schedule(overrides=None):
@@ -1325,10 +1327,11 @@ class RPOTrainerBase(object):
     def _eval_partial(self, obs):
         raise NotImplementedError
 
-    def _eval_action(self, v):
-        """Deterministic policy + eval_steps projection iterations into v.action (rpo_ddpg.py:224-226)."""
+    def _eval_action(self, v, iters=None):
+        """Deterministic policy + eval_steps projection iterations into v.action (rpo_ddpg.py:224-226); ``iters`` (int32 [n],
+        optional): the projection's iteration count per lane."""
         ap = self._eval_partial(v.obs)
-        self.kernels.act_project(v.obs, ap, None, v.action, None, hip_ops.NOISE_NONE, 0.0, 0.0, 0.0, self._box_lo,
+        self.kernels.act_project(v.obs, ap, None, v.action, iters, hip_ops.NOISE_NONE, 0.0, 0.0, 0.0, self._box_lo,
                                  self._box_hi, self.eval_steps, self.eval_lr, self.corr_eps, self.corr_momentum,
                                  **self._act_kw)
 
@@ -1373,6 +1376,18 @@ class RPOTrainerBase(object):
             x = x.cpu().numpy().astype(np.float64)
             out += [x.mean(), x.std()]
         return tuple(out)
+
+    def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None):
+        """Evaluate the current policy on ``episodes`` independent episodes -> ``EvalResult`` (per-episode arrays; ``summary()``
+        is eval()'s 10-tuple).  The policy, projection and horizon are eval()'s: deterministic actor (RPOSAC: the mean head),
+        ``eval_steps`` / ``eval_lr`` / ``corr_eps`` / ``corr_momentum``, at most min(500, max_episode_steps, the env's
+        episode_steps) steps (``horizon`` overrides), no auto-reset.  Episode i starts from the reset stream of env id i of a
+        fresh vector env with seed ``seed`` (None: a fresh seed per call from the trainer seed and a call counter), or from
+        ``init_states[i]`` ([episodes, internal_dim]) when given.  No trainer state changes (networks, env lanes, ctrl, replay,
+        Philox counters, graphs).  Data-parallel runs: evaluates on the calling rank only, with no collective.  See
+        rpo_amd/algo/evaluation.py."""
+        from .evaluation import evaluate
+        return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states)
 
     def _print_eval(self, t, res):
         if self.dist.rank != 0 or not _env_int("RPO_VERBOSE", 1):

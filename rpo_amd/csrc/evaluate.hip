@@ -1,0 +1,228 @@
+// Policy evaluation on the device (trainer.evaluate(), rpo_amd/algo/evaluation.py): many independent episodes with the
+// deterministic policy and the evaluation-time projection, no exploration, no replay scatter, no auto-reset.
+//
+//   eval_kernel          obs tile -> actor MLP (f32 MFMA) -> [mean head] -> Complete -> GRG -> env step -> per-episode
+//                        accumulators, looped over up to `steps` env steps inside the workgroup (its own 16 * RT lanes:
+//                        no grid-wide synchronisation, no co-residency assumption).  The pieces are those of
+//                        rollout_kernel (fused.hip), so the bits are those of the stepwise path.
+//   eval_accumulate      the stepwise path's update: reads the transition rows rpo_<env>_step wrote.
+//
+// Both update a lane's accumulator row through rpo_eval_lane_update (eval_dev.h).
+#include "cartsafe_dev.h"
+#include "eval_dev.h"
+#include "heads_dev.h"
+#include "mlp_tile.h"
+#include "pendulum_dev.h"
+#include "rollout_env.h"
+
+namespace {
+
+using namespace rpo_mlp_dev;
+using rpo_eval_dev::nanmax;
+using rpo_eval_dev::rpo_eval_lane_update;
+
+Mlp to_dev(const rpo_mlp* h) {
+    return Mlp{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H, h->n_out, h->cat, h->head_dim};
+}
+
+template <class ENV>
+struct EvalArgs {
+    Mlp actor;
+    float scale, base;            // tanh box of the actor output (BoxConstraint)
+    int gauss;                    // 0: deterministic actor (DDPG); 1: the mean head of the squashed Gaussian (SAC)
+    int t0, steps;                // env steps [t0, t0 + steps) of the evaluation; t0 == 0 initialises the accumulators
+    float* acc;                   // [n, RPO_EVAL_LEN]
+    typename ENV::ActArgs act;    // projection parameters (RPO_NOISE_NONE), action out
+    typename ENV::StepArgs step;  // env state and bookkeeping (rows = NULL, auto_reset = 0)
+};
+
+// What one env step leaves for the statistics: reward, done and the violations of the transition row, without the row.
+// Observations are staged from the env's observation rows: for SpringPendulum those the stepwise path hands the actor
+// and the projection (after an injected initial state they come from torch's cos / sin, not from sincosf).
+template <class ENV>
+struct EvalEnv;
+
+template <>
+struct EvalEnv<CartEnv> {
+    __device__ static __forceinline__ void stage(const rpo_cart_dev::StepArgs& p, int row0, int rows, float* in_s, int stride) {
+        CartEnv::stage_obs(p, row0, rows, in_s, stride);
+    }
+    __device__ static __forceinline__ void lane(const rpo_cart_dev::StepArgs& p, const rpo_cart_dev::CartConsts& c, int i,
+                                                const float* obs, float2 a, float& reward, float& done, float& ineq, float& eq) {
+        float s[6], ns[6], st[rpo_cart_dev::kStepStats];
+        float4 row[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) s[q] = obs[q];
+        rpo_cart_dev::cart_lane(p, c, i, s, a, rpo_load_episode(p.ep_len, p.ep_ret, p.ep_count, i), ns, row, st);
+        rpo_cart_dev::store_state(p.state + (size_t)i * 6, ns);
+        reward = row[3].z;
+        done = row[3].w;
+        eq = fabsf(row[4].x);
+        // the ineq_viol columns in order, max with NaN propagation (Tensor.max(dim=1))
+        ineq = nanmax(nanmax(nanmax(nanmax(nanmax(row[4].y, row[4].z), row[4].w), row[5].x), row[5].y), row[5].z);
+    }
+};
+
+template <>
+struct EvalEnv<PendEnv> {
+    __device__ static __forceinline__ void stage(const rpo_pend_dev::StepArgs& p, int row0, int rows, float* in_s, int stride) {
+        const int tid = threadIdx.x;
+        if (tid < rows * 5) {
+            const int r = tid / 5, q = tid - r * 5;
+            in_s[r * stride + q] = (row0 + r < p.n) ? p.obs[(size_t)(row0 + r) * 5 + q] : 0.0f;
+        }
+    }
+    __device__ static __forceinline__ void lane(const rpo_pend_dev::StepArgs& p, const PendEnv::Consts&, int i, const float*,
+                                                float2 a, float& reward, float& done, float& ineq, float& eq) {
+        const float4 s = reinterpret_cast<const float4*>(p.internal)[i];
+        float ns[4], ncs, nsn, st[rpo_pend_dev::kStepStats];
+        float4 row[4];
+        rpo_pend_dev::pend_lane(p, i, s, a, rpo_load_episode(p.ep_len, p.ep_ret, p.ep_count, i), ns, ncs, nsn, row, st);
+        reinterpret_cast<float4*>(p.internal)[i] = make_float4(ns[0], ns[1], ns[2], ns[3]);
+        rpo_pend_dev::store_obs(p.obs + (size_t)i * 5, ncs, nsn, ns[1], ns[2], ns[3]);
+        reward = row[3].x;
+        done = row[3].y;
+        eq = fabsf(row[3].z);
+        ineq = row[3].w;
+    }
+};
+
+template <class ENV, int EIN, int H, int RT>
+__global__ __launch_bounds__(kFwdThreads) void eval_kernel(EvalArgs<ENV> p, typename ENV::Consts c) {
+    typedef TileLds<EIN, RT, 8, 8> Lds;                          // 16 * RT lanes per workgroup; OBS <= 8
+    __shared__ Lds lds;
+    constexpr int kInS = Lds::kS;
+    constexpr int kLanes = rpo_mlp_dev::kRows * RT;
+    const int row0 = blockIdx.x * kLanes;
+    const int tid = threadIdx.x;
+    const int n = p.step.n;
+    const int i = row0 + tid;
+    const bool mine = tid < kLanes && i < n;
+    for (int s = p.t0; s < p.t0 + p.steps; ++s) {
+        // a lane's state is read from its accumulator row at every step (nothing of it stays live across the MFMA loops)
+        const bool live = mine && (s == 0 || (__float_as_int(p.acc[(size_t)i * RPO_EVAL_LEN + 7]) & RPO_EVAL_ALIVE));
+        if (!__syncthreads_or(live)) return;                     // (also the barrier in front of the LDS tiles' reuse)
+        EvalEnv<ENV>::stage(p.step, row0, kLanes, lds.in_s, kInS);
+        mlp_tile_forward<EIN, H, RT, Lds>(p.actor, lds, row0, n, nullptr, nullptr, p.gauss ? 0 : 1, p.scale, p.base);
+        if (live) {
+            float ap = lds.out[tid * 2];
+            if (p.gauss) ap = rpo_head_dev::gauss_head_row(ap, lds.out[tid * 2 + 1], 0.0f, p.scale, p.base, p.act.box_lo,
+                                                           p.act.box_hi, 1, nullptr);
+            int k;
+            const float2 a = ENV::project(p.act, c, lds.in_s + tid * kInS, i, ap, 0.0f, 0, k);
+            reinterpret_cast<float2*>(p.act.action)[i] = a;
+            float reward, done, ineq, eq;
+            EvalEnv<ENV>::lane(p.step, c, i, lds.in_s + tid * kInS, a, reward, done, ineq, eq);
+            rpo_eval_lane_update(p.acc + (size_t)i * RPO_EVAL_LEN, s, reward, ineq, eq, done, k, p.step.viol_thresh);
+        }
+        __syncthreads();                                         // every lane has read its observation out of the LDS tile
+    }
+}
+
+template <class ENV>
+int launch_eval(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, void* stream) {
+    // the rollout's tile rule (fused.hip launch_rollout): 64 lanes per workgroup once that still fills the chip.  E = 128
+    // only: the E = 256 instance spills (~150 bytes of scratch per lane) -- such actors evaluate on the stepwise path.
+    if (args.actor.E != 128) return RPO_ERR_ARG;
+    if (n >= 64 * 192) {
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+    } else {
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+    }
+    RPO_LAUNCH_CHECK();
+    return 0;
+}
+
+int check_eval_actor(const Mlp& actor, int obs_dim, int gauss) {
+    if (actor.hd > 1 || actor.S != obs_dim || actor.A != 0 || actor.n_out != (gauss ? 2 : 1) || actor.cat || actor.H != 256 || !actor.Ws ||
+        !actor.W0 || !actor.W1 || (gauss && !actor.W1b))
+        return RPO_ERR_ARG;
+    return 0;
+}
+
+int check_eval_range(int n, int t0, int steps, int max_episode_steps, int max_steps) {
+    if (n <= 0 || t0 < 0 || steps <= 0 || max_episode_steps <= 0 || max_steps < 0) return RPO_ERR_ARG;
+    if ((long long)t0 + steps > (1ll << 24)) return RPO_ERR_ARG;   // lengths and step indices stay exact in the f32 row
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------- stepwise accumulation
+struct AccArgs {
+    int n;
+    const float* rows;
+    int stride, reward_col, done_col, eq_col, eq_num, ineq_col, ineq_num;
+    const int* iters;
+    int step;
+    float viol_thresh;
+    float* acc;
+};
+
+__global__ __launch_bounds__(RPO_BLOCK) void eval_accumulate_kernel(AccArgs p) {
+    for (int i = blockIdx.x * RPO_BLOCK + threadIdx.x; i < p.n; i += gridDim.x * RPO_BLOCK) {
+        const float* r = p.rows + (size_t)i * p.stride;
+        float ineq = r[p.ineq_col], eq = fabsf(r[p.eq_col]);
+        for (int j = 1; j < p.ineq_num; ++j) ineq = nanmax(ineq, r[p.ineq_col + j]);
+        for (int j = 1; j < p.eq_num; ++j) eq = nanmax(eq, fabsf(r[p.eq_col + j]));
+        rpo_eval_lane_update(p.acc + (size_t)i * RPO_EVAL_LEN, p.step, r[p.reward_col], ineq, eq, r[p.done_col],
+                             p.iters ? p.iters[i] : 0, p.viol_thresh);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int rpo_cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                          float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0,
+                          int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                          float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                          float viol_thresh, void* stream) {
+    if (!actor_host) return RPO_ERR_NULL;
+    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
+    if (!state || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
+    EvalArgs<CartEnv> args{};
+    args.actor = to_dev(actor_host);
+    if (int e = check_eval_actor(args.actor, 6, gauss)) return e;
+    rpo_cart_dev::CartConsts c;
+    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
+    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
+    args.act = rpo_cart_dev::ActArgs{n_envs, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, box_lo, box_hi,
+                                     max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    args.step = rpo_cart_dev::StepArgs{n_envs, state, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
+                                       max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
+    return launch_eval<CartEnv>(args, c, n_envs, stream);
+}
+
+int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                          float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                          float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                          float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, void* stream) {
+    if (!actor_host) return RPO_ERR_NULL;
+    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
+    if (!internal || !obs || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
+    EvalArgs<PendEnv> args{};
+    args.actor = to_dev(actor_host);
+    if (int e = check_eval_actor(args.actor, 5, gauss)) return e;
+    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
+    args.act = rpo_pend_dev::ActArgs{n_envs, nullptr, 5, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
+                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    args.step = rpo_pend_dev::StepArgs{n_envs, internal, obs, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
+                                       max_episode_steps, 0, viol_thresh, 0ull, 0u};
+    return launch_eval<PendEnv>(args, PendEnv::Consts{0}, n_envs, stream);
+}
+
+int rpo_eval_accumulate(int n, const float* rows, int row_stride, int reward_col, int done_col, int eq_col, int eq_num,
+                        int ineq_col, int ineq_num, const int* iters, int step, float viol_thresh, float* acc, void* stream) {
+    if (n <= 0 || step < 0 || step >= (1 << 24) || eq_num <= 0 || ineq_num <= 0 || reward_col < 0 || done_col < 0 || eq_col < 0 ||
+        ineq_col < 0)
+        return RPO_ERR_ARG;
+    if (reward_col >= row_stride || done_col >= row_stride || eq_col + eq_num > row_stride || ineq_col + ineq_num > row_stride)
+        return RPO_ERR_ARG;
+    if (!rows || !acc) return RPO_ERR_NULL;
+    const AccArgs a{n, rows, row_stride, reward_col, done_col, eq_col, eq_num, ineq_col, ineq_num, iters, step, viol_thresh, acc};
+    hipLaunchKernelGGL(eval_accumulate_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a);
+    RPO_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -230,6 +230,28 @@ def polyak(param, target, tau):
     check(_lib.load().rpo_polyak(param.numel(), _p(param), _p(target), tau, _stream()), "rpo_polyak")
 
 
+EVAL_LEN = CONST["RPO_EVAL_LEN"]
+EVAL_LANE_STEPS = CONST["RPO_EVAL_LANE_STEPS"]
+
+
+def _eval_acc(acc, n):
+    if acc.dim() != 2 or acc.shape[0] != n or acc.shape[1] != EVAL_LEN:
+        raise RpoHipError("evaluation accumulators must be [%d, %d] float32, got %s" % (n, EVAL_LEN, tuple(acc.shape)))
+    return _p(acc)
+
+
+def eval_accumulate(rows, cols, iters, step, viol_thresh, acc):
+    """Step `step` of a policy evaluation into acc [n, EVAL_LEN] from the transition rows [n, >= row_floats] the env's step
+    kernel wrote (`cols`: the env kernels' column ranges) and the projection's iteration counts (int32 [n], or None)."""
+    n = acc.shape[0]
+    rp, stride = _row_view(rows[:n], rows.shape[1])
+    (r0, _), (d0, _) = cols["reward"], cols["done"]
+    (e0, e1), (i0, i1) = cols["eq_viol"], cols["ineq_viol"]
+    check(_lib.load().rpo_eval_accumulate(n, rp, stride, r0, d0, e0, e1 - e0, i0, i1 - i0,
+                                          _p(iters, torch.int32, allow_none=True), int(step), viol_thresh, _eval_acc(acc, n),
+                                          _stream()), "rpo_eval_accumulate")
+
+
 # =================================================================================================== env kernel sets
 
 class CartSafeKernels(object):
@@ -288,6 +310,16 @@ class CartSafeKernels(object):
             eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr,
             self.partial, max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, int(defer_clock), _stream()),
             "rpo_cartsafe_rollout")
+
+    def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh):
+        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_cartsafe_evaluate); acc [n, EVAL_LEN]."""
+        net = actor_desc.net_struct()
+        check(_lib.load().rpo_cartsafe_evaluate(
+            ctypes.byref(net), int(gauss), scale, base, internal.shape[0], _p(internal), _p(action), _p(ep_len, torch.int32),
+            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, internal.shape[0]),
+            int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
+            max_episode_steps, viol_thresh, _stream()), "rpo_cartsafe_evaluate")
 
     def ddpg_critic_forward(self, actor_target, critic_target, critic, scale, base, rows, cap_steps, n_envs, batch_out,
                             idx_out, idx_in, seed, salt, ctrl, max_steps, corr_lr, corr_eps, corr_momentum, box_lo, box_hi,
@@ -488,6 +520,16 @@ class PendulumKernels(object):
             noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
             max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, int(defer_clock), _stream()),
             "rpo_pendulum_rollout")
+
+    def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh):
+        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_pendulum_evaluate); acc [n, EVAL_LEN]."""
+        net = actor_desc.net_struct()
+        check(_lib.load().rpo_pendulum_evaluate(
+            ctypes.byref(net), int(gauss), scale, base, internal.shape[0], _p(internal), _p(obs), _p(action),
+            _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
+            _eval_acc(acc, internal.shape[0]), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps,
+            corr_momentum, max_episode_steps, viol_thresh, _stream()), "rpo_pendulum_evaluate")
 
     def ddpg_critic_front(self, actor_target, scale, base, rows, cap_steps, n_envs, batch_out, idx_out, idx_in, sample_seed,
                           sample_salt, ctrl, ap_out):
