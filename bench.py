@@ -3,12 +3,17 @@
 (BASELINE.json configs[1]), one constrained policy update of batch 256 per vector step (the reference's cadence,
 rpo/algo/rpo_ddpg.py:160-161).
 
-    python bench.py [--gpus N --steps K --warmup W]          # N > 1: starts N ranks itself (torch.distributed.run)
+    python bench.py [--gpus N --steps K --warmup W] [--full]          # N > 1: starts N ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one vector step: actor forward on N lanes -> noise + equation solver + GRG projection -> fused env step +
 violation bookkeeping + replay scatter -> sample/gather 256 transitions -> critic (and every 4th step actor + dual)
 update.  Rank 0 prints ONE JSON line; everything else goes to stderr.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, --dump-outputs, print the line.  --full
+adds everything else: the CPU baseline, the cart_sac leg, the vector-cadence and num_envs = 1 violation rates, the lanes
+sweep, the rollout-only / UTD-matched / large-batch legs and the kernel clinics (roofline); --no-cpu-baseline, --no-clinic,
+--no-extras, --n1-seeds and --lanes trim a --full run.
 """
 import argparse
 import json
@@ -749,9 +754,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-clinic", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the rollout-only / UTD-matched / cart_sac legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement: CPU baseline, extra legs, violation rates, lanes "
+                         "sweep, kernel clinics (a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-clinic", action="store_true", help="--full without the kernel clinics")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the rollout-only / UTD-matched / cart_sac / n = 1 / "
+                                                               "lanes legs")
     ap.add_argument("--workload", default="cart_ddpg", choices=sorted(WORKLOADS),
                     help="cart_ddpg is the headline (BASELINE.json configs[1]); the others are extra measurements")
     ap.add_argument("--force-dist", action="store_true",
@@ -798,10 +807,12 @@ def main():
     if world != args.gpus:
         log("note: --gpus %d but WORLD_SIZE %d; using WORLD_SIZE" % (args.gpus, world))
     headline = args.workload == "cart_ddpg"
+    extras = args.full and not args.no_extras
+    clinic = args.full and not args.no_clinic
 
     # CPU leg first: forked single-thread workers, before this process initialises the GPU
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.workload)
         log("cpu baseline: %.1f env-steps/s on %d cores (1 core alone: %.1f)" % (cpu["value"], cpu["cores"],
                                                                                 cpu["single_core_value"]))
@@ -841,8 +852,8 @@ def main():
     elapsed = timing["median"]
     value = n_total * args.steps / elapsed
     # the violation rate needs a window of its own: over a few dozen vector steps it is noise (measured 0.325 over
-    # 20 steps vs 0.023 over 2000).  Continue the same run, untimed, to at least 1000 vector steps.
-    if tr._t < 1000:
+    # 20 steps vs 0.023 over 2000).  --full continues the same run, untimed, to at least 1000 vector steps.
+    if args.full and tr._t < 1000:
         tr.run_steps(1000 - tr._t)
     tr._harvest(final=True)
     # did EVERY rank replay captured hipGraphs (data-parallel: with the collectives inside them)?  A rank whose capture
@@ -884,22 +895,22 @@ def main():
                    "allreduce_bytes": {"critic_update": 4 * int(tr.agent.flat.gradient(tr.agent.flat.critic_range).numel()),
                                        "policy_step": 4 * int(sum(t.numel() for t in [tr.agent.flat.gradient(tr.agent.flat.policy_bucket)]))}
                    if tr.dist.on else None},
+        **({"control_flow_check": "gloo%s: control-flow check of the N > 1 path, NOT a scaling figure (the measured "
+                                  "configuration is one rank per GPU over RCCL)" % (", %d ranks time-slicing %d GPU(s)" % (
+                                      world, torch.cuda.device_count()) if shared_gpu else "")}
+           if (world > 1 and args.backend == "gloo") else {}),
+    }
+    if args.full:
         # NOT the reference's quantity: the fraction of (env, vector step) pairs with max(max_ineq, max_eq) > 1e-3 over the
         # first `constraint_violation_window` of THIS run, in which the policy receives one update per VECTOR step (1 / 4096 of
         # the reference's learning per env step) -- it mostly measures how early in training the window sits.  The figure that
         # is comparable with the reference's 3000-step single-env runs is constraint_violation_rate_n1 below (1536 + 1536 seeds
         # in profiles/r06_stat_rows_ddpg_cart.*: +0.12e-3 +- 0.27e-3); at matched UPDATES the vectorised cadence violates 2.2e-3
         # LESS than the reference (profiles/r06_cadence_learning.json).
-        **({"control_flow_check": "gloo%s: control-flow check of the N > 1 path, NOT a scaling figure (the measured "
-                                  "configuration is one rank per GPU over RCCL)" % (", %d ranks time-slicing %d GPU(s)" % (
-                                      world, torch.cuda.device_count()) if shared_gpu else "")}
-           if (world > 1 and args.backend == "gloo") else {}),
-        "constraint_violation_rate_vector_cadence": tr.viol_rate,
-        "constraint_violation_window": "%d vector steps x %d envs" % (tr._t, n_total),
-        "mean_projection_iters": tr.proj_iters_mean,
-    }
+        result.update({"constraint_violation_rate_vector_cadence": tr.viol_rate,
+                       "constraint_violation_window": "%d vector steps x %d envs" % (tr._t, n_total),
+                       "mean_projection_iters": tr.proj_iters_mean})
 
-    extras = not args.no_extras
     if extras and headline:
         # config 4's algorithm (RPOSAC on CartSafe-v0, scripts/cart_exp_sac.py) on the same ranks, same protocol
         del tr
@@ -909,7 +920,7 @@ def main():
         result["cart_sac_env_steps_per_s"] = n_total * args.steps / t2["median"]
         result["cart_sac_ms_per_step"] = t2["ms_per_step"]
         result["cart_sac_ms_per_step_min_max"] = [t2["ms_per_step_min"], t2["ms_per_step_max"]]
-        if not args.no_clinic and world > 1 and sac.fused is not None:
+        if clinic and world > 1 and sac.fused is not None:
             # config 4 IS this algorithm at N = 8: its own roofline on the N > 1 lines (every rank runs the clinic -- its recorded
             # iterations contain the collectives --, rank 0's figures are printed).  At N = 1 `--workload cart_sac` carries it.
             log("kernel clinic of the cart-SAC leg (config 4's algorithm):")
@@ -924,7 +935,7 @@ def main():
     lanes = [int(x) for x in args.lanes.split(",") if x.strip() and int(x) > 0]
     if extras and headline and world == 1 and rank == 0 and lanes:
         result["lanes_sweep"] = lanes_sweep(device, lanes)
-    if not args.no_clinic and world > 1:
+    if clinic and world > 1:
         # every rank runs the clinic (its recorded iterations contain the collectives); rank 0's figures are printed
         if tr is None:
             tr = prepared_trainer(n_total, device, args.workload)
@@ -992,7 +1003,7 @@ def main():
                             "cadence of the headline is better than the reference on both at matched updates (33.4 +- 1.6 / 42.6 +- 2.3, "
                             "1.10e-2 +- 0.06e-2: sampling from 4096 independent histories; one lane reproduces the reference, "
                             "DESIGN.md 5)"}
-                if not args.no_clinic:
+                if clinic:
                     log("kernel clinic of the large-batch update:")
                     cl = kernel_clinic(lb, args.workload)
                     result["large_batch"]["kernels"] = {
@@ -1001,7 +1012,7 @@ def main():
                         for k, v in cl.items() if "@" not in k and v.get("n", 0) == 256 * EPG}
                 del lb
                 torch.cuda.empty_cache()
-        if not args.no_clinic:
+        if clinic:
             if tr is None:
                 tr = prepared_trainer(n_total, device, args.workload)
             if tr.fused is not None:

@@ -41,10 +41,10 @@ def _run_bench(extra_env, args, budget):
 
 @pytest.mark.timeout(900, method="thread")
 def test_bench_two_ranks_over_gloo_on_one_gpu():
-    """`bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline` (the driver's SCALE flags) through the gloo switch: exit code
-    0 from the launcher (i.e. from every rank), ONE JSON line on stdout (rank 1 prints nothing there), and the keys a SCALE
-    run is checked by."""
-    args = ["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
+    """`bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline` (a multi-GPU run with its clinic and cart_sac leg)
+    through the gloo switch: exit code 0 from the launcher (i.e. from every rank), ONE JSON line on stdout (rank 1 prints
+    nothing there), and the keys a SCALE run is checked by."""
+    args = ["--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"]
     t0 = time.time()
     for attempt in range(3):
         # two processes time-slicing one GPU through gloo stall once in ~20 runs on this pool (see

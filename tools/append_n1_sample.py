@@ -3,7 +3,7 @@
 
     python tools/append_n1_sample.py <bench line .json> [label]
 
-Since round 6 every bench.py run draws its 384 seeds from a fresh base (`constraint_violation_rate_n1_seed_base`, printed in the
+Since round 6 every `bench.py --full` run draws its 384 seeds from a fresh base (`constraint_violation_rate_n1_seed_base`, printed in the
 line), so every line is an INDEPENDENT sample of cart-RPODDPG's violation rate in the reference's setting;
 tests/test_statistical_evidence.py pools the samples of this file against the reference's 1536 runs.  A line whose seed range
 overlaps an entry already in the file is refused (it would be counted twice)."""
@@ -23,7 +23,8 @@ def main():
         line = line["line"]
     base, seeds = line.get("constraint_violation_rate_n1_seed_base"), line.get("constraint_violation_rate_n1_seeds")
     if base is None or seeds is None:
-        sys.exit("this line has no independent n = 1 sample (written by a bench.py older than round 6, or --n1-seeds 0)")
+        sys.exit("this line has no independent n = 1 sample (written without --full, by a bench.py older than round 6, or "
+                 "with --n1-seeds 0)")
     hist = json.load(open(PATH)) if os.path.exists(PATH) else {"what": __doc__.split("\n\n")[2], "samples": []}
     for s in hist["samples"]:
         if s["seed_base"] < base + seeds and base < s["seed_base"] + s["seeds"]:

@@ -29,7 +29,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
     [ -n "$DB" ] && python3 $ROOT/tools/rocpd_pmc.py $DB > $OUT/pmc_${C}_$P.txt
   done
 done
-# HBM traffic of every workload's own launches (roofline.traffic of bench.py --workload W): policy_fre periods of the bench
+# HBM traffic of every workload's own launches (roofline.traffic of bench.py --full --workload W): policy_fre periods of the bench
 # trainer, eagerly, one counter per pass
 for W in cart_ddpg cart_sac pen_ddpg pen_sac evopf_ddpg evopf_sac; do
   for C in FETCH_SIZE WRITE_SIZE; do

@@ -13,7 +13,7 @@ this process has touched a GPU (an `exec` from a GPU-initialised process takes t
              construction), the lanes must differ between ranks (sharded env ids), and every rank must have replayed graphs.
   timing     the same workload as one plain process, as a ONE-rank group (the measured intercept of DESIGN 7: one all-reduce +
              rpo_absmax_slots per collective), and as N ranks: microseconds per iteration and per collective.
-  bench      `bench.py --gpus N --steps 20 --warmup 5 --no-cpu-baseline` (the driver's SCALE flags), and the same with
+  bench      `bench.py --gpus N --steps 20 --warmup 5 --full --no-cpu-baseline` (headline, cart_sac leg, clinics), and the same with
              RPO_GRAPH_CYCLE=0 (eager launches, eager collectives): which of the two is broken tells graph capture from RCCL.
   rccl test  tests/test_trainer_gpu.py::test_rccl_two_ranks_one_per_gpu (skips itself below two GPUs).
 
@@ -157,7 +157,7 @@ def run_bench(world, backend, graph_cycle, budget):
     if graph_cycle is not None:
         env["RPO_GRAPH_CYCLE"] = str(graph_cycle)
     rc, out, err = child([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline"], env, budget)
+                          "--full", "--no-cpu-baseline"], env, budget)
     lines = [l for l in out.splitlines() if l.strip().startswith("{")]
     line = json.loads(lines[-1]) if lines else None
     keep = None
