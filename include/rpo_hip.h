@@ -153,6 +153,19 @@ extern "C" {
 #define RPO_EVAL_LEN_SHIFT 2     /* steps taken (the step that ended the episode included) */
 #define RPO_EVAL_LANE_STEPS 4194304  /* lane-steps per evaluate launch the host aims at: steps = clamp(this / n, 1, horizon) */
 
+/* One row of an evaluation curve (rpo_eval_summarize): double[RPO_CURVE_LEN], the accumulator rows of one evaluation
+ * reduced over its episodes.  Means and population standard deviations (numpy's x.mean(), x.std()) of the float32
+ * accumulators widened to float64, in eval()'s order. */
+#define RPO_CURVE_LEN 16
+#define RPO_CURVE_STEP 0         /* ctrl[RPO_CTRL_T] of the training env when the row was written */
+#define RPO_CURVE_EPISODES 1
+#define RPO_CURVE_STATS 2        /* (mean, std) of RPO_EVAL_RET, _MEAN_INEQ, _MEAN_EQ, _MAX_INEQ, _MAX_EQ: slots 2 .. 11 */
+#define RPO_CURVE_LENGTH 12      /* sum of the episode lengths */
+#define RPO_CURVE_VIOL_STEPS 13  /* sum of RPO_EVAL_VIOL_STEPS */
+#define RPO_CURVE_NONFINITE 14   /* episodes with RPO_EVAL_NONFINITE set */
+#define RPO_CURVE_WS 4096        /* doubles of workspace rpo_eval_summarize needs (per-workgroup partials in fixed slots) */
+#define RPO_CURVE_MAX_EPISODES 1048576
+
 /* noise_mode of the *_act_project entry points (agent/ddpg_pa.py:101-112, rpo_ddpg.py:98-106) */
 #define RPO_NOISE_NONE 0      /* deterministic: ap used as is, not clipped          (take_action(deterministic=True)) */
 #define RPO_NOISE_EXPLICIT 1  /* ap += eps * noise[i], then clip to the box         (tests: noise injected)           */
@@ -856,6 +869,16 @@ int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, flo
  * [n, RPO_EVAL_LEN]; step == 0 writes the rows from scratch. */
 int rpo_eval_accumulate(int n, const float* rows, int row_stride, int reward_col, int done_col, int eq_col, int eq_num,
                         int ineq_col, int ineq_num, const int* iters, int step, float viol_thresh, float* acc, void* stream);
+
+/* The accumulator rows acc [n, RPO_EVAL_LEN] of one finished evaluation -> one curve row row_out [RPO_CURVE_LEN] (doubles,
+ * layout RPO_CURVE_*); ctrl: the TRAINING env's control words, ctrl[RPO_CTRL_T] becomes RPO_CURVE_STEP (read on the device);
+ * ws [RPO_CURVE_WS] doubles of scratch (owned by the caller, one evaluation at a time).  1 <= n <= RPO_CURVE_MAX_EPISODES.
+ * No floating-point atomics: a workgroup sums its own contiguous chunk of rows (wave64 butterfly, then the four waves in
+ * order) into its own slot of ws, and the slots are combined in slot order -- the summation order depends on n alone, so the
+ * row is the same bits from run to run and for any placement of the workgroups.  Standard deviations come from the
+ * deviations about the mean (a second pass over the rows).  n <= 1024: one workgroup, one launch; otherwise three launches
+ * (chunk sums | chunk sums of squared deviations | combine). */
+int rpo_eval_summarize(int n, const float* acc, const long long* ctrl, double* row_out, double* ws, void* stream);
 
 /* Forward half of the critic update (rpo_ddpg.py:165-174, 327-337): ReplayBuffer.sample (Philox draw, or idx_in when
  * given) -> batch_out [B,24]; pi_targ(s') -> Complete + Proj -> Q_targ(s', a') = qn_out; Q(s, a) = q_out with the

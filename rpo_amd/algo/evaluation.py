@@ -15,6 +15,9 @@ Both paths compute the same bits (``tests/test_evaluate_gpu.py``).  The evaluati
 its buffers: no trainer state is read-modified-written, so training after an ``evaluate()`` call is the training without it.
 Data-parallel runs: ``evaluate()`` runs on the calling rank alone, with no collective (the replicas' networks are
 identical, so every rank would compute the same result); call it on one rank.
+
+Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
+``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).
 """
 import numpy as np
 import torch
@@ -115,11 +118,19 @@ def fused_ok(tr):
                 and tr._box_affine is not None and f.descs["actor"].E == 128 and tr.device.type == "cuda")
 
 
+def check_episodes(episodes, what="evaluate: episodes"):
+    try:
+        ok = not isinstance(episodes, bool) and int(episodes) == episodes and episodes >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be an integer >= 1, got %r" % (what, episodes))
+    return int(episodes)
+
+
 def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None):
     """See ``RPOTrainerBase.evaluate``."""
-    if isinstance(episodes, bool) or int(episodes) != episodes or episodes < 1:
-        raise ValueError("evaluate: episodes must be an integer >= 1, got %r" % (episodes,))
-    n = int(episodes)
+    n = check_episodes(episodes)
     if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
         raise ValueError("evaluate: horizon must be an integer >= 1, got %r" % (horizon,))
     H = int(horizon) if horizon is not None else default_horizon(tr)
@@ -153,13 +164,14 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None):
     return EvalResult(acc.cpu().numpy(), path, H, seed)
 
 
-def _run_fused(tr, v, acc, H):
+def _run_fused(tr, v, acc, H, desc=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
-    (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes)."""
+    (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
+    trainer's (the curve's parameter snapshot)."""
     n = v.n
     steps = max(1, min(H, hip_ops.EVAL_LANE_STEPS // n))
     scale, base = tr._box_affine
-    desc = tr.fused.descs["actor"]
+    desc = tr.fused.descs["actor"] if desc is None else desc
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
                             v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo, tr._box_hi,
@@ -177,3 +189,212 @@ def _run_stepwise(tr, v, acc, H):
         tr._eval_action(v, iters=iters)
         v.step(v.action, rows=rows, cap_steps=1, auto_reset=False)
         update(rows, k.cols, iters, i, v.viol_thresh, acc)
+
+
+# ------------------------------------------------------------------------------------------------ evaluation curves
+#: curve row layout (include/rpo_hip.h: RPO_CURVE_*)
+CURVE_LEN = 16
+_C_STEP, _C_EPISODES, _C_STATS, _C_LENGTH, _C_VIOL, _C_NONFINITE = 0, 1, 2, 12, 13, 14
+_CURVE_WS = 4096
+_CURVE_RING = 64                                                 # device rows between two harvests
+_STATS = ("ret", "mean_ineq", "mean_eq", "max_ineq", "max_eq")   # eval()'s order
+
+
+def curve_seed(trainer_seed, k):
+    """Seed of the vector env of evaluation point k (k = 0, 1, ... over the life of a trainer) of a curve-mode run:
+    ((trainer_seed ^ 0xC0A7C0A7) + 0x9E3779B97F4A7C15 * (k + 1)) mod 2^63.  Independent of ``evaluate()``'s call counter."""
+    return ((int(trainer_seed) ^ 0xC0A7C0A7) + 0x9E3779B97F4A7C15 * (int(k) + 1)) & (2 ** 63 - 1)
+
+
+class EvalCurve(object):
+    """The learning curve of a curve-mode run (``eval_episodes=N``): numpy arrays with one entry per harvested point.
+
+    ``step`` (vector steps done when the point was taken), ``episodes``, the ten columns of eval()'s tuple (``ret_mean``,
+    ``ret_std``, ``mean_ineq_mean``, ``mean_ineq_std``, ``mean_eq_mean``, ``mean_eq_std``, ``max_ineq_mean``, ``max_ineq_std``,
+    ``max_eq_mean``, ``max_eq_std``), ``length_mean``, ``violation_rate`` (``EvalResult.violation_rate()``) and ``nonfinite``
+    (episodes with the non-finite bit).  ``rows``: the raw [points, 16] float64 rows (RPO_CURVE_* layout)."""
+
+    COLUMNS = ("step", "episodes") + tuple("%s_%s" % (s, m) for s in _STATS for m in ("mean", "std")) + \
+        ("length_mean", "violation_rate", "nonfinite")
+
+    def __init__(self, rows=None):
+        self.rows = np.zeros((0, CURVE_LEN)) if rows is None else np.array(rows, dtype=np.float64).reshape(-1, CURVE_LEN)
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    @property
+    def step(self):
+        return self.rows[:, _C_STEP].astype(np.int64)
+
+    @property
+    def episodes(self):
+        return self.rows[:, _C_EPISODES].astype(np.int64)
+
+    @property
+    def length_mean(self):
+        return self.rows[:, _C_LENGTH] / self.rows[:, _C_EPISODES]
+
+    @property
+    def violation_rate(self):
+        return self.rows[:, _C_VIOL] / self.rows[:, _C_LENGTH]
+
+    @property
+    def nonfinite(self):
+        return self.rows[:, _C_NONFINITE].astype(np.int64)
+
+    def summary(self, k):
+        """Point k as eval()'s 10-tuple."""
+        return tuple(float(x) for x in self.rows[k, _C_STATS:_C_STATS + 10])
+
+    def __repr__(self):
+        return "EvalCurve(points=%d)" % len(self)
+
+
+for _i, _s in enumerate(_STATS):
+    for _j, _m in enumerate(("mean", "std")):
+        setattr(EvalCurve, "%s_%s" % (_s, _m), property(lambda self, c=_C_STATS + 2 * _i + _j: self.rows[:, c].copy()))
+
+
+def summarize_torch(acc, ctrl, row_out):
+    """``rpo_eval_summarize`` in torch ops (backends without the kernel: the CPU oracle): the accumulator rows acc [n, 8] ->
+    one curve row row_out [16] float64, nothing read back to the host.  Means and population standard deviations of the
+    float32 columns widened to float64, the deviations taken about the mean."""
+    n = acc.shape[0]
+    x = acc[:, :5].to(torch.float64)
+    word = acc[:, _WORD].contiguous().view(torch.int32)
+    mean = x.sum(dim=0) / n
+    d = x - mean
+    std = torch.sqrt((d * d).sum(dim=0) / n)
+    row_out[_C_STEP] = ctrl[0].to(torch.float64)
+    row_out[_C_EPISODES] = float(n)
+    row_out[_C_STATS:_C_STATS + 10:2] = mean
+    row_out[_C_STATS + 1:_C_STATS + 10:2] = std
+    row_out[_C_LENGTH] = (word >> _LEN_SHIFT).to(torch.float64).sum()
+    row_out[_C_VIOL] = acc[:, _VIOL].to(torch.float64).sum()
+    row_out[_C_NONFINITE] = ((word & _NONFINITE) != 0).to(torch.float64).sum()
+    row_out[CURVE_LEN - 1] = 0.0
+
+
+class CurveRunner(object):
+    """The evaluation points of a curve-mode trainer (``eval_episodes=N``): enqueued by the training loop, never waited for.
+
+    Point k is what a blocking ``trainer.evaluate(episodes=N, seed=curve_seed(trainer.seed, k))`` at the same place returns,
+    reduced on the device (``rpo_eval_summarize``, or ``summarize_torch``) into row ``k mod 64`` of a device ring; the rows
+    are read by ``harvest()`` (the trainer's statistics harvest, ``save()``, the ``eval_curve`` property) -- the only place
+    that waits for the device.  The evaluation env, the accumulators and the ring are allocated once.
+
+    * fused path (``fused_ok``), schedule ``eval_overlap=1``: the actor's span of the flat parameter buffer and the training
+      env's step counter are copied (eager torch copies on the training stream, outside any captured window) into a snapshot;
+      an event hands over to a dedicated evaluation stream, which runs reset, the evaluate launches on the SNAPSHOT and the
+      summary, and records the point's event.  The training stream goes on with the update at once; the next point, the
+      harvest and ``save()`` wait for that event, so two points never share the snapshot or the accumulators.
+    * everything else (stepwise path; ``eval_overlap=0``): the same launches in order on the training stream."""
+
+    def __init__(self, tr, episodes):
+        self.tr, self.n = tr, check_episodes(episodes, "eval_episodes")
+        self.rows = np.zeros((0, CURVE_LEN))                     # harvested
+        self.points = self.done = 0                              # enqueued / harvested over the life of the trainer
+        self.v = self.event = self.last_seed = None
+
+    def _alloc(self):
+        tr, dev = self.tr, self.tr.device
+        self.v = tr.base_env.make_vec(self.n, seed=0, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev,
+                                      stats_cap=2, viol_thresh=tr.vec.viol_thresh)
+        self.acc = torch.zeros(self.n, 8, device=dev)
+        self.ring = torch.zeros(_CURVE_RING, CURVE_LEN, dtype=torch.float64, device=dev)
+        self.ws = torch.zeros(_CURVE_WS, dtype=torch.float64, device=dev)
+        self.H = default_horizon(tr)
+        self.fused = fused_ok(tr)
+        self.overlap = bool(self.fused and tr.schedule.get("eval_overlap", 1))
+        if self.overlap:
+            flat = tr.agent.flat
+            lo, hi = flat.actor_range
+            d = tr.fused.descs["actor"]
+            self.src, self.snap = flat.param(flat.actor_range), torch.zeros(hi - lo, device=dev)
+            tensors = {}
+            for key, p in d.tensors.items():
+                if p is not None:
+                    off = flat.offset[id(p)] - lo
+                    tensors[key] = self.snap[off:off + p.numel()].view(p.shape)
+            self.desc = tr.backend.MlpDesc(tensors, d.S, d.A, d.E, d.H, d.n_out, d.cat, head_dim=d.head_dim)
+            self.step_word = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.stream = torch.cuda.Stream()
+
+    def enqueue(self):
+        """One evaluation point with the parameters as they are now on the current (training) stream."""
+        tr = self.tr
+        if tr.dist.rank != 0:                                    # rank 0 evaluates, no collective (as evaluate())
+            return
+        if self.v is None:
+            self._alloc()
+        k = self.points
+        if k - self.done >= _CURVE_RING:                         # the ring is harvested before it wraps
+            self.harvest()
+        self.v.seed = self.last_seed = curve_seed(tr.seed, k)
+        row = self.ring[k % _CURVE_RING]
+        with torch.no_grad():
+            if self.overlap:
+                main = torch.cuda.current_stream()
+                if self.event is not None:
+                    main.wait_event(self.event)                  # the previous point has read the snapshot
+                self.snap.copy_(self.src)
+                self.step_word.copy_(tr.vec.ctrl[0:1])
+                ready = torch.cuda.Event()
+                ready.record(main)
+                self.stream.wait_event(ready)
+                with torch.cuda.stream(self.stream):
+                    self._point(row, self.desc, self.step_word)
+                    self.event = torch.cuda.Event()
+                    self.event.record(self.stream)
+            else:
+                self._point(row, None, tr.vec.ctrl)
+        self.points = k + 1
+
+    def _point(self, row, desc, ctrl):
+        tr, v = self.tr, self.v
+        v.ep_count.zero_()                                       # a fresh vector env: episode 0 of every lane's reset stream
+        v.ctrl.zero_()
+        v.reset()
+        if self.fused:
+            _run_fused(tr, v, self.acc, self.H, desc)
+        else:
+            _run_stepwise(tr, v, self.acc, self.H)
+        summarize = getattr(tr.backend, "eval_summarize", None)
+        if summarize is not None:
+            summarize(self.acc, ctrl, row, self.ws)
+        else:
+            summarize_torch(self.acc, ctrl, row)
+
+    def wait(self):
+        if self.event is not None:
+            self.event.synchronize()
+
+    def harvest(self):
+        """Read the outstanding rows (waits for the device) and print their ``Eval:`` lines."""
+        if self.points == self.done:
+            return
+        self.wait()
+        idx = torch.as_tensor([k % _CURVE_RING for k in range(self.done, self.points)], device=self.ring.device)
+        new = self.ring[idx].cpu().numpy()
+        self.rows = np.concatenate([self.rows, new], 0)
+        self.done = self.points
+        for r in new:
+            self.tr._print_eval(int(r[_C_STEP]), tuple(float(x) for x in r[_C_STATS:_C_STATS + 10]), multipliers=False)
+
+    def last(self):
+        """The per-episode results of the last enqueued point (its accumulator rows stay on the device until the next one)."""
+        if self.points == 0:
+            return None
+        self.wait()
+        return EvalResult(self.acc.cpu().numpy(), "fused" if self.fused else "stepwise", self.H, self.last_seed)
+
+    def state(self):
+        self.harvest()
+        return dict(rows=self.rows.copy(), points=self.points, episodes=self.n)
+
+    def load_state(self, st):
+        """``st``: ``state()`` of a checkpoint, or None (a checkpoint written without curve mode: an empty curve)."""
+        self.wait()
+        self.rows = np.zeros((0, CURVE_LEN)) if st is None else np.array(st["rows"], dtype=np.float64).reshape(-1, CURVE_LEN)
+        self.points = self.done = 0 if st is None else int(st["points"])

@@ -265,9 +265,11 @@ def _env_int(name, default):
 #:                  actor-only prefix of the policy step beside the critic update (0: serial windows)
 #:   fused_eval     evaluate(): actor -> head -> Complete -> GRG -> env step -> per-episode statistics as a few launches that
 #:                  loop over the env steps (0: the stepwise path, one _eval_action + step + rpo_eval_accumulate per step)
+#:   eval_overlap   curve mode (`eval_episodes=N`), fused path: an evaluation point runs on its own stream, on a snapshot of the
+#:                  actor, beside the update that follows it (0: in order on the training stream)
 #:   force_dist     (default 0) data-parallel code path over a one-rank process group
 SCHEDULE_DEFAULTS = dict(fused_mlp=1, fused_rollout=1, fused_critic=1, fused_actor=1, split=1, ride=1, front=1, branch=1,
-                         fused_eval=1, force_dist=0)
+                         fused_eval=1, eval_overlap=1, force_dist=0)
 
 
 def parse_schedule(overrides=None):
@@ -415,6 +417,13 @@ class RPOTrainerBase(object):
         self._idx_inject = None     # tests: callable returning the replay indices of the next sampled batch
         self._eval_init_inject = None   # tests: [10, internal_dim] initial states of the evaluation episodes
         self.viol_steps, self.env_steps, self.viol_rate, self.proj_iters_mean = 0.0, 0.0, 0.0, 0.0
+        # curve mode (`eval_episodes=N`, RPO_EVAL_EPISODES): run() enqueues an N-episode evaluation where it would call eval()
+        from .evaluation import CurveRunner
+        ee = getattr(self, "eval_episodes", None)
+        if ee is None:
+            ee = _env_int("RPO_EVAL_EPISODES", None)
+        self._curve = CurveRunner(self, ee) if ee is not None else None      # (ValueError for anything but an integer >= 1)
+        self.eval_episodes = self._curve.n if self._curve is not None else None
 
     # ------------------------------------------------------------------------------------------ projection API
     def process_action(self, state, action_partial, train=True):
@@ -1067,8 +1076,7 @@ class RPOTrainerBase(object):
                 self._iteration(warm, False, False)
                 self._advance_host(t + 1)
                 self._flush_tail()
-                self._harvest()
-                self._print_eval(t + 1, self.eval())
+                self._evaluation_point(t + 1)
                 self._iteration(warm, True, actor_step, rollout=False)
                 self._updates += 1
                 if self.updates_per_step > 1:
@@ -1076,6 +1084,10 @@ class RPOTrainerBase(object):
                     self._extra_updates()
                     self._uctrl[hip_ops.CONST["RPO_CTRL_UPDATES"]] = 0
                 left -= 1
+                if self._curve is not None:                                # (the regular cadence: eval() harvests by itself)
+                    self._poll_flags(every=16)
+                    if t + 1 - self._harvested >= self.vec.stats.shape[0] // 2:
+                        self._harvest()
                 continue
             if L > 1:
                 # one hipGraph for L consecutive iterations (policy_fre-periodic launch pattern): the same launches
@@ -1109,9 +1121,35 @@ class RPOTrainerBase(object):
                 self._harvest()
             if eval_now:                                                   # (rollout-only runs: nothing to order against)
                 self._flush_tail()
-                self._harvest()
-                self._print_eval(t, self.eval())
+                self._evaluation_point(t)
         self._flush_tail()
+
+    def _evaluation_point(self, t):
+        """The evaluation of iteration ``t`` (1-based), behind its rollout and in front of its update.  Default: harvest, the
+        reference's eval() driven from the host, the printed lines.  Curve mode (``eval_episodes=N``): one N-episode evaluation
+        is ENQUEUED (rpo_amd/algo/evaluation.py: CurveRunner) and nothing waits for it -- no harvest, no host read; its row is
+        read and its ``Eval:`` line printed at the next harvest, without the ``lambda / nju`` line (the multipliers have moved
+        on by then)."""
+        if self._curve is not None:
+            self._curve.enqueue()
+            return
+        self._harvest()
+        self._print_eval(t, self.eval())
+
+    @property
+    def eval_curve(self):
+        """The learning curve of a curve-mode run -> ``EvalCurve`` (empty without ``eval_episodes``, and on ranks other than
+        0).  Reading it harvests the outstanding points: the only place that may wait for the device."""
+        from .evaluation import EvalCurve
+        if self._curve is None:
+            return EvalCurve()
+        self._curve.harvest()
+        return EvalCurve(self._curve.rows)
+
+    @property
+    def eval_curve_last(self):
+        """``EvalResult`` (per-episode arrays) of the most recent curve point, or None."""
+        return None if self._curve is None else self._curve.last()
 
     def _advance_host(self, t):
         """Host mirrors of the device-side counters after vector step ``t``."""
@@ -1276,6 +1314,8 @@ class RPOTrainerBase(object):
         ``epoch`` = vector step, ``max_ineq`` / ``max_eq`` = mean over lanes of the per-lane maxima
         (rpo_ddpg.py:120-123), ``reward`` = mean return of the episodes the step belongs to, back-filled when they
         finish (rpo_ddpg.py:135-137; identical to the reference for one lane)."""
+        if self._curve is not None:
+            self._curve.harvest()                                 # curve rows travel with the statistics harvest
         lo, hi = self._harvested, self._t
         if hi <= lo:
             return
@@ -1389,7 +1429,7 @@ class RPOTrainerBase(object):
         from .evaluation import evaluate
         return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states)
 
-    def _print_eval(self, t, res):
+    def _print_eval(self, t, res, multipliers=True):
         if self.dist.rank != 0 or not _env_int("RPO_VERBOSE", 1):
             return
         rmean, rstd, ineqmean, ineqstd, eqmean, eqstd, maxineqmean, maxineqstd, maxeqmean, maxeqstd = res
@@ -1397,7 +1437,8 @@ class RPOTrainerBase(object):
         print(f"Eval: epoch {t}, rewards: {rmean:.4f}({rstd:.4f}), mean_ineq_viol: {ineqmean:.4f}({ineqstd:.4f}),"
               f" mean_eq_viol: {eqmean:.4f}({eqstd:.4f}), max_ineq_viol: {maxineqmean:.4f}({maxineqstd:.4f})"
               f" max_eq_viol: {maxeqmean:.4f}({maxeqstd:.4f})")
-        print(f"lambda: {self.agent.lamb}, nju: {self.agent.nju}")
+        if multipliers:
+            print(f"lambda: {self.agent.lamb}, nju: {self.agent.nju}")
         print("============================\n")
 
     # ------------------------------------------------------------------------------------------ checkpoints
@@ -1421,6 +1462,8 @@ class RPOTrainerBase(object):
                      pending=self._pending, viol_steps=self.viol_steps, env_steps=self.env_steps,
                      capacity=b.capacity, row_floats=self.kernels.row_floats, algo=type(self).__name__,
                      env=self.kernels.name, projection_mode=self.projection_mode)
+        if self._curve is not None:                                 # (an additional entry: older checkpoints load without it)
+            state["eval_curve"] = self._curve.state()
         torch.save(state, os.path.join(d, "trainer_state.pth"))
 
     def load(self, weights_only=False):
@@ -1466,7 +1509,9 @@ class RPOTrainerBase(object):
         b._steps_host = v.steps_host = self._t
         self._pending = list(st["pending"])
         self.viol_steps, self.env_steps = st["viol_steps"], st["env_steps"]
-        self.agent.eps = max(self.eps, self.eps_start - self.decay_value * self._t)
+        if self._curve is not None:
+            self._curve.load_state(st.get("eval_curve"))
+        self.agent.eps =max(self.eps, self.eps_start - self.decay_value * self._t)
 
     def _ckpt_dir(self):
         return self.work_dir if not self.dist.on else os.path.join(self.work_dir, "rank%d" % self.dist.rank)

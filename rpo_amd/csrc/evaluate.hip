@@ -6,6 +6,7 @@
 //                        no grid-wide synchronisation, no co-residency assumption).  The pieces are those of
 //                        rollout_kernel (fused.hip), so the bits are those of the stepwise path.
 //   eval_accumulate      the stepwise path's update: reads the transition rows rpo_<env>_step wrote.
+//   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
 //
 // Both update a lane's accumulator row through rpo_eval_lane_update (eval_dev.h).
 #include "cartsafe_dev.h"
@@ -168,9 +169,157 @@ __global__ __launch_bounds__(RPO_BLOCK) void eval_accumulate_kernel(AccArgs p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------- curve rows (rpo_eval_summarize)
+// Eight float64 sums per evaluation: the five summarised accumulator columns (RPO_EVAL_RET .. RPO_EVAL_MAX_EQ, widened), the
+// lengths, the violating steps and the non-finite episodes (counts: exact in a double whatever the order).  Workgroup b owns
+// rows [b * chunk, (b + 1) * chunk) and slot b of the workspace; nothing is added atomically.
+constexpr int kSumK = 8, kSumStats = 5, kSumSlots = 256, kSumRowsPerBlock = 1024;
+static_assert(RPO_CURVE_WS >= 2 * kSumSlots * kSumK, "workspace: two planes of per-workgroup partials");
+static_assert(RPO_CURVE_MAX_EPISODES <= kSumSlots * 4096, "chunks of at most 4096 rows");
+
+__device__ __forceinline__ double wave_sum_f64(double v) {       // rpo_wave_sum's butterfly on doubles
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, RPO_WAVE);
+    return v;
+}
+
+// Sum of v[k] over the 256 threads of the workgroup, the same bits in every thread: butterfly inside each wave, then
+// (w0 + w1) + (w2 + w3).  lds: [4 * kSumK] doubles.
+__device__ __forceinline__ void block_sum_f64(double (&v)[kSumK], double* lds) {
+    const int lane = threadIdx.x & (RPO_WAVE - 1), wave = threadIdx.x / RPO_WAVE;
+#pragma unroll
+    for (int k = 0; k < kSumK; ++k) {
+        const double r = wave_sum_f64(v[k]);
+        if (lane == 0) lds[wave * kSumK + k] = r;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kSumK; ++k) v[k] = (lds[k] + lds[kSumK + k]) + (lds[2 * kSumK + k] + lds[3 * kSumK + k]);
+    __syncthreads();                                             // (the caller may reuse lds)
+}
+
+// The slots of one workspace plane combined in slot order: thread t holds slot t (zeros beyond `slots`), then block_sum_f64.
+__device__ __forceinline__ void combine_slots(const double* plane, int slots, double (&v)[kSumK], double* lds) {
+#pragma unroll
+    for (int k = 0; k < kSumK; ++k) v[k] = (int)threadIdx.x < slots ? plane[threadIdx.x * kSumK + k] : 0.0;
+    block_sum_f64(v, lds);
+}
+
+// phase 0: the eight sums of the workgroup's rows; phase 1: the squared deviations of the five columns about mean[] (slots
+// kSumStats.. stay zero)
+__device__ __forceinline__ void chunk_sums(const float* acc, int n, int chunk, int phase, const double (&mean)[kSumK],
+                                           double (&v)[kSumK], double* lds) {
+    const int lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+#pragma unroll
+    for (int k = 0; k < kSumK; ++k) v[k] = 0.0;
+    for (int i = lo + threadIdx.x; i < hi; i += RPO_BLOCK) {
+        const float* r = acc + (size_t)i * RPO_EVAL_LEN;
+        if (phase == 0) {
+#pragma unroll
+            for (int k = 0; k < kSumStats; ++k) v[k] += (double)r[RPO_EVAL_RET + k];
+            const int word = __float_as_int(r[RPO_EVAL_WORD]);
+            v[5] += (double)(word >> RPO_EVAL_LEN_SHIFT);
+            v[6] += (double)r[RPO_EVAL_VIOL_STEPS];
+            v[7] += (word & RPO_EVAL_NONFINITE) ? 1.0 : 0.0;
+        } else {
+#pragma unroll
+            for (int k = 0; k < kSumStats; ++k) {
+                const double d = (double)r[RPO_EVAL_RET + k] - mean[k];
+                v[k] += d * d;
+            }
+        }
+    }
+    block_sum_f64(v, lds);
+}
+
+__device__ __forceinline__ void write_curve_row(double* row, const long long* ctrl, int n, const double (&sum)[kSumK],
+                                                const double (&mean)[kSumK], const double (&sq)[kSumK]) {
+    if (threadIdx.x != 0) return;
+    row[RPO_CURVE_STEP] = (double)ctrl[RPO_CTRL_T];
+    row[RPO_CURVE_EPISODES] = (double)n;
+#pragma unroll
+    for (int k = 0; k < kSumStats; ++k) {
+        row[RPO_CURVE_STATS + 2 * k] = mean[k];
+        row[RPO_CURVE_STATS + 2 * k + 1] = sqrt(sq[k] / (double)n);
+    }
+    row[RPO_CURVE_LENGTH] = sum[5];
+    row[RPO_CURVE_VIOL_STEPS] = sum[6];
+    row[RPO_CURVE_NONFINITE] = sum[7];
+    row[RPO_CURVE_LEN - 1] = 0.0;
+}
+
+__device__ __forceinline__ void means_of(const double (&sum)[kSumK], int n, double (&mean)[kSumK]) {
+#pragma unroll
+    for (int k = 0; k < kSumK; ++k) mean[k] = k < kSumStats ? sum[k] / (double)n : 0.0;
+}
+
+// n <= kSumRowsPerBlock: everything in one workgroup
+__global__ __launch_bounds__(RPO_BLOCK) void summarize_one_kernel(int n, const float* acc, const long long* ctrl, double* row) {
+    __shared__ double lds[4 * kSumK];
+    double sum[kSumK], mean[kSumK], sq[kSumK];
+#pragma unroll
+    for (int k = 0; k < kSumK; ++k) mean[k] = 0.0;
+    chunk_sums(acc, n, n, 0, mean, sum, lds);
+    means_of(sum, n, mean);
+    chunk_sums(acc, n, n, 1, mean, sq, lds);
+    write_curve_row(row, ctrl, n, sum, mean, sq);
+}
+
+// launches 1 and 2 of the large form: plane 0 <- chunk sums; plane 1 <- chunk sums of squared deviations about the mean every
+// workgroup derives from plane 0 by the same combine
+__global__ __launch_bounds__(RPO_BLOCK) void summarize_chunks_kernel(int n, const float* acc, int chunk, int phase, double* ws) {
+    __shared__ double lds[4 * kSumK];
+    double sum[kSumK], mean[kSumK], v[kSumK];
+#pragma unroll
+    for (int k = 0; k < kSumK; ++k) mean[k] = 0.0;
+    if (phase == 1) {
+        combine_slots(ws, gridDim.x, sum, lds);
+        means_of(sum, n, mean);
+    }
+    chunk_sums(acc, n, chunk, phase, mean, v, lds);
+    if (threadIdx.x < kSumK) {
+        double mine = 0.0;
+#pragma unroll
+        for (int k = 0; k < kSumK; ++k)
+            if ((int)threadIdx.x == k) mine = v[k];
+        ws[(size_t)phase * kSumSlots * kSumK + blockIdx.x * kSumK + threadIdx.x] = mine;
+    }
+}
+
+__global__ __launch_bounds__(RPO_BLOCK) void summarize_combine_kernel(int n, int slots, const double* ws, const long long* ctrl,
+                                                                      double* row) {
+    __shared__ double lds[4 * kSumK];
+    double sum[kSumK], mean[kSumK], sq[kSumK];
+    combine_slots(ws, slots, sum, lds);
+    means_of(sum, n, mean);
+    combine_slots(ws + kSumSlots * kSumK, slots, sq, lds);
+    write_curve_row(row, ctrl, n, sum, mean, sq);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rpo_eval_summarize(int n, const float* acc, const long long* ctrl, double* row_out, double* ws, void* stream) {
+    if (n <= 0 || n > RPO_CURVE_MAX_EPISODES) return RPO_ERR_ARG;
+    if (!acc || !ctrl || !row_out || !ws) return RPO_ERR_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    if (n <= kSumRowsPerBlock) {
+        hipLaunchKernelGGL(summarize_one_kernel, dim3(1), dim3(RPO_BLOCK), 0, s, n, acc, ctrl, row_out);
+        RPO_LAUNCH_CHECK();
+        return 0;
+    }
+    // slots and chunk are functions of n alone: min(256, ceil(n / 1024)) workgroups, equal chunks rounded up to whole blocks
+    const int slots = min(kSumSlots, (n + kSumRowsPerBlock - 1) / kSumRowsPerBlock);
+    const int chunk = ((n + slots - 1) / slots + RPO_BLOCK - 1) / RPO_BLOCK * RPO_BLOCK;
+    for (int phase = 0; phase < 2; ++phase) {
+        hipLaunchKernelGGL(summarize_chunks_kernel, dim3(slots), dim3(RPO_BLOCK), 0, s, n, acc, chunk, phase, ws);
+        RPO_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(summarize_combine_kernel, dim3(1), dim3(RPO_BLOCK), 0, s, n, slots, (const double*)ws, ctrl, row_out);
+    RPO_LAUNCH_CHECK();
+    return 0;
+}
 
 int rpo_cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
                           float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0,

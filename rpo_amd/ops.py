@@ -252,6 +252,21 @@ def eval_accumulate(rows, cols, iters, step, viol_thresh, acc):
                                           _stream()), "rpo_eval_accumulate")
 
 
+CURVE_LEN = CONST["RPO_CURVE_LEN"]
+CURVE_WS = CONST["RPO_CURVE_WS"]
+
+
+def eval_summarize(acc, ctrl, row_out, ws):
+    """The accumulator rows acc [n, EVAL_LEN] of a finished evaluation -> one curve row row_out [CURVE_LEN] float64
+    (rpo_eval_summarize; layout RPO_CURVE_*).  ctrl: the training env's control words (the row's step is ctrl[0], read on the
+    device); ws: float64 [CURVE_WS] scratch."""
+    n = acc.shape[0]
+    if row_out.numel() != CURVE_LEN or ws.numel() < CURVE_WS:
+        raise RpoHipError("curve row must be float64[%d] and the workspace float64[>= %d]" % (CURVE_LEN, CURVE_WS))
+    check(_lib.load().rpo_eval_summarize(n, _eval_acc(acc, n), _p(ctrl, torch.int64), _p(row_out, torch.float64),
+                                         _p(ws, torch.float64), _stream()), "rpo_eval_summarize")
+
+
 # =================================================================================================== env kernel sets
 
 class CartSafeKernels(object):

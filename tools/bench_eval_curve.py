@@ -1,0 +1,121 @@
+#!/usr/bin/env python
+"""What an evaluation point costs a training run on one MI355X (GPU box); prints ONE JSON line.
+
+    timeout -k 10 900 python tools/bench_eval_curve.py [--rounds 3] [--points 8] [--out profiles/eval_curve_bench.json]
+
+For cart-RPODDPG and pendulum-RPODDPG at 4096 lanes (bench.py's hyper-parameters, eval_fre 500), the wall time of the same
+region -- run_steps(points * eval_fre, eval=...) followed by a read of the results and a device synchronise -- in five legs:
+
+  a  eval=False                                   (training alone)
+  b  eval=True, the host-driven eval()            (today's default)
+  c  eval=True, curve mode, 10 episodes per point, overlapped on the evaluation stream
+  d  the same with schedule eval_overlap=0        (in order on the training stream)
+  e  curve mode, 1024 episodes per point, overlapped
+
+One trainer per leg (b shares a's), every leg warmed by one untimed region (graph captures, allocations), then --rounds
+rounds that alternate the legs; medians.  Reported: the five times, the added time per evaluation point of b..e over a, the
+share of eval() in leg b's wall time, and the time of one rpo_eval_summarize at 10 / 1024 / 2^20 episodes (events around
+100 back-to-back calls).  One process; run it under its own time limit.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from bench import make_trainer, spin_up  # noqa: E402
+
+LANES, EVAL_FRE = 4096, 500
+LEGS = (("a_no_eval", None, {}), ("b_eval", None, {}), ("c_curve10_overlap", 10, dict(eval_overlap=1)),
+        ("d_curve10_inorder", 10, dict(eval_overlap=0)), ("e_curve1024_overlap", 1024, dict(eval_overlap=1)))
+
+
+def trainer(workload, episodes, schedule):
+    kw = {} if episodes is None else dict(eval_episodes=episodes)
+    tr = make_trainer(LANES, torch.device("cuda"), 10 ** 9, capacity=64, workload=workload, eval_fre=EVAL_FRE,
+                      schedule=schedule or None, **kw)
+    tr.vec.reset()
+    return tr
+
+
+def region(tr, n, evaluate):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tr.run_steps(n, eval=evaluate)
+    points = len(tr.eval_curve)                                 # (curve mode: the harvest; empty otherwise)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, points
+
+
+def summarize_us(n, reps=100):
+    from rpo_amd import ops
+    dev = torch.device("cuda")
+    acc = torch.rand(n, ops.EVAL_LEN, device=dev)
+    acc[:, 7] = torch.full((n,), 40, dtype=torch.int32, device=dev).view(torch.float32)
+    ctrl = torch.zeros(ops.CTRL_LEN, dtype=torch.int64, device=dev)
+    row = torch.zeros(ops.CURVE_LEN, dtype=torch.float64, device=dev)
+    ws = torch.zeros(ops.CURVE_WS, dtype=torch.float64, device=dev)
+    for _ in range(5):
+        ops.eval_summarize(acc, ctrl, row, ws)
+    times = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            ops.eval_summarize(acc, ctrl, row, ws)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) * 1e3 / reps)
+    return statistics.median(times)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--points", type=int, default=8)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    os.environ["RPO_VERBOSE"] = "0"
+    n = a.points * EVAL_FRE
+    spin_up(torch.device("cuda"))
+    line = dict(tool="bench_eval_curve", device=torch.cuda.get_device_name(0), lanes=LANES, eval_fre=EVAL_FRE, iterations=n,
+                points=a.points, rounds=a.rounds, configs={})
+    for workload in ("cart_ddpg", "pen_ddpg"):
+        trs = {}
+        for name, episodes, schedule in LEGS:
+            trs[name] = trs["a_no_eval"] if name == "b_eval" else trainer(workload, episodes, schedule)
+        times = {name: [] for name, _, _ in LEGS}
+        for rnd in range(a.rounds + 1):                         # round 0: untimed warm-up of every leg
+            for name, episodes, _ in LEGS:
+                before = len(trs[name].eval_curve)
+                t, points = region(trs[name], n, name != "a_no_eval")
+                if episodes is not None:
+                    assert points - before == a.points, (name, points, before)
+                if rnd:
+                    times[name].append(t)
+        med = {name: statistics.median(ts) for name, ts in times.items()}
+        row = dict(wall_s=med, all_s=times,
+                   added_ms_per_point={name: (med[name] - med["a_no_eval"]) * 1e3 / a.points for name in med if name != "a_no_eval"})
+        row["eval_share_of_leg_b"] = (med["b_eval"] - med["a_no_eval"]) / med["b_eval"]
+        row["us_per_iteration_no_eval"] = med["a_no_eval"] * 1e6 / n
+        row["c_over_b"] = row["added_ms_per_point"]["c_curve10_overlap"] / row["added_ms_per_point"]["b_eval"]
+        line["configs"][workload] = row
+        del trs
+        torch.cuda.empty_cache()
+    line["us_per_summarize"] = {str(k): summarize_us(k) for k in (10, 1024, 1 << 20)}
+    s = json.dumps(line)
+    print(s)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
+if __name__ == "__main__":
+    main()
