@@ -153,6 +153,23 @@ extern "C" {
 #define RPO_EVAL_LEN_SHIFT 2     /* steps taken (the step that ended the episode included) */
 #define RPO_EVAL_LANE_STEPS 4194304  /* lane-steps per evaluate launch the host aims at: steps = clamp(this / n, 1, horizon) */
 
+/* Per-step record of a policy evaluation (rpo_<env>_evaluate_record, rpo_eval_record): float[T, R, W], step-major -- row
+ * (s, i) is env step s of episode i < R, so the lanes of a workgroup write neighbouring rows.  With O / P / A the widths of
+ * the observation, the proposal (the partial action handed to the projection) and the action, a row is
+ *   head [HEAD = (O + P + A + 1) rounded up to RPO_TRACE_ALIGN]: obs[O] | proposal[P] | action[A] | GRG iterations | zeros
+ *   tail [RPO_TRACE_TAIL], at HEAD: the RPO_TRACE_* slots below
+ * and W = HEAD + RPO_TRACE_TAIL (CartSafe-v0 and SpringPendulum-v0: 16).  The head is known before the env step and the tail
+ * after it; both are whole 16-byte stores.  Only live lanes write (a lane is live at step 0, and afterwards while
+ * RPO_EVAL_ALIVE is set in its accumulator word), so the caller hands in a zeroed buffer and the rows of the steps after
+ * an episode's end stay zero; the kernels never clear it. */
+#define RPO_TRACE_ALIGN 4        /* floats: W and HEAD are multiples of it, the buffer is 16-byte aligned */
+#define RPO_TRACE_TAIL 4
+#define RPO_TRACE_REWARD 0       /* tail slots: the step's reward */
+#define RPO_TRACE_DONE 1         /* its done flag (termination or TimeLimit) */
+#define RPO_TRACE_INEQ 2         /* max inequality violation, as rpo_eval_lane_update received it */
+#define RPO_TRACE_EQ 3           /* max |equality residual|, likewise */
+#define RPO_TRACE_MAX_BYTES 1073741824  /* the host refuses a larger trace buffer */
+
 /* One row of an evaluation curve (rpo_eval_summarize): double[RPO_CURVE_LEN], the accumulator rows of one evaluation
  * reduced over its episodes.  Means and population standard deviations (numpy's x.mean(), x.std()) of the float32
  * accumulators widened to float64, in eval()'s order. */
@@ -862,6 +879,34 @@ int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, flo
                           float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
                           float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
                           float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, void* stream);
+
+/* The same launches with a per-step record (layout RPO_TRACE_*, O = 6 | 5, P = 1, A = 2: W = 16): a live lane
+ * i < trace_rows writes row (s, i) of trace [trace_steps, trace_rows, 16] at every step s of [t0, t0 + steps) -- the head
+ * (the observation the actor and the projection read, the proposal, the projected action, the iteration count) before the env
+ * step, the tail after it, as non-temporal 16-byte stores.  The accumulators, the env state and the actions are those of
+ * rpo_<env>_evaluate, bit for bit; launches with t0 > 0 continue the same buffer.  trace: zeroed by the caller, 16-byte
+ * aligned; 1 <= trace_rows <= n_envs and t0 + steps <= trace_steps (RPO_ERR_ARG otherwise). */
+int rpo_cartsafe_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                 float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                 int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                 float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                 float viol_thresh, float* trace, int trace_rows, int trace_steps, void* stream);
+int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                 float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                 float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                 float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
+                                 int trace_rows, int trace_steps, void* stream);
+
+/* The stepwise form of the record (any env): row (step, i), i < trace_rows, of trace [trace_steps, trace_rows, W] from the
+ * transition rows rpo_<env>_step wrote (reward, done and the violations, reduced as in rpo_eval_accumulate), the
+ * observation obs [n, obs_stride] the policy read BEFORE that step (the caller keeps a copy: the step overwrites it), the
+ * proposal [n, partial_dim], the stepped action [n, action_dim] and iters [n] (may be NULL: 0).  W follows from obs_dim,
+ * partial_dim and action_dim (RPO_TRACE_*).  Liveness is read from acc [n, RPO_EVAL_LEN], so the call goes BEFORE
+ * rpo_eval_accumulate of the same step; at step 0 every lane is live.  trace: zeroed by the caller, 16-byte aligned. */
+int rpo_eval_record(int n, const float* rows, int row_stride, int reward_col, int done_col, int eq_col, int eq_num,
+                    int ineq_col, int ineq_num, const float* obs, int obs_stride, int obs_dim, const float* proposal,
+                    int partial_dim, const float* action, int action_dim, const int* iters, int step, const float* acc,
+                    float* trace, int trace_rows, int trace_steps, void* stream);
 
 /* The stepwise form of the same statistics (any env): step `step` of n episodes from the transition rows rpo_<env>_step
  * wrote (rows [n, row_stride], the column layout of the env's replay rows: reward, done, eq_viol [eq_num], ineq_viol

@@ -65,6 +65,10 @@ class _LagrangianBase(RPOTrainerBase):
 
     def _eval_action(self, v, iters=None):                  # (no projection: `iters` stays as it is)
         v.action.copy_(self._deterministic(v.obs))
+        return v.action                                       # ... and the proposal is the action
+
+    def _eval_proposal_dim(self):
+        return self.kernels.action_dim
 
     def grad_steps(self, state, action, train=True):
         return action if train else (action, 0)

@@ -16,8 +16,13 @@ its buffers: no trainer state is read-modified-written, so training after an ``e
 Data-parallel runs: ``evaluate()`` runs on the calling rank alone, with no collective (the replicas' networks are
 identical, so every rank would compute the same result); call it on one rank.
 
+Per-step record (``evaluate(record=True | k)``): both paths write one row per live lane and step into a trace buffer
+[horizon, k, W] (``RPO_TRACE_*``; the fused kernel's REC instances, ``rpo_eval_record`` or ``record_torch`` on the stepwise
+path), returned as ``EvalResult.trajectory`` (``EvalTrajectory``).  The per-episode arrays do not depend on it.
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
-``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).
+``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
+does not record trajectories.
 """
 import numpy as np
 import torch
@@ -40,7 +45,7 @@ class EvalResult(object):
 
     FIELDS = ("ret", "length", "mean_ineq", "mean_eq", "max_ineq", "max_eq", "viol_steps", "proj_iters", "nonfinite")
 
-    def __init__(self, acc, path, horizon, seed):
+    def __init__(self, acc, path, horizon, seed, trajectory=None):
         acc = np.asarray(acc, dtype=np.float32).reshape(-1, 8)
         word = acc[:, _WORD].view(np.int32)
         self.ret = acc[:, _RET].astype(np.float64)
@@ -53,6 +58,7 @@ class EvalResult(object):
         self.proj_iters = acc[:, _ITERS].astype(np.int64)
         self.nonfinite = (word & _NONFINITE) != 0
         self.path, self.horizon, self.seed = path, int(horizon), seed
+        self.trajectory = trajectory
 
     @property
     def episodes(self):
@@ -73,6 +79,96 @@ class EvalResult(object):
     def __repr__(self):
         return "EvalResult(episodes=%d, path=%s, return=%.4f, violation_rate=%.4g)" % (
             self.episodes, self.path, self.ret.mean(), self.violation_rate())
+
+
+class EvalTrajectory(object):
+    """The per-step record of ``evaluate(record=...)``: numpy arrays indexed [episode, step, ...] over the recorded episodes
+    (the first ``episodes`` of the evaluation) and ``horizon`` steps.
+
+    ``obs`` [., ., obs_dim]: the observation the actor and the projection read; ``proposal`` [., ., partial_dim]: the partial
+    action the policy handed to the projection, after the tanh box or the mean head (EVOPF-v0 RPODDPG with the fused MLPs hands
+    over the raw actor output -- its state-dependent box is applied inside the projection kernel -- and that is what is
+    recorded; the Lagrangian baselines have no projection: the proposal is the action); ``action`` [., ., action_dim]: the
+    completed, projected action that was stepped; ``reward``; ``done``; ``ineq`` / ``eq``: the step's max inequality violation
+    / max |equality residual| as the accumulators received them; ``iters``: GRG iterations of the step (0 without a
+    projection); ``valid``: step < length[episode].  Floats are the device's float32 bits; entries of non-valid steps are
+    zero.  ``length``: the recorded episodes' lengths; ``viol_thresh``: the threshold of ``EvalResult.viol_steps``."""
+
+    ARRAYS = ("obs", "proposal", "action", "reward", "done", "ineq", "eq", "iters", "valid", "length")
+
+    def __init__(self, viol_thresh, **arrays):
+        for name in self.ARRAYS:
+            setattr(self, name, np.asarray(arrays[name]))
+        self.viol_thresh = float(viol_thresh)
+
+    @classmethod
+    def from_trace(cls, trace, dims, length, viol_thresh):
+        """trace: the device buffer [T, R, W] as numpy (layout RPO_TRACE_*); dims: (obs_dim, partial_dim, action_dim)."""
+        O, P, A = dims
+        head, W = hip_ops.trace_layout(O, P, A)
+        t = np.ascontiguousarray(np.asarray(trace, dtype=np.float32).reshape(trace.shape[0], -1, W).transpose(1, 0, 2))
+        length = np.asarray(length, dtype=np.int64)
+        tail = {k: t[:, :, head + c].copy() for k, c in hip_ops.TRACE_SLOT.items()}
+        return cls(viol_thresh, obs=t[:, :, :O].copy(), proposal=t[:, :, O:O + P].copy(), action=t[:, :, O + P:O + P + A].copy(),
+                   reward=tail["reward"], done=tail["done"] != 0, ineq=tail["ineq"], eq=tail["eq"],
+                   iters=t[:, :, O + P + A].astype(np.int32), valid=np.arange(t.shape[1])[None, :] < length[:, None],
+                   length=length)
+
+    @property
+    def episodes(self):
+        return self.obs.shape[0]
+
+    @property
+    def horizon(self):
+        return self.obs.shape[1]
+
+    def episode(self, i):
+        """The arrays of episode i, trimmed to its length: a dict name -> [length[i], ...]."""
+        n = int(self.length[i])
+        return {name: getattr(self, name)[i, :n] for name in self.ARRAYS if name not in ("valid", "length")}
+
+    def violations(self):
+        """The (episode, step) index pairs [m, 2] of the valid steps with ineq > viol_thresh (the steps ``viol_steps`` counts)."""
+        return np.argwhere(self.valid & (self.ineq > np.float32(self.viol_thresh)))
+
+    def save(self, path):
+        """One .npz with every array (and viol_thresh); ``EvalTrajectory.load`` reads it back."""
+        with open(path, "wb") as f:
+            np.savez(f, viol_thresh=np.float64(self.viol_thresh), **{name: getattr(self, name) for name in self.ARRAYS})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(float(z["viol_thresh"]), **{name: z[name] for name in cls.ARRAYS})
+
+    def __repr__(self):
+        return "EvalTrajectory(episodes=%d, horizon=%d, steps=%d)" % (self.episodes, self.horizon, int(self.valid.sum()))
+
+
+def record_torch(rows, cols, obs, proposal, action, iters, step, acc, trace):
+    """``rpo_eval_record`` in torch ops (backends without the kernel: the CPU oracle): row (step, i), i < R, of trace
+    [T, R, W] for the lanes that are live BEFORE ``accumulate_torch`` of the same step."""
+    n, R = acc.shape[0], trace.shape[1]
+    O, A = obs.shape[1], action.shape[1]
+    prop = proposal.reshape(n, -1)
+    P = prop.shape[1]
+    head, _ = hip_ops.trace_layout(O, P, A)
+    rows = rows[:R]
+    row = torch.zeros_like(trace[step])
+    row[:, :O] = obs[:R]
+    row[:, O:O + P] = prop[:R]
+    row[:, O + P:O + P + A] = action[:R]
+    if iters is not None:
+        row[:, O + P + A] = iters[:R].to(row.dtype)
+    slot = hip_ops.TRACE_SLOT
+    row[:, head + slot["reward"]] = rows[:, cols["reward"][0]]
+    row[:, head + slot["done"]] = rows[:, cols["done"][0]]
+    row[:, head + slot["ineq"]] = rows[:, cols["ineq_viol"][0]:cols["ineq_viol"][1]].max(dim=1).values
+    row[:, head + slot["eq"]] = rows[:, cols["eq_viol"][0]:cols["eq_viol"][1]].abs().max(dim=1).values
+    if step > 0:
+        live = (acc[:R, _WORD].view(torch.int32) & _ALIVE) != 0
+        row = torch.where(live[:, None], row, trace[step])
+    trace[step] = row
 
 
 def accumulate_torch(rows, cols, iters, step, viol_thresh, acc):
@@ -128,15 +224,39 @@ def check_episodes(episodes, what="evaluate: episodes"):
     return int(episodes)
 
 
-def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None):
+def check_record(record, episodes):
+    """``record`` of evaluate() -> the number of recorded episodes: True: all; an integer 1 <= k <= episodes: k; False / 0: 0."""
+    if record is True:
+        return episodes
+    if record is False:
+        return 0
+    try:
+        ok = int(record) == record and 0 <= record <= episodes
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("evaluate: record must be True, False or an integer in [0, episodes = %d], got %r" % (episodes, record))
+    return int(record)
+
+
+def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False):
     """See ``RPOTrainerBase.evaluate``."""
     n = check_episodes(episodes)
+    R = check_record(record, n)
     if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
         raise ValueError("evaluate: horizon must be an integer >= 1, got %r" % (horizon,))
     H = int(horizon) if horizon is not None else default_horizon(tr)
     if H >= 1 << 24:
         raise ValueError("evaluate: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
     k = tr.kernels
+    fused = fused_ok(tr)
+    dims = (k.obs_dim, k.partial_dim if fused else tr._eval_proposal_dim(), k.action_dim)
+    if R:
+        nbytes = 4 * H * R * hip_ops.trace_layout(*dims)[1]
+        if nbytes > hip_ops.TRACE_MAX_BYTES:
+            raise ValueError("evaluate: record=%r needs a trace buffer of %d bytes (horizon %d x %d episodes x %d floats), above "
+                             "the cap of %d bytes; record fewer episodes (record=k)"
+                             % (record, nbytes, H, R, hip_ops.trace_layout(*dims)[1], hip_ops.TRACE_MAX_BYTES))
     if init_states is not None:
         init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
         if tuple(init_states.shape) != (n, k.internal_dim):
@@ -154,40 +274,55 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None):
     if init_states is not None:
         v.set_internal(init_states)
     acc = torch.zeros(n, 8, device=tr.device)
+    # the record: zeroed here (the kernels write live lanes' rows only and never clear it), [step, episode, W]
+    trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
     with torch.no_grad():
-        if fused_ok(tr):
+        if fused:
             path = "fused"
-            _run_fused(tr, v, acc, H)
+            _run_fused(tr, v, acc, H, trace=trace)
         else:
             path = "stepwise"
-            _run_stepwise(tr, v, acc, H)
-    return EvalResult(acc.cpu().numpy(), path, H, seed)
+            _run_stepwise(tr, v, acc, H, trace=trace)
+    res = EvalResult(acc.cpu().numpy(), path, H, seed)
+    if R:
+        res.trajectory = EvalTrajectory.from_trace(trace.cpu().numpy(), dims, res.length[:R], v.viol_thresh)
+    return res
 
 
-def _run_fused(tr, v, acc, H, desc=None):
+def _run_fused(tr, v, acc, H, desc=None, trace=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
-    trainer's (the curve's parameter snapshot)."""
+    trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
+    (rpo_<env>_evaluate_record)."""
     n = v.n
     steps = max(1, min(H, hip_ops.EVAL_LANE_STEPS // n))
     scale, base = tr._box_affine
     desc = tr.fused.descs["actor"] if desc is None else desc
+    kw = {} if trace is None else dict(trace=trace)
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
                             v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo, tr._box_hi,
-                            tr.eval_steps, tr.eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps, v.viol_thresh)
+                            tr.eval_steps, tr.eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps, v.viol_thresh, **kw)
 
 
-def _run_stepwise(tr, v, acc, H):
+def _run_stepwise(tr, v, acc, H, trace=None):
     """eval()'s loop: the trainer's deterministic action + projection, one env step without auto-reset, the accumulator
-    update.  Finished lanes keep stepping (as in eval()); their rows no longer change."""
+    update.  Finished lanes keep stepping (as in eval()); their rows no longer change.  ``trace``: the zeroed record
+    [H, R, W]; the step's row goes in before the accumulator update (which ends the lanes the step finished), from a copy
+    of the observation the policy read (the step overwrites it)."""
     k = tr.kernels
     rows = torch.zeros(v.n, k.ring_floats, device=tr.device)
     iters = torch.zeros(v.n, dtype=torch.int32, device=tr.device)
     update = getattr(tr.backend, "eval_accumulate", None) or accumulate_torch
+    record = getattr(tr.backend, "eval_record", None) or record_torch
+    obs_in = torch.zeros_like(v.obs) if trace is not None else None
     for i in range(H):
-        tr._eval_action(v, iters=iters)
+        if trace is not None:
+            obs_in.copy_(v.obs)
+        proposal = tr._eval_action(v, iters=iters)
         v.step(v.action, rows=rows, cap_steps=1, auto_reset=False)
+        if trace is not None:
+            record(rows, k.cols, obs_in, proposal, v.action, iters, i, acc, trace)
         update(rows, k.cols, iters, i, v.viol_thresh, acc)
 
 

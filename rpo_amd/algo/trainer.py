@@ -1369,11 +1369,17 @@ class RPOTrainerBase(object):
 
     def _eval_action(self, v, iters=None):
         """Deterministic policy + eval_steps projection iterations into v.action (rpo_ddpg.py:224-226); ``iters`` (int32 [n],
-        optional): the projection's iteration count per lane."""
+        optional): the projection's iteration count per lane.  Returns the proposal: the partial action [n * partial_dim]
+        handed to the projection (``evaluate(record=...)`` records it)."""
         ap = self._eval_partial(v.obs)
         self.kernels.act_project(v.obs, ap, None, v.action, iters, hip_ops.NOISE_NONE, 0.0, 0.0, 0.0, self._box_lo,
                                  self._box_hi, self.eval_steps, self.eval_lr, self.corr_eps, self.corr_momentum,
                                  **self._act_kw)
+        return ap
+
+    def _eval_proposal_dim(self):
+        """Width of the proposal ``_eval_action`` returns."""
+        return self.kernels.partial_dim
 
     def eval(self, rendering=False):
         """10 evaluation episodes of at most 500 steps with the deterministic policy and ``eval_steps`` projection
@@ -1417,17 +1423,20 @@ class RPOTrainerBase(object):
             out += [x.mean(), x.std()]
         return tuple(out)
 
-    def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None):
+    def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None, record=False):
         """Evaluate the current policy on ``episodes`` independent episodes -> ``EvalResult`` (per-episode arrays; ``summary()``
         is eval()'s 10-tuple).  The policy, projection and horizon are eval()'s: deterministic actor (RPOSAC: the mean head),
         ``eval_steps`` / ``eval_lr`` / ``corr_eps`` / ``corr_momentum``, at most min(500, max_episode_steps, the env's
         episode_steps) steps (``horizon`` overrides), no auto-reset.  Episode i starts from the reset stream of env id i of a
         fresh vector env with seed ``seed`` (None: a fresh seed per call from the trainer seed and a call counter), or from
         ``init_states[i]`` ([episodes, internal_dim]) when given.  No trainer state changes (networks, env lanes, ctrl, replay,
-        Philox counters, graphs).  Data-parallel runs: evaluates on the calling rank only, with no collective.  See
-        rpo_amd/algo/evaluation.py."""
+        Philox counters, graphs).  Data-parallel runs: evaluates on the calling rank only, with no collective.
+        ``record``: True records every step of every episode, an integer k (1 <= k <= episodes) those of episodes 0..k-1, into
+        ``result.trajectory`` (``EvalTrajectory``: observation, proposal, projected action, reward, done, violations and GRG
+        iterations per step); False / 0: no record, ``result.trajectory`` is None.  The per-episode arrays are the same bits
+        with and without it.  Curve mode (``eval_episodes=N``) does not record.  See rpo_amd/algo/evaluation.py."""
         from .evaluation import evaluate
-        return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states)
+        return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record)
 
     def _print_eval(self, t, res, multipliers=True):
         if self.dist.rank != 0 or not _env_int("RPO_VERBOSE", 1):

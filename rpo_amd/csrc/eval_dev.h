@@ -44,4 +44,42 @@ __device__ __forceinline__ void rpo_eval_lane_update(float* __restrict__ acc, in
     a4[1] = hi;
 }
 
+// ------------------------------------------------------------------------------------------------ per-step record
+// Row layout of the trace buffer (include/rpo_hip.h: RPO_TRACE_*), one definition for the fused kernel and rpo_eval_record.
+__host__ __device__ constexpr int trace_head(int obs_dim, int partial_dim, int action_dim) {
+    return (obs_dim + partial_dim + action_dim + 1 + RPO_TRACE_ALIGN - 1) / RPO_TRACE_ALIGN * RPO_TRACE_ALIGN;
+}
+__host__ __device__ constexpr int trace_width(int obs_dim, int partial_dim, int action_dim) {
+    return trace_head(obs_dim, partial_dim, action_dim) + RPO_TRACE_TAIL;
+}
+
+typedef float trace_v4 __attribute__((ext_vector_type(4)));
+
+// 16-byte streaming store: the trace is written once and read by the host much later
+__device__ __forceinline__ void trace_store(float* dst, float x, float y, float z, float w) {
+    __builtin_nontemporal_store(trace_v4{x, y, z, w}, reinterpret_cast<trace_v4*>(dst));
+}
+
+// Head of a row of the fused kernels (P = 1, A = 2): everything the step knows before the env runs.
+template <int OBS>
+__device__ __forceinline__ void trace_store_head(float* __restrict__ row, const float* obs, float proposal, float2 action, int iters) {
+    constexpr int kHead = trace_head(OBS, 1, 2);
+    float h[kHead];
+#pragma unroll
+    for (int q = 0; q < kHead; ++q) h[q] = q < OBS ? obs[q] : 0.0f;
+    h[OBS] = proposal;
+    h[OBS + 1] = action.x;
+    h[OBS + 2] = action.y;
+    h[OBS + 3] = (float)iters;
+#pragma unroll
+    for (int q = 0; q < kHead; q += 4) trace_store(row + q, h[q], h[q + 1], h[q + 2], h[q + 3]);
+}
+
+// Tail of a row: what the env step produced, in the RPO_TRACE_* slots.
+__device__ __forceinline__ void trace_store_tail(float* __restrict__ tail, float reward, float done, float ineq, float eq) {
+    static_assert(RPO_TRACE_REWARD == 0 && RPO_TRACE_DONE == 1 && RPO_TRACE_INEQ == 2 && RPO_TRACE_EQ == 3 && RPO_TRACE_TAIL == 4,
+                  "the tail is one 16-byte store in slot order");
+    trace_store(tail, reward, done, ineq, eq);
+}
+
 }  // namespace rpo_eval_dev

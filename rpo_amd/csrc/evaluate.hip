@@ -6,6 +6,8 @@
 //                        no grid-wide synchronisation, no co-residency assumption).  The pieces are those of
 //                        rollout_kernel (fused.hip), so the bits are those of the stepwise path.
 //   eval_accumulate      the stepwise path's update: reads the transition rows rpo_<env>_step wrote.
+//   eval_record          the stepwise path's per-step record (rpo_eval_record); the fused kernel's REC = 1 instances write the
+//                        same rows themselves (eval_dev.h: trace_store_head / trace_store_tail).
 //   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
 //
 // Both update a lane's accumulator row through rpo_eval_lane_update (eval_dev.h).
@@ -21,6 +23,8 @@ namespace {
 using namespace rpo_mlp_dev;
 using rpo_eval_dev::nanmax;
 using rpo_eval_dev::rpo_eval_lane_update;
+using rpo_eval_dev::trace_head;
+using rpo_eval_dev::trace_width;
 
 Mlp to_dev(const rpo_mlp* h) {
     return Mlp{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H, h->n_out, h->cat, h->head_dim};
@@ -33,6 +37,8 @@ struct EvalArgs {
     int gauss;                    // 0: deterministic actor (DDPG); 1: the mean head of the squashed Gaussian (SAC)
     int t0, steps;                // env steps [t0, t0 + steps) of the evaluation; t0 == 0 initialises the accumulators
     float* acc;                   // [n, RPO_EVAL_LEN]
+    float* trace;                 // REC instances: [., trace_rows, W] per-step record (RPO_TRACE_*), lanes i < trace_rows
+    int trace_rows;
     typename ENV::ActArgs act;    // projection parameters (RPO_NOISE_NONE), action out
     typename ENV::StepArgs step;  // env state and bookkeeping (rows = NULL, auto_reset = 0)
 };
@@ -45,6 +51,7 @@ struct EvalEnv;
 
 template <>
 struct EvalEnv<CartEnv> {
+    static constexpr int kObs = 6;
     __device__ static __forceinline__ void stage(const rpo_cart_dev::StepArgs& p, int row0, int rows, float* in_s, int stride) {
         CartEnv::stage_obs(p, row0, rows, in_s, stride);
     }
@@ -66,6 +73,7 @@ struct EvalEnv<CartEnv> {
 
 template <>
 struct EvalEnv<PendEnv> {
+    static constexpr int kObs = 5;
     __device__ static __forceinline__ void stage(const rpo_pend_dev::StepArgs& p, int row0, int rows, float* in_s, int stride) {
         const int tid = threadIdx.x;
         if (tid < rows * 5) {
@@ -88,7 +96,9 @@ struct EvalEnv<PendEnv> {
     }
 };
 
-template <class ENV, int EIN, int H, int RT>
+// REC = 1: a live lane i < p.trace_rows also writes row (s, i) of the trace -- the head before ENV::lane runs (the pendulum lane
+// overwrites its observation row), the tail after it.  Nothing of the record is computed in, or alive across, the MFMA loops.
+template <class ENV, int EIN, int H, int RT, int REC>
 __global__ __launch_bounds__(kFwdThreads) void eval_kernel(EvalArgs<ENV> p, typename ENV::Consts c) {
     typedef TileLds<EIN, RT, 8, 8> Lds;                          // 16 * RT lanes per workgroup; OBS <= 8
     __shared__ Lds lds;
@@ -112,23 +122,29 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(EvalArgs<ENV> p, type
             int k;
             const float2 a = ENV::project(p.act, c, lds.in_s + tid * kInS, i, ap, 0.0f, 0, k);
             reinterpret_cast<float2*>(p.act.action)[i] = a;
+            constexpr int kObs = EvalEnv<ENV>::kObs, kW = trace_width(kObs, 1, 2);
+            if (REC && i < p.trace_rows)
+                rpo_eval_dev::trace_store_head<kObs>(p.trace + ((size_t)s * p.trace_rows + i) * kW, lds.in_s + tid * kInS, ap, a, k);
             float reward, done, ineq, eq;
             EvalEnv<ENV>::lane(p.step, c, i, lds.in_s + tid * kInS, a, reward, done, ineq, eq);
+            if (REC && i < p.trace_rows)
+                rpo_eval_dev::trace_store_tail(p.trace + ((size_t)s * p.trace_rows + i) * kW + trace_head(kObs, 1, 2), reward, done,
+                                               ineq, eq);
             rpo_eval_lane_update(p.acc + (size_t)i * RPO_EVAL_LEN, s, reward, ineq, eq, done, k, p.step.viol_thresh);
         }
         __syncthreads();                                         // every lane has read its observation out of the LDS tile
     }
 }
 
-template <class ENV>
+template <class ENV, int REC>
 int launch_eval(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, void* stream) {
     // the rollout's tile rule (fused.hip launch_rollout): 64 lanes per workgroup once that still fills the chip.  E = 128
     // only: the E = 256 instance spills (~150 bytes of scratch per lane) -- such actors evaluate on the stepwise path.
     if (args.actor.E != 128) return RPO_ERR_ARG;
     if (n >= 64 * 192) {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     } else {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     }
     RPO_LAUNCH_CHECK();
     return 0;
@@ -147,6 +163,15 @@ int check_eval_range(int n, int t0, int steps, int max_episode_steps, int max_st
     return 0;
 }
 
+// The trace arguments of the *_evaluate_record entry points: 1 <= R <= n rows per step, steps [t0, t0 + steps) inside the
+// buffer's T steps, 16-byte aligned for the float4 stores.
+int check_eval_trace(const float* trace, int n, int trace_rows, int trace_steps, int t0, int steps) {
+    if (!trace) return RPO_ERR_NULL;
+    if (trace_rows <= 0 || trace_rows > n || trace_steps <= 0 || (long long)t0 + steps > trace_steps) return RPO_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(trace) % 16) return RPO_ERR_ARG;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------- stepwise accumulation
 struct AccArgs {
     int n;
@@ -158,14 +183,61 @@ struct AccArgs {
     float* acc;
 };
 
+// the step's max inequality violation / max |equality residual| of a transition row, columns in order
+__device__ __forceinline__ void row_violations(const float* r, int ineq_col, int ineq_num, int eq_col, int eq_num, float& ineq,
+                                               float& eq) {
+    ineq = r[ineq_col];
+    eq = fabsf(r[eq_col]);
+    for (int j = 1; j < ineq_num; ++j) ineq = nanmax(ineq, r[ineq_col + j]);
+    for (int j = 1; j < eq_num; ++j) eq = nanmax(eq, fabsf(r[eq_col + j]));
+}
+
 __global__ __launch_bounds__(RPO_BLOCK) void eval_accumulate_kernel(AccArgs p) {
     for (int i = blockIdx.x * RPO_BLOCK + threadIdx.x; i < p.n; i += gridDim.x * RPO_BLOCK) {
         const float* r = p.rows + (size_t)i * p.stride;
-        float ineq = r[p.ineq_col], eq = fabsf(r[p.eq_col]);
-        for (int j = 1; j < p.ineq_num; ++j) ineq = nanmax(ineq, r[p.ineq_col + j]);
-        for (int j = 1; j < p.eq_num; ++j) eq = nanmax(eq, fabsf(r[p.eq_col + j]));
+        float ineq, eq;
+        row_violations(r, p.ineq_col, p.ineq_num, p.eq_col, p.eq_num, ineq, eq);
         rpo_eval_lane_update(p.acc + (size_t)i * RPO_EVAL_LEN, p.step, r[p.reward_col], ineq, eq, r[p.done_col],
                              p.iters ? p.iters[i] : 0, p.viol_thresh);
+    }
+}
+
+// ------------------------------------------------------------------------------------------- stepwise record
+struct RecArgs {
+    AccArgs a;                    // the transition rows and their columns, the step, the accumulators (liveness)
+    const float *obs, *proposal, *action;
+    int obs_stride, O, P, A;
+    float* trace;                 // [., R, W]
+    int R, head, W;
+};
+
+// element c of lane i's row head: obs | proposal | action | iterations | zeros
+__device__ __forceinline__ float record_head_element(const RecArgs& p, int i, int c) {
+    if (c < p.O) return p.obs[(size_t)i * p.obs_stride + c];
+    c -= p.O;
+    if (c < p.P) return p.proposal[(size_t)i * p.P + c];
+    c -= p.P;
+    if (c < p.A) return p.action[(size_t)i * p.A + c];
+    return c == p.A && p.a.iters ? (float)p.a.iters[i] : 0.0f;
+}
+
+// One thread per 16-byte chunk of a row: the chunks of a step's R rows are contiguous, so a wave stores 1 KiB in a piece.
+__global__ __launch_bounds__(RPO_BLOCK) void eval_record_kernel(RecArgs p) {
+    const int chunks = p.W / 4;
+    const long long total = (long long)p.R * chunks;
+    for (long long t = (long long)blockIdx.x * RPO_BLOCK + threadIdx.x; t < total; t += (long long)gridDim.x * RPO_BLOCK) {
+        const int i = (int)(t / chunks), c = (int)(t - (long long)i * chunks) * 4;
+        if (p.a.step > 0 && !(__float_as_int(p.a.acc[(size_t)i * RPO_EVAL_LEN + RPO_EVAL_WORD]) & RPO_EVAL_ALIVE)) continue;
+        float* dst = p.trace + ((size_t)p.a.step * p.R + i) * p.W + c;
+        if (c < p.head) {
+            rpo_eval_dev::trace_store(dst, record_head_element(p, i, c), record_head_element(p, i, c + 1),
+                                      record_head_element(p, i, c + 2), record_head_element(p, i, c + 3));
+        } else {
+            const float* r = p.a.rows + (size_t)i * p.a.stride;
+            float ineq, eq;
+            row_violations(r, p.a.ineq_col, p.a.ineq_num, p.a.eq_col, p.a.eq_num, ineq, eq);
+            rpo_eval_dev::trace_store_tail(dst, r[p.a.reward_col], r[p.a.done_col], ineq, eq);
+        }
     }
 }
 
@@ -296,6 +368,56 @@ __global__ __launch_bounds__(RPO_BLOCK) void summarize_combine_kernel(int n, int
     write_curve_row(row, ctrl, n, sum, mean, sq);
 }
 
+// rpo_cartsafe_evaluate (rec = 0: trace arguments unused) and rpo_cartsafe_evaluate_record (rec = 1)
+int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state, float* action,
+                      int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
+                      float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, const float* consts_host,
+                      int partial, int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows,
+                      int trace_steps, void* stream) {
+    if (!actor_host) return RPO_ERR_NULL;
+    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
+    if (!state || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
+    if (rec)
+        if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
+    EvalArgs<CartEnv> args{};
+    args.actor = to_dev(actor_host);
+    if (int e = check_eval_actor(args.actor, 6, gauss)) return e;
+    rpo_cart_dev::CartConsts c;
+    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
+    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
+    args.act = rpo_cart_dev::ActArgs{n_envs, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, box_lo, box_hi,
+                                     max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    args.step = rpo_cart_dev::StepArgs{n_envs, state, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
+                                       max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
+    args.trace = rec ? trace : nullptr;
+    args.trace_rows = rec ? trace_rows : 0;
+    return rec ? launch_eval<CartEnv, 1>(args, c, n_envs, stream) : launch_eval<CartEnv, 0>(args, c, n_envs, stream);
+}
+
+int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal, float* obs,
+                      float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps,
+                      float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                      int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows, int trace_steps,
+                      void* stream) {
+    if (!actor_host) return RPO_ERR_NULL;
+    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
+    if (!internal || !obs || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
+    if (rec)
+        if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
+    EvalArgs<PendEnv> args{};
+    args.actor = to_dev(actor_host);
+    if (int e = check_eval_actor(args.actor, 5, gauss)) return e;
+    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
+    args.act = rpo_pend_dev::ActArgs{n_envs, nullptr, 5, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
+                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    args.step = rpo_pend_dev::StepArgs{n_envs, internal, obs, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
+                                       max_episode_steps, 0, viol_thresh, 0ull, 0u};
+    args.trace = rec ? trace : nullptr;
+    args.trace_rows = rec ? trace_rows : 0;
+    const PendEnv::Consts c{0};
+    return rec ? launch_eval<PendEnv, 1>(args, c, n_envs, stream) : launch_eval<PendEnv, 0>(args, c, n_envs, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -326,38 +448,38 @@ int rpo_cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, flo
                           int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
                           float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
                           float viol_thresh, void* stream) {
-    if (!actor_host) return RPO_ERR_NULL;
-    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
-    if (!state || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
-    EvalArgs<CartEnv> args{};
-    args.actor = to_dev(actor_host);
-    if (int e = check_eval_actor(args.actor, 6, gauss)) return e;
-    rpo_cart_dev::CartConsts c;
-    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
-    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
-    args.act = rpo_cart_dev::ActArgs{n_envs, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, box_lo, box_hi,
-                                     max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    args.step = rpo_cart_dev::StepArgs{n_envs, state, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
-                                       max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
-    return launch_eval<CartEnv>(args, c, n_envs, stream);
+    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
+                             viol_thresh, 0, nullptr, 0, 0, stream);
+}
+
+int rpo_cartsafe_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                 float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                 int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                 float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                 float viol_thresh, float* trace, int trace_rows, int trace_steps, void* stream) {
+    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
+                             viol_thresh, 1, trace, trace_rows, trace_steps, stream);
 }
 
 int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
                           float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
                           float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
                           float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, void* stream) {
-    if (!actor_host) return RPO_ERR_NULL;
-    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
-    if (!internal || !obs || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
-    EvalArgs<PendEnv> args{};
-    args.actor = to_dev(actor_host);
-    if (int e = check_eval_actor(args.actor, 5, gauss)) return e;
-    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
-    args.act = rpo_pend_dev::ActArgs{n_envs, nullptr, 5, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
-                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    args.step = rpo_pend_dev::StepArgs{n_envs, internal, obs, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
-                                       max_episode_steps, 0, viol_thresh, 0ull, 0u};
-    return launch_eval<PendEnv>(args, PendEnv::Consts{0}, n_envs, stream);
+    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
+                             nullptr, 0, 0, stream);
+}
+
+int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                 float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                 float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                 float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
+                                 int trace_rows, int trace_steps, void* stream) {
+    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 1,
+                             trace, trace_rows, trace_steps, stream);
 }
 
 int rpo_eval_accumulate(int n, const float* rows, int row_stride, int reward_col, int done_col, int eq_col, int eq_num,
@@ -370,6 +492,35 @@ int rpo_eval_accumulate(int n, const float* rows, int row_stride, int reward_col
     if (!rows || !acc) return RPO_ERR_NULL;
     const AccArgs a{n, rows, row_stride, reward_col, done_col, eq_col, eq_num, ineq_col, ineq_num, iters, step, viol_thresh, acc};
     hipLaunchKernelGGL(eval_accumulate_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a);
+    RPO_LAUNCH_CHECK();
+    return 0;
+}
+
+int rpo_eval_record(int n, const float* rows, int row_stride, int reward_col, int done_col, int eq_col, int eq_num,
+                    int ineq_col, int ineq_num, const float* obs, int obs_stride, int obs_dim, const float* proposal,
+                    int partial_dim, const float* action, int action_dim, const int* iters, int step, const float* acc,
+                    float* trace, int trace_rows, int trace_steps, void* stream) {
+    if (n <= 0 || step < 0 || step >= (1 << 24) || eq_num <= 0 || ineq_num <= 0 || reward_col < 0 || done_col < 0 || eq_col < 0 ||
+        ineq_col < 0)
+        return RPO_ERR_ARG;
+    if (reward_col >= row_stride || done_col >= row_stride || eq_col + eq_num > row_stride || ineq_col + ineq_num > row_stride)
+        return RPO_ERR_ARG;
+    if (obs_dim <= 0 || partial_dim <= 0 || action_dim <= 0 || obs_dim > 4096 || partial_dim > 4096 || action_dim > 4096 ||
+        obs_stride < obs_dim)
+        return RPO_ERR_ARG;
+    if (trace_rows <= 0 || trace_rows > n || step >= trace_steps) return RPO_ERR_ARG;
+    if (!rows || !obs || !proposal || !action || !acc || !trace) return RPO_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(trace) % 16) return RPO_ERR_ARG;
+    RecArgs r{};
+    r.a = AccArgs{n, rows, row_stride, reward_col, done_col, eq_col, eq_num, ineq_col, ineq_num, iters, step, 0.0f,
+                  const_cast<float*>(acc)};              // (read only: liveness)
+    r.obs = obs; r.proposal = proposal; r.action = action;
+    r.obs_stride = obs_stride; r.O = obs_dim; r.P = partial_dim; r.A = action_dim;
+    r.trace = trace; r.R = trace_rows;
+    r.head = trace_head(obs_dim, partial_dim, action_dim);
+    r.W = trace_width(obs_dim, partial_dim, action_dim);
+    hipLaunchKernelGGL(eval_record_kernel, dim3(rpo_grid_for((long long)trace_rows * (r.W / 4))), dim3(RPO_BLOCK), 0,
+                       (hipStream_t)stream, r);
     RPO_LAUNCH_CHECK();
     return 0;
 }

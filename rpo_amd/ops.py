@@ -252,6 +252,46 @@ def eval_accumulate(rows, cols, iters, step, viol_thresh, acc):
                                           _stream()), "rpo_eval_accumulate")
 
 
+TRACE_ALIGN = CONST["RPO_TRACE_ALIGN"]
+TRACE_TAIL = CONST["RPO_TRACE_TAIL"]
+TRACE_MAX_BYTES = CONST["RPO_TRACE_MAX_BYTES"]
+TRACE_SLOT = {k: CONST["RPO_TRACE_" + k.upper()] for k in ("reward", "done", "ineq", "eq")}    # offsets in the tail
+
+
+def trace_layout(obs_dim, partial_dim, action_dim):
+    """(head, W) of a trace row (include/rpo_hip.h: RPO_TRACE_*): obs | proposal | action | iterations, padded to a multiple of
+    TRACE_ALIGN floats, then the TRACE_TAIL floats reward, done, ineq, eq."""
+    head = (obs_dim + partial_dim + action_dim + 1 + TRACE_ALIGN - 1) // TRACE_ALIGN * TRACE_ALIGN
+    return head, head + TRACE_TAIL
+
+
+def _trace(trace, n, width):
+    """(pointer, rows, steps) of a trace buffer [T, R, W] for n lanes."""
+    if trace.dim() != 3 or trace.shape[2] != width or not 1 <= trace.shape[1] <= n:
+        raise RpoHipError("trace buffer must be [steps, 1..%d, %d] float32, got %s" % (n, width, tuple(trace.shape)))
+    return _p(trace), int(trace.shape[1]), int(trace.shape[0])
+
+
+def eval_record(rows, cols, obs, proposal, action, iters, step, acc, trace):
+    """Step `step` of a policy evaluation into the per-step record trace [T, R, W] (rpo_eval_record; before eval_accumulate of
+    the same step): the transition rows the env's step kernel wrote, the observation `obs` the policy read before that step,
+    the proposal [n * partial_dim] it handed to the projection, the stepped action and the iteration counts (int32 [n], or
+    None)."""
+    n = acc.shape[0]
+    rp, stride = _row_view(rows[:n], rows.shape[1])
+    op, ostride = _row_view(obs, obs.shape[1])
+    (r0, _), (d0, _) = cols["reward"], cols["done"]
+    (e0, e1), (i0, i1) = cols["eq_viol"], cols["ineq_viol"]
+    O, A = obs.shape[1], action.shape[1]
+    P = proposal.numel() // n
+    if obs.shape[0] != n or action.shape[0] != n or proposal.numel() != n * P or P < 1:
+        raise RpoHipError("eval_record: obs / proposal / action do not have %d rows" % n)
+    tp, R, T = _trace(trace, n, trace_layout(O, P, A)[1])
+    check(_lib.load().rpo_eval_record(n, rp, stride, r0, d0, e0, e1 - e0, i0, i1 - i0, op, ostride, O, _p(proposal), P,
+                                      _p(action), A, _p(iters, torch.int32, allow_none=True), int(step), _eval_acc(acc, n),
+                                      tp, R, T, _stream()), "rpo_eval_record")
+
+
 CURVE_LEN = CONST["RPO_CURVE_LEN"]
 CURVE_WS = CONST["RPO_CURVE_WS"]
 
@@ -327,14 +367,20 @@ class CartSafeKernels(object):
             "rpo_cartsafe_rollout")
 
     def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh):
-        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_cartsafe_evaluate); acc [n, EVAL_LEN]."""
+                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None):
+        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_cartsafe_evaluate); acc [n, EVAL_LEN].
+        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_cartsafe_evaluate_record)."""
         net = actor_desc.net_struct()
-        check(_lib.load().rpo_cartsafe_evaluate(
-            ctypes.byref(net), int(gauss), scale, base, internal.shape[0], _p(internal), _p(action), _p(ep_len, torch.int32),
-            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, internal.shape[0]),
-            int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
-            max_episode_steps, viol_thresh, _stream()), "rpo_cartsafe_evaluate")
+        n = internal.shape[0]
+        args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32),
+                _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n),
+                int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
+                max_episode_steps, viol_thresh)
+        if trace is None:
+            check(_lib.load().rpo_cartsafe_evaluate(*args, _stream()), "rpo_cartsafe_evaluate")
+        else:
+            tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
+            check(_lib.load().rpo_cartsafe_evaluate_record(*args, *tr, _stream()), "rpo_cartsafe_evaluate_record")
 
     def ddpg_critic_forward(self, actor_target, critic_target, critic, scale, base, rows, cap_steps, n_envs, batch_out,
                             idx_out, idx_in, seed, salt, ctrl, max_steps, corr_lr, corr_eps, corr_momentum, box_lo, box_hi,
@@ -537,14 +583,20 @@ class PendulumKernels(object):
             "rpo_pendulum_rollout")
 
     def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh):
-        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_pendulum_evaluate); acc [n, EVAL_LEN]."""
+                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None):
+        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_pendulum_evaluate); acc [n, EVAL_LEN].
+        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_pendulum_evaluate_record)."""
         net = actor_desc.net_struct()
-        check(_lib.load().rpo_pendulum_evaluate(
-            ctypes.byref(net), int(gauss), scale, base, internal.shape[0], _p(internal), _p(obs), _p(action),
-            _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
-            _eval_acc(acc, internal.shape[0]), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps,
-            corr_momentum, max_episode_steps, viol_thresh, _stream()), "rpo_pendulum_evaluate")
+        n = internal.shape[0]
+        args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action),
+                _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
+                _eval_acc(acc, n), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps,
+                corr_momentum, max_episode_steps, viol_thresh)
+        if trace is None:
+            check(_lib.load().rpo_pendulum_evaluate(*args, _stream()), "rpo_pendulum_evaluate")
+        else:
+            tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
+            check(_lib.load().rpo_pendulum_evaluate_record(*args, *tr, _stream()), "rpo_pendulum_evaluate_record")
 
     def ddpg_critic_front(self, actor_target, scale, base, rows, cap_steps, n_envs, batch_out, idx_out, idx_in, sample_seed,
                           sample_salt, ctrl, ap_out):

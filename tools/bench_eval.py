@@ -4,6 +4,7 @@
     python tools/bench_eval.py [--reps R] [--sizes 4096,65536,1048576] [--out FILE]
     python tools/bench_eval.py --profile-only [--sizes 65536]     # fused evaluations only, for a rocprofv3 pass:
     rocprofv3 --kernel-trace --stats -d DIR -o eval -- python tools/bench_eval.py --profile-only
+    python tools/bench_eval.py --record [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_record_bench.json]
 
 Per configuration (cart-RPODDPG, cart-RPOSAC, pendulum-RPODDPG: fused; EVOPF-RPODDPG: stepwise only) a trainer with
 bench.py's hyper-parameters is trained for a few vector steps (a policy that has left its initialisation), then:
@@ -11,6 +12,10 @@ bench.py's hyper-parameters is trained for a few vector steps (a policy that has
   * the fused path at --sizes episodes: wall time, episodes/s, env-steps/s (the live steps the episodes took) and the
     actor's algorithmic f32 FLOP over those steps as a share of the 157.3 TFLOP/s f32 MFMA peak (a lower bound: the
     finished lanes of a live 16-lane tile still go through the MLP).
+--record: the cost of evaluate(record=...) (the per-step trajectory).  Fused cart-RPODDPG and pendulum-RPODDPG at --sizes
+episodes, stepwise EVOPF-RPODDPG at 10 and 1024: the legs record=False / record=64 / record=True are timed ALTERNATELY, --reps
+rounds after one warm-up round, and reported as medians with the min-max spread of each leg (a leg's cost over record=False
+means something only beyond that spread).  A record=True leg includes the read-back and the numpy views of the trace.
 Every call ends with a host read of the results (evaluate()'s .cpu(), eval()'s), so wall times include the device work.
 Run each GPU step under its own time limit (timeout -k 10 ...).
 """
@@ -27,6 +32,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from bench import ROLLOUT_FLOP_PER_LANE, make_trainer  # noqa: E402
+from rpo_amd import ops  # noqa: E402
 
 PEAK_F32_MFMA = 157.3e12
 CONFIGS = [("cart_ddpg", True), ("cart_sac", True), ("pen_ddpg", True), ("evopf_ddpg", False)]
@@ -61,14 +67,63 @@ def evaluate_path(tr, fused, **kw):
         tr.schedule["fused_eval"] = 1
 
 
+def alternating(legs, reps):
+    """legs: {name: fn}; one warm-up round, then `reps` rounds of every leg in turn -> {name: dict(median_s, min_s, max_s)}."""
+    ts = {k: [] for k in legs}
+    for rnd in range(reps + 1):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if rnd:
+                ts[k].append(time.perf_counter() - t0)
+    return {k: dict(median_s=statistics.median(v), min_s=min(v), max_s=max(v)) for k, v in ts.items()}
+
+
+def record_bench(a, sizes):
+    line = dict(tool="bench_eval --record", device=torch.cuda.get_device_name(0), reps=a.reps, configs={})
+    for workload, has_fused in (("cart_ddpg", True), ("pen_ddpg", True), ("evopf_ddpg", False)):
+        tr = trainer(workload)
+        row = {}
+        for n in (sizes if has_fused else [10, 1024]):
+            legs = {"record_false": lambda: tr.evaluate(n, seed=5)}
+            if n > 64:
+                legs["record_64"] = lambda: tr.evaluate(n, seed=5, record=64)
+            legs["record_true"] = lambda: tr.evaluate(n, seed=5, record=True)
+            res = alternating(legs, a.reps)
+            r = tr.evaluate(n, seed=5, record=True)
+            assert r.path == ("fused" if has_fused else "stepwise")
+            base = res["record_false"]["median_s"]
+            for k in res:
+                res[k]["over_record_false_s"] = res[k]["median_s"] - base
+            tj = r.trajectory
+            width = ops.trace_layout(tj.obs.shape[2], tj.proposal.shape[2], tj.action.shape[2])[1]
+            res.update(horizon=r.horizon, env_steps=int(r.length.sum()), path=r.path, trace_bytes_record_true=4 * r.horizon * n * width)
+            row[str(n)] = res
+            del r, tj
+        line["configs"][workload] = row
+        del tr
+        torch.cuda.empty_cache()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="4096,65536,1048576")
     ap.add_argument("--profile-only", action="store_true")
+    ap.add_argument("--record", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sizes = [int(x) for x in a.sizes.split(",") if x]
+    if a.record:
+        s = json.dumps(record_bench(a, [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes))
+        print(s)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(s + "\n")
+        return
     if a.profile_only:
         tr = trainer("cart_ddpg")
         for n in sizes:
