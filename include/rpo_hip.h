@@ -897,6 +897,26 @@ int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float sca
                                  float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
                                  int trace_rows, int trace_steps, void* stream);
 
+/* Projected actions for caller-supplied observations (RPOTrainerBase.act, rpo_amd/algo/acting.py): n rows obs [n, obs_stride]
+ * (obs_stride >= 6 | 5 floats) -> action [n, 2] (8-byte aligned), and where the pointer is not NULL: proposal [n] (what the
+ * policy handed to the projection), iters [n] (GRG iterations of the row), eq_resid [n] and ineq_resid [n, 6 | 1] (signed,
+ * at the returned action; CartSafe-v0: 8-byte aligned).  One launch, rows independent (per-row stop test), no env state, no
+ * control word, no generator; the outputs leave as non-temporal stores.
+ * == the sequence of launches rpo_mlp_forward (+ rpo_gauss_head(deterministic)) + rpo_<env>_act_project(RPO_NOISE_NONE,
+ *    iters) + rpo_<env>_resid on the same rows, bit for bit.
+ * form: 0 = chosen by n (row tile below RPO_ROLLOUT_STREAM_FROM rows, streaming from there, 64-row groups once every wave
+ *   of the chip gets one), 1 = row tile (16 rows per workgroup, 64 from 12 288 rows), 2 = streaming with 16-row groups,
+ *   3 = streaming with 64-row groups; RPO_ERR_ARG where the asked form does not apply.
+ * The actor: embed width E = 128, hidden 256 (RPO_ERR_ARG otherwise); n > 0, max_steps >= 0 (0: complete_partial only). */
+int rpo_cartsafe_policy_act(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
+                            int obs_stride, float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid,
+                            float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                            const float* consts_host, int partial, int form, void* stream);
+int rpo_pendulum_policy_act(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
+                            int obs_stride, float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid,
+                            float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                            int form, void* stream);
+
 /* The stepwise form of the record (any env): row (step, i), i < trace_rows, of trace [trace_steps, trace_rows, W] from the
  * transition rows rpo_<env>_step wrote (reward, done and the violations, reduced as in rpo_eval_accumulate), the
  * observation obs [n, obs_stride] the policy read BEFORE that step (the caller keeps a copy: the step overwrites it), the

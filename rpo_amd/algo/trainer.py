@@ -265,11 +265,13 @@ def _env_int(name, default):
 #:                  actor-only prefix of the policy step beside the critic update (0: serial windows)
 #:   fused_eval     evaluate(): actor -> head -> Complete -> GRG -> env step -> per-episode statistics as a few launches that
 #:                  loop over the env steps (0: the stepwise path, one _eval_action + step + rpo_eval_accumulate per step)
+#:   fused_act      act(): actor -> head -> Complete -> GRG -> residuals as ONE launch (0: the stepwise path, the trainer's
+#:                  deterministic proposal + rpo_*_act_project + rpo_*_resid)
 #:   eval_overlap   curve mode (`eval_episodes=N`), fused path: an evaluation point runs on its own stream, on a snapshot of the
 #:                  actor, beside the update that follows it (0: in order on the training stream)
 #:   force_dist     (default 0) data-parallel code path over a one-rank process group
 SCHEDULE_DEFAULTS = dict(fused_mlp=1, fused_rollout=1, fused_critic=1, fused_actor=1, split=1, ride=1, front=1, branch=1,
-                         fused_eval=1, eval_overlap=1, force_dist=0)
+                         fused_eval=1, fused_act=1, eval_overlap=1, force_dist=0)
 
 
 def parse_schedule(overrides=None):
@@ -1437,6 +1439,29 @@ class RPOTrainerBase(object):
         with and without it.  Curve mode (``eval_episodes=N``) does not record.  See rpo_amd/algo/evaluation.py."""
         from .evaluation import evaluate
         return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record)
+
+    def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0):
+        """The policy's projected actions for caller-supplied observations -> ``ActResult`` (torch tensors on the trainer's
+        device, nothing waits for the device): ``action`` [n, action_dim], the completed + projected action ``eval()`` would
+        step in that state; ``proposal`` [n, P], what the policy handed to the projection; ``iters`` int32 [n], GRG iterations
+        per row (0 for the Lagrangian baselines); ``eq_resid`` / ``ineq_resid``, the signed residuals at ``action`` (ineq > 0
+        is a violation; None with ``residuals=False``).  ``obs``: [n, obs_dim] or [obs_dim] (n = 1), a float32 tensor on the
+        trainer's device or anything ``torch.as_tensor`` accepts.  The policy is eval()'s (deterministic actor; RPOSAC: the mean
+        head), the projection uses ``eval_steps`` / ``eval_lr`` / ``corr_eps`` / ``corr_momentum``; ``eval_steps=`` /
+        ``eval_lr=`` override them for this call only (``eval_steps=0``: Complete(proposal), ``iters == 0``).
+        Rows are ALWAYS projected independently, each with its own stop test (the B = 1 semantics of the rollout and of
+        eval()): SpringPendulum's batch-coupled reference projection is never used here, whatever ``batch_reference`` is, so
+        ``act(obs)[i]`` equals ``act(obs[i:i+1])``.  ``out``: an earlier ``ActResult`` of the same n and ``residuals``, whose
+        tensors are written again instead of new ones (the fused path then allocates nothing; the stepwise path's scratch is
+        cached per n by the fused-MLP buffers, the torch-module policies allocate as torch does).  ``form`` (measurements and
+        tests): 0 chosen by n, 1 the row-tile launch, 2 / 3 the streaming launch with 16- / 64-row groups.  A NaN observation
+        is no error and involves no control word: it stays in its row, where the NaN-propagating clamps carry it into the
+        action wherever it reaches them (the fused MLP kernels' ReLU, the hardware maximum, drops a NaN behind the first layer).  No trainer state changes (networks, env lanes, ctrl, replay,
+        Philox counters, graphs) and nothing is drawn from a generator.  Data-parallel runs: the calling rank acts alone, no
+        collective.  ValueError: wrong width, n = 0, a non-finite ``eval_lr``, ``eval_steps`` not an integer >= 0, ``out`` of
+        another n or ``residuals``, a ``form`` on a stepwise configuration.  See rpo_amd/algo/acting.py."""
+        from .acting import act
+        return act(self, obs, eval_steps=eval_steps, eval_lr=eval_lr, residuals=residuals, out=out, form=form)
 
     def _print_eval(self, t, res, multipliers=True):
         if self.dist.rank != 0 or not _env_int("RPO_VERBOSE", 1):

@@ -14,9 +14,11 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["cartsafe.hip", "pendulum.hip", "evopf.hip", "replay.hip", "train_ops.hip", "mlp.hip", "fused.hip", "nsplit.hip",
-           "rollout_stream.hip", "mlp_bwd_stream.hip", "evaluate.hip"]
-# per-file flags: the streaming rollout and the streaming backward are compiled without SLP vectorisation (see their headers)
-FILE_FLAGS = {"rollout_stream.hip": ["-fno-slp-vectorize"], "mlp_bwd_stream.hip": ["-fno-slp-vectorize"]}
+           "rollout_stream.hip", "mlp_bwd_stream.hip", "evaluate.hip", "act.hip", "act_stream.hip"]
+# per-file flags: the streaming rollout, the streaming backward and the streaming policy_act are compiled without SLP
+# vectorisation (see their headers)
+FILE_FLAGS = {"rollout_stream.hip": ["-fno-slp-vectorize"], "mlp_bwd_stream.hip": ["-fno-slp-vectorize"],
+              "act_stream.hip": ["-fno-slp-vectorize"]}
 HEADERS = sorted(f for f in os.listdir(HERE) if f.endswith(".h")) + [os.path.join("..", "..", "include", "rpo_hip.h")]   # (every header: a stale object is worse than a rebuild)
 TARGET = os.path.join(HERE, "librpo_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

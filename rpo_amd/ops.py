@@ -307,6 +307,17 @@ def eval_summarize(acc, ctrl, row_out, ws):
                                          _p(ws, torch.float64), _stream()), "rpo_eval_summarize")
 
 
+def _act_outputs(kernels, n, action, proposal, iters, eq_resid, ineq_resid):
+    """Shapes of the outputs of ``policy_act`` (the kernels index them by row: a smaller buffer would be written out of bounds)."""
+    want = (("action", action, (n, kernels.action_dim)), ("proposal", proposal, (n, kernels.partial_dim)), ("iters", iters, (n,)),
+            ("eq_resid", eq_resid, (n, kernels.eq_num)), ("ineq_resid", ineq_resid, (n, kernels.ineq_num)))
+    for name, t, shape in want:
+        if t is not None and tuple(t.shape) != shape:
+            raise RpoHipError("policy_act: %s must be %s, got %s" % (name, shape, tuple(t.shape)))
+    if action is None or n < 1:
+        raise RpoHipError("policy_act: needs n >= 1 rows and an action buffer")
+
+
 # =================================================================================================== env kernel sets
 
 class CartSafeKernels(object):
@@ -381,6 +392,19 @@ class CartSafeKernels(object):
         else:
             tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
             check(_lib.load().rpo_cartsafe_evaluate_record(*args, *tr, _stream()), "rpo_cartsafe_evaluate_record")
+
+    def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
+                   max_steps, corr_lr, corr_eps, corr_momentum, form=0):
+        """obs [n, 6] (row view) -> action [n, 2] and, where not None, proposal [n], iters int32 [n], eq_resid [n, 1],
+        ineq_resid [n, 6], in one launch (rpo_cartsafe_policy_act); form: 0 by size, 1 row tile, 2 / 3 streaming (G = 1 / 4)."""
+        net = actor_desc.net_struct()
+        op, ostride = _row_view(obs, self.obs_dim)
+        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
+        check(_lib.load().rpo_cartsafe_policy_act(
+            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
+            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
+            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, int(form), _stream()),
+            "rpo_cartsafe_policy_act")
 
     def ddpg_critic_forward(self, actor_target, critic_target, critic, scale, base, rows, cap_steps, n_envs, batch_out,
                             idx_out, idx_in, seed, salt, ctrl, max_steps, corr_lr, corr_eps, corr_momentum, box_lo, box_hi,
@@ -597,6 +621,18 @@ class PendulumKernels(object):
         else:
             tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
             check(_lib.load().rpo_pendulum_evaluate_record(*args, *tr, _stream()), "rpo_pendulum_evaluate_record")
+
+    def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
+                   max_steps, corr_lr, corr_eps, corr_momentum, form=0):
+        """obs [n, 5] (row view) -> action [n, 2] and, where not None, proposal [n], iters int32 [n], eq_resid [n, 1],
+        ineq_resid [n, 1], in one launch (rpo_pendulum_policy_act); form: 0 by size, 1 row tile, 2 / 3 streaming (G = 1 / 4)."""
+        net = actor_desc.net_struct()
+        op, ostride = _row_view(obs, self.obs_dim)
+        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
+        check(_lib.load().rpo_pendulum_policy_act(
+            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
+            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
+            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, int(form), _stream()), "rpo_pendulum_policy_act")
 
     def ddpg_critic_front(self, actor_target, scale, base, rows, cap_steps, n_envs, batch_out, idx_out, idx_in, sample_seed,
                           sample_salt, ctrl, ap_out):
