@@ -917,6 +917,33 @@ int rpo_pendulum_policy_act(const rpo_mlp* actor_host, int gauss, float scale, f
                             float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                             int form, void* stream);
 
+/* Projection profiles (RPOTrainerBase.act(profile=True)): the same rows with every budget 0..K of the projection written down
+ * in ONE launch, K = max_steps >= 0.  profile [K + 1, n, 4] (16-byte aligned; RPO_ERR_ARG when NULL or misaligned): plane b,
+ * row i = (a0, a1, eq_resid, max_j ineq_resid_j) of the row's iterate after min(b, iters[i]) GRG steps, signed residuals with
+ * the bits of rpo_<env>_resid, one non-temporal 16-byte store per row and plane.  Every plane of every row is written (a row
+ * whose stop test has fired repeats its final iterate): the buffer needs no zeroing.  The other outputs are those of the call
+ * without the profile, for the budget K.  Row-tile form only (16 rows per workgroup, 64 from 12 288 rows).
+ * == for b = 0..K: rpo_<env>_policy_act(max_steps = b, form 1), plane b = (action, eq_resid, max_j ineq_resid), bit for bit. */
+int rpo_cartsafe_policy_act_profile(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
+                                    int obs_stride, float* action, float* proposal, int* iters, float* eq_resid,
+                                    float* ineq_resid, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                    float corr_momentum, const float* consts_host, int partial, float* profile, void* stream);
+int rpo_pendulum_policy_act_profile(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
+                                    int obs_stride, float* action, float* proposal, int* iters, float* eq_resid,
+                                    float* ineq_resid, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                    float corr_momentum, float* profile, void* stream);
+/* The projection alone, behind the caller's proposal launches: rpo_<env>_act_project under RPO_NOISE_NONE (its arguments
+ * without the noise, the box, the generator, ctrl and stats) with the profile of the budgets 0..K, K = max_steps >= 0; one
+ * thread per row.  action [n, 2] (8-byte aligned), iters [n] (may be NULL), profile as above.
+ * == for b = 0..K: rpo_<env>_act_project(RPO_NOISE_NONE, max_steps = b) + rpo_<env>_resid, plane b = (action, eq_resid,
+ *    max_j ineq_resid), bit for bit. */
+int rpo_cartsafe_project_profile(int n, const float* ap_raw, float* action, int* iters, int max_steps, float corr_lr,
+                                 float corr_eps, float corr_momentum, const float* consts_host, int partial, float* profile,
+                                 void* stream);
+int rpo_pendulum_project_profile(int n, const float* obs, int obs_stride, const float* ap_raw, float* action, int* iters,
+                                 int max_steps, float corr_lr, float corr_eps, float corr_momentum, float* profile,
+                                 void* stream);
+
 /* The stepwise form of the record (any env): row (step, i), i < trace_rows, of trace [trace_steps, trace_rows, W] from the
  * transition rows rpo_<env>_step wrote (reward, done and the violations, reduced as in rpo_eval_accumulate), the
  * observation obs [n, obs_stride] the policy read BEFORE that step (the caller keeps a copy: the step overwrites it), the

@@ -12,17 +12,24 @@ chosen like ``evaluate()``'s:
   backend, schedule ``fused_act=0``): the trainer's deterministic proposal, ``act_project(NOISE_NONE, iters)`` and the env's
   residual kernel, launch by launch.
 
-Both paths compute the same bits (``tests/test_act_gpu.py``).  Rows are ALWAYS projected independently with a per-row stop
-test -- the B = 1 semantics of the rollout and of ``eval()``; SpringPendulum's batch-coupled reference projection is never
+``act(obs, profile=True)`` also returns how the projection CONVERGES (``ActResult.profile``, a ``ProjectionProfile``): for
+every budget b = 0..K (K = the call's ``eval_steps``) what ``act(obs, eval_steps=b)`` would return, written down by ONE run at
+the budget K -- the loop is deterministic and every row has its own stop test, so a run at K passes through every smaller
+budget's result.  Three paths: **fused** (``rpo_<env>_policy_act_profile``, the row tile), **stepwise** (the proposal launches +
+``rpo_<env>_project_profile`` + the residual kernel) and **sweep** (EVOPF-v0, the oracle backend: K + 1 stepwise ``act()`` calls
+assembled with torch ops; correct by construction and slow).
+
+All paths compute the same bits (``tests/test_act_gpu.py``, ``tests/test_act_profile_gpu.py``).  Rows are ALWAYS projected
+independently with a per-row stop test -- the B = 1 semantics of the rollout and of ``eval()``; SpringPendulum's batch-coupled reference projection is never
 used here, whatever ``batch_reference`` is: ``act(obs)[i]`` is ``act(obs[i:i+1])``.  The call reads the actor's parameters
 and writes its result buffers, nothing else: no env lane, control word, replay row, Philox counter or graph is touched, nothing
 is drawn from a generator, and nothing waits for the device.  Data-parallel runs: the calling rank acts alone, no collective.
 """
-import math
-
+import numpy as np
 import torch
 
 from .. import ops as hip_ops
+from .evaluation import check_budget
 
 _FORMS = {0: None, 1: "tile", 2: "stream", 3: "stream"}
 
@@ -35,13 +42,14 @@ class ActResult(object):
     RPODDPG with the fused MLPs: the raw actor output; the Lagrangian baselines have no projection: the proposal IS the action,
     the same tensor); ``iters`` [n]: GRG iterations of the row (0 for the baselines); ``eq_resid`` [n, eq_num] /
     ``ineq_resid`` [n, ineq_num]: the signed residuals at ``action`` (ineq > 0 is a violation; None with ``residuals=False``).
-    ``path``: "fused" | "stepwise"; ``form``: "tile" | "stream" on the fused path, else None."""
+    ``path``: "fused" | "stepwise" ("sweep": a profiled call assembled from K + 1 stepwise calls); ``form``: "tile" | "stream" on
+    the fused path, else None.  ``profile``: the ``ProjectionProfile`` of a call with ``profile=True``, else None."""
 
     FIELDS = ("action", "proposal", "iters", "eq_resid", "ineq_resid")
 
     def __init__(self, action, proposal, iters, eq_resid=None, ineq_resid=None, path=None, form=None):
         self.action, self.proposal, self.iters, self.eq_resid, self.ineq_resid = action, proposal, iters, eq_resid, ineq_resid
-        self.path, self.form = path, form
+        self.path, self.form, self.profile = path, form, None
 
     @classmethod
     def empty(cls, tr, n, residuals):
@@ -76,6 +84,76 @@ class ActResult(object):
         return "ActResult(n=%d, path=%s, form=%s, residuals=%s)" % (self.n, self.path, self.form, self.residuals)
 
 
+class ProjectionProfile(object):
+    """The projection at every budget 0..K of one ``act(obs, profile=True)`` call.
+
+    ``data``: float32 [K + 1, n, 4] on the trainer's device; plane b, row i = (a0, a1, eq_resid, max_j ineq_resid_j) of what
+    ``act(obs, eval_steps=b)`` returns for that row (signed residuals; EVOPF-v0: the first two action components).  ``iters``:
+    int32 [n], the GRG iterations at the budget K.  Plane 0 is Complete alone and plane 1 is always one step further (the
+    loop's first iteration is unconditional), even for a row that was already feasible.  The helpers are plain torch ops on
+    ``data``; none of them is on ``act()``'s path."""
+
+    def __init__(self, data, iters):
+        self.data, self.iters = data, iters
+
+    @property
+    def K(self):
+        return self.data.shape[0] - 1
+
+    @property
+    def n(self):
+        return self.data.shape[1]
+
+    def _plane(self, b):
+        if isinstance(b, bool) or int(b) != b or not 0 <= b <= self.K:
+            raise ValueError("ProjectionProfile: the budget must be an integer in [0, %d], got %r" % (self.K, b))
+        return self.data[int(b)]
+
+    def action(self, b):
+        """[n, 2]: the action at budget b (a view)."""
+        return self._plane(b)[:, 0:2]
+
+    def eq(self, b):
+        """[n]: the signed equality residual at budget b (a view)."""
+        return self._plane(b)[:, 2]
+
+    def ineq(self, b):
+        """[n]: the largest signed inequality residual at budget b (a view; > 0: violated)."""
+        return self._plane(b)[:, 3]
+
+    def iters_at(self, b):
+        """int32 [n]: the GRG iterations of ``act(obs, eval_steps=b)``: min(b, iters)."""
+        self._plane(b)
+        return torch.clamp(self.iters, max=int(b))
+
+    def max_violation(self):
+        """[K + 1, n]: max(|eq|, relu(ineq)) per budget and row."""
+        return torch.maximum(self.data[:, :, 2].abs(), torch.relu(self.data[:, :, 3]))
+
+    def violation_rate(self, thresh):
+        """[K + 1]: the share of rows whose ``max_violation`` is above ``thresh``, per budget."""
+        return (self.max_violation() > float(thresh)).to(torch.float32).mean(dim=1)
+
+    def budget(self, tol, share=1.0):
+        """The smallest budget b at which at least ``share`` of the rows are within ``tol`` (``max_violation <= tol``), or None
+        when no budget up to K reaches it (waits for the device)."""
+        within = (self.max_violation() <= float(tol)).sum(dim=1).cpu().numpy()
+        ok = np.nonzero(within >= float(share) * self.n)[0]
+        return int(ok[0]) if ok.size else None
+
+    def numpy(self):
+        """``data`` as a numpy array (waits for the device)."""
+        return self.data.detach().cpu().numpy()
+
+    def __repr__(self):
+        return "ProjectionProfile(K=%d, n=%d)" % (self.K, self.n)
+
+
+def profile_max_rows(steps):
+    """The largest n whose profile of the budget ``steps`` fits RPO_TRACE_MAX_BYTES."""
+    return hip_ops.TRACE_MAX_BYTES // (16 * (int(steps) + 1))
+
+
 def _projects(tr):
     """The trainer has a projection (RPODDPG / RPOSAC); the Lagrangian baselines step the actor's output as it is."""
     return not hasattr(tr, "_deterministic")
@@ -88,41 +166,88 @@ def fused_ok(tr):
                 and _projects(tr) and tr._box_affine is not None and f.descs["actor"].E == 128 and tr.device.type == "cuda")
 
 
-def _check(tr, obs, eval_steps, eval_lr, residuals, out, form):
+def _check(tr, obs, eval_steps, eval_lr, residuals, out, form, profile=False):
     k = tr.kernels
     obs = torch.as_tensor(obs, dtype=torch.float32, device=tr.device)
     if obs.dim() == 1:
         obs = obs[None, :]
     if obs.dim() != 2 or obs.shape[1] != k.obs_dim or obs.shape[0] == 0:
         raise ValueError("act: obs must be [n, %d] with n >= 1 (or [%d]), got %s" % (k.obs_dim, k.obs_dim, tuple(obs.shape)))
-    if obs.stride(1) != 1 or (obs.shape[0] > 1 and obs.stride(0) < k.obs_dim):
-        obs = obs.contiguous()
-    steps = tr.eval_steps if eval_steps is None else eval_steps
-    try:
-        ok = not isinstance(steps, bool) and int(steps) == steps and steps >= 0
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        raise ValueError("act: eval_steps must be an integer >= 0, got %r" % (eval_steps,))
-    lr = tr.eval_lr if eval_lr is None else eval_lr
-    try:
-        lr = float(lr)
-    except (TypeError, ValueError):
-        lr = float("nan")
-    if not math.isfinite(lr):
-        raise ValueError("act: eval_lr must be a finite number, got %r" % (eval_lr,))
+    steps, lr = check_budget(tr, eval_steps, eval_lr, "act")
     if form not in _FORMS:
         raise ValueError("act: form must be 0 (by size), 1 (row tile), 2 or 3 (streaming, 16- / 64-row groups), got %r" % (form,))
     if out is not None:
         if not isinstance(out, ActResult) or out.n != obs.shape[0] or out.residuals != bool(residuals):
             raise ValueError("act: out must be an ActResult of the same n (%d) and the same residuals (%r), got %r"
                              % (obs.shape[0], bool(residuals), out))
+    if profile:
+        n, steps = obs.shape[0], int(steps)
+        if not _projects(tr):
+            raise ValueError("act: profile=True needs a trainer that projects (RPODDPG / RPOSAC); %s has no projection" % type(tr).__name__)
+        if form != 0:
+            raise ValueError("act: profile=True has the row-tile launch only; form must be 0, got %r" % (form,))
+        if 16 * (steps + 1) * n > hip_ops.TRACE_MAX_BYTES:        # (shape arithmetic: nothing has been allocated)
+            raise ValueError("act: profile=True needs %d bytes (%d planes x %d rows x 16), above the cap of %d bytes; at most n = %d "
+                             "rows fit at eval_steps = %d" % (16 * (steps + 1) * n, steps + 1, n, hip_ops.TRACE_MAX_BYTES,
+                                                             profile_max_rows(steps), steps))
+        have = None if out is None or out.profile is None else out.profile.data
+        if out is not None and (have is None or tuple(have.shape) != (steps + 1, n, 4)):
+            raise ValueError("act: profile=True with out= needs an ActResult whose profile is [%d, %d, 4], got %s"
+                             % (steps + 1, n, None if have is None else tuple(have.shape)))
+    if obs.stride(1) != 1 or (obs.shape[0] > 1 and obs.stride(0) < k.obs_dim):
+        obs = obs.contiguous()                                   # (behind the refusals: they allocate nothing)
     return obs, int(steps), lr
 
 
-def act(tr, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0):
+def _sweep(tr, obs, steps, lr, residuals, r, data):
+    """The profile from K + 1 stepwise calls (EVOPF-v0, backends without the profile kernels): plane b from ``act(eval_steps=b)``;
+    the last call, at the budget K, fills ``r``."""
+    for b in range(steps + 1):
+        last = b == steps
+        x = act(tr, obs, eval_steps=b, eval_lr=lr, residuals=True, out=r if last and residuals else None)
+        data[b, :, 0:2].copy_(x.action[:, 0:2])
+        data[b, :, 2].copy_(x.eq_resid[:, 0] if x.eq_resid.shape[1] == 1 else _signed_absmax(x.eq_resid))
+        data[b, :, 3].copy_(x.ineq_resid.max(dim=1).values)
+        if last and not residuals:
+            for f in ("action", "proposal", "iters"):
+                getattr(r, f).copy_(getattr(x, f))
+    r.path, r.form = "sweep", None
+
+
+def _signed_absmax(x):
+    """[n, m] -> [n]: the entry of largest magnitude of every row, with its sign (EVOPF-v0 has many equalities)."""
+    return x.gather(1, x.abs().argmax(dim=1, keepdim=True))[:, 0]
+
+
+def _act_profile(tr, obs, steps, lr, residuals, out):
+    n, k = obs.shape[0], tr.kernels
+    r = out if out is not None else ActResult.empty(tr, n, residuals)
+    data = out.profile.data if out is not None else torch.empty(steps + 1, n, 4, device=tr.device)
+    with torch.no_grad():
+        if fused_ok(tr) and hasattr(k, "policy_act_profile"):
+            scale, base = tr._box_affine
+            k.policy_act_profile(tr.fused.descs["actor"], tr._gauss_policy, scale, base, obs, r.action, r.proposal, r.iters,
+                                 r.eq_resid, r.ineq_resid, tr._box_lo, tr._box_hi, steps, lr, tr.corr_eps, tr.corr_momentum, data)
+            r.path, r.form = "fused", "tile"
+        elif hasattr(k, "project_profile") and tr.device.type == "cuda":
+            obs = obs.contiguous()
+            ap = tr._eval_partial(obs)
+            r.proposal.copy_(ap.reshape(r.proposal.shape))
+            k.project_profile(obs, ap, r.action, r.iters, steps, lr, tr.corr_eps, tr.corr_momentum, data)
+            if residuals:
+                k.resid(obs, r.action, r.eq_resid, r.ineq_resid)
+            r.path, r.form = "stepwise", None
+        else:
+            _sweep(tr, obs, steps, lr, residuals, r, data)
+    r.profile = ProjectionProfile(data, r.iters)
+    return r
+
+
+def act(tr, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0, profile=False):
     """See ``RPOTrainerBase.act``."""
-    obs, steps, lr = _check(tr, obs, eval_steps, eval_lr, residuals, out, form)
+    obs, steps, lr = _check(tr, obs, eval_steps, eval_lr, residuals, out, form, profile)
+    if profile:
+        return _act_profile(tr, obs, steps, lr, residuals, out)
     n = obs.shape[0]
     fused = fused_ok(tr)
     if form and not fused:
@@ -136,7 +261,7 @@ def act(tr, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0
             k.policy_act(desc, tr._gauss_policy, scale, base, obs, r.action, r.proposal, r.iters, r.eq_resid, r.ineq_resid,
                          tr._box_lo, tr._box_hi, steps, lr, tr.corr_eps, tr.corr_momentum, form=form)
             stream = n >= hip_ops.CONST["RPO_ROLLOUT_STREAM_FROM"] and desc.tensors["W0"].data_ptr() % 16 == 0
-            r.path, r.form = "fused", _FORMS[form] or ("stream" if stream else "tile")
+            r.path, r.form, r.profile = "fused", _FORMS[form] or ("stream" if stream else "tile"), None
             return r
         obs = obs.contiguous()
         if _projects(tr):
@@ -150,5 +275,5 @@ def act(tr, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0
             r.iters.zero_()
         if residuals:
             k.resid(obs, r.action, r.eq_resid, r.ineq_resid)
-    r.path, r.form = "stepwise", None
+    r.path, r.form, r.profile = "stepwise", None, None
     return r

@@ -63,7 +63,7 @@ class _LagrangianBase(RPOTrainerBase):
                 pen = max_eq + rows[:, c["ineq_viol"][0]:c["ineq_viol"][1]].max(dim=1).values
                 rows[:, c["reward"][0]] -= 10.0 * pen
 
-    def _eval_action(self, v, iters=None):                  # (no projection: `iters` stays as it is)
+    def _eval_action(self, v, iters=None, eval_steps=None, eval_lr=None):    # (no projection: `iters` stays as it is)
         v.action.copy_(self._deterministic(v.obs))
         return v.action                                       # ... and the proposal is the action
 

@@ -24,6 +24,8 @@ Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues su
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
 does not record trajectories.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -239,9 +241,30 @@ def check_record(record, episodes):
     return int(record)
 
 
-def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False):
+def check_budget(tr, eval_steps, eval_lr, what="evaluate"):
+    """The per-call projection overrides of ``evaluate()`` / ``act()`` -> (eval_steps, eval_lr) with None replaced by the
+    trainer's: ``eval_steps`` an integer >= 0, ``eval_lr`` a finite number (ValueError otherwise)."""
+    steps = tr.eval_steps if eval_steps is None else eval_steps
+    try:
+        ok = not isinstance(steps, bool) and int(steps) == steps and steps >= 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s: eval_steps must be an integer >= 0, got %r" % (what, eval_steps))
+    lr = tr.eval_lr if eval_lr is None else eval_lr
+    try:
+        lr = float(lr)
+    except (TypeError, ValueError):
+        lr = float("nan")
+    if not math.isfinite(lr):
+        raise ValueError("%s: eval_lr must be a finite number, got %r" % (what, eval_lr))
+    return int(steps), lr
+
+
+def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None):
     """See ``RPOTrainerBase.evaluate``."""
     n = check_episodes(episodes)
+    budget = (None, None) if eval_steps is None and eval_lr is None else check_budget(tr, eval_steps, eval_lr)
     R = check_record(record, n)
     if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
         raise ValueError("evaluate: horizon must be an integer >= 1, got %r" % (horizon,))
@@ -279,22 +302,24 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     with torch.no_grad():
         if fused:
             path = "fused"
-            _run_fused(tr, v, acc, H, trace=trace)
+            _run_fused(tr, v, acc, H, trace=trace, budget=budget)
         else:
             path = "stepwise"
-            _run_stepwise(tr, v, acc, H, trace=trace)
+            _run_stepwise(tr, v, acc, H, trace=trace, budget=budget)
     res = EvalResult(acc.cpu().numpy(), path, H, seed)
     if R:
         res.trajectory = EvalTrajectory.from_trace(trace.cpu().numpy(), dims, res.length[:R], v.viol_thresh)
     return res
 
 
-def _run_fused(tr, v, acc, H, desc=None, trace=None):
+def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None)):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
     trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
-    (rpo_<env>_evaluate_record)."""
+    (rpo_<env>_evaluate_record).  ``budget``: evaluate()'s per-call (eval_steps, eval_lr), None: the trainer's."""
     n = v.n
+    eval_steps = tr.eval_steps if budget[0] is None else budget[0]
+    eval_lr = tr.eval_lr if budget[1] is None else budget[1]
     steps = max(1, min(H, hip_ops.EVAL_LANE_STEPS // n))
     scale, base = tr._box_affine
     desc = tr.fused.descs["actor"] if desc is None else desc
@@ -302,10 +327,10 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None):
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
                             v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo, tr._box_hi,
-                            tr.eval_steps, tr.eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps, v.viol_thresh, **kw)
+                            eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps, v.viol_thresh, **kw)
 
 
-def _run_stepwise(tr, v, acc, H, trace=None):
+def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None)):
     """eval()'s loop: the trainer's deterministic action + projection, one env step without auto-reset, the accumulator
     update.  Finished lanes keep stepping (as in eval()); their rows no longer change.  ``trace``: the zeroed record
     [H, R, W]; the step's row goes in before the accumulator update (which ends the lanes the step finished), from a copy
@@ -319,7 +344,8 @@ def _run_stepwise(tr, v, acc, H, trace=None):
     for i in range(H):
         if trace is not None:
             obs_in.copy_(v.obs)
-        proposal = tr._eval_action(v, iters=iters)
+        proposal = tr._eval_action(v, iters=iters) if budget == (None, None) else \
+            tr._eval_action(v, iters=iters, eval_steps=budget[0], eval_lr=budget[1])
         v.step(v.action, rows=rows, cap_steps=1, auto_reset=False)
         if trace is not None:
             record(rows, k.cols, obs_in, proposal, v.action, iters, i, acc, trace)

@@ -1369,13 +1369,15 @@ class RPOTrainerBase(object):
     def _eval_partial(self, obs):
         raise NotImplementedError
 
-    def _eval_action(self, v, iters=None):
+    def _eval_action(self, v, iters=None, eval_steps=None, eval_lr=None):
         """Deterministic policy + eval_steps projection iterations into v.action (rpo_ddpg.py:224-226); ``iters`` (int32 [n],
         optional): the projection's iteration count per lane.  Returns the proposal: the partial action [n * partial_dim]
-        handed to the projection (``evaluate(record=...)`` records it)."""
+        handed to the projection (``evaluate(record=...)`` records it).  ``eval_steps`` / ``eval_lr``: ``evaluate()``'s
+        per-call overrides (None: the trainer's)."""
         ap = self._eval_partial(v.obs)
         self.kernels.act_project(v.obs, ap, None, v.action, iters, hip_ops.NOISE_NONE, 0.0, 0.0, 0.0, self._box_lo,
-                                 self._box_hi, self.eval_steps, self.eval_lr, self.corr_eps, self.corr_momentum,
+                                 self._box_hi, self.eval_steps if eval_steps is None else eval_steps,
+                                 self.eval_lr if eval_lr is None else eval_lr, self.corr_eps, self.corr_momentum,
                                  **self._act_kw)
         return ap
 
@@ -1425,7 +1427,7 @@ class RPOTrainerBase(object):
             out += [x.mean(), x.std()]
         return tuple(out)
 
-    def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None, record=False):
+    def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None):
         """Evaluate the current policy on ``episodes`` independent episodes -> ``EvalResult`` (per-episode arrays; ``summary()``
         is eval()'s 10-tuple).  The policy, projection and horizon are eval()'s: deterministic actor (RPOSAC: the mean head),
         ``eval_steps`` / ``eval_lr`` / ``corr_eps`` / ``corr_momentum``, at most min(500, max_episode_steps, the env's
@@ -1436,11 +1438,15 @@ class RPOTrainerBase(object):
         ``record``: True records every step of every episode, an integer k (1 <= k <= episodes) those of episodes 0..k-1, into
         ``result.trajectory`` (``EvalTrajectory``: observation, proposal, projected action, reward, done, violations and GRG
         iterations per step); False / 0: no record, ``result.trajectory`` is None.  The per-episode arrays are the same bits
-        with and without it.  Curve mode (``eval_episodes=N``) does not record.  See rpo_amd/algo/evaluation.py."""
+        with and without it.  Curve mode (``eval_episodes=N``) does not record.  ``eval_steps=`` / ``eval_lr=`` override the
+        projection's budget and step size for this call only, validated like ``act()``'s (a budget read off a
+        ``ProjectionProfile`` can be confirmed on whole episodes); the trainer's attributes stay as they are, and curve mode
+        and eval() never see an override.  See rpo_amd/algo/evaluation.py."""
         from .evaluation import evaluate
-        return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record)
+        return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record,
+                        eval_steps=eval_steps, eval_lr=eval_lr)
 
-    def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0):
+    def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0, profile=False):
         """The policy's projected actions for caller-supplied observations -> ``ActResult`` (torch tensors on the trainer's
         device, nothing waits for the device): ``action`` [n, action_dim], the completed + projected action ``eval()`` would
         step in that state; ``proposal`` [n, P], what the policy handed to the projection; ``iters`` int32 [n], GRG iterations
@@ -1459,9 +1465,14 @@ class RPOTrainerBase(object):
         action wherever it reaches them (the fused MLP kernels' ReLU, the hardware maximum, drops a NaN behind the first layer).  No trainer state changes (networks, env lanes, ctrl, replay,
         Philox counters, graphs) and nothing is drawn from a generator.  Data-parallel runs: the calling rank acts alone, no
         collective.  ValueError: wrong width, n = 0, a non-finite ``eval_lr``, ``eval_steps`` not an integer >= 0, ``out`` of
-        another n or ``residuals``, a ``form`` on a stepwise configuration.  See rpo_amd/algo/acting.py."""
+        another n or ``residuals``, a ``form`` on a stepwise configuration.
+        ``profile=True``: the result also carries ``profile``, a ``ProjectionProfile`` whose ``data`` [K + 1, n, 4] (K = the
+        call's ``eval_steps``) holds for every budget b = 0..K the row's (a0, a1, eq_resid, max ineq_resid) -- what
+        ``act(obs, eval_steps=b)`` returns -- written by one launch; ``path`` is "fused", "stepwise" or "sweep" (EVOPF-v0:
+        K + 1 stepwise calls).  ``out=`` then needs a result whose profile has the same shape.  ValueError: a trainer without
+        a projection, ``form != 0``, a profile above RPO_TRACE_MAX_BYTES.  See rpo_amd/algo/acting.py."""
         from .acting import act
-        return act(self, obs, eval_steps=eval_steps, eval_lr=eval_lr, residuals=residuals, out=out, form=form)
+        return act(self, obs, eval_steps=eval_steps, eval_lr=eval_lr, residuals=residuals, out=out, form=form, profile=profile)
 
     def _print_eval(self, t, res, multipliers=True):
         if self.dist.rank != 0 or not _env_int("RPO_VERBOSE", 1):

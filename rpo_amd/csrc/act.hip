@@ -6,6 +6,9 @@
 //                        residuals -> stores; 16 rows per workgroup, 64 once that still fills the chip.
 //   (act_stream.hip)     the STREAMING form from RPO_ROLLOUT_STREAM_FROM rows: rollout_stream_kernel's structure.
 //
+//   project_profile_kernel  the stand-alone projection of trainer.act(profile=True)'s stepwise path; policy_act_kernel's
+//                        PROFILE = 1 instances are its fused path.
+//
 // Nothing is carried between rows, no env state, control word or generator is touched.  The per-row chain is act_dev.h's.
 #include "act_dev.h"
 
@@ -17,8 +20,11 @@ Mlp act_to_dev(const rpo_mlp* h) {
     return Mlp{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H, h->n_out, h->cat, h->head_dim};
 }
 
-template <class ENV, int RT>
-__global__ __launch_bounds__(kFwdThreads) void policy_act_kernel(PolicyActArgs<ENV> p, typename ENV::Consts c) {
+// PROFILE = 1: the row's projection also writes its entries of the profile planes (act_dev.h: act_project_profile); the
+// PROFILE = 0 instances take no profile argument and are the kernel as it was.  The profile is touched behind the forward only.
+template <class ENV, int RT, int PROFILE>
+__global__ __launch_bounds__(kFwdThreads) void policy_act_kernel(PolicyActArgs<ENV> p, typename ENV::Consts c,
+                                                                 typename std::conditional<PROFILE != 0, ActProfile, ActNoProfile>::type prof) {
     typedef TileLds<128, RT, 8, 8> Lds;                          // 16 * RT rows per workgroup; OBS <= 8
     __shared__ Lds lds;
     constexpr int kInS = Lds::kS, kRowsWg = kRows * RT, OBS = ENV::OBS;
@@ -30,8 +36,41 @@ __global__ __launch_bounds__(kFwdThreads) void policy_act_kernel(PolicyActArgs<E
     }
     mlp_tile_forward<128, 256, RT, Lds>(p.actor, lds, row0, p.n, nullptr, nullptr, p.gauss ? 0 : 1, p.scale, p.base);
     const int i = row0 + tid;
-    if (tid < kRowsWg && i < p.n)                                // (nothing per-row was alive across the MFMA loops)
-        policy_act_row<ENV>(p, c, lds.in_s + tid * kInS, i, lds.out[tid * 2], lds.out[tid * 2 + 1]);
+    if (tid < kRowsWg && i < p.n) {                              // (nothing per-row was alive across the MFMA loops)
+        if constexpr (PROFILE != 0) policy_act_row_profile<ENV>(p, c, lds.in_s + tid * kInS, i, lds.out[tid * 2], lds.out[tid * 2 + 1], prof);
+        else policy_act_row<ENV>(p, c, lds.in_s + tid * kInS, i, lds.out[tid * 2], lds.out[tid * 2 + 1]);
+    }
+}
+
+// The stand-alone profiled projection (the stepwise path's launch behind the proposal launches): one thread per row, as
+// *_act_project under RPO_NOISE_NONE; obs: SpringPendulum's rows (CartSafe's projection does not read the state).
+template <class ENV>
+__global__ __launch_bounds__(RPO_BLOCK) void project_profile_kernel(typename ENV::ActArgs p, typename ENV::Consts c, const float* obs,
+                                                                    int obs_stride, ActProfile q) {
+    for (int i = blockIdx.x * RPO_BLOCK + threadIdx.x; i < p.n; i += gridDim.x * RPO_BLOCK) {
+        int k;
+        const float2 a = act_project_profile<ENV>(p, c, obs ? obs + (size_t)i * obs_stride : nullptr, i, p.n, p.ap_raw[i], q, k);
+        act_store2(p.action + (size_t)i * 2, a.x, a.y);
+        if (p.iters) act_store(p.iters + i, k);
+    }
+}
+
+int check_profile(const float* profile, int K) {                 // [K + 1, n, 4]: written with 16-byte stores
+    if (!profile || K < 0 || reinterpret_cast<uintptr_t>(profile) % 16) return RPO_ERR_ARG;
+    return 0;
+}
+
+template <class ENV>
+int launch_project_profile(const typename ENV::ActArgs& a, const typename ENV::Consts& c, const float* obs, int obs_stride,
+                           float* profile, void* stream) {
+    if (a.n <= 0) return RPO_ERR_ARG;
+    if (!a.ap_raw || !a.action) return RPO_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(a.action) % 8) return RPO_ERR_ARG;
+    if (int e = check_profile(profile, a.max_steps)) return e;
+    hipLaunchKernelGGL((project_profile_kernel<ENV>), dim3(rpo_grid_for(a.n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a, c, obs,
+                       obs_stride, ActProfile{profile, a.max_steps});
+    RPO_LAUNCH_CHECK();
+    return 0;
 }
 
 int check_act_actor(const Mlp& actor, int obs_dim, int gauss) {  // (check_eval_actor's conditions; E below)
@@ -55,9 +94,24 @@ int launch_act(const PolicyActArgs<ENV>& args, const typename ENV::Consts& c, in
         return e < 0 ? RPO_ERR_ARG : e;
     }
     if (n >= 64 * 192) {                                         // launch_eval's tile rule
-        hipLaunchKernelGGL((policy_act_kernel<ENV, 4>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((policy_act_kernel<ENV, 4, 0>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, ActNoProfile{});
     } else {
-        hipLaunchKernelGGL((policy_act_kernel<ENV, 1>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((policy_act_kernel<ENV, 1, 0>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, ActNoProfile{});
+    }
+    RPO_LAUNCH_CHECK();
+    return 0;
+}
+
+// the PROFILE = 1 instances: always the row tile (a profile instance of the streaming form does not exist)
+template <class ENV>
+int launch_act_profile(const PolicyActArgs<ENV>& args, const typename ENV::Consts& c, float* profile, void* stream) {
+    const int n = args.n;
+    if (int e = check_profile(profile, args.act.max_steps)) return e;
+    const ActProfile q{profile, args.act.max_steps};
+    if (n >= 64 * 192) {
+        hipLaunchKernelGGL((policy_act_kernel<ENV, 4, 1>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, q);
+    } else {
+        hipLaunchKernelGGL((policy_act_kernel<ENV, 1, 1>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, q);
     }
     RPO_LAUNCH_CHECK();
     return 0;
@@ -109,6 +163,54 @@ int rpo_pendulum_policy_act(const rpo_mlp* actor_host, int gauss, float scale, f
                                      box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
     const PendEnv::Consts c{0};
     return launch_act<PendEnv>(args, c, 1, form, stream);
+}
+
+int rpo_cartsafe_policy_act_profile(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
+                                    int obs_stride, float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid,
+                                    float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                                    const float* consts_host, int partial, float* profile, void* stream) {
+    PolicyActArgs<CartEnv> args{};
+    if (int e = fill_act_args<CartEnv>(args, actor_host, gauss, scale, base, n, obs, obs_stride, action, proposal, iters, eq_resid,
+                                       ineq_resid, max_steps))
+        return e;
+    rpo_cart_dev::CartConsts c;
+    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
+    args.act = rpo_cart_dev::ActArgs{n, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, box_lo, box_hi,
+                                     max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    return launch_act_profile<CartEnv>(args, c, profile, stream);
+}
+
+int rpo_pendulum_policy_act_profile(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
+                                    int obs_stride, float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid,
+                                    float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                                    float* profile, void* stream) {
+    PolicyActArgs<PendEnv> args{};
+    if (int e = fill_act_args<PendEnv>(args, actor_host, gauss, scale, base, n, obs, obs_stride, action, proposal, iters, eq_resid,
+                                       ineq_resid, max_steps))
+        return e;
+    args.act = rpo_pend_dev::ActArgs{n, nullptr, 5, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
+                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    const PendEnv::Consts c{0};
+    return launch_act_profile<PendEnv>(args, c, profile, stream);
+}
+
+int rpo_cartsafe_project_profile(int n, const float* ap_raw, float* action, int* iters, int max_steps, float corr_lr, float corr_eps,
+                                 float corr_momentum, const float* consts_host, int partial, float* profile, void* stream) {
+    rpo_cart_dev::CartConsts c;
+    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
+    const rpo_cart_dev::ActArgs a{n, ap_raw, nullptr, action, iters, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
+                                  max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    return launch_project_profile<CartEnv>(a, c, nullptr, 0, profile, stream);
+}
+
+int rpo_pendulum_project_profile(int n, const float* obs, int obs_stride, const float* ap_raw, float* action, int* iters,
+                                 int max_steps, float corr_lr, float corr_eps, float corr_momentum, float* profile, void* stream) {
+    if (n > 0 && !obs) return RPO_ERR_NULL;
+    if (obs_stride < 5) return RPO_ERR_ARG;
+    const rpo_pend_dev::ActArgs a{n, obs, obs_stride, ap_raw, nullptr, action, iters, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
+                                  max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    const PendEnv::Consts c{0};
+    return launch_project_profile<PendEnv>(a, c, obs, obs_stride, profile, stream);
 }
 
 }  // extern "C"

@@ -318,6 +318,14 @@ def _act_outputs(kernels, n, action, proposal, iters, eq_resid, ineq_resid):
         raise RpoHipError("policy_act: needs n >= 1 rows and an action buffer")
 
 
+def _act_profile(profile, n, steps):
+    """Pointer of the profile buffer of ``policy_act_profile`` / ``project_profile``: float32 [steps + 1, n, 4], contiguous (the
+    kernels index it by plane and row: a smaller buffer would be written out of bounds)."""
+    if profile is None or tuple(profile.shape) != (int(steps) + 1, n, 4):
+        raise RpoHipError("profile must be [%d, %d, 4], got %s" % (int(steps) + 1, n, None if profile is None else tuple(profile.shape)))
+    return _p(profile)
+
+
 # =================================================================================================== env kernel sets
 
 class CartSafeKernels(object):
@@ -405,6 +413,26 @@ class CartSafeKernels(object):
             _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
             box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, int(form), _stream()),
             "rpo_cartsafe_policy_act")
+
+    def policy_act_profile(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo,
+                           box_hi, max_steps, corr_lr, corr_eps, corr_momentum, profile):
+        """``policy_act`` (row tile) that also writes profile [max_steps + 1, n, 4]: plane b = (a0, a1, eq_resid, max ineq_resid)
+        of the budget b (rpo_cartsafe_policy_act_profile)."""
+        net = actor_desc.net_struct()
+        op, ostride = _row_view(obs, self.obs_dim)
+        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
+        check(_lib.load().rpo_cartsafe_policy_act_profile(
+            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
+            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
+            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
+            _act_profile(profile, obs.shape[0], max_steps), _stream()), "rpo_cartsafe_policy_act_profile")
+
+    def project_profile(self, obs, ap_raw, action, iters, max_steps, corr_lr, corr_eps, corr_momentum, profile):
+        """``act_project(NOISE_NONE)`` that also writes profile [max_steps + 1, n, 4] (rpo_cartsafe_project_profile)."""
+        n = action.shape[0]
+        check(_lib.load().rpo_cartsafe_project_profile(
+            n, _p(ap_raw), _p(action), _p(iters, torch.int32, allow_none=True), int(max_steps), corr_lr, corr_eps, corr_momentum,
+            self._cptr, self.partial, _act_profile(profile, n, max_steps), _stream()), "rpo_cartsafe_project_profile")
 
     def ddpg_critic_forward(self, actor_target, critic_target, critic, scale, base, rows, cap_steps, n_envs, batch_out,
                             idx_out, idx_in, seed, salt, ctrl, max_steps, corr_lr, corr_eps, corr_momentum, box_lo, box_hi,
@@ -633,6 +661,27 @@ class PendulumKernels(object):
             ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
             _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
             box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, int(form), _stream()), "rpo_pendulum_policy_act")
+
+    def policy_act_profile(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo,
+                           box_hi, max_steps, corr_lr, corr_eps, corr_momentum, profile):
+        """``policy_act`` (row tile) that also writes profile [max_steps + 1, n, 4]: plane b = (a0, a1, eq_resid, ineq_resid) of
+        the budget b (rpo_pendulum_policy_act_profile)."""
+        net = actor_desc.net_struct()
+        op, ostride = _row_view(obs, self.obs_dim)
+        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
+        check(_lib.load().rpo_pendulum_policy_act_profile(
+            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
+            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
+            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, _act_profile(profile, obs.shape[0], max_steps), _stream()),
+            "rpo_pendulum_policy_act_profile")
+
+    def project_profile(self, obs, ap_raw, action, iters, max_steps, corr_lr, corr_eps, corr_momentum, profile):
+        """``act_project(NOISE_NONE)`` that also writes profile [max_steps + 1, n, 4] (rpo_pendulum_project_profile)."""
+        n = action.shape[0]
+        op, ostride = _row_view(obs, 5)
+        check(_lib.load().rpo_pendulum_project_profile(
+            n, op, ostride, _p(ap_raw), _p(action), _p(iters, torch.int32, allow_none=True), int(max_steps), corr_lr, corr_eps,
+            corr_momentum, _act_profile(profile, n, max_steps), _stream()), "rpo_pendulum_project_profile")
 
     def ddpg_critic_front(self, actor_target, scale, base, rows, cap_steps, n_envs, batch_out, idx_out, idx_in, sample_seed,
                           sample_salt, ctrl, ap_out):
