@@ -170,6 +170,17 @@ extern "C" {
 #define RPO_TRACE_EQ 3           /* max |equality residual|, likewise */
 #define RPO_TRACE_MAX_BYTES 1073741824  /* the host refuses a larger trace buffer */
 
+/* Per-constraint report of a policy evaluation (rpo_<env>_evaluate_constraints, rpo_eval_constraints): float[n, W], one row
+ * per episode, W = (2 * ineq_num + eq_num) rounded up to RPO_CON_ALIGN:
+ *   ineq_max[ineq_num] | ineq_steps[ineq_num] | eq_max[eq_num] | zeros
+ * ineq_max[j]: maximum over the episode's live steps of ineq_viol[j] of the step's transition row (clamped at 0 there),
+ * NaN-propagating and started at 0 like RPO_EVAL_MAX_INEQ; ineq_steps[j]: the live steps with ineq_viol[j] > viol_thresh (a
+ * count kept as a float: exact below 2^24, the bound on the step index); eq_max[j]: the maximum of |eq_viol[j]|.  A step is
+ * live for the report exactly when it is for the accumulator row (step 0, and afterwards while RPO_EVAL_ALIVE is set BEFORE
+ * the step's accumulator update).  Step 0 writes the whole row, padding included: nothing needs clearing.  CartSafe-v0: W = 16
+ * (6 + 6 + 1); SpringPendulum-v0: W = 4; EVOPF-v0: W = 144 (58 + 58 + 28). */
+#define RPO_CON_ALIGN 4          /* floats: W is a multiple of it, the buffer is 16-byte aligned */
+
 /* One row of an evaluation curve (rpo_eval_summarize): double[RPO_CURVE_LEN], the accumulator rows of one evaluation
  * reduced over its episodes.  Means and population standard deviations (numpy's x.mean(), x.std()) of the float32
  * accumulators widened to float64, in eval()'s order. */
@@ -897,6 +908,25 @@ int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float sca
                                  float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
                                  int trace_rows, int trace_steps, void* stream);
 
+/* The same launches with the per-constraint report con [n_envs, W] (layout RPO_CON_*; W = 16 | 4; 16-byte aligned, RPO_ERR_NULL
+ * / RPO_ERR_ARG otherwise): after the env step a live lane folds the step's ineq_viol / eq_viol -- the values of the
+ * transition row rpo_<env>_step writes, bit for bit -- into its row with 16-byte loads and stores; launches with t0 > 0
+ * continue the rows.  trace == NULL: no per-step record (trace_rows, trace_steps unused); otherwise the arguments and the
+ * record of rpo_<env>_evaluate_record.  Accumulators, env state, actions and trace are those of the calls without con.
+ * == per step: ... + rpo_eval_constraints in front of rpo_eval_accumulate, bit for bit. */
+int rpo_cartsafe_evaluate_constraints(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                      float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                      float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                      float corr_eps, float corr_momentum, const float* consts_host, int partial,
+                                      int max_episode_steps, float viol_thresh, float* trace, int trace_rows, int trace_steps,
+                                      float* con, void* stream);
+int rpo_pendulum_evaluate_constraints(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs,
+                                      float* internal, float* obs, float* action, int* ep_len, float* ep_ret,
+                                      unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
+                                      float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                                      int max_episode_steps, float viol_thresh, float* trace, int trace_rows, int trace_steps,
+                                      float* con, void* stream);
+
 /* Projected actions for caller-supplied observations (RPOTrainerBase.act, rpo_amd/algo/acting.py): n rows obs [n, obs_stride]
  * (obs_stride >= 6 | 5 floats) -> action [n, 2] (8-byte aligned), and where the pointer is not NULL: proposal [n] (what the
  * policy handed to the projection), iters [n] (GRG iterations of the row), eq_resid [n] and ineq_resid [n, 6 | 1] (signed,
@@ -954,6 +984,14 @@ int rpo_eval_record(int n, const float* rows, int row_stride, int reward_col, in
                     int ineq_col, int ineq_num, const float* obs, int obs_stride, int obs_dim, const float* proposal,
                     int partial_dim, const float* action, int action_dim, const int* iters, int step, const float* acc,
                     float* trace, int trace_rows, int trace_steps, void* stream);
+
+/* The stepwise form of the per-constraint report (any env): step `step` of n episodes from the transition rows
+ * rpo_<env>_step wrote into con [n, W] (layout RPO_CON_*, W from ineq_num and eq_num).  One thread per (episode, cell) -- a
+ * wave reads neighbouring columns of a row and stores neighbouring cells; every cell has one owner, nothing is reduced across
+ * threads.  Liveness is read from acc [n, RPO_EVAL_LEN], so the call goes BEFORE rpo_eval_accumulate of the same step; at step
+ * 0 every lane is live and every cell is written. */
+int rpo_eval_constraints(int n, const float* rows, int row_stride, int eq_col, int eq_num, int ineq_col, int ineq_num, int step,
+                         float viol_thresh, const float* acc, float* con, void* stream);
 
 /* The stepwise form of the same statistics (any env): step `step` of n episodes from the transition rows rpo_<env>_step
  * wrote (rows [n, row_stride], the column layout of the env's replay rows: reward, done, eq_viol [eq_num], ineq_viol

@@ -20,9 +20,15 @@ Per-step record (``evaluate(record=True | k)``): both paths write one row per li
 [horizon, k, W] (``RPO_TRACE_*``; the fused kernel's REC instances, ``rpo_eval_record`` or ``record_torch`` on the stepwise
 path), returned as ``EvalResult.trajectory`` (``EvalTrajectory``).  The per-episode arrays do not depend on it.
 
+Per-constraint report (``evaluate(constraints=True)``): both paths keep one row per episode on the device (``RPO_CON_*``: the
+maximum of every inequality's violation and of every |equality residual| over the episode's live steps, and the number of
+live steps on which each inequality exceeds ``viol_thresh``), folded from the values of the step's transition row -- by the
+fused kernel's CON instances, ``rpo_eval_constraints`` or ``constraints_torch`` on the stepwise path -- and returned as
+``EvalResult.constraints`` (``ConstraintReport``).  Every other result is the same bits with and without it.
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
-does not record trajectories.
+does not record trajectories and produces no per-constraint reports.
 """
 import math
 
@@ -43,11 +49,13 @@ class EvalResult(object):
     ``ret``, ``length``; ``mean_ineq`` / ``mean_eq``: running means over the episode's steps of the step's max inequality
     violation / max |equality residual| (eval()'s definitions); ``max_ineq`` / ``max_eq``: their maxima; ``viol_steps``: steps
     whose max inequality violation exceeds the vector env's ``viol_thresh``; ``proj_iters``: GRG iterations summed over the
-    episode; ``nonfinite``: a live step produced a non-finite reward or violation.  ``path``: "fused" or "stepwise"."""
+    episode; ``nonfinite``: a live step produced a non-finite reward or violation.  ``path``: "fused" or "stepwise".
+    ``trajectory`` / ``constraints``: the ``EvalTrajectory`` of ``record=`` / the ``ConstraintReport`` of ``constraints=True``,
+    else None."""
 
     FIELDS = ("ret", "length", "mean_ineq", "mean_eq", "max_ineq", "max_eq", "viol_steps", "proj_iters", "nonfinite")
 
-    def __init__(self, acc, path, horizon, seed, trajectory=None):
+    def __init__(self, acc, path, horizon, seed, trajectory=None, constraints=None):
         acc = np.asarray(acc, dtype=np.float32).reshape(-1, 8)
         word = acc[:, _WORD].view(np.int32)
         self.ret = acc[:, _RET].astype(np.float64)
@@ -61,6 +69,7 @@ class EvalResult(object):
         self.nonfinite = (word & _NONFINITE) != 0
         self.path, self.horizon, self.seed = path, int(horizon), seed
         self.trajectory = trajectory
+        self.constraints = constraints
 
     @property
     def episodes(self):
@@ -145,6 +154,99 @@ class EvalTrajectory(object):
 
     def __repr__(self):
         return "EvalTrajectory(episodes=%d, horizon=%d, steps=%d)" % (self.episodes, self.horizon, int(self.valid.sum()))
+
+
+class ConstraintReport(object):
+    """The per-constraint report of ``evaluate(constraints=True)``: numpy arrays indexed [episode, constraint].
+
+    ``ineq_max`` [n, ineq_num]: the maximum over the episode's live steps of the step's violation of inequality j, as the
+    transition row carries it (clamped at 0; a NaN propagates), the device's float32 bits widened; ``ineq_steps``
+    [n, ineq_num] int64: the live steps on which that value is > ``viol_thresh`` (the threshold and comparison of
+    ``EvalResult.viol_steps``); ``eq_max`` [n, eq_num]: the maximum of |eq_j|.  A step counts exactly when it counts for
+    ``EvalResult.length``; ``length``: those lengths.  ``names`` / ``eq_names``: the env's names of the constraints.
+    ``ineq_max.max(1)`` is ``max_ineq``, ``eq_max.max(1)`` is ``max_eq`` and
+    ``ineq_steps.max(1) <= viol_steps <= ineq_steps.sum(1)`` (while no violation is a NaN)."""
+
+    ARRAYS = ("ineq_max", "ineq_steps", "eq_max", "length")
+
+    def __init__(self, viol_thresh, names, eq_names, **arrays):
+        for name in self.ARRAYS:
+            setattr(self, name, np.asarray(arrays[name]))
+        self.viol_thresh = float(viol_thresh)
+        self.names, self.eq_names = tuple(str(x) for x in names), tuple(str(x) for x in eq_names)
+        if len(self.names) != self.ineq_max.shape[1] or len(self.eq_names) != self.eq_max.shape[1]:
+            raise ValueError("ConstraintReport: %d / %d names for %d inequalities / %d equalities"
+                             % (len(self.names), len(self.eq_names), self.ineq_max.shape[1], self.eq_max.shape[1]))
+
+    @classmethod
+    def from_rows(cls, con, ineq_num, eq_num, length, viol_thresh, names=None, eq_names=None):
+        """con: the device buffer [n, W] as numpy (layout RPO_CON_*)."""
+        con = np.asarray(con, dtype=np.float32).reshape(-1, hip_ops.con_width(ineq_num, eq_num))
+        names = ["ineq[%d]" % j for j in range(ineq_num)] if names is None else names
+        eq_names = ["eq[%d]" % j for j in range(eq_num)] if eq_names is None else eq_names
+        return cls(viol_thresh, names, eq_names, ineq_max=con[:, :ineq_num].astype(np.float64),
+                   ineq_steps=con[:, ineq_num:2 * ineq_num].astype(np.int64),
+                   eq_max=con[:, 2 * ineq_num:2 * ineq_num + eq_num].astype(np.float64), length=np.asarray(length, dtype=np.int64))
+
+    @property
+    def episodes(self):
+        return self.ineq_max.shape[0]
+
+    def rate(self):
+        """Per inequality: the fraction of the evaluated env steps on which it exceeds ``viol_thresh`` [ineq_num]."""
+        return self.ineq_steps.sum(0) / float(self.length.sum())
+
+    def worst(self, k=5):
+        """The k inequalities with the most violating steps over all episodes (ties: the lower index first), as tuples
+        (index, name, steps, max): ``ineq_steps.sum(0)[index]`` and ``ineq_max[:, index].max()``."""
+        steps = self.ineq_steps.sum(0)
+        order = np.argsort(-steps, kind="stable")[:max(0, int(k))]
+        return [(int(j), self.names[j], int(steps[j]), float(self.ineq_max[:, j].max())) for j in order]
+
+    def save(self, path):
+        """One .npz with every array, the names and viol_thresh; ``ConstraintReport.load`` reads it back."""
+        with open(path, "wb") as f:
+            np.savez(f, viol_thresh=np.float64(self.viol_thresh), names=np.array(self.names), eq_names=np.array(self.eq_names),
+                     **{name: getattr(self, name) for name in self.ARRAYS})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(float(z["viol_thresh"]), [str(x) for x in z["names"]], [str(x) for x in z["eq_names"]],
+                       **{name: z[name] for name in cls.ARRAYS})
+
+    def __repr__(self):
+        w = self.worst(1)
+        return "ConstraintReport(episodes=%d, inequalities=%d, equalities=%d, violated=%d, worst=%s)" % (
+            self.episodes, len(self.names), len(self.eq_names), int((self.ineq_steps.sum(0) > 0).sum()),
+            "%s: %d steps" % (w[0][1], w[0][2]) if w and w[0][2] else None)
+
+
+def _nanmax_torch(a, b):
+    """rpo_eval_dev::nanmax: torch.maximum's NaN propagation, and the FIRST operand where they compare equal (signed zeros)."""
+    return torch.where(a != a, a, torch.where(b != b, b, torch.where(b > a, b, a)))
+
+
+def constraints_torch(rows, cols, step, viol_thresh, acc, con):
+    """``rpo_eval_constraints`` in torch ops (backends without the kernel: the CPU oracle): the step's ineq_viol / eq_viol
+    columns into con [n, W] for the lanes that are live BEFORE ``accumulate_torch`` of the same step; step 0 writes every row
+    from scratch."""
+    n = acc.shape[0]
+    rows = rows[:n]
+    ineq = rows[:, cols["ineq_viol"][0]:cols["ineq_viol"][1]]
+    eq = rows[:, cols["eq_viol"][0]:cols["eq_viol"][1]].abs()
+    ni, ne = ineq.shape[1], eq.shape[1]
+    if step == 0:
+        con.zero_()
+    old = con.clone()
+    new = torch.zeros_like(con)
+    new[:, :ni] = _nanmax_torch(old[:, :ni], ineq)
+    new[:, ni:2 * ni] = old[:, ni:2 * ni] + (ineq > viol_thresh).to(con.dtype)
+    new[:, 2 * ni:2 * ni + ne] = _nanmax_torch(old[:, 2 * ni:2 * ni + ne], eq)
+    if step > 0:
+        live = (acc[:, _WORD].view(torch.int32) & _ALIVE) != 0
+        new = torch.where(live[:, None], new, old)
+    con.copy_(new)
 
 
 def record_torch(rows, cols, obs, proposal, action, iters, step, acc, trace):
@@ -241,6 +343,13 @@ def check_record(record, episodes):
     return int(record)
 
 
+def check_constraints(constraints):
+    """``constraints`` of evaluate(): a bool (ValueError otherwise)."""
+    if not isinstance(constraints, (bool, np.bool_)):
+        raise ValueError("evaluate: constraints must be True or False, got %r" % (constraints,))
+    return bool(constraints)
+
+
 def check_budget(tr, eval_steps, eval_lr, what="evaluate"):
     """The per-call projection overrides of ``evaluate()`` / ``act()`` -> (eval_steps, eval_lr) with None replaced by the
     trainer's: ``eval_steps`` an integer >= 0, ``eval_lr`` a finite number (ValueError otherwise)."""
@@ -261,9 +370,11 @@ def check_budget(tr, eval_steps, eval_lr, what="evaluate"):
     return int(steps), lr
 
 
-def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None):
+def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
+             constraints=False):
     """See ``RPOTrainerBase.evaluate``."""
     n = check_episodes(episodes)
+    want_con = check_constraints(constraints)
     budget = (None, None) if eval_steps is None and eval_lr is None else check_budget(tr, eval_steps, eval_lr)
     R = check_record(record, n)
     if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
@@ -299,24 +410,31 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     acc = torch.zeros(n, 8, device=tr.device)
     # the record: zeroed here (the kernels write live lanes' rows only and never clear it), [step, episode, W]
     trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
+    # the per-constraint report: step 0 writes every row from scratch, nothing to clear
+    con = torch.empty(n, hip_ops.con_width(k.ineq_num, k.eq_num), device=tr.device) if want_con else None
     with torch.no_grad():
         if fused:
             path = "fused"
-            _run_fused(tr, v, acc, H, trace=trace, budget=budget)
+            _run_fused(tr, v, acc, H, trace=trace, budget=budget, con=con)
         else:
             path = "stepwise"
-            _run_stepwise(tr, v, acc, H, trace=trace, budget=budget)
+            _run_stepwise(tr, v, acc, H, trace=trace, budget=budget, con=con)
     res = EvalResult(acc.cpu().numpy(), path, H, seed)
+    if want_con:
+        res.constraints = ConstraintReport.from_rows(con.cpu().numpy(), k.ineq_num, k.eq_num, res.length, v.viol_thresh,
+                                                     getattr(tr.base_env, "ineq_names", None),
+                                                     getattr(tr.base_env, "eq_names", None))
     if R:
         res.trajectory = EvalTrajectory.from_trace(trace.cpu().numpy(), dims, res.length[:R], v.viol_thresh)
     return res
 
 
-def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None)):
+def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
     trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
-    (rpo_<env>_evaluate_record).  ``budget``: evaluate()'s per-call (eval_steps, eval_lr), None: the trainer's."""
+    (rpo_<env>_evaluate_record).  ``budget``: evaluate()'s per-call (eval_steps, eval_lr), None: the trainer's.  ``con``: the
+    per-constraint report [n, W] every launch continues (rpo_<env>_evaluate_constraints)."""
     n = v.n
     eval_steps = tr.eval_steps if budget[0] is None else budget[0]
     eval_lr = tr.eval_lr if budget[1] is None else budget[1]
@@ -324,22 +442,26 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None)):
     scale, base = tr._box_affine
     desc = tr.fused.descs["actor"] if desc is None else desc
     kw = {} if trace is None else dict(trace=trace)
+    if con is not None:
+        kw["con"] = con
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
                             v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo, tr._box_hi,
                             eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps, v.viol_thresh, **kw)
 
 
-def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None)):
+def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None):
     """eval()'s loop: the trainer's deterministic action + projection, one env step without auto-reset, the accumulator
     update.  Finished lanes keep stepping (as in eval()); their rows no longer change.  ``trace``: the zeroed record
     [H, R, W]; the step's row goes in before the accumulator update (which ends the lanes the step finished), from a copy
-    of the observation the policy read (the step overwrites it)."""
+    of the observation the policy read (the step overwrites it).  ``con``: the per-constraint report [n, W], updated before
+    the accumulators for the same reason."""
     k = tr.kernels
     rows = torch.zeros(v.n, k.ring_floats, device=tr.device)
     iters = torch.zeros(v.n, dtype=torch.int32, device=tr.device)
     update = getattr(tr.backend, "eval_accumulate", None) or accumulate_torch
     record = getattr(tr.backend, "eval_record", None) or record_torch
+    report = getattr(tr.backend, "eval_constraints", None) or constraints_torch
     obs_in = torch.zeros_like(v.obs) if trace is not None else None
     for i in range(H):
         if trace is not None:
@@ -349,6 +471,8 @@ def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None)):
         v.step(v.action, rows=rows, cap_steps=1, auto_reset=False)
         if trace is not None:
             record(rows, k.cols, obs_in, proposal, v.action, iters, i, acc, trace)
+        if con is not None:
+            report(rows, k.cols, i, v.viol_thresh, acc, con)
         update(rows, k.cols, iters, i, v.viol_thresh, acc)
 
 

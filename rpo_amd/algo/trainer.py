@@ -1427,7 +1427,8 @@ class RPOTrainerBase(object):
             out += [x.mean(), x.std()]
         return tuple(out)
 
-    def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None):
+    def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
+                 constraints=False):
         """Evaluate the current policy on ``episodes`` independent episodes -> ``EvalResult`` (per-episode arrays; ``summary()``
         is eval()'s 10-tuple).  The policy, projection and horizon are eval()'s: deterministic actor (RPOSAC: the mean head),
         ``eval_steps`` / ``eval_lr`` / ``corr_eps`` / ``corr_momentum``, at most min(500, max_episode_steps, the env's
@@ -1441,10 +1442,14 @@ class RPOTrainerBase(object):
         with and without it.  Curve mode (``eval_episodes=N``) does not record.  ``eval_steps=`` / ``eval_lr=`` override the
         projection's budget and step size for this call only, validated like ``act()``'s (a budget read off a
         ``ProjectionProfile`` can be confirmed on whole episodes); the trainer's attributes stay as they are, and curve mode
-        and eval() never see an override.  See rpo_amd/algo/evaluation.py."""
+        and eval() never see an override.  ``constraints=True`` (a bool; ValueError otherwise) keeps a per-episode,
+        per-constraint breakdown on the device and returns it as ``result.constraints`` (``ConstraintReport``: ``ineq_max``,
+        ``ineq_steps``, ``eq_max`` [episode, constraint], ``names``, ``worst()``, ``rate()``); it combines with every other
+        argument and changes no other result; False: ``result.constraints`` is None and the launches are those without it.
+        Curve mode produces no reports: ``eval_curve_last.constraints`` is None.  See rpo_amd/algo/evaluation.py."""
         from .evaluation import evaluate
         return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record,
-                        eval_steps=eval_steps, eval_lr=eval_lr)
+                        eval_steps=eval_steps, eval_lr=eval_lr, constraints=constraints)
 
     def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0, profile=False):
         """The policy's projected actions for caller-supplied observations -> ``ActResult`` (torch tensors on the trainer's

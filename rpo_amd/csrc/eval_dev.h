@@ -44,6 +44,51 @@ __device__ __forceinline__ void rpo_eval_lane_update(float* __restrict__ acc, in
     a4[1] = hi;
 }
 
+// ------------------------------------------------------------------------------------------------ per-constraint report
+// Row layout of the report (include/rpo_hip.h: RPO_CON_*): ineq_max[NI] | ineq_steps[NI] | eq_max[NE] | zeros, and ONE
+// definition of a cell's update for the fused kernel's CON = 1 instances and rpo_eval_constraints.
+__host__ __device__ constexpr int con_width(int ineq_num, int eq_num) {
+    return (2 * ineq_num + eq_num + RPO_CON_ALIGN - 1) / RPO_CON_ALIGN * RPO_CON_ALIGN;
+}
+
+// index into ineq_viol (cells < 2 NI) or eq_viol (the NE cells behind them) of the value cell c folds in; -1: padding
+__device__ __forceinline__ int con_cell_source(int c, int ineq_num, int eq_num) {
+    return c < ineq_num ? c : (c < 2 * ineq_num ? c - ineq_num : (c < 2 * ineq_num + eq_num ? c - 2 * ineq_num : -1));
+}
+
+// Cell c of a live lane's row after a step: `old` the cell before it (0 at step 0), `v` the transition row's ineq_viol[j] /
+// eq_viol[j] for j = con_cell_source(c).  The maxima start at 0 and propagate a NaN, the count compares like viol_steps:
+// rpo_eval_lane_update's expressions, per constraint.
+__device__ __forceinline__ float rpo_eval_con_cell(int c, int ineq_num, int eq_num, float old, float v, float viol_thresh) {
+    RPO_FP_STRICT
+    if (c < ineq_num) return nanmax(old, v);                     // ineq_max
+    if (c < 2 * ineq_num) return old + ((v > viol_thresh) ? 1.0f : 0.0f);   // ineq_steps
+    if (c < 2 * ineq_num + eq_num) return nanmax(old, fabsf(v)); // eq_max
+    return 0.0f;
+}
+
+// The whole row of one live lane (the fused kernels: NI, NE and so every cell's kind are compile-time): W / 4 16-byte loads
+// (none at step 0) and stores.  Plain (cached) accesses: the row is read again at the lane's next step.
+template <int NI, int NE>
+__device__ __forceinline__ void rpo_eval_con_lane_update(float* __restrict__ con, int step, const float (&ineq)[NI],
+                                                         const float (&eq)[NE], float viol_thresh) {
+    constexpr int kW = con_width(NI, NE);
+    float4* c4 = reinterpret_cast<float4*>(con);
+    float r[kW];
+#pragma unroll
+    for (int q = 0; q < kW / 4; ++q) {
+        const float4 x = step > 0 ? c4[q] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        r[4 * q] = x.x; r[4 * q + 1] = x.y; r[4 * q + 2] = x.z; r[4 * q + 3] = x.w;
+    }
+#pragma unroll
+    for (int c = 0; c < kW; ++c) {
+        const int j = con_cell_source(c, NI, NE);
+        r[c] = rpo_eval_con_cell(c, NI, NE, r[c], j < 0 ? 0.0f : (c < 2 * NI ? ineq[j] : eq[j]), viol_thresh);
+    }
+#pragma unroll
+    for (int q = 0; q < kW / 4; ++q) c4[q] = make_float4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
+}
+
 // ------------------------------------------------------------------------------------------------ per-step record
 // Row layout of the trace buffer (include/rpo_hip.h: RPO_TRACE_*), one definition for the fused kernel and rpo_eval_record.
 __host__ __device__ constexpr int trace_head(int obs_dim, int partial_dim, int action_dim) {

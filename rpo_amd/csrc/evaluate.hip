@@ -8,6 +8,8 @@
 //   eval_accumulate      the stepwise path's update: reads the transition rows rpo_<env>_step wrote.
 //   eval_record          the stepwise path's per-step record (rpo_eval_record); the fused kernel's REC = 1 instances write the
 //                        same rows themselves (eval_dev.h: trace_store_head / trace_store_tail).
+//   eval_constraints     the stepwise path's per-constraint report (rpo_eval_constraints); the fused kernel's CON = 1 instances
+//                        update the same rows themselves (eval_dev.h: rpo_eval_con_lane_update).
 //   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
 //
 // Both update a lane's accumulator row through rpo_eval_lane_update (eval_dev.h).
@@ -21,6 +23,7 @@
 namespace {
 
 using namespace rpo_mlp_dev;
+using rpo_eval_dev::con_width;
 using rpo_eval_dev::nanmax;
 using rpo_eval_dev::rpo_eval_lane_update;
 using rpo_eval_dev::trace_head;
@@ -43,7 +46,16 @@ struct EvalArgs {
     typename ENV::StepArgs step;  // env state and bookkeeping (rows = NULL, auto_reset = 0)
 };
 
-// What one env step leaves for the statistics: reward, done and the violations of the transition row, without the row.
+// The CON = 1 instances take the report behind the same arguments; the CON = 0 instances keep EvalArgs as their parameter.
+template <class ENV>
+struct EvalConArgs : EvalArgs<ENV> {
+    float* con;                   // [n, con_width(kIneq, kEq)] per-constraint report (RPO_CON_*)
+};
+template <class ENV, int CON> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
+template <class ENV> struct EvalArgsOf<ENV, 1> { typedef EvalConArgs<ENV> type; };
+
+// What one env step leaves for the statistics: reward, done and the violations of the transition row, without the row --
+// their maxima for the accumulators, and the row's ineq_viol / eq_viol columns themselves (gi / he) for the report.
 // Observations are staged from the env's observation rows: for SpringPendulum those the stepwise path hands the actor
 // and the projection (after an injected initial state they come from torch's cos / sin, not from sincosf).
 template <class ENV>
@@ -51,12 +63,13 @@ struct EvalEnv;
 
 template <>
 struct EvalEnv<CartEnv> {
-    static constexpr int kObs = 6;
+    static constexpr int kObs = 6, kIneq = 6, kEq = 1;
     __device__ static __forceinline__ void stage(const rpo_cart_dev::StepArgs& p, int row0, int rows, float* in_s, int stride) {
         CartEnv::stage_obs(p, row0, rows, in_s, stride);
     }
     __device__ static __forceinline__ void lane(const rpo_cart_dev::StepArgs& p, const rpo_cart_dev::CartConsts& c, int i,
-                                                const float* obs, float2 a, float& reward, float& done, float& ineq, float& eq) {
+                                                const float* obs, float2 a, float& reward, float& done, float& ineq, float& eq,
+                                                float (&gi)[kIneq], float (&he)[kEq]) {
         float s[6], ns[6], st[rpo_cart_dev::kStepStats];
         float4 row[6];
 #pragma unroll
@@ -68,12 +81,14 @@ struct EvalEnv<CartEnv> {
         eq = fabsf(row[4].x);
         // the ineq_viol columns in order, max with NaN propagation (Tensor.max(dim=1))
         ineq = nanmax(nanmax(nanmax(nanmax(nanmax(row[4].y, row[4].z), row[4].w), row[5].x), row[5].y), row[5].z);
+        he[0] = row[4].x;
+        gi[0] = row[4].y; gi[1] = row[4].z; gi[2] = row[4].w; gi[3] = row[5].x; gi[4] = row[5].y; gi[5] = row[5].z;
     }
 };
 
 template <>
 struct EvalEnv<PendEnv> {
-    static constexpr int kObs = 5;
+    static constexpr int kObs = 5, kIneq = 1, kEq = 1;
     __device__ static __forceinline__ void stage(const rpo_pend_dev::StepArgs& p, int row0, int rows, float* in_s, int stride) {
         const int tid = threadIdx.x;
         if (tid < rows * 5) {
@@ -82,7 +97,8 @@ struct EvalEnv<PendEnv> {
         }
     }
     __device__ static __forceinline__ void lane(const rpo_pend_dev::StepArgs& p, const PendEnv::Consts&, int i, const float*,
-                                                float2 a, float& reward, float& done, float& ineq, float& eq) {
+                                                float2 a, float& reward, float& done, float& ineq, float& eq,
+                                                float (&gi)[kIneq], float (&he)[kEq]) {
         const float4 s = reinterpret_cast<const float4*>(p.internal)[i];
         float ns[4], ncs, nsn, st[rpo_pend_dev::kStepStats];
         float4 row[4];
@@ -93,13 +109,17 @@ struct EvalEnv<PendEnv> {
         done = row[3].y;
         eq = fabsf(row[3].z);
         ineq = row[3].w;
+        he[0] = row[3].z;
+        gi[0] = row[3].w;
     }
 };
 
 // REC = 1: a live lane i < p.trace_rows also writes row (s, i) of the trace -- the head before ENV::lane runs (the pendulum lane
 // overwrites its observation row), the tail after it.  Nothing of the record is computed in, or alive across, the MFMA loops.
-template <class ENV, int EIN, int H, int RT, int REC>
-__global__ __launch_bounds__(kFwdThreads) void eval_kernel(EvalArgs<ENV> p, typename ENV::Consts c) {
+// CON = 1: a live lane also folds the step's per-constraint values into row i of p.con, read and written in global memory
+// inside the step (rpo_eval_con_lane_update) -- likewise nothing of it crosses the MFMA loops.
+template <class ENV, int EIN, int H, int RT, int REC, int CON>
+__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON>::type p, typename ENV::Consts c) {
     typedef TileLds<EIN, RT, 8, 8> Lds;                          // 16 * RT lanes per workgroup; OBS <= 8
     __shared__ Lds lds;
     constexpr int kInS = Lds::kS;
@@ -125,29 +145,42 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(EvalArgs<ENV> p, type
             constexpr int kObs = EvalEnv<ENV>::kObs, kW = trace_width(kObs, 1, 2);
             if (REC && i < p.trace_rows)
                 rpo_eval_dev::trace_store_head<kObs>(p.trace + ((size_t)s * p.trace_rows + i) * kW, lds.in_s + tid * kInS, ap, a, k);
-            float reward, done, ineq, eq;
-            EvalEnv<ENV>::lane(p.step, c, i, lds.in_s + tid * kInS, a, reward, done, ineq, eq);
+            float reward, done, ineq, eq, gi[EvalEnv<ENV>::kIneq], he[EvalEnv<ENV>::kEq];
+            EvalEnv<ENV>::lane(p.step, c, i, lds.in_s + tid * kInS, a, reward, done, ineq, eq, gi, he);
             if (REC && i < p.trace_rows)
                 rpo_eval_dev::trace_store_tail(p.trace + ((size_t)s * p.trace_rows + i) * kW + trace_head(kObs, 1, 2), reward, done,
                                                ineq, eq);
+            if constexpr (CON)
+                rpo_eval_dev::rpo_eval_con_lane_update(p.con + (size_t)i * con_width(EvalEnv<ENV>::kIneq, EvalEnv<ENV>::kEq), s, gi, he,
+                                                       p.step.viol_thresh);
             rpo_eval_lane_update(p.acc + (size_t)i * RPO_EVAL_LEN, s, reward, ineq, eq, done, k, p.step.viol_thresh);
         }
         __syncthreads();                                         // every lane has read its observation out of the LDS tile
     }
 }
 
-template <class ENV, int REC>
-int launch_eval(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, void* stream) {
+template <class ENV, int REC, int CON>
+int launch_eval(const typename EvalArgsOf<ENV, CON>::type& args, const typename ENV::Consts& c, int n, void* stream) {
     // the rollout's tile rule (fused.hip launch_rollout): 64 lanes per workgroup once that still fills the chip.  E = 128
     // only: the E = 256 instance spills (~150 bytes of scratch per lane) -- such actors evaluate on the stepwise path.
     if (args.actor.E != 128) return RPO_ERR_ARG;
     if (n >= 64 * 192) {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     } else {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     }
     RPO_LAUNCH_CHECK();
     return 0;
+}
+
+// rec / con of the entry points -> the instance; con == NULL: the launches of rpo_<env>_evaluate[_record] as they were
+template <class ENV>
+int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, int rec, float* con, void* stream) {
+    if (!con) return rec ? launch_eval<ENV, 1, 0>(args, c, n, stream) : launch_eval<ENV, 0, 0>(args, c, n, stream);
+    EvalConArgs<ENV> ca;
+    static_cast<EvalArgs<ENV>&>(ca) = args;
+    ca.con = con;
+    return rec ? launch_eval<ENV, 1, 1>(ca, c, n, stream) : launch_eval<ENV, 0, 1>(ca, c, n, stream);
 }
 
 int check_eval_actor(const Mlp& actor, int obs_dim, int gauss) {
@@ -170,6 +203,12 @@ int check_eval_trace(const float* trace, int n, int trace_rows, int trace_steps,
     if (trace_rows <= 0 || trace_rows > n || trace_steps <= 0 || (long long)t0 + steps > trace_steps) return RPO_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(trace) % 16) return RPO_ERR_ARG;
     return 0;
+}
+
+// The report of the *_evaluate_constraints entry points: 16-byte aligned for the float4 accesses.
+int check_eval_con(const float* con) {
+    if (!con) return RPO_ERR_NULL;
+    return reinterpret_cast<uintptr_t>(con) % 16 ? RPO_ERR_ARG : 0;
 }
 
 // ------------------------------------------------------------------------------------------- stepwise accumulation
@@ -238,6 +277,31 @@ __global__ __launch_bounds__(RPO_BLOCK) void eval_record_kernel(RecArgs p) {
             row_violations(r, p.a.ineq_col, p.a.ineq_num, p.a.eq_col, p.a.eq_num, ineq, eq);
             rpo_eval_dev::trace_store_tail(dst, r[p.a.reward_col], r[p.a.done_col], ineq, eq);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------- stepwise per-constraint report
+struct ConArgs {
+    int n;
+    const float* rows;
+    int stride, eq_col, eq_num, ineq_col, ineq_num, step;
+    float viol_thresh;
+    const float* acc;
+    float* con;                   // [n, W]
+    int W;
+};
+
+// One thread per (lane, cell): the threads of a wave read neighbouring columns of a transition row (ineq_viol twice, then
+// eq_viol) and store neighbouring cells -- the cells of a step's lanes are contiguous.  Every cell has one owner.
+__global__ __launch_bounds__(RPO_BLOCK) void eval_constraints_kernel(ConArgs p) {
+    const long long total = (long long)p.n * p.W;
+    for (long long t = (long long)blockIdx.x * RPO_BLOCK + threadIdx.x; t < total; t += (long long)gridDim.x * RPO_BLOCK) {
+        const int i = (int)(t / p.W), c = (int)(t - (long long)i * p.W);
+        if (p.step > 0 && !(__float_as_int(p.acc[(size_t)i * RPO_EVAL_LEN + RPO_EVAL_WORD]) & RPO_EVAL_ALIVE)) continue;
+        const int j = rpo_eval_dev::con_cell_source(c, p.ineq_num, p.eq_num);
+        const float v = j < 0 ? 0.0f : p.rows[(size_t)i * p.stride + (c < 2 * p.ineq_num ? p.ineq_col : p.eq_col) + j];
+        const float old = p.step > 0 ? p.con[t] : 0.0f;
+        p.con[t] = rpo_eval_dev::rpo_eval_con_cell(c, p.ineq_num, p.eq_num, old, v, p.viol_thresh);
     }
 }
 
@@ -368,17 +432,20 @@ __global__ __launch_bounds__(RPO_BLOCK) void summarize_combine_kernel(int n, int
     write_curve_row(row, ctrl, n, sum, mean, sq);
 }
 
-// rpo_cartsafe_evaluate (rec = 0: trace arguments unused) and rpo_cartsafe_evaluate_record (rec = 1)
+// rpo_cartsafe_evaluate (rec = 0: trace arguments unused), rpo_cartsafe_evaluate_record (rec = 1) and
+// rpo_cartsafe_evaluate_constraints (with_con = 1; rec = whether it got a trace)
 int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state, float* action,
                       int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, const float* consts_host,
                       int partial, int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows,
-                      int trace_steps, void* stream) {
+                      int trace_steps, int with_con, float* con, void* stream) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (!state || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
+    if (with_con)
+        if (int e = check_eval_con(con)) return e;
     EvalArgs<CartEnv> args{};
     args.actor = to_dev(actor_host);
     if (int e = check_eval_actor(args.actor, 6, gauss)) return e;
@@ -391,19 +458,21 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                                        max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
-    return rec ? launch_eval<CartEnv, 1>(args, c, n_envs, stream) : launch_eval<CartEnv, 0>(args, c, n_envs, stream);
+    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream);
 }
 
 int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal, float* obs,
                       float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps,
                       float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                       int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows, int trace_steps,
-                      void* stream) {
+                      int with_con, float* con, void* stream) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (!internal || !obs || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
+    if (with_con)
+        if (int e = check_eval_con(con)) return e;
     EvalArgs<PendEnv> args{};
     args.actor = to_dev(actor_host);
     if (int e = check_eval_actor(args.actor, 5, gauss)) return e;
@@ -415,7 +484,7 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
     const PendEnv::Consts c{0};
-    return rec ? launch_eval<PendEnv, 1>(args, c, n_envs, stream) : launch_eval<PendEnv, 0>(args, c, n_envs, stream);
+    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream);
 }
 
 }  // namespace
@@ -450,7 +519,7 @@ int rpo_cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, flo
                           float viol_thresh, void* stream) {
     return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
                              box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, 0, nullptr, 0, 0, stream);
+                             viol_thresh, 0, nullptr, 0, 0, 0, nullptr, stream);
 }
 
 int rpo_cartsafe_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -460,7 +529,7 @@ int rpo_cartsafe_evaluate_record(const rpo_mlp* actor_host, int gauss, float sca
                                  float viol_thresh, float* trace, int trace_rows, int trace_steps, void* stream) {
     return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
                              box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, 1, trace, trace_rows, trace_steps, stream);
+                             viol_thresh, 1, trace, trace_rows, trace_steps, 0, nullptr, stream);
 }
 
 int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
@@ -469,7 +538,7 @@ int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, flo
                           float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, void* stream) {
     return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                              steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
-                             nullptr, 0, 0, stream);
+                             nullptr, 0, 0, 0, nullptr, stream);
 }
 
 int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
@@ -479,7 +548,43 @@ int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float sca
                                  int trace_rows, int trace_steps, void* stream) {
     return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                              steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 1,
-                             trace, trace_rows, trace_steps, stream);
+                             trace, trace_rows, trace_steps, 0, nullptr, stream);
+}
+
+int rpo_cartsafe_evaluate_constraints(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                      float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                      float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                      float corr_eps, float corr_momentum, const float* consts_host, int partial,
+                                      int max_episode_steps, float viol_thresh, float* trace, int trace_rows, int trace_steps,
+                                      float* con, void* stream) {
+    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
+                             viol_thresh, trace ? 1 : 0, trace, trace_rows, trace_steps, 1, con, stream);
+}
+
+int rpo_pendulum_evaluate_constraints(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs,
+                                      float* internal, float* obs, float* action, int* ep_len, float* ep_ret,
+                                      unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
+                                      float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                                      int max_episode_steps, float viol_thresh, float* trace, int trace_rows, int trace_steps,
+                                      float* con, void* stream) {
+    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                             trace ? 1 : 0, trace, trace_rows, trace_steps, 1, con, stream);
+}
+
+int rpo_eval_constraints(int n, const float* rows, int row_stride, int eq_col, int eq_num, int ineq_col, int ineq_num, int step,
+                         float viol_thresh, const float* acc, float* con, void* stream) {
+    if (n <= 0 || step < 0 || step >= (1 << 24) || eq_num <= 0 || ineq_num <= 0 || eq_col < 0 || ineq_col < 0 || eq_num > 4096 ||
+        ineq_num > 4096)
+        return RPO_ERR_ARG;
+    if (eq_col + eq_num > row_stride || ineq_col + ineq_num > row_stride) return RPO_ERR_ARG;
+    if (!rows || !acc || !con) return RPO_ERR_NULL;
+    const int W = con_width(ineq_num, eq_num);
+    const ConArgs a{n, rows, row_stride, eq_col, eq_num, ineq_col, ineq_num, step, viol_thresh, acc, con, W};
+    hipLaunchKernelGGL(eval_constraints_kernel, dim3(rpo_grid_for((long long)n * W)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a);
+    RPO_LAUNCH_CHECK();
+    return 0;
 }
 
 int rpo_eval_accumulate(int n, const float* rows, int row_stride, int reward_col, int done_col, int eq_col, int eq_num,

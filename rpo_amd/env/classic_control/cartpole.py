@@ -18,6 +18,9 @@ spaces = gym.spaces
 
 class CartSafeEnv(HardConstraintEnv):
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 50}
+    #: the rows of diff_ineq / diff_eq: |a . cos(delta)| <= 8 (net horizontal force), |a_i| <= 10; a . sin(delta) = 0
+    ineq_names = ("hforce_max", "hforce_min", "a_max[0]", "a_min[0]", "a_max[1]", "a_min[1]")
+    eq_names = ("vforce",)
 
     def __init__(self, partial_actions=None, backend=None, device=None):
         super().__init__(backend, device)

@@ -14,6 +14,8 @@ spaces = gym.spaces
 
 class SpringPendulumEnv(HardConstraintEnv):
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 30}
+    ineq_names = ("force_norm",)                                           # |f|^2 <= 32
+    eq_names = ("radial",)                                                 # l_dot' = 0
 
     def __init__(self, g=10.0, backend=None, device=None):
         super().__init__(backend, device)

@@ -70,6 +70,12 @@ class EVOPFEnv(HardConstraintEnv):
         self.observation_space = spaces.Box(low=low.astype(np.float32), high=high.astype(np.float32), dtype=np.float32)
         self.state_dim, self.action_dim = self.observation_space.shape[0], self.action_space.shape[0]
         self.eq_num, self.ineq_num = 28, 58                                               # evopf.py:336-337
+        # the blocks of ineq_resid (evopf.py:548-563) / eq_resid in their order: generator limits, voltage bands, battery
+        # charge rates (pg - pmax, pmin - pg, ...); active and reactive power balance per bus
+        blocks = (("pgmax", self.ng), ("pgmin", self.ng), ("qgmax", self.ng), ("qgmin", self.ng), ("vmax", self.nbus),
+                  ("vmin", self.nbus), ("pemax", self.ne), ("pemin", self.ne))
+        self.ineq_names = tuple("%s[%d]" % (b, j) for b, m in blocks for j in range(m))
+        self.eq_names = tuple("%s[%d]" % (b, j) for b in ("pbal", "qbal") for j in range(self.nbus))
         self._table = case14.kernel_constants(hip_ops.CONST, hip_ops.CONST["RPO_EVOPF_CONSTS_LEN"])
         self._box_cache = {}
         self.seed()

@@ -292,6 +292,32 @@ def eval_record(rows, cols, obs, proposal, action, iters, step, acc, trace):
                                       tp, R, T, _stream()), "rpo_eval_record")
 
 
+CON_ALIGN = CONST["RPO_CON_ALIGN"]
+
+
+def con_width(ineq_num, eq_num):
+    """Floats of a row of the per-constraint report (include/rpo_hip.h: RPO_CON_*): ineq_max[ineq_num] | ineq_steps[ineq_num] |
+    eq_max[eq_num], padded to a multiple of CON_ALIGN."""
+    return (2 * ineq_num + eq_num + CON_ALIGN - 1) // CON_ALIGN * CON_ALIGN
+
+
+def _con(con, n, width):
+    """Pointer of a report buffer [n, W] (the kernels index it by lane: a smaller one would be written out of bounds)."""
+    if con.dim() != 2 or tuple(con.shape) != (n, width):
+        raise RpoHipError("constraint report must be [%d, %d] float32, got %s" % (n, width, tuple(con.shape)))
+    return _p(con)
+
+
+def eval_constraints(rows, cols, step, viol_thresh, acc, con):
+    """Step `step` of a policy evaluation into the per-constraint report con [n, W] (rpo_eval_constraints; before
+    eval_accumulate of the same step) from the transition rows the env's step kernel wrote."""
+    n = acc.shape[0]
+    rp, stride = _row_view(rows[:n], rows.shape[1])
+    (e0, e1), (i0, i1) = cols["eq_viol"], cols["ineq_viol"]
+    check(_lib.load().rpo_eval_constraints(n, rp, stride, e0, e1 - e0, i0, i1 - i0, int(step), viol_thresh, _eval_acc(acc, n),
+                                           _con(con, n, con_width(i1 - i0, e1 - e0)), _stream()), "rpo_eval_constraints")
+
+
 CURVE_LEN = CONST["RPO_CURVE_LEN"]
 CURVE_WS = CONST["RPO_CURVE_WS"]
 
@@ -386,16 +412,22 @@ class CartSafeKernels(object):
             "rpo_cartsafe_rollout")
 
     def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None):
+                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None,
+                 con=None):
         """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_cartsafe_evaluate); acc [n, EVAL_LEN].
-        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_cartsafe_evaluate_record)."""
+        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_cartsafe_evaluate_record).
+        con [n, con_width]: the per-constraint report, with or without a trace (rpo_cartsafe_evaluate_constraints)."""
         net = actor_desc.net_struct()
         n = internal.shape[0]
         args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32),
                 _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n),
                 int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
                 max_episode_steps, viol_thresh)
-        if trace is None:
+        if con is not None:
+            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
+            check(_lib.load().rpo_cartsafe_evaluate_constraints(*args, *tr, _con(con, n, con_width(self.ineq_num, self.eq_num)),
+                                                                _stream()), "rpo_cartsafe_evaluate_constraints")
+        elif trace is None:
             check(_lib.load().rpo_cartsafe_evaluate(*args, _stream()), "rpo_cartsafe_evaluate")
         else:
             tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
@@ -635,16 +667,22 @@ class PendulumKernels(object):
             "rpo_pendulum_rollout")
 
     def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None):
+                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None,
+                 con=None):
         """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_pendulum_evaluate); acc [n, EVAL_LEN].
-        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_pendulum_evaluate_record)."""
+        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_pendulum_evaluate_record).
+        con [n, con_width]: the per-constraint report, with or without a trace (rpo_pendulum_evaluate_constraints)."""
         net = actor_desc.net_struct()
         n = internal.shape[0]
         args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action),
                 _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
                 _eval_acc(acc, n), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps,
                 corr_momentum, max_episode_steps, viol_thresh)
-        if trace is None:
+        if con is not None:
+            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
+            check(_lib.load().rpo_pendulum_evaluate_constraints(*args, *tr, _con(con, n, con_width(self.ineq_num, self.eq_num)),
+                                                                _stream()), "rpo_pendulum_evaluate_constraints")
+        elif trace is None:
             check(_lib.load().rpo_pendulum_evaluate(*args, _stream()), "rpo_pendulum_evaluate")
         else:
             tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])

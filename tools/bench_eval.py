@@ -5,6 +5,7 @@
     python tools/bench_eval.py --profile-only [--sizes 65536]     # fused evaluations only, for a rocprofv3 pass:
     rocprofv3 --kernel-trace --stats -d DIR -o eval -- python tools/bench_eval.py --profile-only
     python tools/bench_eval.py --record [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_record_bench.json]
+    python tools/bench_eval.py --constraints [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_constraints_bench.json]
 
 Per configuration (cart-RPODDPG, cart-RPOSAC, pendulum-RPODDPG: fused; EVOPF-RPODDPG: stepwise only) a trainer with
 bench.py's hyper-parameters is trained for a few vector steps (a policy that has left its initialisation), then:
@@ -16,6 +17,10 @@ bench.py's hyper-parameters is trained for a few vector steps (a policy that has
 episodes, stepwise EVOPF-RPODDPG at 10 and 1024: the legs record=False / record=64 / record=True are timed ALTERNATELY, --reps
 rounds after one warm-up round, and reported as medians with the min-max spread of each leg (a leg's cost over record=False
 means something only beyond that spread).  A record=True leg includes the read-back and the numpy views of the trace.
+--constraints: the cost of evaluate(constraints=True) (the per-constraint report), by the same method.  Fused cart-RPODDPG at
+--sizes episodes, stepwise EVOPF-RPODDPG at 10 and 1024: the legs constraints=False / constraints=True (and, on the fused path,
+record=True for comparison) alternate; per size the ratio of the medians constraints=True / constraints=False is reported next
+to the two legs' own min-max spreads.
 Every call ends with a host read of the results (evaluate()'s .cpu(), eval()'s), so wall times include the device work.
 Run each GPU step under its own time limit (timeout -k 10 ...).
 """
@@ -108,17 +113,46 @@ def record_bench(a, sizes):
     return line
 
 
+def constraints_bench(a, sizes):
+    line = dict(tool="bench_eval --constraints", device=torch.cuda.get_device_name(0), reps=a.reps, configs={})
+    for workload, has_fused in (("cart_ddpg", True), ("evopf_ddpg", False)):
+        tr = trainer(workload)
+        row = {}
+        for n in (sizes if has_fused else [10, 1024]):
+            legs = {"constraints_false": lambda: tr.evaluate(n, seed=5),
+                    "constraints_true": lambda: tr.evaluate(n, seed=5, constraints=True)}
+            if has_fused:
+                legs["record_true"] = lambda: tr.evaluate(n, seed=5, record=True)
+            res = alternating(legs, a.reps)
+            r = tr.evaluate(n, seed=5, constraints=True)
+            assert r.path == ("fused" if has_fused else "stepwise")
+            base = res["constraints_false"]["median_s"]
+            for k in list(res):
+                res[k]["ratio_to_constraints_false"] = res[k]["median_s"] / base
+            k = tr.kernels
+            res.update(horizon=r.horizon, env_steps=int(r.length.sum()), path=r.path,
+                       report_bytes=4 * n * ops.con_width(k.ineq_num, k.eq_num))
+            row[str(n)] = res
+            del r
+        line["configs"][workload] = row
+        del tr
+        torch.cuda.empty_cache()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="4096,65536,1048576")
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--record", action="store_true")
+    ap.add_argument("--constraints", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sizes = [int(x) for x in a.sizes.split(",") if x]
-    if a.record:
-        s = json.dumps(record_bench(a, [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes))
+    if a.record or a.constraints:
+        small = [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes
+        s = json.dumps(constraints_bench(a, small) if a.constraints else record_bench(a, small))
         print(s)
         if a.out:
             with open(a.out, "w") as f:
