@@ -1010,6 +1010,21 @@ int rpo_eval_accumulate(int n, const float* rows, int row_stride, int reward_col
  * (chunk sums | chunk sums of squared deviations | combine). */
 int rpo_eval_summarize(int n, const float* acc, const long long* ctrl, double* row_out, double* ws, void* stream);
 
+/* Keep the best policy of a curve-mode run (trainer argument keep_best): the curve row `row` [RPO_CURVE_LEN] that
+ * rpo_eval_summarize has just written for evaluation point `point` (>= 0) is compared ON THE DEVICE with the incumbent's row
+ * best_row [RPO_CURVE_LEN]; best_point[0] is the point held, -1 for none.  With rate = row[VIOL_STEPS] / row[LENGTH] (+inf when
+ * LENGTH == 0) and ret = row[RPO_CURVE_STATS]: a candidate with row[NONFINITE] > 0 or a NaN ret is never taken; a point is safe
+ * when rate <= max_violation_rate (>= 0, RPO_ERR_ARG otherwise); a candidate wins when there is no incumbent, when it is safe
+ * and the incumbent is not, when both are safe and its ret is strictly higher, or when both are unsafe and its rate is
+ * strictly lower or equal with a strictly higher ret (rpo_eval_dev::keep_best_wins).  Ties keep the earlier point.
+ * Two launches on `stream`, kernels only, nothing read on the host: one wave decides and, if the candidate wins, writes
+ * best_row = row and best_point[0] = point; then every thread of the copy reads best_point[0] and, where it equals `point`,
+ * copies its share of src [n_params] (the actor's span of the flat parameter buffer, or its snapshot) into best [n_params] --
+ * 16-byte accesses where src and best sit at the same offset from a 16-byte boundary (scalar head and tail), scalar accesses
+ * otherwise; neither needs more than float alignment (RPO_ERR_ARG below that).  A losing candidate leaves best untouched. */
+int rpo_eval_keep_best(long long n_params, const float* src, float* best, const double* row, double* best_row,
+                       long long* best_point, long long point, double max_violation_rate, void* stream);
+
 /* Forward half of the critic update (rpo_ddpg.py:165-174, 327-337): ReplayBuffer.sample (Philox draw, or idx_in when
  * given) -> batch_out [B,24]; pi_targ(s') -> Complete + Proj -> Q_targ(s', a') = qn_out; Q(s, a) = q_out with the
  * critic's pre-activations saved (x0_save [B,E], h1_save [B,H]) for rpo_mlp_backward.  Two workgroups per 16-row tile

@@ -17,6 +17,7 @@ _CTYPES = (
     ("long long", ctypes.c_longlong),
     ("unsigned", ctypes.c_uint),
     ("float", ctypes.c_float),
+    ("double", ctypes.c_double),
     ("int", ctypes.c_int),
 )
 

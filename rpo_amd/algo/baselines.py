@@ -98,7 +98,7 @@ class DDPG_LA(_LagrangianBase):
                  corr_eps=1e-3, corr_momentum=0.5, batch_size=256, policy_fre=2, eval_fre=500, max_epochs=100000,
                  grad_eps=1e-3, eval_steps=None, init_lamb=0.0, init_nju=0.0, fixed=False, clip_thres="inf", shape=False,
                  device=torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"),
-                 num_envs=None, seed=None, backend=None, eval_episodes=None):
+                 num_envs=None, seed=None, backend=None, eval_episodes=None, keep_best=None):
         base = getattr(env, "unwrapped", env)
         agent = PDDDPG_PA(
             base.state_dim, base.action_dim, base.eq_num, base.ineq_num, embed_dim=embed_dim, hidden_dim=hidden_dim,
@@ -112,7 +112,7 @@ class DDPG_LA(_LagrangianBase):
                   corr_mode=corr_mode, grad_eps=grad_eps, clip_thres=clip_thres, eval_steps=eval_steps,
                   batch_size=batch_size, policy_fre=policy_fre, eval_fre=eval_fre, warmup=warmup, max_epochs=max_epochs,
                   fixed=fixed, partial=False, eps=eps, eps_start=eps, eps_epoch=1,      # constant exploration scale
-                  eval_episodes=eval_episodes)
+                  eval_episodes=eval_episodes, keep_best=keep_best)
         self._setup_la(env, work_dir, name, logger, agent, hp, device, num_envs, seed, backend, shape)
 
     def _noisy(self, ap, state, noise):
@@ -158,7 +158,7 @@ class SAC_LA(_LagrangianBase):
                  batch_size=256, policy_fre=2, eval_fre=500, max_epochs=100000, grad_eps=1e-3, eval_steps=None,
                  init_lamb=0.0, init_nju=0.0, fixed=False, clip_thres="inf", shape=False,
                  device=torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"),
-                 num_envs=None, seed=None, backend=None, eval_episodes=None):
+                 num_envs=None, seed=None, backend=None, eval_episodes=None, keep_best=None):
         base = getattr(env, "unwrapped", env)
         agent = PDSAC_PA(
             automatic_entropy_tuning, base.state_dim, base.action_dim, base.eq_num, base.ineq_num, embed_dim=embed_dim,
@@ -173,7 +173,7 @@ class SAC_LA(_LagrangianBase):
         hp = dict(max_steps=max_steps, corr_lr=corr_lr, eval_lr=corr_lr, corr_eps=corr_eps, corr_momentum=corr_momentum,
                   corr_mode=corr_mode, grad_eps=grad_eps, clip_thres=clip_thres, eval_steps=eval_steps,
                   batch_size=batch_size, policy_fre=policy_fre, eval_fre=eval_fre, warmup=warmup, max_epochs=max_epochs,
-                  fixed=fixed, partial=False, eps=eps, eps_start=eps, eps_epoch=1, eval_episodes=eval_episodes)
+                  fixed=fixed, partial=False, eps=eps, eps_start=eps, eps_epoch=1, eval_episodes=eval_episodes, keep_best=keep_best)
         self._setup_la(env, work_dir, name, logger, agent, hp, device, num_envs, seed, backend, shape)
 
     def _sample_action(self, state, noise, log_pi=False):

@@ -28,7 +28,10 @@ fused kernel's CON instances, ``rpo_eval_constraints`` or ``constraints_torch`` 
 
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
-does not record trajectories and produces no per-constraint reports.
+does not record trajectories and produces no per-constraint reports.  With the trainer argument ``keep_best`` every point's
+row is compared with the incumbent's on the device right behind its summary (``rpo_eval_keep_best``, or ``keep_best_torch``)
+and the actor's parameters of a winning point are kept: ``trainer.best`` (``BestPolicy``), ``restore_best()``,
+``using_best()``.
 """
 import math
 
@@ -561,6 +564,86 @@ def summarize_torch(acc, ctrl, row_out):
     row_out[CURVE_LEN - 1] = 0.0
 
 
+def _rate_torch(row):
+    length = row[_C_LENGTH]
+    return torch.where(length == 0, torch.full_like(length, float("inf")), row[_C_VIOL] / length)
+
+
+def keep_best_torch(src, best, row, best_row, best_point, point, max_violation_rate):
+    """``rpo_eval_keep_best`` in torch ops (backends without the kernel: the CPU oracle), nothing read on the host: the
+    criterion of include/rpo_hip.h as a 0-dim bool, then the three predicated writes."""
+    ret, best_ret = row[_C_STATS], best_row[_C_STATS]
+    rate, best_rate = _rate_torch(row), _rate_torch(best_row)
+    safe, best_safe = rate <= max_violation_rate, best_rate <= max_violation_rate
+    eligible = ~(row[_C_NONFINITE] > 0) & (ret == ret)
+    wins = (best_point[0] < 0) | (safe & ~best_safe) | (safe & best_safe & (ret > best_ret)) | \
+        (~safe & ~best_safe & ((rate < best_rate) | ((rate == best_rate) & (ret > best_ret))))
+    take = eligible & wins
+    best.copy_(torch.where(take, src, best))
+    best_row.copy_(torch.where(take, row, best_row))
+    best_point.copy_(torch.where(take, torch.full_like(best_point, int(point)), best_point))
+
+
+def check_keep_best(keep_best):
+    """The trainers' ``keep_best`` -> None (off: False / None) or ``max_violation_rate`` as a float (True: 0.0; a number
+    >= 0, inf allowed).  ValueError for a negative or NaN rate and for anything that is no number."""
+    if keep_best is None or keep_best is False:
+        return None
+    if keep_best is True:
+        return 0.0
+    if isinstance(keep_best, (str, bytes)) or not isinstance(keep_best, (int, float, np.integer, np.floating)):
+        raise ValueError("keep_best must be False, True or a violation rate >= 0, got %r" % (keep_best,))
+    rate = float(keep_best)
+    if not rate >= 0.0:
+        raise ValueError("keep_best: the violation rate must be >= 0, got %r" % (keep_best,))
+    return rate
+
+
+def keep_best_from_env(text):
+    """``RPO_KEEP_BEST``: unset / "" / "0" / "false" / "off": off; "1" / "true" / "on": True; anything else: the rate."""
+    t = (text or "").strip().lower()
+    if t in ("", "0", "false", "off"):
+        return False
+    if t in ("1", "true", "on"):
+        return True
+    try:
+        return float(t)
+    except ValueError:
+        raise ValueError("RPO_KEEP_BEST must be 0, 1 or a violation rate >= 0, got %r" % (text,))
+
+
+class BestPolicy(object):
+    """The policy a ``keep_best`` run holds: the evaluation point that won on the device (``rpo_eval_keep_best``).
+
+    ``point``: its index (``curve_seed(seed, point)`` seeded it); ``step``: the vector steps done when it was taken;
+    ``row``: its curve row as a one-point ``EvalCurve`` (``row.ret_mean[0]``, ``row.violation_rate[0]``, ...); ``params``:
+    a clone of the actor's span of the flat parameter buffer at that point, float32, on the trainer's device (on the CPU
+    after ``load``); ``max_violation_rate``: the rate up to which a point counted as safe."""
+
+    def __init__(self, point, row, params, max_violation_rate):
+        self.point = int(point)
+        self.row = EvalCurve(row)
+        self.step = int(self.row.rows[0, _C_STEP])
+        self.params = params
+        self.max_violation_rate = float(max_violation_rate)
+
+    def save(self, path):
+        """One .npz (point, the raw row, the parameters, the rate); ``BestPolicy.load`` reads it back."""
+        with open(path, "wb") as f:
+            np.savez(f, point=np.int64(self.point), row=self.row.rows[0], params=self.params.detach().cpu().numpy(),
+                     max_violation_rate=np.float64(self.max_violation_rate))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(int(z["point"]), z["row"], torch.from_numpy(np.array(z["params"], dtype=np.float32)),
+                       float(z["max_violation_rate"]))
+
+    def __repr__(self):
+        return "BestPolicy(point=%d, step=%d, return=%.4f, violation_rate=%.4g)" % (
+            self.point, self.step, self.row.ret_mean[0], self.row.violation_rate[0])
+
+
 class CurveRunner(object):
     """The evaluation points of a curve-mode trainer (``eval_episodes=N``): enqueued by the training loop, never waited for.
 
@@ -574,13 +657,23 @@ class CurveRunner(object):
       an event hands over to a dedicated evaluation stream, which runs reset, the evaluate launches on the SNAPSHOT and the
       summary, and records the point's event.  The training stream goes on with the update at once; the next point, the
       harvest and ``save()`` wait for that event, so two points never share the snapshot or the accumulators.
-    * everything else (stepwise path; ``eval_overlap=0``): the same launches in order on the training stream."""
+    * everything else (stepwise path; ``eval_overlap=0``): the same launches in order on the training stream.
 
-    def __init__(self, tr, episodes):
+    ``keep_best`` (None: off; else the violation rate up to which a point is safe): behind the summary, on the same stream,
+    ``rpo_eval_keep_best`` compares the point's row with the incumbent's (``best_row``, ``best_point``: -1 for none) and
+    copies the snapshot (overlapped) or the live actor span (in order) into ``best`` if the point wins.  No host read, no
+    launch inside a captured window; off, the launches are those without it."""
+
+    def __init__(self, tr, episodes, keep_best=None):
         self.tr, self.n = tr, check_episodes(episodes, "eval_episodes")
         self.rows = np.zeros((0, CURVE_LEN))                     # harvested
         self.points = self.done = 0                              # enqueued / harvested over the life of the trainer
         self.v = self.event = self.last_seed = None
+        self.keep_rate = keep_best                               # None: off; else max_violation_rate (check_keep_best)
+        self.best = self._best_pending = None
+        if keep_best is not None and getattr(getattr(tr.agent, "flat", None), "actor_range", None) is None:
+            raise ValueError("keep_best needs the actor in the flat parameter buffer (agent.flat.actor_range): %s has none"
+                             % type(tr.agent).__name__)
 
     def _alloc(self):
         tr, dev = self.tr, self.tr.device
@@ -605,6 +698,21 @@ class CurveRunner(object):
             self.desc = tr.backend.MlpDesc(tensors, d.S, d.A, d.E, d.H, d.n_out, d.cat, head_dim=d.head_dim)
             self.step_word = torch.zeros(1, dtype=torch.int64, device=dev)
             self.stream = torch.cuda.Stream()
+        if self.keep_rate is not None:
+            self._alloc_best()
+
+    def _alloc_best(self):
+        """The incumbent: the actor's span, its curve row and the index of its point (-1: none), filled outside any window."""
+        if self.best is not None:
+            return
+        flat, dev = self.tr.agent.flat, self.tr.device
+        self.live = flat.param(flat.actor_range)
+        self.best = torch.zeros_like(self.live)
+        self.best_row = torch.zeros(CURVE_LEN, dtype=torch.float64, device=dev)
+        self.best_point = torch.full((1,), -1, dtype=torch.int64, device=dev)
+        if self._best_pending is not None:
+            self._load_best(self._best_pending)
+            self._best_pending = None
 
     def enqueue(self):
         """One evaluation point with the parameters as they are now on the current (training) stream."""
@@ -629,14 +737,14 @@ class CurveRunner(object):
                 ready.record(main)
                 self.stream.wait_event(ready)
                 with torch.cuda.stream(self.stream):
-                    self._point(row, self.desc, self.step_word)
+                    self._point(row, self.desc, self.step_word, k, self.snap)
                     self.event = torch.cuda.Event()
                     self.event.record(self.stream)
             else:
-                self._point(row, None, tr.vec.ctrl)
+                self._point(row, None, tr.vec.ctrl, k, self.live if self.keep_rate is not None else None)
         self.points = k + 1
 
-    def _point(self, row, desc, ctrl):
+    def _point(self, row, desc, ctrl, k, src):
         tr, v = self.tr, self.v
         v.ep_count.zero_()                                       # a fresh vector env: episode 0 of every lane's reset stream
         v.ctrl.zero_()
@@ -650,6 +758,11 @@ class CurveRunner(object):
             summarize(self.acc, ctrl, row, self.ws)
         else:
             summarize_torch(self.acc, ctrl, row)
+        if self.keep_rate is not None:
+            # the decision and the predicated copy, behind the summary on its stream: src is the snapshot (overlapped: the
+            # point's event keeps the next point from overwriting it) or the live span (in order), read before the update
+            keep = getattr(tr.backend, "eval_keep_best", None) or keep_best_torch
+            keep(src, self.best, row, self.best_row, self.best_point, k, self.keep_rate)
 
     def wait(self):
         if self.event is not None:
@@ -676,10 +789,60 @@ class CurveRunner(object):
 
     def state(self):
         self.harvest()
-        return dict(rows=self.rows.copy(), points=self.points, episodes=self.n)
+        st = dict(rows=self.rows.copy(), points=self.points, episodes=self.n)
+        if self.keep_rate is not None:                           # (additional entries: a checkpoint without them has no incumbent)
+            self._alloc_best()
+            self.wait()
+            st.update(best=self.best.clone(), best_row=self.best_row.clone(), best_point=self.best_point.clone(),
+                      keep_rate=self.keep_rate)
+        return st
 
     def load_state(self, st):
-        """``st``: ``state()`` of a checkpoint, or None (a checkpoint written without curve mode: an empty curve)."""
+        """``st``: ``state()`` of a checkpoint, or None (a checkpoint written without curve mode: an empty curve).  The
+        incumbent of a ``keep_best`` run comes back with it; a checkpoint that holds none leaves none."""
         self.wait()
         self.rows = np.zeros((0, CURVE_LEN)) if st is None else np.array(st["rows"], dtype=np.float64).reshape(-1, CURVE_LEN)
         self.points = self.done = 0 if st is None else int(st["points"])
+        if self.keep_rate is not None:
+            held = st if st is not None and st.get("best") is not None else None
+            if self.best is None:                                # (nothing allocated yet: applied by _alloc_best)
+                self._best_pending = held
+            else:
+                self._load_best(held)
+
+    def _load_best(self, st):
+        if st is None:
+            self.best.zero_()
+            self.best_row.zero_()
+            self.best_point.fill_(-1)
+            return
+        if st["best"].numel() != self.best.numel():
+            raise ValueError("checkpoint holds a best policy of %d parameters, this trainer's actor has %d"
+                             % (st["best"].numel(), self.best.numel()))
+        self.best.copy_(st["best"])
+        self.best_row.copy_(st["best_row"])
+        self.best_point.copy_(st["best_point"])
+
+    # -------------------------------------------------------------------------------------------- the kept policy
+    def _order_after_points(self):
+        """The current stream waits (on the device) for the last enqueued point: its decision and copy have landed."""
+        if self.event is not None:
+            torch.cuda.current_stream().wait_event(self.event)
+
+    def best_policy(self):
+        """``BestPolicy`` of the incumbent, or None (no eligible point yet).  Waits for the last point's event."""
+        if self.keep_rate is None or (self.best is None and self._best_pending is None):
+            return None
+        self._alloc_best()
+        self.wait()
+        point = int(self.best_point.cpu()[0])
+        if point < 0:
+            return None
+        return BestPolicy(point, self.best_row.cpu().numpy(), self.best.clone(), self.keep_rate)
+
+    def restore_best(self):
+        """live actor span <- the kept span where a point is held, as device copies on the current stream: no host read."""
+        self._alloc_best()
+        self._order_after_points()
+        with torch.no_grad():
+            self.live.copy_(torch.where(self.best_point[0] >= 0, self.best, self.live))

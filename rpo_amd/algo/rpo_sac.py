@@ -50,7 +50,7 @@ class RPOSAC(RPOTrainerBase):
                  clip_thres="inf", partial=False, partial_idx=None,
                  device=torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"),
                  num_envs=None, seed=None, backend=None, use_graph=None, updates_per_step=None, schedule=None,
-                 eval_episodes=None):
+                 eval_episodes=None, keep_best=None):
         base = getattr(env, "unwrapped", env)
         agent = PDSAC_PA(
             automatic_entropy_tuning, base.state_dim, base.action_dim, base.eq_num, base.ineq_num,
@@ -67,7 +67,7 @@ class RPOSAC(RPOTrainerBase):
                   corr_mode=corr_mode, grad_eps=grad_eps, clip_thres=clip_thres, eval_steps=eval_steps,
                   batch_size=batch_size, policy_fre=policy_fre, eval_fre=eval_fre, warmup=warmup, max_epochs=max_epochs,
                   fixed=fixed, partial=partial, eps=eps, eps_start=eps_start, eps_epoch=eps_epoch,
-                  eval_episodes=eval_episodes)
+                  eval_episodes=eval_episodes, keep_best=keep_best)
         self._setup(env, work_dir, name, logger, agent, hp, device, num_envs, seed, backend, use_graph, updates_per_step,
                     schedule=schedule)
         self._act_kw = {}        # the Gaussian head kernels emit finished (boxed, clipped) basic actions, never raw ones

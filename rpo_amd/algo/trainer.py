@@ -11,6 +11,7 @@ Data parallelism (``torch.distributed`` initialised, backend nccl == RCCL): rank
 ``[r * n_local, (r + 1) * n_local)`` and its own replay shard; the flat gradient slice of each optimiser is
 all-reduced (mean) once per update, so replicas stay bit-identical without parameter broadcasts.
 """
+import contextlib
 import copy
 import os
 
@@ -424,8 +425,19 @@ class RPOTrainerBase(object):
         ee = getattr(self, "eval_episodes", None)
         if ee is None:
             ee = _env_int("RPO_EVAL_EPISODES", None)
-        self._curve = CurveRunner(self, ee) if ee is not None else None      # (ValueError for anything but an integer >= 1)
+        # keep_best (RPO_KEEP_BEST): False, True (no violating step allowed) or the violation rate up to which a point is safe;
+        # the best evaluation point's actor is kept on the device (rpo_eval_keep_best), see `best` / `restore_best` / `using_best`
+        from .evaluation import check_keep_best, keep_best_from_env
+        kb = getattr(self, "keep_best", None)
+        if kb is None:
+            kb = keep_best_from_env(os.environ.get("RPO_KEEP_BEST"))
+        kb = check_keep_best(kb)
+        if kb is not None and ee is None:
+            raise ValueError("keep_best needs curve mode: the points it chooses among are those of eval_episodes=N "
+                             "(RPO_EVAL_EPISODES), which is not set")
+        self._curve = CurveRunner(self, ee, keep_best=kb) if ee is not None else None   # (ValueError for anything but an integer >= 1)
         self.eval_episodes = self._curve.n if self._curve is not None else None
+        self.keep_best = False if kb is None else kb
 
     # ------------------------------------------------------------------------------------------ projection API
     def process_action(self, state, action_partial, train=True):
@@ -1153,6 +1165,43 @@ class RPOTrainerBase(object):
         """``EvalResult`` (per-episode arrays) of the most recent curve point, or None."""
         return None if self._curve is None else self._curve.last()
 
+    @property
+    def best(self):
+        """The policy a ``keep_best`` run holds -> ``BestPolicy`` (``point``, ``step``, ``row``, ``params``, ``save(path)``), or
+        None: ``keep_best`` off, no eligible point yet, or a rank other than 0.  The choice was made on the device behind
+        every point's summary (``rpo_eval_keep_best``: the highest mean return among the points whose violation rate is at
+        most ``keep_best``; while there is none, the lowest rate); reading it waits for the last point's event."""
+        return None if self._curve is None else self._curve.best_policy()
+
+    def _need_keep_best(self, what):
+        if self._curve is None or self._curve.keep_rate is None:
+            raise ValueError("%s needs keep_best (with eval_episodes=N): this trainer keeps no best policy" % what)
+        return self._curve
+
+    def restore_best(self):
+        """"Restore best weights" at the end of a run: the kept span is copied into the live actor's span of the flat parameter
+        buffer (shared_param=True: the state embedding it shares with the critic included) by device copies on the current
+        stream, behind the last point's event -- no host synchronisation; nothing happens while no point is held.  Targets,
+        the rest of the critic, the multipliers, the Adam moments and step counters are untouched: training that goes on
+        afterwards steps the restored weights with the old moments."""
+        self._need_keep_best("restore_best()").restore_best()
+
+    @contextlib.contextmanager
+    def using_best(self):
+        """``with trainer.using_best():`` -- inside, the live actor IS the kept policy (``evaluate()``, ``act()``, ``eval()``
+        on either path see it); on exit, exception or not, the live span is back bit for bit.  Torch copies on the current
+        stream, no host read; with no point held the live policy stays.  Do not train inside the context."""
+        curve = self._need_keep_best("using_best()")
+        curve._alloc_best()
+        with torch.no_grad():
+            stash = curve.live.clone()
+        curve.restore_best()
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                curve.live.copy_(stash)
+
     def _advance_host(self, t):
         """Host mirrors of the device-side counters after vector step ``t``."""
         self._t = t
@@ -1512,8 +1561,8 @@ class RPOTrainerBase(object):
                      pending=self._pending, viol_steps=self.viol_steps, env_steps=self.env_steps,
                      capacity=b.capacity, row_floats=self.kernels.row_floats, algo=type(self).__name__,
                      env=self.kernels.name, projection_mode=self.projection_mode)
-        if self._curve is not None:                                 # (an additional entry: older checkpoints load without it)
-            state["eval_curve"] = self._curve.state()
+        if self._curve is not None:                                 # (an additional entry: older checkpoints load without it;
+            state["eval_curve"] = self._curve.state()               #  keep_best: + the kept span, its row and its point index)
         torch.save(state, os.path.join(d, "trainer_state.pth"))
 
     def load(self, weights_only=False):

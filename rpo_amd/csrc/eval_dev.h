@@ -89,6 +89,26 @@ __device__ __forceinline__ void rpo_eval_con_lane_update(float* __restrict__ con
     for (int q = 0; q < kW / 4; ++q) c4[q] = make_float4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
 }
 
+// ------------------------------------------------------------------------------------------------ keep-best criterion
+// ONE definition of "the candidate's curve row beats the incumbent's" (rpo_eval_keep_best; include/rpo_hip.h states it in
+// words, tests/test_keep_best_gpu.py in numpy).  A plain constexpr function: no launch-side qualifier, so the same
+// text compiles for the decide kernel and for host code.  IEEE comparisons only: a NaN compares false everywhere, so a
+// candidate whose rate is a NaN is unsafe and beats no incumbent.
+constexpr double keep_best_rate(const double* row) {
+    return row[RPO_CURVE_LENGTH] == 0.0 ? __builtin_huge_val() : row[RPO_CURVE_VIOL_STEPS] / row[RPO_CURVE_LENGTH];
+}
+
+constexpr bool keep_best_wins(const double* row, const double* best_row, long long best_point, double max_violation_rate) {
+    const double ret = row[RPO_CURVE_STATS];
+    if (row[RPO_CURVE_NONFINITE] > 0.0 || ret != ret) return false;          // ineligible: never taken
+    if (best_point < 0) return true;                                         // no incumbent
+    const double rate = keep_best_rate(row), best_rate = keep_best_rate(best_row), best_ret = best_row[RPO_CURVE_STATS];
+    const bool safe = rate <= max_violation_rate, best_safe = best_rate <= max_violation_rate;
+    if (safe != best_safe) return safe;
+    if (safe) return ret > best_ret;
+    return rate < best_rate || (rate == best_rate && ret > best_ret);
+}
+
 // ------------------------------------------------------------------------------------------------ per-step record
 // Row layout of the trace buffer (include/rpo_hip.h: RPO_TRACE_*), one definition for the fused kernel and rpo_eval_record.
 __host__ __device__ constexpr int trace_head(int obs_dim, int partial_dim, int action_dim) {

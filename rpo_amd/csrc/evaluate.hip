@@ -11,6 +11,8 @@
 //   eval_constraints     the stepwise path's per-constraint report (rpo_eval_constraints); the fused kernel's CON = 1 instances
 //                        update the same rows themselves (eval_dev.h: rpo_eval_con_lane_update).
 //   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
+//   keep_best_*_kernel   that row against the incumbent's on the device, and the predicated copy of the actor's parameters
+//                        (rpo_eval_keep_best; the criterion is eval_dev.h: keep_best_wins).
 //
 // Both update a lane's accumulator row through rpo_eval_lane_update (eval_dev.h).
 #include "cartsafe_dev.h"
@@ -432,6 +434,38 @@ __global__ __launch_bounds__(RPO_BLOCK) void summarize_combine_kernel(int n, int
     write_curve_row(row, ctrl, n, sum, mean, sq);
 }
 
+// ------------------------------------------------------------------------------------------- keep-best (rpo_eval_keep_best)
+// decide: ONE wave.  Every lane reads both rows and the held point (wave-uniform loads) and evaluates the criterion, so the
+// verdict is uniform; the loads of all lanes precede the stores in program order, and the stores have one owner each:
+// lane c < RPO_CURVE_LEN writes best_row[c], lane RPO_CURVE_LEN writes best_point[0].  A losing candidate writes nothing.
+__global__ __launch_bounds__(RPO_WAVE) void keep_best_decide_kernel(const double* row, double* best_row, long long* best_point,
+                                                                    long long point, double max_violation_rate) {
+    static_assert(RPO_CURVE_LEN < RPO_WAVE, "one lane per word of the row and one for the point");
+    const int lane = threadIdx.x;
+    const double mine = lane < RPO_CURVE_LEN ? row[lane] : 0.0;
+    const bool wins = rpo_eval_dev::keep_best_wins(row, best_row, best_point[0], max_violation_rate);
+    if (!wins) return;
+    if (lane < RPO_CURVE_LEN) best_row[lane] = mine;
+    else if (lane == RPO_CURVE_LEN) best_point[0] = point;
+}
+
+typedef float keep_v4 __attribute__((ext_vector_type(4)));
+
+// copy: predicated on the word the decide launch left (stream order makes it visible).  head: the floats in front of the
+// first 16-byte boundary of BOTH pointers -- all n when they sit at different offsets from one; then n4 16-byte chunks;
+// then the tail.  Grid-stride loops, 64-bit indices; every float of best has one writer.
+__global__ __launch_bounds__(RPO_BLOCK) void keep_best_copy_kernel(long long n, long long head, long long n4,
+                                                                   const float* __restrict__ src, float* __restrict__ best,
+                                                                   const long long* best_point, long long point) {
+    if (best_point[0] != point) return;
+    const long long tid = (long long)blockIdx.x * RPO_BLOCK + threadIdx.x, stride = (long long)gridDim.x * RPO_BLOCK;
+    const keep_v4* s4 = reinterpret_cast<const keep_v4*>(src + head);
+    keep_v4* d4 = reinterpret_cast<keep_v4*>(best + head);
+    for (long long i = tid; i < n4; i += stride) d4[i] = s4[i];
+    for (long long i = tid; i < head; i += stride) best[i] = src[i];
+    for (long long i = head + 4 * n4 + tid; i < n; i += stride) best[i] = src[i];
+}
+
 // rpo_cartsafe_evaluate (rec = 0: trace arguments unused), rpo_cartsafe_evaluate_record (rec = 1) and
 // rpo_cartsafe_evaluate_constraints (with_con = 1; rec = whether it got a trace)
 int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state, float* action,
@@ -508,6 +542,29 @@ int rpo_eval_summarize(int n, const float* acc, const long long* ctrl, double* r
         RPO_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(summarize_combine_kernel, dim3(1), dim3(RPO_BLOCK), 0, s, n, slots, (const double*)ws, ctrl, row_out);
+    RPO_LAUNCH_CHECK();
+    return 0;
+}
+
+int rpo_eval_keep_best(long long n_params, const float* src, float* best, const double* row, double* best_row,
+                       long long* best_point, long long point, double max_violation_rate, void* stream) {
+    if (n_params < 1 || point < 0 || !(max_violation_rate >= 0.0)) return RPO_ERR_ARG;
+    if (!src || !best || !row || !best_row || !best_point) return RPO_ERR_NULL;
+    const unsigned so = (unsigned)((uintptr_t)src & 15u), bo = (unsigned)((uintptr_t)best & 15u);
+    if (((so | bo) & 3u) || (((uintptr_t)row | (uintptr_t)best_row | (uintptr_t)best_point) & 7u)) return RPO_ERR_ARG;
+    // the same offset from a 16-byte boundary: scalar floats up to it, 16-byte chunks, scalar tail; otherwise all scalar
+    const long long to_boundary = ((16u - so) & 15u) / 4u;
+    const long long head = so != bo ? n_params : (to_boundary < n_params ? to_boundary : n_params);
+    const long long n4 = (n_params - head) / 4;
+    const long long widest = n4 > head ? n4 : head;            // (the tail is at most 3 floats: one workgroup at least)
+    const long long want = (widest + RPO_BLOCK - 1) / RPO_BLOCK;
+    const int blocks = (int)(want < 1 ? 1 : (want > RPO_MAX_GRID ? RPO_MAX_GRID : want));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(keep_best_decide_kernel, dim3(1), dim3(RPO_WAVE), 0, s, row, best_row, best_point, point,
+                       max_violation_rate);
+    RPO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(keep_best_copy_kernel, dim3(blocks), dim3(RPO_BLOCK), 0, s, n_params, head, n4, src, best,
+                       (const long long*)best_point, point);
     RPO_LAUNCH_CHECK();
     return 0;
 }

@@ -333,6 +333,22 @@ def eval_summarize(acc, ctrl, row_out, ws):
                                          _p(ws, torch.float64), _stream()), "rpo_eval_summarize")
 
 
+def eval_keep_best(src, best, row, best_row, best_point, point, max_violation_rate):
+    """Keep the best policy of a curve (rpo_eval_keep_best): the curve row ``row`` [CURVE_LEN] float64 of evaluation point
+    ``point`` against the incumbent's ``best_row``; if it wins (the criterion: include/rpo_hip.h), ``best_row`` <- ``row``,
+    ``best_point[0]`` <- ``point`` (int64 [1], -1: none held) and ``best`` <- ``src`` (float32 [n] each, any float alignment).
+    Decided and copied on the device: two launches, nothing read on the host."""
+    n = src.numel()
+    if src.dim() != 1 or best.dim() != 1 or best.numel() != n or n < 1:
+        raise RpoHipError("src and best must be float32 vectors of one length >= 1, got %s and %s"
+                          % (tuple(src.shape), tuple(best.shape)))
+    if row.numel() != CURVE_LEN or best_row.numel() != CURVE_LEN or best_point.numel() != 1:
+        raise RpoHipError("row and best_row must be float64[%d] and best_point int64[1]" % CURVE_LEN)
+    check(_lib.load().rpo_eval_keep_best(n, _p(src), _p(best), _p(row, torch.float64), _p(best_row, torch.float64),
+                                         _p(best_point, torch.int64), int(point), float(max_violation_rate), _stream()),
+          "rpo_eval_keep_best")
+
+
 def _act_outputs(kernels, n, action, proposal, iters, eq_resid, ineq_resid):
     """Shapes of the outputs of ``policy_act`` (the kernels index them by row: a smaller buffer would be written out of bounds)."""
     want = (("action", action, (n, kernels.action_dim)), ("proposal", proposal, (n, kernels.partial_dim)), ("iters", iters, (n,)),

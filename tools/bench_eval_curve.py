@@ -16,6 +16,14 @@ One trainer per leg (b shares a's), every leg warmed by one untimed region (grap
 rounds that alternate the legs; medians.  Reported: the five times, the added time per evaluation point of b..e over a, the
 share of eval() in leg b's wall time, and the time of one rpo_eval_summarize at 10 / 1024 / 2^20 episodes (events around
 100 back-to-back calls).  One process; run it under its own time limit.
+
+    timeout -k 10 900 python tools/bench_eval_curve.py --keep-best [--rounds 3] [--points 8] [--out profiles/eval_keep_best_bench.json]
+
+The ``keep_best`` leg instead: what keeping the best policy on the device (``rpo_eval_keep_best`` behind every point's summary)
+adds to a point.  For both workloads, 10 and 1024 episodes per point, overlapped and in order: two trainers of the same build,
+``keep_best=True`` and off (off: the launches of curve mode as it was), the same region, one untimed round and --rounds
+alternating rounds; medians, every sample, and the added time per point.  And the device time of ``rpo_eval_keep_best`` alone
+on a span of the cart actor's length, on the taken and on the not-taken branch (events around 100 back-to-back calls).
 """
 import argparse
 import json
@@ -76,15 +84,88 @@ def summarize_us(n, reps=100):
     return statistics.median(times)
 
 
+def keep_best_us(n_params, taken, reps=100):
+    """Device time of one rpo_eval_keep_best on a span of n_params floats.  taken: every call's return is strictly higher
+    than the incumbent's (decide writes, the copy runs); otherwise every call after the first ties and loses."""
+    from rpo_amd import ops
+    dev = torch.device("cuda")
+    src, best = torch.rand(n_params, device=dev), torch.zeros(n_params, device=dev)
+    rows = torch.zeros(reps + 6, ops.CURVE_LEN, dtype=torch.float64, device=dev)
+    rows[:, 12] = 200.0                                         # RPO_CURVE_LENGTH (no violating step: safe)
+    best_row = torch.zeros(ops.CURVE_LEN, dtype=torch.float64, device=dev)
+    best_point = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    times = []
+    for _ in range(6):
+        best_point.fill_(-1)
+        rows[:, 2] = torch.arange(reps + 6, device=dev, dtype=torch.float64) if taken else 1.0   # RPO_CURVE_STATS: the return
+        for k in range(5):
+            ops.eval_keep_best(src, best, rows[k], best_row, best_point, k, 0.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for k in range(5, reps + 5):
+            ops.eval_keep_best(src, best, rows[k], best_row, best_point, k, 0.0)
+        e1.record()
+        torch.cuda.synchronize()
+        assert int(best_point.cpu()[0]) == (reps + 4 if taken else 0)
+        times.append(e0.elapsed_time(e1) * 1e3 / reps)
+    return dict(median=statistics.median(times[1:]), all=times[1:])
+
+
+def keep_best_leg(a):
+    n = a.points * EVAL_FRE
+    line = dict(tool="bench_eval_curve --keep-best", device=torch.cuda.get_device_name(0), lanes=LANES, eval_fre=EVAL_FRE,
+                iterations=n, points=a.points, rounds=a.rounds, configs={})
+    span = None
+    for workload in ("cart_ddpg", "pen_ddpg"):
+        line["configs"][workload] = {}
+        for episodes in (10, 1024):
+            for overlap in (1, 0):
+                trs = {}
+                for name, kw in (("off", {}), ("on", dict(keep_best=True))):
+                    tr = make_trainer(LANES, torch.device("cuda"), 10 ** 9, capacity=64, workload=workload, eval_fre=EVAL_FRE,
+                                      schedule=dict(eval_overlap=overlap), eval_episodes=episodes, **kw)
+                    tr.vec.reset()
+                    trs[name] = tr
+                times = {name: [] for name in trs}
+                for rnd in range(a.rounds + 1):                 # round 0: untimed warm-up of both
+                    for name in (("off", "on") if rnd % 2 else ("on", "off")):
+                        before = len(trs[name].eval_curve)
+                        t, points = region(trs[name], n, True)
+                        assert points - before == a.points, (name, points, before)
+                        if rnd:
+                            times[name].append(t)
+                assert trs["on"].best is not None and trs["off"].best is None
+                lo, hi = trs["on"].agent.flat.actor_range
+                span = hi - lo if workload == "cart_ddpg" else span
+                med = {name: statistics.median(ts) for name, ts in times.items()}
+                line["configs"][workload]["%d_%s" % (episodes, "overlap" if overlap else "inorder")] = dict(
+                    wall_s=med, all_s=times, span_floats=hi - lo, best_point=trs["on"].best.point,
+                    added_ms_per_point=(med["on"] - med["off"]) * 1e3 / a.points,
+                    spread_ms_per_point={name: (max(ts) - min(ts)) * 1e3 / a.points for name, ts in times.items()})
+                del trs
+                torch.cuda.empty_cache()
+    line["us_per_keep_best"] = dict(span_floats=span, taken=keep_best_us(span, True), not_taken=keep_best_us(span, False))
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--points", type=int, default=8)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--keep-best", action="store_true", help="the keep_best leg instead of legs a..e")
     a = ap.parse_args()
     os.environ["RPO_VERBOSE"] = "0"
     n = a.points * EVAL_FRE
     spin_up(torch.device("cuda"))
+    if a.keep_best:
+        s = json.dumps(keep_best_leg(a))
+        print(s)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(s + "\n")
+        return
     line = dict(tool="bench_eval_curve", device=torch.cuda.get_device_name(0), lanes=LANES, eval_fre=EVAL_FRE, iterations=n,
                 points=a.points, rounds=a.rounds, configs={})
     for workload in ("cart_ddpg", "pen_ddpg"):
