@@ -208,6 +208,7 @@ extern "C" {
 #define RPO_STREAM_POLICY 4
 #define RPO_STREAM_EVOPF_DEMAND 5 /* episode load profile: Dirichlet + power factors (data/demand.py:53-62) */
 #define RPO_STREAM_EVOPF_PRICE 6  /* episode price profile: magnitude + hourly noise   (data/price.py:41-43)  */
+#define RPO_STREAM_EVAL_OBS 7     /* evaluate(obs_noise=): counter (episode, step, this + 0x100 * column, 0), words 0 and 1 */
 
 int rpo_abi_version(void);
 
@@ -926,6 +927,39 @@ int rpo_pendulum_evaluate_constraints(const rpo_mlp* actor_host, int gauss, floa
                                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                                       int max_episode_steps, float viol_thresh, float* trace, int trace_rows, int trace_steps,
                                       float* con, void* stream);
+
+/* The same launches with observation noise (RPOTrainerBase.evaluate(obs_noise=)): at every step s the actor and the projection
+ * of episode i read o~[q] = o[q] + sigma[q] * z(i, s, q) -- an f32 multiply, then an f32 add, not fused -- with z the Box-Muller
+ * normal of words 0 and 1 of Philox(noise_seed; i, s, RPO_STREAM_EVAL_OBS + 0x100 * q, 0), keyed by the ABSOLUTE step: the
+ * split of the horizon over launches changes nothing.  A column with sigma[q] == 0 is not drawn and keeps its bits.  The env
+ * steps the TRUE state: rewards, violations, accumulators, the tail of the record and the report are those of the true state
+ * under the action chosen from the noisy observation, and nothing of the noise reaches the env's state or observation rows;
+ * the head of the record holds o~, what the policy read.  sigma_host: sigma_len = 6 | 5 host floats >= 0, copied into the
+ * launch (NULL: RPO_ERR_NULL; another length, a negative or a non-finite entry: RPO_ERR_ARG, before any HIP call).  trace
+ * and con may each be NULL (no record / no report); otherwise the arguments of rpo_<env>_evaluate_constraints.
+ * == per step: rpo_eval_obs_noise(step s) in front of the launches of rpo_<env>_evaluate_constraints' sequence, the actor and
+ *    the projection reading its output, bit for bit. */
+int rpo_cartsafe_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                float viol_thresh, float* trace, int trace_rows, int trace_steps, float* con,
+                                const float* sigma_host, int sigma_len, unsigned long long noise_seed, void* stream);
+int rpo_pendulum_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
+                                int trace_rows, int trace_steps, float* con, const float* sigma_host, int sigma_len,
+                                unsigned long long noise_seed, void* stream);
+
+/* The stepwise form of the noise (any env): out[i, q] = obs[i, q] + sigma[q] * z(i, step, q) for i < n, q < obs_dim, with the
+ * draw and the arithmetic above (== per column q with sigma[q] != 0: rpo_philox_normal(n, ., seed, 0, step,
+ * RPO_STREAM_EVAL_OBS + 0x100 * q, NULL), then the unfused multiply and add); a column with sigma[q] == 0 is copied.  obs
+ * [n, obs_stride], out [n, out_stride] (strides >= obs_dim; columns beyond obs_dim are not touched), sigma: obs_dim DEVICE
+ * floats.  out is a buffer of its own, never obs (RPO_ERR_ARG): CartSafe-v0's observation rows are the env's state.
+ * 1 <= obs_dim <= 4096, 0 <= step < 2^24.  One thread per element, grid-stride. */
+int rpo_eval_obs_noise(int n, const float* obs, int obs_stride, int obs_dim, const float* sigma, unsigned long long seed,
+                       int step, float* out, int out_stride, void* stream);
 
 /* Projected actions for caller-supplied observations (RPOTrainerBase.act, rpo_amd/algo/acting.py): n rows obs [n, obs_stride]
  * (obs_stride >= 6 | 5 floats) -> action [n, 2] (8-byte aligned), and where the pointer is not NULL: proposal [n] (what the

@@ -63,8 +63,8 @@ class _LagrangianBase(RPOTrainerBase):
                 pen = max_eq + rows[:, c["ineq_viol"][0]:c["ineq_viol"][1]].max(dim=1).values
                 rows[:, c["reward"][0]] -= 10.0 * pen
 
-    def _eval_action(self, v, iters=None, eval_steps=None, eval_lr=None):    # (no projection: `iters` stays as it is)
-        v.action.copy_(self._deterministic(v.obs))
+    def _eval_action(self, v, iters=None, eval_steps=None, eval_lr=None, obs=None):    # (no projection: `iters` stays as it is)
+        v.action.copy_(self._deterministic(v.obs if obs is None else obs))
         return v.action                                       # ... and the proposal is the action
 
     def _eval_proposal_dim(self):

@@ -26,6 +26,14 @@ live steps on which each inequality exceeds ``viol_thresh``), folded from the va
 fused kernel's CON instances, ``rpo_eval_constraints`` or ``constraints_torch`` on the stepwise path -- and returned as
 ``EvalResult.constraints`` (``ConstraintReport``).  Every other result is the same bits with and without it.
 
+Observation noise (``evaluate(obs_noise=sigma)``): at every step the actor and the projection read ``o + sigma * z`` while the
+env steps the true state.  ``z(i, s, q)`` for episode i, evaluation step s, column q is the Box-Muller normal of words 0 and 1
+of Philox with key = the evaluation's seed and counter (i, s, RPO_STREAM_EVAL_OBS + 0x100 q, 0) -- ``philox_normal(seed,
+id_base 0, salt s, that tag)`` of every backend -- and the sum is an f32 multiply, then an f32 add.  The fused kernel's NOISE
+instances add it to their staged tile (``rpo_<env>_evaluate_noisy``); the stepwise path fills a buffer of its own per step
+(``rpo_eval_obs_noise``, or ``obs_noise_torch``) and hands it to ``_eval_action(obs=)`` and the record.  Both paths compute
+the same bits; None, 0 and all-zero run the clean evaluation's launches.  ``eval()``, curve mode and ``act()`` never see noise.
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
 does not record trajectories and produces no per-constraint reports.  With the trainer argument ``keep_best`` every point's
@@ -54,11 +62,11 @@ class EvalResult(object):
     whose max inequality violation exceeds the vector env's ``viol_thresh``; ``proj_iters``: GRG iterations summed over the
     episode; ``nonfinite``: a live step produced a non-finite reward or violation.  ``path``: "fused" or "stepwise".
     ``trajectory`` / ``constraints``: the ``EvalTrajectory`` of ``record=`` / the ``ConstraintReport`` of ``constraints=True``,
-    else None."""
+    else None.  ``obs_noise``: the float32 sigma vector [obs_dim] of ``obs_noise=``, None for a clean evaluation."""
 
     FIELDS = ("ret", "length", "mean_ineq", "mean_eq", "max_ineq", "max_eq", "viol_steps", "proj_iters", "nonfinite")
 
-    def __init__(self, acc, path, horizon, seed, trajectory=None, constraints=None):
+    def __init__(self, acc, path, horizon, seed, trajectory=None, constraints=None, obs_noise=None):
         acc = np.asarray(acc, dtype=np.float32).reshape(-1, 8)
         word = acc[:, _WORD].view(np.int32)
         self.ret = acc[:, _RET].astype(np.float64)
@@ -73,6 +81,7 @@ class EvalResult(object):
         self.path, self.horizon, self.seed = path, int(horizon), seed
         self.trajectory = trajectory
         self.constraints = constraints
+        self.obs_noise = None if obs_noise is None else np.array(obs_noise, dtype=np.float32)
 
     @property
     def episodes(self):
@@ -99,7 +108,8 @@ class EvalTrajectory(object):
     """The per-step record of ``evaluate(record=...)``: numpy arrays indexed [episode, step, ...] over the recorded episodes
     (the first ``episodes`` of the evaluation) and ``horizon`` steps.
 
-    ``obs`` [., ., obs_dim]: the observation the actor and the projection read; ``proposal`` [., ., partial_dim]: the partial
+    ``obs`` [., ., obs_dim]: the observation the actor and the projection read -- with ``evaluate(obs_noise=)`` the NOISY one,
+    what the policy saw, not the state the env stepped (reward, done, ineq and eq are the true state's); ``proposal`` [., ., partial_dim]: the partial
     action the policy handed to the projection, after the tanh box or the mean head (EVOPF-v0 RPODDPG with the fused MLPs hands
     over the raw actor output -- its state-dependent box is applied inside the projection kernel -- and that is what is
     recorded; the Lagrangian baselines have no projection: the proposal is the action); ``action`` [., ., action_dim]: the
@@ -278,6 +288,20 @@ def record_torch(rows, cols, obs, proposal, action, iters, step, acc, trace):
     trace[step] = row
 
 
+def obs_noise_torch(tr, obs, sigma, seed, step, out):
+    """``rpo_eval_obs_noise`` from the backend's ``philox_normal`` and torch ops (backends without the kernel: the CPU oracle):
+    out[:, q] = obs[:, q] + sigma[q] * z(., step, q), an unfused multiply and add; a column with sigma[q] == 0 is copied.
+    obs, out [n, obs_dim]; sigma: float32 numpy [obs_dim]."""
+    n = obs.shape[0]
+    out.copy_(obs)
+    z = torch.zeros(n, dtype=torch.float32, device=obs.device)
+    for q in range(obs.shape[1]):
+        if sigma[q] == 0:
+            continue
+        tr.backend.philox_normal(z, seed, 0, int(step), hip_ops.STREAM_EVAL_OBS + 0x100 * q)
+        out[:, q] = obs[:, q] + z * float(sigma[q])
+
+
 def accumulate_torch(rows, cols, iters, step, viol_thresh, acc):
     """``rpo_eval_accumulate`` in torch ops (backends without the kernel: the CPU oracle), with eval()'s expressions."""
     n = acc.shape[0]
@@ -353,6 +377,37 @@ def check_constraints(constraints):
     return bool(constraints)
 
 
+def check_obs_noise(obs_noise, obs_dim):
+    """``obs_noise`` of evaluate() -> None (None) or the float32 sigma vector [obs_dim]: a number >= 0 is broadcast, a sequence
+    of ``obs_dim`` numbers >= 0 is taken as it is.  ValueError for a negative or non-finite entry, a bool (alone or as an
+    entry), another length or anything that is no number."""
+    if obs_noise is None:
+        return None
+    bad = ValueError("evaluate: obs_noise must be None, a number >= 0 or %d numbers >= 0, got %r" % (obs_dim, obs_noise))
+    if isinstance(obs_noise, (bool, np.bool_, str, bytes)):
+        raise bad
+    if isinstance(obs_noise, torch.Tensor):
+        obs_noise = obs_noise.detach().cpu().numpy()
+    try:
+        if np.ndim(obs_noise) and any(isinstance(x, (bool, np.bool_)) for x in np.asarray(obs_noise, dtype=object).reshape(-1)):
+            raise bad
+        a = np.asarray(obs_noise)
+        if a.dtype == np.bool_ or a.dtype.kind not in "fiu":
+            raise bad
+        a = a.astype(np.float64)
+    except (TypeError, ValueError):
+        raise bad
+    if a.ndim == 0:
+        a = np.full(obs_dim, float(a))
+    if a.shape != (obs_dim,) or not np.all(np.isfinite(a)) or np.any(a < 0):
+        raise bad
+    with np.errstate(over="ignore"):
+        sigma = a.astype(np.float32)
+    if not np.all(np.isfinite(sigma)):                           # (a float64 above the float32 range)
+        raise bad
+    return sigma
+
+
 def check_budget(tr, eval_steps, eval_lr, what="evaluate"):
     """The per-call projection overrides of ``evaluate()`` / ``act()`` -> (eval_steps, eval_lr) with None replaced by the
     trainer's: ``eval_steps`` an integer >= 0, ``eval_lr`` a finite number (ValueError otherwise)."""
@@ -374,10 +429,13 @@ def check_budget(tr, eval_steps, eval_lr, what="evaluate"):
 
 
 def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
-             constraints=False):
+             constraints=False, obs_noise=None):
     """See ``RPOTrainerBase.evaluate``."""
     n = check_episodes(episodes)
     want_con = check_constraints(constraints)
+    sigma = check_obs_noise(obs_noise, tr.kernels.obs_dim)
+    if sigma is not None and not sigma.any():                    # 0 and all-zero: the clean evaluation, nothing new runs
+        sigma = None
     budget = (None, None) if eval_steps is None and eval_lr is None else check_budget(tr, eval_steps, eval_lr)
     R = check_record(record, n)
     if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
@@ -415,14 +473,15 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
     # the per-constraint report: step 0 writes every row from scratch, nothing to clear
     con = torch.empty(n, hip_ops.con_width(k.ineq_num, k.eq_num), device=tr.device) if want_con else None
+    noise = {} if sigma is None else dict(noise=(sigma, seed))   # keyed by the evaluation's seed, like the reset stream
     with torch.no_grad():
         if fused:
             path = "fused"
-            _run_fused(tr, v, acc, H, trace=trace, budget=budget, con=con)
+            _run_fused(tr, v, acc, H, trace=trace, budget=budget, con=con, **noise)
         else:
             path = "stepwise"
-            _run_stepwise(tr, v, acc, H, trace=trace, budget=budget, con=con)
-    res = EvalResult(acc.cpu().numpy(), path, H, seed)
+            _run_stepwise(tr, v, acc, H, trace=trace, budget=budget, con=con, **noise)
+    res = EvalResult(acc.cpu().numpy(), path, H, seed, obs_noise=sigma)
     if want_con:
         res.constraints = ConstraintReport.from_rows(con.cpu().numpy(), k.ineq_num, k.eq_num, res.length, v.viol_thresh,
                                                      getattr(tr.base_env, "ineq_names", None),
@@ -432,12 +491,14 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     return res
 
 
-def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None):
+def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
     trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
     (rpo_<env>_evaluate_record).  ``budget``: evaluate()'s per-call (eval_steps, eval_lr), None: the trainer's.  ``con``: the
-    per-constraint report [n, W] every launch continues (rpo_<env>_evaluate_constraints)."""
+    per-constraint report [n, W] every launch continues (rpo_<env>_evaluate_constraints).  ``noise``: (sigma float32 numpy
+    [obs_dim], seed) of ``obs_noise=`` (rpo_<env>_evaluate_noisy; the draw is keyed by the absolute step t0 + s); None: the
+    kernels' ``evaluate`` gets no such keyword."""
     n = v.n
     eval_steps = tr.eval_steps if budget[0] is None else budget[0]
     eval_lr = tr.eval_lr if budget[1] is None else budget[1]
@@ -447,30 +508,44 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
     kw = {} if trace is None else dict(trace=trace)
     if con is not None:
         kw["con"] = con
+    if noise is not None:
+        kw["noise"] = noise
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
                             v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo, tr._box_hi,
                             eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps, v.viol_thresh, **kw)
 
 
-def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None):
+def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, noise=None):
     """eval()'s loop: the trainer's deterministic action + projection, one env step without auto-reset, the accumulator
     update.  Finished lanes keep stepping (as in eval()); their rows no longer change.  ``trace``: the zeroed record
     [H, R, W]; the step's row goes in before the accumulator update (which ends the lanes the step finished), from a copy
     of the observation the policy read (the step overwrites it).  ``con``: the per-constraint report [n, W], updated before
-    the accumulators for the same reason."""
+    the accumulators for the same reason.  ``noise``: (sigma, seed) of ``obs_noise=``: step i's noisy observation goes into a
+    buffer of its own (never into the env's rows: CartSafe-v0's observation IS its state), which the policy, the projection
+    and the record read; the env steps what it holds."""
     k = tr.kernels
     rows = torch.zeros(v.n, k.ring_floats, device=tr.device)
     iters = torch.zeros(v.n, dtype=torch.int32, device=tr.device)
     update = getattr(tr.backend, "eval_accumulate", None) or accumulate_torch
     record = getattr(tr.backend, "eval_record", None) or record_torch
     report = getattr(tr.backend, "eval_constraints", None) or constraints_torch
-    obs_in = torch.zeros_like(v.obs) if trace is not None else None
+    obs_in = torch.zeros_like(v.obs) if trace is not None or noise is not None else None
+    kw = {} if budget == (None, None) else dict(eval_steps=budget[0], eval_lr=budget[1])
+    if noise is not None:
+        sigma, seed = noise
+        perturb = getattr(tr.backend, "eval_obs_noise", None)
+        sigma_dev = torch.as_tensor(sigma, device=tr.device)
+        kw["obs"] = obs_in
     for i in range(H):
-        if trace is not None:
+        if noise is not None:
+            if perturb is not None:
+                perturb(v.obs, sigma_dev, seed, i, obs_in)
+            else:
+                obs_noise_torch(tr, v.obs, sigma, seed, i, obs_in)
+        elif trace is not None:
             obs_in.copy_(v.obs)
-        proposal = tr._eval_action(v, iters=iters) if budget == (None, None) else \
-            tr._eval_action(v, iters=iters, eval_steps=budget[0], eval_lr=budget[1])
+        proposal = tr._eval_action(v, iters=iters, **kw)
         v.step(v.action, rows=rows, cap_steps=1, auto_reset=False)
         if trace is not None:
             record(rows, k.cols, obs_in, proposal, v.action, iters, i, acc, trace)

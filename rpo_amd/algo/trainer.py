@@ -1418,13 +1418,15 @@ class RPOTrainerBase(object):
     def _eval_partial(self, obs):
         raise NotImplementedError
 
-    def _eval_action(self, v, iters=None, eval_steps=None, eval_lr=None):
+    def _eval_action(self, v, iters=None, eval_steps=None, eval_lr=None, obs=None):
         """Deterministic policy + eval_steps projection iterations into v.action (rpo_ddpg.py:224-226); ``iters`` (int32 [n],
         optional): the projection's iteration count per lane.  Returns the proposal: the partial action [n * partial_dim]
         handed to the projection (``evaluate(record=...)`` records it).  ``eval_steps`` / ``eval_lr``: ``evaluate()``'s
-        per-call overrides (None: the trainer's)."""
-        ap = self._eval_partial(v.obs)
-        self.kernels.act_project(v.obs, ap, None, v.action, iters, hip_ops.NOISE_NONE, 0.0, 0.0, 0.0, self._box_lo,
+        per-call overrides (None: the trainer's).  ``obs``: the observation the actor and the projection read instead of
+        ``v.obs`` (``evaluate(obs_noise=)``: a buffer of its own, the env's rows stay as they are)."""
+        obs = v.obs if obs is None else obs
+        ap = self._eval_partial(obs)
+        self.kernels.act_project(obs, ap, None, v.action, iters, hip_ops.NOISE_NONE, 0.0, 0.0, 0.0, self._box_lo,
                                  self._box_hi, self.eval_steps if eval_steps is None else eval_steps,
                                  self.eval_lr if eval_lr is None else eval_lr, self.corr_eps, self.corr_momentum,
                                  **self._act_kw)
@@ -1477,7 +1479,7 @@ class RPOTrainerBase(object):
         return tuple(out)
 
     def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
-                 constraints=False):
+                 constraints=False, obs_noise=None):
         """Evaluate the current policy on ``episodes`` independent episodes -> ``EvalResult`` (per-episode arrays; ``summary()``
         is eval()'s 10-tuple).  The policy, projection and horizon are eval()'s: deterministic actor (RPOSAC: the mean head),
         ``eval_steps`` / ``eval_lr`` / ``corr_eps`` / ``corr_momentum``, at most min(500, max_episode_steps, the env's
@@ -1495,10 +1497,20 @@ class RPOTrainerBase(object):
         per-constraint breakdown on the device and returns it as ``result.constraints`` (``ConstraintReport``: ``ineq_max``,
         ``ineq_steps``, ``eq_max`` [episode, constraint], ``names``, ``worst()``, ``rate()``); it combines with every other
         argument and changes no other result; False: ``result.constraints`` is None and the launches are those without it.
-        Curve mode produces no reports: ``eval_curve_last.constraints`` is None.  See rpo_amd/algo/evaluation.py."""
+        Curve mode produces no reports: ``eval_curve_last.constraints`` is None.  ``obs_noise``: sensor noise -- None
+        (default), a number sigma >= 0 or a sequence of ``obs_dim`` numbers >= 0 (ValueError for a negative or non-finite
+        entry, a bool or another length).  At every step the actor AND the projection of episode i read
+        ``o + sigma * z`` with ``z ~ N(0, 1)`` drawn on the device (Philox keyed by ``seed``, the episode, the step and the
+        column: reproducible from ``(seed, obs_noise)``, the same on both paths and for any split into launches), while the
+        env steps the TRUE state: returns, violations, the constraint report and the reward / violation columns of the record
+        are those of the true trajectory under the actions chosen from the noisy observations;
+        ``result.trajectory.obs`` holds the noisy observation, ``result.obs_noise`` the float32 sigma vector.  A column with
+        sigma 0 keeps its bits; None, 0 and all-zero are the clean evaluation (the same launches and bits as without the
+        argument, ``result.obs_noise`` None).  ``eval()``, curve mode, ``keep_best``, ``act()``, training and checkpoints
+        never see noise.  See rpo_amd/algo/evaluation.py."""
         from .evaluation import evaluate
         return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record,
-                        eval_steps=eval_steps, eval_lr=eval_lr, constraints=constraints)
+                        eval_steps=eval_steps, eval_lr=eval_lr, constraints=constraints, obs_noise=obs_noise)
 
     def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0, profile=False):
         """The policy's projected actions for caller-supplied observations -> ``ActResult`` (torch tensors on the trainer's

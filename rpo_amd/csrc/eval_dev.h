@@ -44,6 +44,20 @@ __device__ __forceinline__ void rpo_eval_lane_update(float* __restrict__ acc, in
     a4[1] = hi;
 }
 
+// ------------------------------------------------------------------------------------------------ observation noise
+// evaluate(obs_noise=): ONE definition of the perturbed observation for the fused kernel's NOISE = 1 instances and
+// rpo_eval_obs_noise.  Column q of episode i at the evaluation's absolute step: o + sigma * z, z = the normal of
+// rpo_philox_normal(seed, id_base 0, salt step, RPO_STREAM_EVAL_OBS + 0x100 * q) -- the reset's idiom for further blocks of
+// one stream -- as an f32 multiply and an f32 add (torch's obs + sigma * z).  sigma == 0: not drawn, the bits of o.
+__device__ __forceinline__ float rpo_eval_noisy_obs(float o, float sigma, uint64_t seed, int i, int step, int q) {
+    RPO_FP_STRICT
+    if (sigma == 0.0f) return o;
+    const rpo_u4 r = rpo_philox(seed, (uint32_t)i, (uint32_t)step, (uint32_t)RPO_STREAM_EVAL_OBS + 0x100u * (uint32_t)q);
+    const float z = rpo_normal(r.x, r.y);
+    const float d = sigma * z;
+    return o + d;
+}
+
 // ------------------------------------------------------------------------------------------------ per-constraint report
 // Row layout of the report (include/rpo_hip.h: RPO_CON_*): ineq_max[NI] | ineq_steps[NI] | eq_max[NE] | zeros, and ONE
 // definition of a cell's update for the fused kernel's CON = 1 instances and rpo_eval_constraints.

@@ -8,6 +8,8 @@
 //   eval_accumulate      the stepwise path's update: reads the transition rows rpo_<env>_step wrote.
 //   eval_record          the stepwise path's per-step record (rpo_eval_record); the fused kernel's REC = 1 instances write the
 //                        same rows themselves (eval_dev.h: trace_store_head / trace_store_tail).
+//   eval_obs_noise       the stepwise path's observation noise (rpo_eval_obs_noise); the fused kernel's NOISE = 1 instances
+//                        add the same values to their staged tile (eval_dev.h: rpo_eval_noisy_obs).
 //   eval_constraints     the stepwise path's per-constraint report (rpo_eval_constraints); the fused kernel's CON = 1 instances
 //                        update the same rows themselves (eval_dev.h: rpo_eval_con_lane_update).
 //   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
@@ -53,13 +55,22 @@ template <class ENV>
 struct EvalConArgs : EvalArgs<ENV> {
     float* con;                   // [n, con_width(kIneq, kEq)] per-constraint report (RPO_CON_*)
 };
-template <class ENV, int CON> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
-template <class ENV> struct EvalArgsOf<ENV, 1> { typedef EvalConArgs<ENV> type; };
+// The NOISE = 1 instances (evaluate(obs_noise=)) take sigma by value and the key of the draw behind the same arguments (con:
+// NULL for their CON = 0 instances, which never read it); the NOISE = 0 instances keep their parameter types.
+template <class ENV>
+struct EvalNoiseArgs : EvalConArgs<ENV> {
+    float sigma[8];               // per observation column, zeros beyond kObs; 0: the column is not drawn
+    unsigned long long noise_seed;
+};
+template <class ENV, int CON, int NOISE> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
+template <class ENV> struct EvalArgsOf<ENV, 1, 0> { typedef EvalConArgs<ENV> type; };
+template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 1> { typedef EvalNoiseArgs<ENV> type; };
 
 // What one env step leaves for the statistics: reward, done and the violations of the transition row, without the row --
 // their maxima for the accumulators, and the row's ineq_viol / eq_viol columns themselves (gi / he) for the report.
 // Observations are staged from the env's observation rows: for SpringPendulum those the stepwise path hands the actor
-// and the projection (after an injected initial state they come from torch's cos / sin, not from sincosf).
+// and the projection (after an injected initial state they come from torch's cos / sin, not from sincosf).  `stage` writes
+// element (r, q) of the tile with thread r * kObs + q (stage_noise below relies on it).
 template <class ENV>
 struct EvalEnv;
 
@@ -68,6 +79,12 @@ struct EvalEnv<CartEnv> {
     static constexpr int kObs = 6, kIneq = 6, kEq = 1;
     __device__ static __forceinline__ void stage(const rpo_cart_dev::StepArgs& p, int row0, int rows, float* in_s, int stride) {
         CartEnv::stage_obs(p, row0, rows, in_s, stride);
+    }
+    // the state `lane` steps: the staged row IS the state -- unless it carries noise, then the env's own row (the same bits
+    // without noise: the row was staged from it)
+    template <int NOISE>
+    __device__ static __forceinline__ const float* true_state(const rpo_cart_dev::StepArgs& p, int i, const float* staged) {
+        return NOISE ? p.state + (size_t)i * 6 : staged;
     }
     __device__ static __forceinline__ void lane(const rpo_cart_dev::StepArgs& p, const rpo_cart_dev::CartConsts& c, int i,
                                                 const float* obs, float2 a, float& reward, float& done, float& ineq, float& eq,
@@ -98,6 +115,10 @@ struct EvalEnv<PendEnv> {
             in_s[r * stride + q] = (row0 + r < p.n) ? p.obs[(size_t)(row0 + r) * 5 + q] : 0.0f;
         }
     }
+    template <int NOISE>                                         // (`lane` reads p.internal whatever was staged)
+    __device__ static __forceinline__ const float* true_state(const rpo_pend_dev::StepArgs&, int, const float* staged) {
+        return staged;
+    }
     __device__ static __forceinline__ void lane(const rpo_pend_dev::StepArgs& p, const PendEnv::Consts&, int i, const float*,
                                                 float2 a, float& reward, float& done, float& ineq, float& eq,
                                                 float (&gi)[kIneq], float (&he)[kEq]) {
@@ -120,8 +141,26 @@ struct EvalEnv<PendEnv> {
 // overwrites its observation row), the tail after it.  Nothing of the record is computed in, or alive across, the MFMA loops.
 // CON = 1: a live lane also folds the step's per-constraint values into row i of p.con, read and written in global memory
 // inside the step (rpo_eval_con_lane_update) -- likewise nothing of it crosses the MFMA loops.
-template <class ENV, int EIN, int H, int RT, int REC, int CON>
-__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON>::type p, typename ENV::Consts c) {
+// NOISE = 1: the thread that staged element (r, q) of the tile adds sigma[q] * z(row0 + r, s, q) to it in LDS
+// (rpo_eval_noisy_obs) before the forward's barrier -- the actor, the projection and the record's head read the noisy tile, the
+// env steps its own state (EvalEnv::true_state).  The draw ends in that LDS word: nothing of it is alive in the MFMA loops.
+template <class ENV, class ARGS>
+__device__ __forceinline__ void stage_noise(const ARGS& p, int row0, int rows, int n, int s, float* in_s, int stride) {
+    constexpr int kObs = EvalEnv<ENV>::kObs;
+    const int tid = threadIdx.x;
+    if (tid >= rows * kObs) return;
+    const int r = tid / kObs, q = tid - r * kObs;
+    if (row0 + r >= n) return;
+    float sigma = 0.0f;
+#pragma unroll
+    for (int u = 0; u < kObs; ++u)                               // (selects on constant indices: the by-value array stays in SGPRs)
+        if (q == u) sigma = p.sigma[u];
+    float* o = in_s + r * stride + q;
+    *o = rpo_eval_dev::rpo_eval_noisy_obs(*o, sigma, p.noise_seed, row0 + r, s, q);
+}
+
+template <class ENV, int EIN, int H, int RT, int REC, int CON, int NOISE>
+__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON, NOISE>::type p, typename ENV::Consts c) {
     typedef TileLds<EIN, RT, 8, 8> Lds;                          // 16 * RT lanes per workgroup; OBS <= 8
     __shared__ Lds lds;
     constexpr int kInS = Lds::kS;
@@ -136,6 +175,7 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
         const bool live = mine && (s == 0 || (__float_as_int(p.acc[(size_t)i * RPO_EVAL_LEN + 7]) & RPO_EVAL_ALIVE));
         if (!__syncthreads_or(live)) return;                     // (also the barrier in front of the LDS tiles' reuse)
         EvalEnv<ENV>::stage(p.step, row0, kLanes, lds.in_s, kInS);
+        if constexpr (NOISE) stage_noise<ENV>(p, row0, kLanes, n, s, lds.in_s, kInS);
         mlp_tile_forward<EIN, H, RT, Lds>(p.actor, lds, row0, n, nullptr, nullptr, p.gauss ? 0 : 1, p.scale, p.base);
         if (live) {
             float ap = lds.out[tid * 2];
@@ -148,7 +188,8 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
             if (REC && i < p.trace_rows)
                 rpo_eval_dev::trace_store_head<kObs>(p.trace + ((size_t)s * p.trace_rows + i) * kW, lds.in_s + tid * kInS, ap, a, k);
             float reward, done, ineq, eq, gi[EvalEnv<ENV>::kIneq], he[EvalEnv<ENV>::kEq];
-            EvalEnv<ENV>::lane(p.step, c, i, lds.in_s + tid * kInS, a, reward, done, ineq, eq, gi, he);
+            EvalEnv<ENV>::lane(p.step, c, i, EvalEnv<ENV>::template true_state<NOISE>(p.step, i, lds.in_s + tid * kInS), a, reward,
+                               done, ineq, eq, gi, he);
             if (REC && i < p.trace_rows)
                 rpo_eval_dev::trace_store_tail(p.trace + ((size_t)s * p.trace_rows + i) * kW + trace_head(kObs, 1, 2), reward, done,
                                                ineq, eq);
@@ -161,23 +202,48 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
     }
 }
 
-template <class ENV, int REC, int CON>
-int launch_eval(const typename EvalArgsOf<ENV, CON>::type& args, const typename ENV::Consts& c, int n, void* stream) {
+template <class ENV, int REC, int CON, int NOISE = 0>
+int launch_eval(const typename EvalArgsOf<ENV, CON, NOISE>::type& args, const typename ENV::Consts& c, int n, void* stream) {
     // the rollout's tile rule (fused.hip launch_rollout): 64 lanes per workgroup once that still fills the chip.  E = 128
     // only: the E = 256 instance spills (~150 bytes of scratch per lane) -- such actors evaluate on the stepwise path.
     if (args.actor.E != 128) return RPO_ERR_ARG;
     if (n >= 64 * 192) {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON, NOISE>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     } else {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON, NOISE>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     }
     RPO_LAUNCH_CHECK();
     return 0;
 }
 
-// rec / con of the entry points -> the instance; con == NULL: the launches of rpo_<env>_evaluate[_record] as they were
+// The sigma of the *_evaluate_noisy entry points: `len` host floats, finite and >= 0 (checked before any HIP call).
+struct EvalNoise {
+    const float* sigma_host;
+    int len;
+    unsigned long long seed;
+};
+int check_eval_noise(const EvalNoise& nz, int obs_dim) {
+    if (!nz.sigma_host) return RPO_ERR_NULL;
+    if (nz.len != obs_dim) return RPO_ERR_ARG;
+    for (int q = 0; q < obs_dim; ++q)
+        if (!(nz.sigma_host[q] >= 0.0f) || !__builtin_isfinite(nz.sigma_host[q])) return RPO_ERR_ARG;
+    return 0;
+}
+
+// rec / con of the entry points -> the instance; con == NULL: the launches of rpo_<env>_evaluate[_record] as they were;
+// noise != NULL: the NOISE = 1 instances
 template <class ENV>
-int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, int rec, float* con, void* stream) {
+int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, int rec, float* con, void* stream,
+                    const EvalNoise* noise = nullptr) {
+    if (noise) {
+        EvalNoiseArgs<ENV> na{};
+        static_cast<EvalArgs<ENV>&>(na) = args;
+        na.con = con;
+        for (int q = 0; q < noise->len; ++q) na.sigma[q] = noise->sigma_host[q];
+        na.noise_seed = noise->seed;
+        if (!con) return rec ? launch_eval<ENV, 1, 0, 1>(na, c, n, stream) : launch_eval<ENV, 0, 0, 1>(na, c, n, stream);
+        return rec ? launch_eval<ENV, 1, 1, 1>(na, c, n, stream) : launch_eval<ENV, 0, 1, 1>(na, c, n, stream);
+    }
     if (!con) return rec ? launch_eval<ENV, 1, 0>(args, c, n, stream) : launch_eval<ENV, 0, 0>(args, c, n, stream);
     EvalConArgs<ENV> ca;
     static_cast<EvalArgs<ENV>&>(ca) = args;
@@ -279,6 +345,28 @@ __global__ __launch_bounds__(RPO_BLOCK) void eval_record_kernel(RecArgs p) {
             row_violations(r, p.a.ineq_col, p.a.ineq_num, p.a.eq_col, p.a.eq_num, ineq, eq);
             rpo_eval_dev::trace_store_tail(dst, r[p.a.reward_col], r[p.a.done_col], ineq, eq);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------- stepwise observation noise
+struct NoiseArgs {
+    int n;
+    const float* obs;
+    int obs_stride, O;
+    const float* sigma;           // device, [O]
+    uint64_t seed;
+    int step;
+    float* out;
+    int out_stride;
+};
+
+// One thread per element: a wave reads and writes neighbouring columns of neighbouring rows.
+__global__ __launch_bounds__(RPO_BLOCK) void eval_obs_noise_kernel(NoiseArgs p) {
+    const long long total = (long long)p.n * p.O;
+    for (long long t = (long long)blockIdx.x * RPO_BLOCK + threadIdx.x; t < total; t += (long long)gridDim.x * RPO_BLOCK) {
+        const int i = (int)(t / p.O), q = (int)(t - (long long)i * p.O);
+        p.out[(size_t)i * p.out_stride + q] =
+            rpo_eval_dev::rpo_eval_noisy_obs(p.obs[(size_t)i * p.obs_stride + q], p.sigma[q], p.seed, i, p.step, q);
     }
 }
 
@@ -472,9 +560,11 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                       int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, const float* consts_host,
                       int partial, int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows,
-                      int trace_steps, int with_con, float* con, void* stream) {
+                      int trace_steps, int with_con, float* con, void* stream, const EvalNoise* noise = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
+    if (noise)
+        if (int e = check_eval_noise(*noise, 6)) return e;
     if (!state || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
@@ -492,16 +582,18 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                                        max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
-    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream);
+    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise);
 }
 
 int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal, float* obs,
                       float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps,
                       float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                       int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows, int trace_steps,
-                      int with_con, float* con, void* stream) {
+                      int with_con, float* con, void* stream, const EvalNoise* noise = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
+    if (noise)
+        if (int e = check_eval_noise(*noise, 5)) return e;
     if (!internal || !obs || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
@@ -518,7 +610,7 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
     const PendEnv::Consts c{0};
-    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream);
+    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise);
 }
 
 }  // namespace
@@ -628,6 +720,42 @@ int rpo_pendulum_evaluate_constraints(const rpo_mlp* actor_host, int gauss, floa
     return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                              steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
                              trace ? 1 : 0, trace, trace_rows, trace_steps, 1, con, stream);
+}
+
+int rpo_cartsafe_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                float viol_thresh, float* trace, int trace_rows, int trace_steps, float* con,
+                                const float* sigma_host, int sigma_len, unsigned long long noise_seed, void* stream) {
+    const EvalNoise noise{sigma_host, sigma_len, noise_seed};
+    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
+                             viol_thresh, trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, &noise);
+}
+
+int rpo_pendulum_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
+                                int trace_rows, int trace_steps, float* con, const float* sigma_host, int sigma_len,
+                                unsigned long long noise_seed, void* stream) {
+    const EvalNoise noise{sigma_host, sigma_len, noise_seed};
+    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                             trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, &noise);
+}
+
+int rpo_eval_obs_noise(int n, const float* obs, int obs_stride, int obs_dim, const float* sigma, unsigned long long seed,
+                       int step, float* out, int out_stride, void* stream) {
+    if (n <= 0 || step < 0 || step >= (1 << 24) || obs_dim <= 0 || obs_dim > 4096 || obs_stride < obs_dim || out_stride < obs_dim)
+        return RPO_ERR_ARG;
+    if (!obs || !sigma || !out) return RPO_ERR_NULL;
+    if (out == obs) return RPO_ERR_ARG;
+    const NoiseArgs a{n, obs, obs_stride, obs_dim, sigma, (uint64_t)seed, step, out, out_stride};
+    hipLaunchKernelGGL(eval_obs_noise_kernel, dim3(rpo_grid_for((long long)n * obs_dim)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a);
+    RPO_LAUNCH_CHECK();
+    return 0;
 }
 
 int rpo_eval_constraints(int n, const float* rows, int row_stride, int eq_col, int eq_num, int ineq_col, int ineq_num, int step,

@@ -318,6 +318,32 @@ def eval_constraints(rows, cols, step, viol_thresh, acc, con):
                                            _con(con, n, con_width(i1 - i0, e1 - e0)), _stream()), "rpo_eval_constraints")
 
 
+STREAM_EVAL_OBS = CONST["RPO_STREAM_EVAL_OBS"]
+
+
+def eval_obs_noise(obs, sigma, seed, step, out):
+    """out [n, obs_dim] <- obs + sigma * z(episode, step, column) (rpo_eval_obs_noise): the observation the policy and the
+    projection of ``evaluate(obs_noise=)`` read at evaluation step `step`.  obs, out: row views [n, obs_dim] (out a buffer of
+    its own); sigma: float32 [obs_dim] on the device, a zero leaves its column's bits; seed: the evaluation's."""
+    n, O = obs.shape
+    op, ostride = _row_view(obs, O)
+    dp, dstride = _row_view(out, O)
+    if out.shape[0] != n or sigma.numel() != O:
+        raise RpoHipError("eval_obs_noise: out must have %d rows and sigma %d entries" % (n, O))
+    check(_lib.load().rpo_eval_obs_noise(n, op, ostride, O, _p(sigma), int(seed), int(step), dp, dstride, _stream()),
+          "rpo_eval_obs_noise")
+
+
+def _eval_noise(noise, obs_dim):
+    """``noise=(sigma, seed)`` of the env kernels' ``evaluate`` -> the trailing arguments of rpo_<env>_evaluate_noisy; sigma: a
+    host float32 array [obs_dim], copied into the launch."""
+    sigma, seed = noise
+    sigma = np.ascontiguousarray(sigma, dtype=np.float32)
+    if sigma.shape != (obs_dim,):
+        raise RpoHipError("evaluate: noise sigma must be float32 [%d], got %s" % (obs_dim, sigma.shape))
+    return sigma, (_host_ptr(sigma), obs_dim, int(seed))
+
+
 CURVE_LEN = CONST["RPO_CURVE_LEN"]
 CURVE_WS = CONST["RPO_CURVE_WS"]
 
@@ -429,17 +455,24 @@ class CartSafeKernels(object):
 
     def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
                  box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None,
-                 con=None):
+                 con=None, noise=None):
         """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_cartsafe_evaluate); acc [n, EVAL_LEN].
         trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_cartsafe_evaluate_record).
-        con [n, con_width]: the per-constraint report, with or without a trace (rpo_cartsafe_evaluate_constraints)."""
+        con [n, con_width]: the per-constraint report, with or without a trace (rpo_cartsafe_evaluate_constraints).
+        noise (sigma, seed): observation noise, sigma a host float32 [obs_dim], with or without trace and con
+        (rpo_cartsafe_evaluate_noisy)."""
         net = actor_desc.net_struct()
         n = internal.shape[0]
         args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32),
                 _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n),
                 int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
                 max_episode_steps, viol_thresh)
-        if con is not None:
+        if noise is not None:
+            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
+            sigma, tail = _eval_noise(noise, self.obs_dim)       # (sigma: kept alive over the call that copies it)
+            check(_lib.load().rpo_cartsafe_evaluate_noisy(*args, *tr, None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)),
+                                                    *tail, _stream()), "rpo_cartsafe_evaluate_noisy")
+        elif con is not None:
             tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
             check(_lib.load().rpo_cartsafe_evaluate_constraints(*args, *tr, _con(con, n, con_width(self.ineq_num, self.eq_num)),
                                                                 _stream()), "rpo_cartsafe_evaluate_constraints")
@@ -684,17 +717,24 @@ class PendulumKernels(object):
 
     def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
                  box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None,
-                 con=None):
+                 con=None, noise=None):
         """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_pendulum_evaluate); acc [n, EVAL_LEN].
         trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_pendulum_evaluate_record).
-        con [n, con_width]: the per-constraint report, with or without a trace (rpo_pendulum_evaluate_constraints)."""
+        con [n, con_width]: the per-constraint report, with or without a trace (rpo_pendulum_evaluate_constraints).
+        noise (sigma, seed): observation noise, sigma a host float32 [obs_dim], with or without trace and con
+        (rpo_pendulum_evaluate_noisy)."""
         net = actor_desc.net_struct()
         n = internal.shape[0]
         args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action),
                 _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
                 _eval_acc(acc, n), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps,
                 corr_momentum, max_episode_steps, viol_thresh)
-        if con is not None:
+        if noise is not None:
+            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
+            sigma, tail = _eval_noise(noise, self.obs_dim)       # (sigma: kept alive over the call that copies it)
+            check(_lib.load().rpo_pendulum_evaluate_noisy(*args, *tr, None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)),
+                                                    *tail, _stream()), "rpo_pendulum_evaluate_noisy")
+        elif con is not None:
             tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
             check(_lib.load().rpo_pendulum_evaluate_constraints(*args, *tr, _con(con, n, con_width(self.ineq_num, self.eq_num)),
                                                                 _stream()), "rpo_pendulum_evaluate_constraints")

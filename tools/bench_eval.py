@@ -6,6 +6,7 @@
     rocprofv3 --kernel-trace --stats -d DIR -o eval -- python tools/bench_eval.py --profile-only
     python tools/bench_eval.py --record [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_record_bench.json]
     python tools/bench_eval.py --constraints [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_constraints_bench.json]
+    python tools/bench_eval.py --obs-noise [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_noise_bench.json]
 
 Per configuration (cart-RPODDPG, cart-RPOSAC, pendulum-RPODDPG: fused; EVOPF-RPODDPG: stepwise only) a trainer with
 bench.py's hyper-parameters is trained for a few vector steps (a policy that has left its initialisation), then:
@@ -21,6 +22,11 @@ means something only beyond that spread).  A record=True leg includes the read-b
 --sizes episodes, stepwise EVOPF-RPODDPG at 10 and 1024: the legs constraints=False / constraints=True (and, on the fused path,
 record=True for comparison) alternate; per size the ratio of the medians constraints=True / constraints=False is reported next
 to the two legs' own min-max spreads.
+--obs-noise: the cost of evaluate(obs_noise=sigma) (sensor noise drawn inside the kernel), by the same method.  Fused
+cart-RPODDPG and pendulum-RPOSAC at --sizes episodes, stepwise EVOPF-RPODDPG at 10 and 1024: the legs obs_noise=None /
+obs_noise=sigma of ONE build alternate (sigma 0.05; EVOPF-v0 1e-3); the ratio of the medians is reported next to the legs' own
+spreads.  A noisy policy takes other episodes than a clean one, so every leg also reports the env steps it took and its time
+per env step.
 Every call ends with a host read of the results (evaluate()'s .cpu(), eval()'s), so wall times include the device work.
 Run each GPU step under its own time limit (timeout -k 10 ...).
 """
@@ -140,6 +146,32 @@ def constraints_bench(a, sizes):
     return line
 
 
+def noise_bench(a, sizes):
+    line = dict(tool="bench_eval --obs-noise", device=torch.cuda.get_device_name(0), reps=a.reps, configs={})
+    for workload, has_fused in (("cart_ddpg", True), ("pen_sac", True), ("evopf_ddpg", False)):
+        tr = trainer(workload)
+        sigma = 0.05 if has_fused else 1e-3
+        row = {}
+        for n in (sizes if has_fused else [10, 1024]):
+            legs = {"obs_noise_none": lambda: tr.evaluate(n, seed=5, obs_noise=None),
+                    "obs_noise_sigma": lambda: tr.evaluate(n, seed=5, obs_noise=sigma)}
+            res = alternating(legs, a.reps)
+            base = res["obs_noise_none"]["median_s"]
+            for k, fn in legs.items():
+                r = fn()
+                assert r.path == ("fused" if has_fused else "stepwise") and (r.obs_noise is None) == (k == "obs_noise_none")
+                steps = int(r.length.sum())
+                res[k].update(ratio_to_obs_noise_none=res[k]["median_s"] / base, env_steps=steps,
+                              s_per_env_step=res[k]["median_s"] / steps, violation_rate=r.violation_rate())
+            res.update(horizon=r.horizon, path=r.path, sigma=sigma)
+            row[str(n)] = res
+            del r
+        line["configs"][workload] = row
+        del tr
+        torch.cuda.empty_cache()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -147,12 +179,14 @@ def main():
     ap.add_argument("--profile-only", action="store_true")
     ap.add_argument("--record", action="store_true")
     ap.add_argument("--constraints", action="store_true")
+    ap.add_argument("--obs-noise", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sizes = [int(x) for x in a.sizes.split(",") if x]
-    if a.record or a.constraints:
+    if a.record or a.constraints or a.obs_noise:
         small = [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes
-        s = json.dumps(constraints_bench(a, small) if a.constraints else record_bench(a, small))
+        bench = noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
+        s = json.dumps(bench(a, small))
         print(s)
         if a.out:
             with open(a.out, "w") as f:
