@@ -952,6 +952,28 @@ int rpo_pendulum_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scal
                                 int trace_rows, int trace_steps, float* con, const float* sigma_host, int sigma_len,
                                 unsigned long long noise_seed, void* stream);
 
+/* The same launches with a projection budget PER LANE (RPOTrainerBase.evaluate_budgets): a live lane i projects with at most
+ * lane_steps[i] GRG iterations at step size lane_lr[i] in place of max_steps / corr_lr, which are validated and otherwise
+ * unused; corr_eps, corr_momentum and everything else stay launch-uniform.  lane_steps (int), lane_lr (float): DEVICE arrays
+ * [n_envs], 4-byte aligned (NULL: RPO_ERR_NULL; misaligned: RPO_ERR_ARG, before any HIP call).  The arguments are those of
+ * rpo_<env>_evaluate_constraints with con optional (NULL: no report); there is no record and no noise with it: trace must be
+ * NULL (RPO_ERR_ARG otherwise; trace_rows, trace_steps unused).  With B budgets tiled group-major over n_envs = B * episodes
+ * lanes that share their initial states, lane g * episodes + e is episode e under budget g: lanes never read one another, so
+ * == rpo_<env>_evaluate[_constraints] of the episodes-lane env with max_steps = lane_steps[g], corr_lr = lane_lr[g], bit for
+ *    bit, for every g. */
+int rpo_cartsafe_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                  float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                  int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                  float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                  float viol_thresh, float* trace, int trace_rows, int trace_steps, float* con,
+                                  const int* lane_steps, const float* lane_lr, void* stream);
+int rpo_pendulum_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                  float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                  float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                  float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
+                                  int trace_rows, int trace_steps, float* con, const int* lane_steps, const float* lane_lr,
+                                  void* stream);
+
 /* The stepwise form of the noise (any env): out[i, q] = obs[i, q] + sigma[q] * z(i, step, q) for i < n, q < obs_dim, with the
  * draw and the arithmetic above (== per column q with sigma[q] != 0: rpo_philox_normal(n, ., seed, 0, step,
  * RPO_STREAM_EVAL_OBS + 0x100 * q, NULL), then the unfused multiply and add); a column with sigma[q] == 0 is copied.  obs

@@ -34,6 +34,11 @@ instances add it to their staged tile (``rpo_<env>_evaluate_noisy``); the stepwi
 (``rpo_eval_obs_noise``, or ``obs_noise_torch``) and hands it to ``_eval_action(obs=)`` and the record.  Both paths compute
 the same bits; None, 0 and all-zero run the clean evaluation's launches.  ``eval()``, curve mode and ``act()`` never see noise.
 
+Budget sweeps (``evaluate_budgets(episodes, eval_steps=[...])`` -> ``BudgetSweep``): B projection budgets on the SAME initial
+states, group g being bit for bit the ``evaluate()`` call with ``eval_steps[g]`` / ``eval_lr[g]`` and the shared seed.  On the
+fused path the B groups run side by side as B x episodes lanes of one launch sequence (``rpo_<env>_evaluate_budgets``: the fused
+kernel's BUD instances read the budget and the step size per lane); every other configuration runs the B calls ("sweep").
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
 does not record trajectories and produces no per-constraint reports.  With the trainer argument ``keep_best`` every point's
@@ -428,6 +433,14 @@ def check_budget(tr, eval_steps, eval_lr, what="evaluate"):
     return int(steps), lr
 
 
+def fresh_seed(tr):
+    """The seed of an ``evaluate()`` / ``evaluate_budgets()`` call without one: fresh initial states at every call, like eval(),
+    from the trainer seed and a call counter (host-side only), which it advances."""
+    calls = getattr(tr, "_evaluate_calls", 0)
+    tr._evaluate_calls = calls + 1
+    return int(((tr.seed ^ 0xE7A1E7A1) + 0x9E3779B97F4A7C15 * (calls + 1)) & (2 ** 63 - 1))
+
+
 def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
              constraints=False, obs_noise=None):
     """See ``RPOTrainerBase.evaluate``."""
@@ -457,12 +470,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
         if tuple(init_states.shape) != (n, k.internal_dim):
             raise ValueError("evaluate: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
                              % (n, k.internal_dim, tuple(init_states.shape)))
-    if seed is None:
-        # fresh initial states at every call, like eval(): from the trainer seed and a call counter (host-side only)
-        calls = getattr(tr, "_evaluate_calls", 0)
-        tr._evaluate_calls = calls + 1
-        seed = ((tr.seed ^ 0xE7A1E7A1) + 0x9E3779B97F4A7C15 * (calls + 1)) & (2 ** 63 - 1)
-    seed = int(seed)
+    seed = fresh_seed(tr) if seed is None else int(seed)
     v = tr.base_env.make_vec(n, seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=tr.device,
                              stats_cap=2, viol_thresh=tr.vec.viol_thresh)
     v.reset()
@@ -491,14 +499,15 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     return res
 
 
-def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None):
+def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None, lanes=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
     trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
     (rpo_<env>_evaluate_record).  ``budget``: evaluate()'s per-call (eval_steps, eval_lr), None: the trainer's.  ``con``: the
     per-constraint report [n, W] every launch continues (rpo_<env>_evaluate_constraints).  ``noise``: (sigma float32 numpy
     [obs_dim], seed) of ``obs_noise=`` (rpo_<env>_evaluate_noisy; the draw is keyed by the absolute step t0 + s); None: the
-    kernels' ``evaluate`` gets no such keyword."""
+    kernels' ``evaluate`` gets no such keyword.  ``lanes``: (eval_steps int32 [n], eval_lr float32 [n]) on the device, the budget
+    and step size of every lane in place of ``budget`` (rpo_<env>_evaluate_budgets; con only, neither trace nor noise)."""
     n = v.n
     eval_steps = tr.eval_steps if budget[0] is None else budget[0]
     eval_lr = tr.eval_lr if budget[1] is None else budget[1]
@@ -510,6 +519,15 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
         kw["con"] = con
     if noise is not None:
         kw["noise"] = noise
+    if lanes is not None:
+        if trace is not None or noise is not None:
+            raise ValueError("per-lane budgets run without a record and without observation noise")
+        for t0 in range(0, H, steps):
+            tr.kernels.evaluate_budgets(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs,
+                                        v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
+                                        tr._box_hi, lanes[0], lanes[1], tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
+                                        v.viol_thresh, **kw)
+        return
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
                             v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo, tr._box_hi,
@@ -552,6 +570,150 @@ def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, nois
         if con is not None:
             report(rows, k.cols, i, v.viol_thresh, acc, con)
         update(rows, k.cols, iters, i, v.viol_thresh, acc)
+
+
+# ------------------------------------------------------------------------------------------------ budget sweeps
+MAX_BUDGETS = 64
+_FUSED_BUDGET_LANES = 1 << 24                                    # B x episodes lanes of one fused launch; beyond: "sweep"
+
+
+class BudgetSweep(object):
+    """The result of ``evaluate_budgets()``: B projection budgets evaluated on the same initial states.
+
+    ``eval_steps`` int64 [B] / ``eval_lr`` float32 [B]: the budgets in the caller's order; ``results``: B ``EvalResult``s
+    (``sweep[g]`` is ``results[g]``), each what ``evaluate(eval_steps=eval_steps[g], eval_lr=eval_lr[g])`` with the shared seed
+    returns.  ``ret``, ``length``, ``mean_ineq``, ``mean_eq``, ``max_ineq``, ``max_eq``, ``viol_steps``, ``proj_iters`` (also
+    ``iters``), ``nonfinite``: [B, episodes] arrays whose rows ARE the results' arrays (one memory).  ``path``: "fused" (one
+    launch sequence over B x episodes lanes) or "sweep" (B ``evaluate()`` calls).  ``seed``, ``horizon``: the shared ones."""
+
+    def __init__(self, results, eval_steps, eval_lr, path):
+        self.results = list(results)
+        self.eval_steps = np.array(eval_steps, dtype=np.int64).reshape(-1)
+        self.eval_lr = np.array(eval_lr, dtype=np.float32).reshape(-1)
+        if not self.results or not len(self.results) == len(self.eval_steps) == len(self.eval_lr):
+            raise ValueError("BudgetSweep: %d results for %d budgets and %d step sizes"
+                             % (len(self.results), len(self.eval_steps), len(self.eval_lr)))
+        if len(set(r.episodes for r in self.results)) != 1:
+            raise ValueError("BudgetSweep: the results have different numbers of episodes")
+        self.path = path
+        self.seed, self.horizon = self.results[0].seed, self.results[0].horizon
+        for f in EvalResult.FIELDS:
+            rows = np.stack([getattr(r, f) for r in self.results])
+            setattr(self, f, rows)
+            for g, r in enumerate(self.results):                 # the result's array becomes row g of the stack
+                setattr(r, f, rows[g])
+        self.iters = self.proj_iters
+
+    def __len__(self):
+        return len(self.results)
+
+    def __getitem__(self, g):
+        return self.results[g]
+
+    @property
+    def episodes(self):
+        return self.ret.shape[1]
+
+    def violation_rate(self):
+        """Per budget: the fraction of its evaluated env steps whose max inequality violation exceeds ``viol_thresh`` [B]."""
+        return self.viol_steps.sum(axis=1).astype(np.float64) / self.length.sum(axis=1).astype(np.float64)
+
+    def ret_mean(self):
+        """Per budget: the mean return over the episodes [B]."""
+        return self.ret.mean(axis=1)
+
+    def budget(self, max_rate=0.0):
+        """The smallest ``eval_steps[g]`` whose ``violation_rate()[g]`` is <= ``max_rate``; None if no budget of the sweep is."""
+        ok = self.violation_rate() <= max_rate
+        return int(self.eval_steps[ok].min()) if ok.any() else None
+
+    def __repr__(self):
+        return "BudgetSweep(budgets=%s, episodes=%d, path=%s, violation_rate=%s)" % (
+            self.eval_steps.tolist(), self.episodes, self.path, np.array2string(self.violation_rate(), precision=4))
+
+
+def check_budgets(tr, eval_steps, eval_lr):
+    """``eval_steps`` / ``eval_lr`` of evaluate_budgets() -> (list of B ints, list of B floats): a non-empty sequence of at most
+    ``MAX_BUDGETS`` integers >= 0 (duplicates allowed, order kept); ``eval_lr`` None (the trainer's), one finite number or B finite
+    numbers (ValueError otherwise)."""
+    what = "evaluate_budgets"
+    if eval_steps is None or isinstance(eval_steps, (str, bytes)) or np.ndim(eval_steps) != 1:
+        raise ValueError("%s: eval_steps must be a non-empty sequence of integers >= 0, got %r" % (what, eval_steps))
+    steps = list(eval_steps)
+    if not 1 <= len(steps) <= MAX_BUDGETS:
+        raise ValueError("%s: eval_steps must hold 1 to %d budgets, got %d" % (what, MAX_BUDGETS, len(steps)))
+    if eval_lr is None or (np.ndim(eval_lr) == 0 and not isinstance(eval_lr, (str, bytes))):
+        lrs = [eval_lr] * len(steps)
+    elif isinstance(eval_lr, (str, bytes)) or np.ndim(eval_lr) != 1 or len(eval_lr) != len(steps):
+        raise ValueError("%s: eval_lr must be None, one finite number or %d finite numbers, got %r" % (what, len(steps), eval_lr))
+    else:
+        lrs = list(eval_lr)
+    out = []
+    for b, lr in zip(steps, lrs):
+        if b is None or isinstance(b, (bool, np.bool_)) or isinstance(lr, (bool, np.bool_)):
+            raise ValueError("%s: eval_steps must be integers >= 0 and eval_lr finite numbers, got %r / %r" % (what, b, lr))
+        out.append(check_budget(tr, b, lr, what))
+    return [b for b, _ in out], [lr for _, lr in out]
+
+
+def evaluate_budgets(tr, episodes=10, eval_steps=None, eval_lr=None, horizon=None, seed=None, init_states=None, constraints=False):
+    """See ``RPOTrainerBase.evaluate_budgets``."""
+    from .acting import _projects
+    n = check_episodes(episodes, "evaluate_budgets: episodes")
+    want_con = check_constraints(constraints)
+    if not _projects(tr):
+        raise ValueError("evaluate_budgets needs a trainer that projects (RPODDPG / RPOSAC); %s has no projection" % type(tr).__name__)
+    steps, lrs = check_budgets(tr, eval_steps, eval_lr)
+    B = len(steps)
+    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
+        raise ValueError("evaluate_budgets: horizon must be an integer >= 1, got %r" % (horizon,))
+    H = int(horizon) if horizon is not None else default_horizon(tr)
+    if H >= 1 << 24:
+        raise ValueError("evaluate_budgets: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
+    k = tr.kernels
+    if init_states is not None:
+        init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
+        if tuple(init_states.shape) != (n, k.internal_dim):
+            raise ValueError("evaluate_budgets: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
+                             % (n, k.internal_dim, tuple(init_states.shape)))
+    seed = fresh_seed(tr) if seed is None else int(seed)         # ONE seed (and one tick of the call counter) for all budgets
+    fused = bool(fused_ok(tr) and hasattr(k, "evaluate_budgets") and tr.schedule.get("fused_budgets", 1)
+                 and B * n <= _FUSED_BUDGET_LANES)
+    if not fused:
+        results = [evaluate(tr, episodes=n, horizon=H, seed=seed, init_states=init_states, eval_steps=b, eval_lr=lr,
+                            constraints=want_con) for b, lr in zip(steps, lrs)]
+        return BudgetSweep(results, steps, lrs, "sweep")
+    dev = tr.device
+    make = dict(seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev, stats_cap=2,
+                viol_thresh=tr.vec.viol_thresh)
+    v = tr.base_env.make_vec(n, **make)                          # the initial states of evaluate(): reset, then the injection
+    v.reset()
+    if init_states is not None:
+        v.set_internal(init_states)
+    # B copies, group-major: lane g * n + e is episode e under budget g.  internal AND obs are tiled (SpringPendulum's injected
+    # observation comes from torch's cos / sin: recomputing it here would not be evaluate()'s bits); the bookkeeping of the
+    # new env is zero, like the reset one's
+    big = tr.base_env.make_vec(B * n, **make)
+    big.internal.view(B, n, -1).copy_(v.internal)
+    if big.obs is not big.internal:
+        big.obs.view(B, n, -1).copy_(v.obs)
+    lanes = (torch.tensor(steps, dtype=torch.int32, device=dev).repeat_interleave(n),
+             torch.tensor(lrs, dtype=torch.float32, device=dev).repeat_interleave(n))
+    acc = torch.zeros(B * n, 8, device=dev)
+    con = torch.empty(B * n, hip_ops.con_width(k.ineq_num, k.eq_num), device=dev) if want_con else None
+    with torch.no_grad():
+        _run_fused(tr, big, acc, H, con=con, lanes=lanes)
+    acc_host = acc.cpu().numpy().reshape(B, n, 8)
+    con_host = con.cpu().numpy().reshape(B, n, -1) if want_con else None
+    results = []
+    for g in range(B):
+        res = EvalResult(acc_host[g], "fused", H, seed)
+        if want_con:
+            res.constraints = ConstraintReport.from_rows(con_host[g], k.ineq_num, k.eq_num, res.length, big.viol_thresh,
+                                                         getattr(tr.base_env, "ineq_names", None),
+                                                         getattr(tr.base_env, "eq_names", None))
+        results.append(res)
+    return BudgetSweep(results, steps, lrs, "fused")
 
 
 # ------------------------------------------------------------------------------------------------ evaluation curves

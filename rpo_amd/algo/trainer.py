@@ -1512,6 +1512,34 @@ class RPOTrainerBase(object):
         return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record,
                         eval_steps=eval_steps, eval_lr=eval_lr, constraints=constraints, obs_noise=obs_noise)
 
+    def evaluate_budgets(self, episodes=10, eval_steps=None, eval_lr=None, horizon=None, seed=None, init_states=None,
+                         constraints=False):
+        """Evaluate the current policy under B projection budgets at once -> ``BudgetSweep``: which ``eval_steps`` does a
+        deployment need, on whole episodes?  ``eval_steps``: a non-empty sequence of at most 64 integers >= 0 (duplicates
+        allowed, order kept); ``eval_lr``: None (the trainer's), one finite number or a sequence of B finite numbers;
+        ``episodes``, ``horizon``, ``seed``, ``init_states`` ([episodes, internal_dim], shared by all budgets) and
+        ``constraints`` are ``evaluate()``'s and validated like them.  Definition: group g is, bit for bit,
+        ``evaluate(episodes, horizon, seed=seed, init_states=init_states, eval_steps=eval_steps[g], eval_lr=eval_lr[g],
+        constraints=constraints)`` -- every budget starts from the same initial states (a paired comparison), and
+        ``seed=None`` draws ONE seed as ``evaluate()`` does (one tick of its call counter).  ``sweep.results[g]`` /
+        ``sweep[g]`` are the B ``EvalResult``s; ``sweep.ret``, ``.length``, ``.viol_steps``, ``.max_ineq``, ``.max_eq``,
+        ``.iters`` ... are [B, episodes] arrays over the same memory; ``sweep.violation_rate()`` and ``sweep.ret_mean()`` are
+        [B]; ``sweep.budget(max_rate=0.0)`` is the smallest ``eval_steps[g]`` whose violation rate is <= ``max_rate`` (None if
+        none is).  ``sweep.path``: "fused" -- where ``evaluate()`` takes its fused path (schedule ``fused_budgets=0`` switches
+        it off), the B groups run side by side as B x episodes lanes of ONE launch sequence whose kernel reads the budget and
+        the step size per lane: about one evaluation's time while the lanes do not fill the chip, one vector env, one read-back
+        -- or "sweep": EVOPF-v0, 256-wide actors, ``fused_mlp=0`` and the oracle backend run the B ``evaluate()`` calls of the
+        definition.  EVOPF-v0 keys a lane's day by (seed, env id, episode), so B separate ``episodes``-lane vector envs are
+        the only pairing that is right there without changing its kernels.  No ``record=`` and no ``obs_noise=``: the noise
+        draw is keyed by the lane index, so lanes g * episodes + e of a fused sweep would not see episode e's draw (a paired
+        noisy sweep needs the NOISE kernels to key by episode); call ``evaluate()`` per budget for either.  ValueError: an
+        empty ``eval_steps`` or more than 64, an entry that is no integer >= 0, an ``eval_lr`` of another length or not
+        finite, a trainer without a projection (the Lagrangian baselines).  No trainer state changes, as for ``evaluate()``.
+        See rpo_amd/algo/evaluation.py."""
+        from .evaluation import evaluate_budgets
+        return evaluate_budgets(self, episodes=episodes, eval_steps=eval_steps, eval_lr=eval_lr, horizon=horizon, seed=seed,
+                                init_states=init_states, constraints=constraints)
+
     def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0, profile=False):
         """The policy's projected actions for caller-supplied observations -> ``ActResult`` (torch tensors on the trainer's
         device, nothing waits for the device): ``action`` [n, action_dim], the completed + projected action ``eval()`` would

@@ -210,8 +210,11 @@ __device__ __forceinline__ float reduced_grad(const CartConsts& c, float ap) {
 
 // Exploration (ddpg_pa.py:108-110 / model/utils.py:53-62) + complete_partial (cartpole.py:369-373) + grad_steps
 // (rpo_ddpg.py:266-286, corr_mode 0, per-lane stop test) for one lane.  Returns the full action and the iteration count.
+// `bud`: where the loop's budget and step size come from (common.h: RpoBudgetOfArgs, p.max_steps / p.corr_lr, unless a lane
+// brings its own).
+template <class BUDGET = RpoBudgetOfArgs>
 __device__ __forceinline__ float2 cart_explore_project(const ActArgs& p, const CartConsts& c, int i, float ap_in, float eps_t,
-                                                       long long t, int& iters) {
+                                                       long long t, int& iters, const BUDGET bud = BUDGET()) {
     RPO_FP_STRICT
     float ap = (p.noise_mode == RPO_NOISE_UNIFORM) ? 0.0f : ap_in;
     if (p.noise_mode == RPO_NOISE_EXPLICIT) {
@@ -231,7 +234,7 @@ __device__ __forceinline__ float2 cart_explore_project(const ActArgs& p, const C
     // grad_steps, rpo_ddpg.py:266-286 (corr_mode 0), per-lane stop test
     float old_p = 0.0f, old_o = 0.0f;
     int k = 0;
-    for (; k < p.max_steps; ++k) {
+    for (; k < bud.max_steps(p); ++k) {
         const float a0 = c.partial == 0 ? ap : ao, a1 = c.partial == 0 ? ao : ap;
         float h, g[6];
         eq_ineq(c, a0, a1, h, g);
@@ -241,8 +244,8 @@ __device__ __forceinline__ float2 cart_explore_project(const ActArgs& p, const C
         if (k > 0 && !(fabsf(h) > p.corr_eps || mx > p.corr_eps)) break;
         const float gp = reduced_grad(c, ap);
         const float go = -(gp * c.C_p) * c.C_o_inv;                                      // cartpole.py:407
-        const float sp = p.corr_lr * gp + p.corr_momentum * old_p;
-        const float so = p.corr_lr * go + p.corr_momentum * old_o;
+        const float sp = bud.corr_lr(p) * gp + p.corr_momentum * old_p;
+        const float so = bud.corr_lr(p) * go + p.corr_momentum * old_o;
         ap -= sp; ao -= so;
         old_p = sp; old_o = so;
     }

@@ -213,6 +213,20 @@ __device__ __forceinline__ void rpo_atomic_max_nonneg(float* addr, float v) {
 
 // Episode bookkeeping of a lane (gym TimeLimit counter, running return, episode index of the reset stream): loaded as
 // early as the kernel allows -- the step itself is a dependent chain, and these three loads would otherwise sit at its end.
+// Where a lane's GRG loop (cart_explore_project / pend_explore_project) takes its budget and step size from: the launch's
+// ActArgs, read where the loop uses them (every kernel but the evaluation's BUD = 1 instances) -- or the lane's own two words
+// (evaluate.hip, BUD = 1: budgets side by side in one launch).
+struct RpoBudgetOfArgs {
+    template <class A> __device__ __forceinline__ int max_steps(const A& p) const { return p.max_steps; }
+    template <class A> __device__ __forceinline__ float corr_lr(const A& p) const { return p.corr_lr; }
+};
+struct RpoBudgetOfLane {
+    int steps;
+    float lr;
+    template <class A> __device__ __forceinline__ int max_steps(const A&) const { return steps; }
+    template <class A> __device__ __forceinline__ float corr_lr(const A&) const { return lr; }
+};
+
 struct RpoEpisode { int len; float ret; unsigned count; };
 __device__ __forceinline__ RpoEpisode rpo_load_episode(const int* ep_len, const float* ep_ret, const unsigned* ep_count, int i) {
     return RpoEpisode{ep_len[i], ep_ret[i], ep_count[i]};

@@ -12,6 +12,8 @@
 //                        add the same values to their staged tile (eval_dev.h: rpo_eval_noisy_obs).
 //   eval_constraints     the stepwise path's per-constraint report (rpo_eval_constraints); the fused kernel's CON = 1 instances
 //                        update the same rows themselves (eval_dev.h: rpo_eval_con_lane_update).
+//   (no kernel)          evaluate_budgets(): the fused kernel's BUD = 1 instances (rpo_<env>_evaluate_budgets) read the projection's
+//                        budget and step size per lane, so B budgets x episodes run side by side in one launch.
 //   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
 //   keep_best_*_kernel   that row against the incumbent's on the device, and the predicated copy of the actor's parameters
 //                        (rpo_eval_keep_best; the criterion is eval_dev.h: keep_best_wins).
@@ -62,9 +64,17 @@ struct EvalNoiseArgs : EvalConArgs<ENV> {
     float sigma[8];               // per observation column, zeros beyond kObs; 0: the column is not drawn
     unsigned long long noise_seed;
 };
-template <class ENV, int CON, int NOISE> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
-template <class ENV> struct EvalArgsOf<ENV, 1, 0> { typedef EvalConArgs<ENV> type; };
-template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 1> { typedef EvalNoiseArgs<ENV> type; };
+// The BUD = 1 instances (evaluate_budgets()) take the lanes' budgets behind the EvalConArgs arguments (con: NULL for their
+// CON = 0 instances, which never read it); the BUD = 0 instances keep their parameter types.
+template <class ENV>
+struct EvalBudArgs : EvalConArgs<ENV> {
+    const int* lane_steps;        // [n] GRG iterations at most, in place of act.max_steps
+    const float* lane_lr;         // [n] step size, in place of act.corr_lr
+};
+template <class ENV, int CON, int NOISE, int BUD = 0> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
+template <class ENV> struct EvalArgsOf<ENV, 1, 0, 0> { typedef EvalConArgs<ENV> type; };
+template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 1, 0> { typedef EvalNoiseArgs<ENV> type; };
+template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 0, 1> { typedef EvalBudArgs<ENV> type; };
 
 // What one env step leaves for the statistics: reward, done and the violations of the transition row, without the row --
 // their maxima for the accumulators, and the row's ineq_viol / eq_viol columns themselves (gi / he) for the report.
@@ -159,8 +169,19 @@ __device__ __forceinline__ void stage_noise(const ARGS& p, int row0, int rows, i
     *o = rpo_eval_dev::rpo_eval_noisy_obs(*o, sigma, p.noise_seed, row0 + r, s, q);
 }
 
-template <class ENV, int EIN, int H, int RT, int REC, int CON, int NOISE>
-__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON, NOISE>::type p, typename ENV::Consts c) {
+// BUD = 1: a live lane reads its own budget and step size (p.lane_steps[i], p.lane_lr[i]) behind the forward and projects with
+// them in place of p.act.max_steps / p.act.corr_lr: two more VGPRs and a vector loop bound in a loop that rows of one wave
+// already leave at different iterations; everything else of p.act stays launch-uniform, nothing of it crosses the MFMA loops.
+template <class ENV, int BUD, class ARGS>
+__device__ __forceinline__ float2 eval_project(const ARGS& p, const typename ENV::Consts& c, const float* obs, int i, float ap,
+                                               int& k) {
+    if constexpr (BUD) return ENV::project_budget(p.act, c, obs, i, ap, p.lane_steps[i], p.lane_lr[i], k);
+    else return ENV::project(p.act, c, obs, i, ap, 0.0f, 0, k);
+}
+
+template <class ENV, int EIN, int H, int RT, int REC, int CON, int NOISE, int BUD = 0>
+__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON, NOISE, BUD>::type p, typename ENV::Consts c) {
+    static_assert(!BUD || (!REC && !NOISE), "per-lane budgets: no record, no observation noise");
     typedef TileLds<EIN, RT, 8, 8> Lds;                          // 16 * RT lanes per workgroup; OBS <= 8
     __shared__ Lds lds;
     constexpr int kInS = Lds::kS;
@@ -182,7 +203,7 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
             if (p.gauss) ap = rpo_head_dev::gauss_head_row(ap, lds.out[tid * 2 + 1], 0.0f, p.scale, p.base, p.act.box_lo,
                                                            p.act.box_hi, 1, nullptr);
             int k;
-            const float2 a = ENV::project(p.act, c, lds.in_s + tid * kInS, i, ap, 0.0f, 0, k);
+            const float2 a = eval_project<ENV, BUD>(p, c, lds.in_s + tid * kInS, i, ap, k);
             reinterpret_cast<float2*>(p.act.action)[i] = a;
             constexpr int kObs = EvalEnv<ENV>::kObs, kW = trace_width(kObs, 1, 2);
             if (REC && i < p.trace_rows)
@@ -202,15 +223,15 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
     }
 }
 
-template <class ENV, int REC, int CON, int NOISE = 0>
-int launch_eval(const typename EvalArgsOf<ENV, CON, NOISE>::type& args, const typename ENV::Consts& c, int n, void* stream) {
+template <class ENV, int REC, int CON, int NOISE = 0, int BUD = 0>
+int launch_eval(const typename EvalArgsOf<ENV, CON, NOISE, BUD>::type& args, const typename ENV::Consts& c, int n, void* stream) {
     // the rollout's tile rule (fused.hip launch_rollout): 64 lanes per workgroup once that still fills the chip.  E = 128
     // only: the E = 256 instance spills (~150 bytes of scratch per lane) -- such actors evaluate on the stepwise path.
     if (args.actor.E != 128) return RPO_ERR_ARG;
     if (n >= 64 * 192) {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON, NOISE>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON, NOISE, BUD>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     } else {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON, NOISE>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON, NOISE, BUD>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     }
     RPO_LAUNCH_CHECK();
     return 0;
@@ -230,11 +251,29 @@ int check_eval_noise(const EvalNoise& nz, int obs_dim) {
     return 0;
 }
 
+// The per-lane budgets of the *_evaluate_budgets entry points: device arrays [n], 4-byte aligned.
+struct EvalLanes {
+    const int* steps;
+    const float* lr;
+};
+int check_eval_lanes(const EvalLanes& l) {
+    if (!l.steps || !l.lr) return RPO_ERR_NULL;
+    return (reinterpret_cast<uintptr_t>(l.steps) | reinterpret_cast<uintptr_t>(l.lr)) % 4 ? RPO_ERR_ARG : 0;
+}
+
 // rec / con of the entry points -> the instance; con == NULL: the launches of rpo_<env>_evaluate[_record] as they were;
-// noise != NULL: the NOISE = 1 instances
+// noise != NULL: the NOISE = 1 instances; lanes != NULL: the BUD = 1 instances (no record, no noise: checked by the callers)
 template <class ENV>
 int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, int rec, float* con, void* stream,
-                    const EvalNoise* noise = nullptr) {
+                    const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr) {
+    if (lanes) {
+        EvalBudArgs<ENV> ba{};
+        static_cast<EvalArgs<ENV>&>(ba) = args;
+        ba.con = con;
+        ba.lane_steps = lanes->steps;
+        ba.lane_lr = lanes->lr;
+        return con ? launch_eval<ENV, 0, 1, 0, 1>(ba, c, n, stream) : launch_eval<ENV, 0, 0, 0, 1>(ba, c, n, stream);
+    }
     if (noise) {
         EvalNoiseArgs<ENV> na{};
         static_cast<EvalArgs<ENV>&>(na) = args;
@@ -560,12 +599,17 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                       int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, const float* consts_host,
                       int partial, int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows,
-                      int trace_steps, int with_con, float* con, void* stream, const EvalNoise* noise = nullptr) {
+                      int trace_steps, int with_con, float* con, void* stream, const EvalNoise* noise = nullptr,
+                      const EvalLanes* lanes = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (noise)
         if (int e = check_eval_noise(*noise, 6)) return e;
     if (!state || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
+    if (lanes) {
+        if (int e = check_eval_lanes(*lanes)) return e;
+        if (rec || noise) return RPO_ERR_ARG;
+    }
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
     if (with_con)
@@ -582,19 +626,23 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                                        max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
-    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise);
+    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes);
 }
 
 int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal, float* obs,
                       float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps,
                       float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                       int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows, int trace_steps,
-                      int with_con, float* con, void* stream, const EvalNoise* noise = nullptr) {
+                      int with_con, float* con, void* stream, const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (noise)
         if (int e = check_eval_noise(*noise, 5)) return e;
     if (!internal || !obs || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
+    if (lanes) {
+        if (int e = check_eval_lanes(*lanes)) return e;
+        if (rec || noise) return RPO_ERR_ARG;
+    }
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
     if (with_con)
@@ -610,7 +658,7 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
     const PendEnv::Consts c{0};
-    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise);
+    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes);
 }
 
 }  // namespace
@@ -744,6 +792,30 @@ int rpo_pendulum_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scal
     return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                              steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
                              trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, &noise);
+}
+
+int rpo_cartsafe_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                  float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                  int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                  float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                  float viol_thresh, float* trace, int trace_rows, int trace_steps, float* con,
+                                  const int* lane_steps, const float* lane_lr, void* stream) {
+    const EvalLanes lanes{lane_steps, lane_lr};
+    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
+                             viol_thresh, trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, nullptr, &lanes);
+}
+
+int rpo_pendulum_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                  float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                  float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                  float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
+                                  int trace_rows, int trace_steps, float* con, const int* lane_steps, const float* lane_lr,
+                                  void* stream) {
+    const EvalLanes lanes{lane_steps, lane_lr};
+    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                             trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, nullptr, &lanes);
 }
 
 int rpo_eval_obs_noise(int n, const float* obs, int obs_stride, int obs_dim, const float* sigma, unsigned long long seed,

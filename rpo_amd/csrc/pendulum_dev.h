@@ -162,9 +162,11 @@ __device__ __forceinline__ void ipg_row(const Eq& e, float ax, float ay, float& 
 }
 
 // Exploration + complete_partial (pendulum.py:256-262) + grad_steps with the row-wise ineq_partial_grad
-// (pendulum.py:331-343 as evaluated for B = 1) for one lane whose observation is o[0..4].
+// (pendulum.py:331-343 as evaluated for B = 1) for one lane whose observation is o[0..4].  `bud`: where the loop's
+// budget and step size come from (common.h: RpoBudgetOfArgs, p.max_steps / p.corr_lr, unless a lane brings its own).
+template <class BUDGET = RpoBudgetOfArgs>
 __device__ __forceinline__ float2 pend_explore_project(const ActArgs& p, const float* o, int i, float ap_in, float eps_t,
-                                                       long long t, int& iters) {
+                                                       long long t, int& iters, const BUDGET bud = BUDGET()) {
     RPO_FP_STRICT
     const Eq e = set_eq(o[0], o[1], o[2], o[3], o[4]);
     float ax = (p.noise_mode == RPO_NOISE_UNIFORM) ? 0.0f : ap_in;
@@ -183,14 +185,14 @@ __device__ __forceinline__ float2 pend_explore_project(const ActArgs& p, const f
     float ay = (e.b - ax * e.C_p) * e.C_o_inv;                               // complete_partial :256-262
     float old_x = 0.0f, old_y = 0.0f;
     int k = 0;
-    for (; k < p.max_steps; ++k) {                                           // grad_steps, rpo_ddpg.py:266-286
+    for (; k < bud.max_steps(p); ++k) {                                      // grad_steps, rpo_ddpg.py:266-286
         const float h = e.b - (ax * e.C_p + ay * e.C_o);
         const float g = ax * ax + ay * ay - kMaxSum;
         if (k > 0 && !(fabsf(h) > p.corr_eps || g > p.corr_eps)) break;
         float gx, gy;
         ipg_row(e, ax, ay, gx, gy);
-        const float sx = p.corr_lr * gx + p.corr_momentum * old_x;
-        const float sy = p.corr_lr * gy + p.corr_momentum * old_y;
+        const float sx = bud.corr_lr(p) * gx + p.corr_momentum * old_x;
+        const float sy = bud.corr_lr(p) * gy + p.corr_momentum * old_y;
         ax -= sx; ay -= sy;
         old_x = sx; old_y = sy;
     }

@@ -29,6 +29,11 @@ struct CartEnv {
                                                      float eps_t, long long t, int& k) {
         return rpo_cart_dev::cart_explore_project(a, c, i, ap, eps_t, t, k);
     }
+    // the same with the lane's own budget and step size (the evaluation's BUD = 1 instances, evaluate.hip)
+    __device__ static __forceinline__ float2 project_budget(const ActArgs& a, const Consts& c, const float* obs, int i, float ap,
+                                                            int max_steps, float corr_lr, int& k) {
+        return rpo_cart_dev::cart_explore_project(a, c, i, ap, 0.0f, 0, k, RpoBudgetOfLane{max_steps, corr_lr});
+    }
     __device__ static __forceinline__ RpoEpisode episode(const StepArgs& p, int i) {
         return rpo_load_episode(p.ep_len, p.ep_ret, p.ep_count, i);
     }
@@ -83,6 +88,10 @@ struct PendEnv {
     __device__ static __forceinline__ float2 project(const ActArgs& a, const Consts&, const float* obs, int i, float ap,
                                                      float eps_t, long long t, int& k) {
         return rpo_pend_dev::pend_explore_project(a, obs, i, ap, eps_t, t, k);
+    }
+    __device__ static __forceinline__ float2 project_budget(const ActArgs& a, const Consts&, const float* obs, int i, float ap,
+                                                            int max_steps, float corr_lr, int& k) {
+        return rpo_pend_dev::pend_explore_project(a, obs, i, ap, 0.0f, 0, k, RpoBudgetOfLane{max_steps, corr_lr});
     }
     __device__ static __forceinline__ RpoEpisode episode(const StepArgs& p, int i) {
         return rpo_load_episode(p.ep_len, p.ep_ret, p.ep_count, i);

@@ -344,6 +344,15 @@ def _eval_noise(noise, obs_dim):
     return sigma, (_host_ptr(sigma), obs_dim, int(seed))
 
 
+def _eval_lanes(lane_steps, lane_lr, n):
+    """Pointers of the per-lane budgets of the env kernels' ``evaluate_budgets``: int32 [n] and float32 [n] on the device (the
+    kernels index them by lane: a smaller one would be read out of bounds)."""
+    if tuple(lane_steps.shape) != (n,) or tuple(lane_lr.shape) != (n,):
+        raise RpoHipError("evaluate_budgets: lane_steps / lane_lr must be [%d], got %s / %s"
+                          % (n, tuple(lane_steps.shape), tuple(lane_lr.shape)))
+    return _p(lane_steps, torch.int32), _p(lane_lr)
+
+
 CURVE_LEN = CONST["RPO_CURVE_LEN"]
 CURVE_WS = CONST["RPO_CURVE_WS"]
 
@@ -481,6 +490,21 @@ class CartSafeKernels(object):
         else:
             tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
             check(_lib.load().rpo_cartsafe_evaluate_record(*args, *tr, _stream()), "rpo_cartsafe_evaluate_record")
+
+    def evaluate_budgets(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                         steps, box_lo, box_hi, lane_steps, lane_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                         con=None):
+        """``evaluate`` with a projection budget per lane (rpo_cartsafe_evaluate_budgets): lane_steps int32 [n] / lane_lr
+        float32 [n] on the device in place of max_steps / corr_lr; con as there; no record, no noise."""
+        net = actor_desc.net_struct()
+        n = internal.shape[0]
+        sp, lp = _eval_lanes(lane_steps, lane_lr, n)
+        check(_lib.load().rpo_cartsafe_evaluate_budgets(
+            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
+            _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0), int(steps), box_lo,
+            box_hi, 0, 0.0, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh, None, 0, 0,
+            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), sp, lp, _stream()),
+            "rpo_cartsafe_evaluate_budgets")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):
@@ -743,6 +767,21 @@ class PendulumKernels(object):
         else:
             tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
             check(_lib.load().rpo_pendulum_evaluate_record(*args, *tr, _stream()), "rpo_pendulum_evaluate_record")
+
+    def evaluate_budgets(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                         steps, box_lo, box_hi, lane_steps, lane_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                         con=None):
+        """``evaluate`` with a projection budget per lane (rpo_pendulum_evaluate_budgets): lane_steps int32 [n] / lane_lr
+        float32 [n] on the device in place of max_steps / corr_lr; con as there; no record, no noise."""
+        net = actor_desc.net_struct()
+        n = internal.shape[0]
+        sp, lp = _eval_lanes(lane_steps, lane_lr, n)
+        check(_lib.load().rpo_pendulum_evaluate_budgets(
+            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action), _p(ep_len, torch.int32),
+            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0),
+            int(steps), box_lo, box_hi, 0, 0.0, corr_eps, corr_momentum, max_episode_steps, viol_thresh, None, 0, 0,
+            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), sp, lp, _stream()),
+            "rpo_pendulum_evaluate_budgets")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):

@@ -7,6 +7,7 @@
     python tools/bench_eval.py --record [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_record_bench.json]
     python tools/bench_eval.py --constraints [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_constraints_bench.json]
     python tools/bench_eval.py --obs-noise [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_noise_bench.json]
+    python tools/bench_eval.py --budgets [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_budgets_bench.json]
 
 Per configuration (cart-RPODDPG, cart-RPOSAC, pendulum-RPODDPG: fused; EVOPF-RPODDPG: stepwise only) a trainer with
 bench.py's hyper-parameters is trained for a few vector steps (a policy that has left its initialisation), then:
@@ -27,6 +28,12 @@ cart-RPODDPG and pendulum-RPOSAC at --sizes episodes, stepwise EVOPF-RPODDPG at 
 obs_noise=sigma of ONE build alternate (sigma 0.05; EVOPF-v0 1e-3); the ratio of the medians is reported next to the legs' own
 spreads.  A noisy policy takes other episodes than a clean one, so every leg also reports the env steps it took and its time
 per env step.
+--budgets: ONE evaluate_budgets() call with B = 8 budgets (eval_steps 0..7 at the trainer's eval_lr) against the 8 evaluate()
+calls it is defined by, in ONE build, by the same method (alternating rounds, medians and min-max spreads of the whole call's
+wall time, read-backs included).  Fused cart-RPODDPG and pendulum-RPOSAC at --sizes episodes, stepwise EVOPF-RPODDPG at 10
+(where evaluate_budgets() runs those 8 calls itself: the ratio there measures only its bookkeeping).  Reported per size: the two
+legs, the ratio sweep / eight calls, and the sweep against ONE evaluate() call at the largest budget (the claim to test:
+about one call's time while B x episodes lanes do not fill the chip).
 Every call ends with a host read of the results (evaluate()'s .cpu(), eval()'s), so wall times include the device work.
 Run each GPU step under its own time limit (timeout -k 10 ...).
 """
@@ -172,6 +179,33 @@ def noise_bench(a, sizes):
     return line
 
 
+def budgets_bench(a, sizes):
+    line = dict(tool="bench_eval --budgets", device=torch.cuda.get_device_name(0), reps=a.reps, configs={})
+    budgets = list(range(8))
+    for workload, has_fused in (("cart_ddpg", True), ("pen_sac", True), ("evopf_ddpg", False)):
+        tr = trainer(workload)
+        row = {}
+        for n in (sizes if has_fused else [10]):
+            legs = {"evaluate_budgets": lambda: tr.evaluate_budgets(n, eval_steps=budgets, seed=5),
+                    "eight_evaluate_calls": lambda: [tr.evaluate(n, seed=5, eval_steps=b, eval_lr=tr.eval_lr) for b in budgets],
+                    "one_evaluate_call": lambda: tr.evaluate(n, seed=5, eval_steps=budgets[-1], eval_lr=tr.eval_lr)}
+            res = alternating(legs, a.reps)
+            s, calls = legs["evaluate_budgets"](), legs["eight_evaluate_calls"]()
+            assert s.path == ("fused" if has_fused else "sweep")
+            for g, r in enumerate(calls):                        # faster and different is not faster: the same bits
+                assert all(getattr(s[g], f).tobytes() == getattr(r, f).tobytes() for f in r.FIELDS), (workload, n, g)
+            res.update(ratio_to_eight_calls=res["evaluate_budgets"]["median_s"] / res["eight_evaluate_calls"]["median_s"],
+                       ratio_to_one_call=res["evaluate_budgets"]["median_s"] / res["one_evaluate_call"]["median_s"],
+                       budgets=budgets, lanes=len(budgets) * n, horizon=s.horizon, path=s.path, env_steps=int(s.length.sum()),
+                       violation_rate=s.violation_rate().tolist())
+            row[str(n)] = res
+            del s, calls
+        line["configs"][workload] = row
+        del tr
+        torch.cuda.empty_cache()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -180,12 +214,13 @@ def main():
     ap.add_argument("--record", action="store_true")
     ap.add_argument("--constraints", action="store_true")
     ap.add_argument("--obs-noise", action="store_true")
+    ap.add_argument("--budgets", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sizes = [int(x) for x in a.sizes.split(",") if x]
-    if a.record or a.constraints or a.obs_noise:
+    if a.record or a.constraints or a.obs_noise or a.budgets:
         small = [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes
-        bench = noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
+        bench = budgets_bench if a.budgets else noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
         s = json.dumps(bench(a, small))
         print(s)
         if a.out:
