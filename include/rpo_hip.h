@@ -974,6 +974,30 @@ int rpo_pendulum_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float sc
                                   int trace_rows, int trace_steps, float* con, const int* lane_steps, const float* lane_lr,
                                   void* stream);
 
+/* The same launches with an actor PER GROUP of lanes (RPOTrainerBase.evaluate_policies): P policies on the same initial
+ * states in one launch sequence.  The n_envs lanes are P groups of group_lanes lanes, group-major; group g evaluates the
+ * actor whose parameters lie g * policy_stride floats behind those of actor_host -- every non-NULL pointer of the descriptor
+ * is advanced by that much, so actor_host describes policy 0 of a DEVICE bank [P, policy_stride] in which every policy has the
+ * layout of policy 0.  Of every group the first `episodes` lanes are live; the others are padding: they are never stepped,
+ * never keep a workgroup alive, and their rows of acc, con, action and of the env arrays are neither read into a result nor
+ * written.  policy_stride: > 0 and a multiple of 4 (W0 of every policy stays 16-byte aligned); group_lanes: > 0 and a multiple
+ * of 64 (no workgroup's lanes belong to two policies); 1 <= episodes <= group_lanes; n_envs a whole multiple of group_lanes
+ * (RPO_ERR_ARG otherwise, before any HIP call).  The arguments are those of rpo_<env>_evaluate_constraints without a trace
+ * and with con optional (NULL: no report); no record, no noise, one budget.  acc, con, action and the env arrays have
+ * n_envs rows.  Lanes never read one another, so rows [g * group_lanes, g * group_lanes + episodes) are
+ * == rpo_<env>_evaluate[_constraints] of the episodes-lane env with the g-th actor, bit for bit, for every g. */
+int rpo_cartsafe_evaluate_policies(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                   float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                   int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                   float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                   float viol_thresh, float* con, int policy_stride, int group_lanes, int episodes,
+                                   void* stream);
+int rpo_pendulum_evaluate_policies(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                   float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                   float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                   float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* con,
+                                   int policy_stride, int group_lanes, int episodes, void* stream);
+
 /* The stepwise form of the noise (any env): out[i, q] = obs[i, q] + sigma[q] * z(i, step, q) for i < n, q < obs_dim, with the
  * draw and the arithmetic above (== per column q with sigma[q] != 0: rpo_philox_normal(n, ., seed, 0, step,
  * RPO_STREAM_EVAL_OBS + 0x100 * q, NULL), then the unfused multiply and add); a column with sigma[q] == 0 is copied.  obs

@@ -39,6 +39,13 @@ states, group g being bit for bit the ``evaluate()`` call with ``eval_steps[g]``
 fused path the B groups run side by side as B x episodes lanes of one launch sequence (``rpo_<env>_evaluate_budgets``: the fused
 kernel's BUD instances read the budget and the step size per lane); every other configuration runs the B calls ("sweep").
 
+Policy sweeps (``evaluate_policies([None, p, trainer.best, "b.npz"], episodes)`` -> ``PolicySweep``): P actors on the SAME initial
+states, group g being bit for bit the ``evaluate()`` call under ``using_policy(policies[g])`` with the shared seed.  On the fused
+path the P actor spans are gathered into one bank [P, span] and the groups run side by side, each padded to whole 64-lane tiles,
+as P x padded lanes of one launch sequence (``rpo_<env>_evaluate_policies``: the fused kernel's POL instances take their
+group's actor out of the bank); every other configuration runs the P calls ("sweep").  The live actor is never written on the
+fused path and is back bit for bit after the sweep path.
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
 does not record trajectories and produces no per-constraint reports.  With the trainer argument ``keep_best`` every point's
@@ -46,7 +53,10 @@ row is compared with the incumbent's on the device right behind its summary (``r
 and the actor's parameters of a winning point are kept: ``trainer.best`` (``BestPolicy``), ``restore_best()``,
 ``using_best()``.
 """
+import collections
+import contextlib
 import math
+import os
 
 import numpy as np
 import torch
@@ -499,7 +509,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     return res
 
 
-def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None, lanes=None):
+def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None, lanes=None, groups=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
     trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
@@ -507,7 +517,9 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
     per-constraint report [n, W] every launch continues (rpo_<env>_evaluate_constraints).  ``noise``: (sigma float32 numpy
     [obs_dim], seed) of ``obs_noise=`` (rpo_<env>_evaluate_noisy; the draw is keyed by the absolute step t0 + s); None: the
     kernels' ``evaluate`` gets no such keyword.  ``lanes``: (eval_steps int32 [n], eval_lr float32 [n]) on the device, the budget
-    and step size of every lane in place of ``budget`` (rpo_<env>_evaluate_budgets; con only, neither trace nor noise)."""
+    and step size of every lane in place of ``budget`` (rpo_<env>_evaluate_budgets; con only, neither trace nor noise).
+    ``groups``: (bank [P, span], group_lanes, episodes) with ``desc`` over bank[0]: an actor per group of lanes
+    (rpo_<env>_evaluate_policies; con only, neither trace nor noise nor lanes)."""
     n = v.n
     eval_steps = tr.eval_steps if budget[0] is None else budget[0]
     eval_lr = tr.eval_lr if budget[1] is None else budget[1]
@@ -527,6 +539,15 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
                                         v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
                                         tr._box_hi, lanes[0], lanes[1], tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
                                         v.viol_thresh, **kw)
+        return
+    if groups is not None:
+        if trace is not None or noise is not None:
+            raise ValueError("policy groups run without a record and without observation noise")
+        for t0 in range(0, H, steps):
+            tr.kernels.evaluate_policies(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs,
+                                         v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
+                                         tr._box_hi, eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
+                                         v.viol_thresh, *groups, **kw)
         return
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
@@ -577,25 +598,16 @@ MAX_BUDGETS = 64
 _FUSED_BUDGET_LANES = 1 << 24                                    # B x episodes lanes of one fused launch; beyond: "sweep"
 
 
-class BudgetSweep(object):
-    """The result of ``evaluate_budgets()``: B projection budgets evaluated on the same initial states.
+class ResultSweep(object):
+    """What ``BudgetSweep`` and ``PolicySweep`` share: G ``EvalResult``s of the same episodes (``sweep[g]`` is ``results[g]``)
+    and their fields stacked into [G, episodes] arrays whose rows ARE the results' arrays (one memory)."""
 
-    ``eval_steps`` int64 [B] / ``eval_lr`` float32 [B]: the budgets in the caller's order; ``results``: B ``EvalResult``s
-    (``sweep[g]`` is ``results[g]``), each what ``evaluate(eval_steps=eval_steps[g], eval_lr=eval_lr[g])`` with the shared seed
-    returns.  ``ret``, ``length``, ``mean_ineq``, ``mean_eq``, ``max_ineq``, ``max_eq``, ``viol_steps``, ``proj_iters`` (also
-    ``iters``), ``nonfinite``: [B, episodes] arrays whose rows ARE the results' arrays (one memory).  ``path``: "fused" (one
-    launch sequence over B x episodes lanes) or "sweep" (B ``evaluate()`` calls).  ``seed``, ``horizon``: the shared ones."""
-
-    def __init__(self, results, eval_steps, eval_lr, path):
+    def _stack(self, results):
         self.results = list(results)
-        self.eval_steps = np.array(eval_steps, dtype=np.int64).reshape(-1)
-        self.eval_lr = np.array(eval_lr, dtype=np.float32).reshape(-1)
-        if not self.results or not len(self.results) == len(self.eval_steps) == len(self.eval_lr):
-            raise ValueError("BudgetSweep: %d results for %d budgets and %d step sizes"
-                             % (len(self.results), len(self.eval_steps), len(self.eval_lr)))
+        if not self.results:
+            raise ValueError("%s: no results" % type(self).__name__)
         if len(set(r.episodes for r in self.results)) != 1:
-            raise ValueError("BudgetSweep: the results have different numbers of episodes")
-        self.path = path
+            raise ValueError("%s: the results have different numbers of episodes" % type(self).__name__)
         self.seed, self.horizon = self.results[0].seed, self.results[0].horizon
         for f in EvalResult.FIELDS:
             rows = np.stack([getattr(r, f) for r in self.results])
@@ -615,12 +627,32 @@ class BudgetSweep(object):
         return self.ret.shape[1]
 
     def violation_rate(self):
-        """Per budget: the fraction of its evaluated env steps whose max inequality violation exceeds ``viol_thresh`` [B]."""
+        """Per group: the fraction of its evaluated env steps whose max inequality violation exceeds ``viol_thresh`` [G]."""
         return self.viol_steps.sum(axis=1).astype(np.float64) / self.length.sum(axis=1).astype(np.float64)
 
     def ret_mean(self):
-        """Per budget: the mean return over the episodes [B]."""
+        """Per group: the mean return over the episodes [G]."""
         return self.ret.mean(axis=1)
+
+
+class BudgetSweep(ResultSweep):
+    """The result of ``evaluate_budgets()``: B projection budgets evaluated on the same initial states.
+
+    ``eval_steps`` int64 [B] / ``eval_lr`` float32 [B]: the budgets in the caller's order; ``results``: B ``EvalResult``s
+    (``sweep[g]`` is ``results[g]``), each what ``evaluate(eval_steps=eval_steps[g], eval_lr=eval_lr[g])`` with the shared seed
+    returns.  ``ret``, ``length``, ``mean_ineq``, ``mean_eq``, ``max_ineq``, ``max_eq``, ``viol_steps``, ``proj_iters`` (also
+    ``iters``), ``nonfinite``: [B, episodes] arrays whose rows ARE the results' arrays (one memory).  ``path``: "fused" (one
+    launch sequence over B x episodes lanes) or "sweep" (B ``evaluate()`` calls).  ``seed``, ``horizon``: the shared ones."""
+
+    def __init__(self, results, eval_steps, eval_lr, path):
+        results = list(results)
+        self.eval_steps = np.array(eval_steps, dtype=np.int64).reshape(-1)
+        self.eval_lr = np.array(eval_lr, dtype=np.float32).reshape(-1)
+        if not results or not len(results) == len(self.eval_steps) == len(self.eval_lr):
+            raise ValueError("BudgetSweep: %d results for %d budgets and %d step sizes"
+                             % (len(results), len(self.eval_steps), len(self.eval_lr)))
+        self._stack(results)
+        self.path = path
 
     def budget(self, max_rate=0.0):
         """The smallest ``eval_steps[g]`` whose ``violation_rate()[g]`` is <= ``max_rate``; None if no budget of the sweep is."""
@@ -714,6 +746,230 @@ def evaluate_budgets(tr, episodes=10, eval_steps=None, eval_lr=None, horizon=Non
                                                          getattr(tr.base_env, "eq_names", None))
         results.append(res)
     return BudgetSweep(results, steps, lrs, "fused")
+
+
+# ------------------------------------------------------------------------------------------------ policy sweeps
+MAX_POLICIES = 64
+_FUSED_POLICY_LANES = 1 << 24                                    # P x padded lanes of one fused launch; beyond: "sweep"
+Paired = collections.namedtuple("Paired", "mean stderr n")
+
+
+class PolicySweep(ResultSweep):
+    """The result of ``evaluate_policies()``: P actors evaluated on the same initial states.
+
+    ``names``: P strings in the caller's order; ``results``: P ``EvalResult``s (``sweep[g]`` is ``results[g]``), each what
+    ``evaluate()`` under ``using_policy(policies[g])`` with the shared seed returns.  ``ret``, ``length``, ``mean_ineq``,
+    ``mean_eq``, ``max_ineq``, ``max_eq``, ``viol_steps``, ``proj_iters`` (also ``iters``), ``nonfinite``: [P, episodes] arrays
+    whose rows ARE the results' arrays (one memory).  ``path``: "fused" (one launch sequence over P x padded lanes) or "sweep"
+    (P ``evaluate()`` calls).  ``seed``, ``horizon``: the shared ones."""
+
+    def __init__(self, results, names, path):
+        results, self.names = list(results), tuple(str(x) for x in names)
+        if not results or len(results) != len(self.names):
+            raise ValueError("PolicySweep: %d results for %d names" % (len(results), len(self.names)))
+        self._stack(results)
+        self.path = path
+
+    def paired(self, a, b):
+        """The paired comparison of policies a and b: ``Paired(mean, stderr, n)`` of the per-episode return difference
+        ``ret[a] - ret[b]`` (episode e of both started from the same state); stderr: the sample standard deviation (n - 1)
+        over sqrt(n), NaN for n = 1."""
+        d = self.ret[a] - self.ret[b]
+        n = d.shape[0]
+        return Paired(float(d.mean()), float(d.std(ddof=1) / math.sqrt(n)) if n > 1 else float("nan"), n)
+
+    def best(self, max_rate=0.0):
+        """The index ``keep_best`` would hold after seeing the groups in order (``keep_best_wins`` of csrc/eval_dev.h on the
+        groups' summaries): a group is safe when its violation rate is <= ``max_rate``; safe beats unsafe; among safe groups
+        the strictly higher mean return wins; among unsafe ones the strictly lower rate, then the higher return; ties keep the
+        earlier group; a group with a non-finite episode or a NaN mean return is never taken.  None: no group is eligible."""
+        length, viol, ret = self.length.sum(axis=1), self.viol_steps.sum(axis=1), self.ret_mean()
+        held = held_rate = None
+        for g in range(len(self)):
+            if self.nonfinite[g].any() or ret[g] != ret[g]:
+                continue
+            rate = float("inf") if length[g] == 0 else float(viol[g]) / float(length[g])
+            if held is not None:
+                safe, held_safe = rate <= max_rate, held_rate <= max_rate
+                if safe != held_safe:
+                    wins = safe
+                elif safe:
+                    wins = ret[g] > ret[held]
+                else:
+                    wins = rate < held_rate or (rate == held_rate and ret[g] > ret[held])
+                if not wins:
+                    continue
+            held, held_rate = g, rate
+        return held
+
+    def __repr__(self):
+        return "PolicySweep(policies=%s, episodes=%d, path=%s, return=%s, violation_rate=%s)" % (
+            list(self.names), self.episodes, self.path, np.array2string(self.ret_mean(), precision=4),
+            np.array2string(self.violation_rate(), precision=4))
+
+
+def actor_span(tr, what):
+    """(flat buffer, actor_range) of a trainer whose actor lives in the flat parameter buffer (ValueError otherwise)."""
+    flat = getattr(tr.agent, "flat", None)
+    if getattr(flat, "actor_range", None) is None:
+        raise ValueError("%s needs the actor in the flat parameter buffer (agent.flat.actor_range): %s has none"
+                         % (what, type(tr.agent).__name__))
+    return flat, flat.actor_range
+
+
+def check_policy(entry, size, what):
+    """One policy of ``using_policy()`` / ``evaluate_policies()`` -> None (the live actor) or a flat float32 tensor of ``size``
+    floats: None; a float32 tensor or numpy array of exactly ``size`` floats; a ``BestPolicy``; a path ``BestPolicy.load`` reads
+    (ValueError for anything else, another length, another dtype, a file that does not load)."""
+    if entry is None:
+        return None
+    if isinstance(entry, (str, bytes, os.PathLike)):
+        if not os.path.isfile(entry):
+            raise ValueError("%s: %r is not a file" % (what, entry))
+        try:
+            entry = BestPolicy.load(entry)
+        except Exception as e:                                   # noqa: BLE001 (np.load's own errors, a missing key)
+            raise ValueError("%s: BestPolicy.load cannot read %r (%s)" % (what, entry, e))
+    if isinstance(entry, BestPolicy):
+        entry = entry.params
+    if isinstance(entry, np.ndarray) and entry.dtype == np.float32:
+        entry = torch.from_numpy(np.ascontiguousarray(entry))
+    if not isinstance(entry, torch.Tensor) or entry.dtype != torch.float32:
+        raise ValueError("%s: a policy is None, a float32 tensor / array of %d floats, a BestPolicy or a path, got %s"
+                         % (what, size, type(entry).__name__ if not hasattr(entry, "dtype") else entry.dtype))
+    if entry.numel() != size:
+        raise ValueError("%s: the actor's span of the flat parameter buffer has %d floats, the policy has %d"
+                         % (what, size, entry.numel()))
+    return entry.detach().reshape(-1)
+
+
+def policy_params(tr):
+    """See ``RPOTrainerBase.policy_params``."""
+    flat, rng = actor_span(tr, "policy_params()")
+    with torch.no_grad():
+        return flat.param(rng).clone()
+
+
+@contextlib.contextmanager
+def using_policy(tr, policy):
+    """See ``RPOTrainerBase.using_policy``."""
+    flat, rng = actor_span(tr, "using_policy()")
+    src = check_policy(policy, rng[1] - rng[0], "using_policy()")
+    if src is None:                                              # the live actor is the live actor
+        yield tr
+        return
+    live = flat.param(rng)
+    with torch.no_grad():
+        stash = live.clone()
+        live.copy_(src)
+    try:
+        yield tr
+    finally:
+        with torch.no_grad():
+            live.copy_(stash)
+
+
+def _policy_name(entry, g):
+    if entry is None:
+        return "live"
+    if isinstance(entry, (str, bytes, os.PathLike)):
+        return os.fspath(entry) if not isinstance(entry, bytes) else os.fsdecode(entry)
+    return "best[%d]" % entry.point if isinstance(entry, BestPolicy) else "policy[%d]" % g
+
+
+def check_policies(tr, policies, names):
+    """``policies`` / ``names`` of evaluate_policies() -> (flat, actor_range, list of P spans (None: the live actor), P names): a
+    sequence of 1 to ``MAX_POLICIES`` entries ``check_policy`` takes; ``names`` None or P strings (ValueError otherwise)."""
+    what = "evaluate_policies"
+    flat, rng = actor_span(tr, what + "()")
+    if policies is None or isinstance(policies, (str, bytes, torch.Tensor, np.ndarray, BestPolicy)) or not hasattr(policies, "__len__"):
+        raise ValueError("%s: policies must be a sequence of 1 to %d policies, got %r" % (what, MAX_POLICIES, type(policies).__name__))
+    entries = list(policies)
+    if not 1 <= len(entries) <= MAX_POLICIES:
+        raise ValueError("%s: policies must hold 1 to %d policies, got %d" % (what, MAX_POLICIES, len(entries)))
+    spans = [check_policy(e, rng[1] - rng[0], "%s: policies[%d]" % (what, g)) for g, e in enumerate(entries)]
+    if names is None:
+        names = [_policy_name(e, g) for g, e in enumerate(entries)]
+    elif isinstance(names, (str, bytes)) or not hasattr(names, "__len__") or len(names) != len(entries) or \
+            not all(isinstance(x, str) for x in names):
+        raise ValueError("%s: names must be None or %d strings, got %r" % (what, len(entries), names))
+    return flat, rng, spans, list(names)
+
+
+def policy_bank(tr, spans):
+    """(bank, descriptor) of the fused path: the P spans (None: the live actor's) side by side in one device tensor
+    [P, span] -- the span is a multiple of 4 floats by FlatParams' padding, so every policy's tensors keep the alignment of
+    the live ones -- and ONE ``MlpDesc`` over policy 0, built as ``CurveRunner._alloc`` builds its snapshot's."""
+    flat, (lo, hi) = actor_span(tr, "evaluate_policies()")
+    live, d = flat.param((lo, hi)), tr.fused.descs["actor"]
+    bank = torch.empty(len(spans), hi - lo, device=tr.device)
+    for g, src in enumerate(spans):
+        bank[g].copy_(live if src is None else src)
+    tensors = {}
+    for key, p in d.tensors.items():
+        if p is not None:
+            off = flat.offset[id(p)] - lo
+            tensors[key] = bank[0, off:off + p.numel()].view(p.shape)
+    return bank, tr.backend.MlpDesc(tensors, d.S, d.A, d.E, d.H, d.n_out, d.cat, head_dim=d.head_dim)
+
+
+def evaluate_policies(tr, policies, episodes=10, seed=None, horizon=None, init_states=None, constraints=False, names=None):
+    """See ``RPOTrainerBase.evaluate_policies``."""
+    _, _, spans, names = check_policies(tr, policies, names)
+    n = check_episodes(episodes, "evaluate_policies: episodes")
+    want_con = check_constraints(constraints)
+    P = len(spans)
+    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
+        raise ValueError("evaluate_policies: horizon must be an integer >= 1, got %r" % (horizon,))
+    H = int(horizon) if horizon is not None else default_horizon(tr)
+    if H >= 1 << 24:
+        raise ValueError("evaluate_policies: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
+    k = tr.kernels
+    if init_states is not None:
+        init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
+        if tuple(init_states.shape) != (n, k.internal_dim):
+            raise ValueError("evaluate_policies: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
+                             % (n, k.internal_dim, tuple(init_states.shape)))
+    seed = fresh_seed(tr) if seed is None else int(seed)         # ONE seed (and one tick of the call counter) for all policies
+    GL = (n + hip_ops.POLICY_GROUP_ALIGN - 1) // hip_ops.POLICY_GROUP_ALIGN * hip_ops.POLICY_GROUP_ALIGN
+    fused = bool(fused_ok(tr) and hasattr(k, "evaluate_policies") and tr.schedule.get("fused_policies", 1)
+                 and P * GL <= _FUSED_POLICY_LANES)
+    if not fused:
+        results = []
+        for src in spans:
+            with using_policy(tr, src):
+                results.append(evaluate(tr, episodes=n, horizon=H, seed=seed, init_states=init_states, constraints=want_con))
+        return PolicySweep(results, names, "sweep")
+    dev = tr.device
+    make = dict(seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev, stats_cap=2,
+                viol_thresh=tr.vec.viol_thresh)
+    v = tr.base_env.make_vec(n, **make)                          # the initial states of evaluate(): reset, then the injection
+    v.reset()
+    if init_states is not None:
+        v.set_internal(init_states)
+    with torch.no_grad():
+        bank, desc = policy_bank(tr, spans)
+        # P copies of the initial states, group-major, every group padded to GL lanes: lane g * GL + e is episode e under
+        # policy g; internal AND obs are tiled, as in evaluate_budgets().  The padding lanes keep the new env's rows: the
+        # kernel neither steps nor writes them
+        big = tr.base_env.make_vec(P * GL, **make)
+        big.internal.view(P, GL, -1)[:, :n].copy_(v.internal)
+        if big.obs is not big.internal:
+            big.obs.view(P, GL, -1)[:, :n].copy_(v.obs)
+        acc = torch.zeros(P * GL, 8, device=dev)
+        con = torch.zeros(P * GL, hip_ops.con_width(k.ineq_num, k.eq_num), device=dev) if want_con else None
+        _run_fused(tr, big, acc, H, desc=desc, con=con, groups=(bank, GL, n))
+    acc_host = acc.cpu().numpy().reshape(P, GL, 8)
+    con_host = con.cpu().numpy().reshape(P, GL, -1) if want_con else None
+    results = []
+    for g in range(P):
+        res = EvalResult(acc_host[g, :n], "fused", H, seed)
+        if want_con:
+            res.constraints = ConstraintReport.from_rows(con_host[g, :n], k.ineq_num, k.eq_num, res.length, big.viol_thresh,
+                                                         getattr(tr.base_env, "ineq_names", None),
+                                                         getattr(tr.base_env, "eq_names", None))
+        results.append(res)
+    return PolicySweep(results, names, "fused")
 
 
 # ------------------------------------------------------------------------------------------------ evaluation curves

@@ -1202,6 +1202,24 @@ class RPOTrainerBase(object):
             with torch.no_grad():
                 curve.live.copy_(stash)
 
+    def policy_params(self):
+        """A clone of the live actor's span of the flat parameter buffer (``agent.flat.actor_range``; shared_param=True: the
+        state embedding it shares with the critic included): float32 on the trainer's device, the layout of
+        ``BestPolicy.params``.  Training afterwards does not change it.  What ``using_policy()`` and ``evaluate_policies()``
+        take; ValueError for an agent without ``actor_range``."""
+        from .evaluation import policy_params
+        return policy_params(self)
+
+    def using_policy(self, policy):
+        """``with trainer.using_policy(p):`` -- inside, the live actor IS ``p`` (``evaluate()``, ``act()``, ``eval()`` on
+        either path see it); on exit, exception or not, the live span is back bit for bit.  ``p``: what one entry of
+        ``evaluate_policies()`` may be -- None (the live policy stays), a float32 tensor / array of the span's length
+        (``policy_params()``), a ``BestPolicy`` or a path ``BestPolicy.load`` reads; ValueError otherwise, before anything is
+        written.  Torch copies on the current stream, no host read; needs no ``keep_best``.  Targets, the rest of the critic,
+        the Adam moments and step counters are untouched.  Do not train inside the context."""
+        from .evaluation import using_policy
+        return using_policy(self, policy)
+
     def _advance_host(self, t):
         """Host mirrors of the device-side counters after vector step ``t``."""
         self._t = t
@@ -1539,6 +1557,35 @@ class RPOTrainerBase(object):
         from .evaluation import evaluate_budgets
         return evaluate_budgets(self, episodes=episodes, eval_steps=eval_steps, eval_lr=eval_lr, horizon=horizon, seed=seed,
                                 init_states=init_states, constraints=constraints)
+
+    def evaluate_policies(self, policies, episodes=10, seed=None, horizon=None, init_states=None, constraints=False, names=None):
+        """Evaluate P policies on the SAME episodes -> ``PolicySweep``: which of these actors is better, with the initial
+        states taken out of the comparison?  ``policies``: a sequence of 1 to 64 entries, each None (the live actor), a
+        float32 tensor / array of exactly ``actor_range[1] - actor_range[0]`` floats (``policy_params()``, the ``params`` of
+        a ``BestPolicy``, another trainer's span), a ``BestPolicy`` (``trainer.best``) or a path ``BestPolicy.load`` reads;
+        ``names``: None or P strings for ``sweep.names``; ``episodes``, ``horizon``, ``seed``, ``init_states``
+        ([episodes, internal_dim], shared by all policies) and ``constraints`` are ``evaluate()``'s and validated like them.
+        Definition: group g is, bit for bit, ``with trainer.using_policy(policies[g]): trainer.evaluate(episodes, horizon,
+        seed=seed, init_states=init_states, constraints=constraints)`` -- every policy starts from the same initial states,
+        and ``seed=None`` draws ONE seed as ``evaluate()`` does (one tick of its call counter).  ``sweep.results[g]`` /
+        ``sweep[g]`` are the P ``EvalResult``s; ``sweep.ret``, ``.length``, ``.viol_steps``, ``.max_ineq``, ``.iters`` ... are
+        [P, episodes] arrays over the same memory; ``sweep.violation_rate()`` and ``sweep.ret_mean()`` are [P];
+        ``sweep.paired(a, b)`` is (mean, stderr, n) of the per-episode return difference ``ret[a] - ret[b]`` (stderr: sample
+        standard deviation / sqrt(n), NaN for n = 1); ``sweep.best(max_rate=0.0)`` is the index ``keep_best``'s criterion
+        picks among the groups (safe beats unsafe, then the higher mean return; among unsafe groups the lower rate; ties keep
+        the earlier group; None when every group is non-finite).  ``sweep.path``: "fused" -- where ``evaluate()`` takes its
+        fused path (schedule ``fused_policies=0`` switches it off), the P spans are gathered into one device bank and the
+        groups, each padded to whole 64-lane tiles, run as P x padded lanes of ONE launch sequence whose workgroups take
+        their group's actor out of the bank: one vector env, one read-back, the live actor never written -- or "sweep":
+        EVOPF-v0, the Lagrangian baselines, 256-wide actors, ``fused_mlp=0``, the oracle backend and more than 2^24 padded
+        lanes run the P calls of the definition, and the live span is back bit for bit afterwards.  No ``record=``,
+        ``obs_noise=``, ``eval_steps=`` or ``eval_lr=``: call ``evaluate()`` under ``using_policy()`` for those.  ValueError,
+        before anything is allocated and without a tick of the call counter: no or more than 64 policies, an entry of
+        another kind, length or dtype, a path that is no file, an agent without ``actor_range``.  No trainer state changes
+        (flat buffer, targets, Adam moments, training env), as for ``evaluate()``.  See rpo_amd/algo/evaluation.py."""
+        from .evaluation import evaluate_policies
+        return evaluate_policies(self, policies, episodes=episodes, seed=seed, horizon=horizon, init_states=init_states,
+                                 constraints=constraints, names=names)
 
     def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0, profile=False):
         """The policy's projected actions for caller-supplied observations -> ``ActResult`` (torch tensors on the trainer's

@@ -14,6 +14,8 @@
 //                        update the same rows themselves (eval_dev.h: rpo_eval_con_lane_update).
 //   (no kernel)          evaluate_budgets(): the fused kernel's BUD = 1 instances (rpo_<env>_evaluate_budgets) read the projection's
 //                        budget and step size per lane, so B budgets x episodes run side by side in one launch.
+//   (no kernel)          evaluate_policies(): the fused kernel's POL = 1 instances (rpo_<env>_evaluate_policies) run every group of
+//                        group_lanes lanes on an actor of its own out of a bank, so P policies x episodes run in one launch.
 //   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
 //   keep_best_*_kernel   that row against the incumbent's on the device, and the predicated copy of the actor's parameters
 //                        (rpo_eval_keep_best; the criterion is eval_dev.h: keep_best_wins).
@@ -71,10 +73,20 @@ struct EvalBudArgs : EvalConArgs<ENV> {
     const int* lane_steps;        // [n] GRG iterations at most, in place of act.max_steps
     const float* lane_lr;         // [n] step size, in place of act.corr_lr
 };
-template <class ENV, int CON, int NOISE, int BUD = 0> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
-template <class ENV> struct EvalArgsOf<ENV, 1, 0, 0> { typedef EvalConArgs<ENV> type; };
-template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 1, 0> { typedef EvalNoiseArgs<ENV> type; };
-template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 0, 1> { typedef EvalBudArgs<ENV> type; };
+// The POL = 1 instances (evaluate_policies()) take the groups' geometry behind the EvalConArgs arguments (con: NULL for their
+// CON = 0 instances, which never read it); `actor` describes policy 0 of the bank; the POL = 0 instances keep their parameter
+// types.
+template <class ENV>
+struct EvalPolArgs : EvalConArgs<ENV> {
+    int policy_stride;            // floats from one policy of the bank to the next: > 0, a multiple of 4
+    int group_lanes;              // lanes per policy, padding included: a multiple of 64; n = P * group_lanes
+    int episodes;                 // live lanes per group: 1 <= episodes <= group_lanes
+};
+template <class ENV, int CON, int NOISE, int BUD = 0, int POL = 0> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
+template <class ENV> struct EvalArgsOf<ENV, 1, 0, 0, 0> { typedef EvalConArgs<ENV> type; };
+template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 1, 0, 0> { typedef EvalNoiseArgs<ENV> type; };
+template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 0, 1, 0> { typedef EvalBudArgs<ENV> type; };
+template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 0, 0, 1> { typedef EvalPolArgs<ENV> type; };
 
 // What one env step leaves for the statistics: reward, done and the violations of the transition row, without the row --
 // their maxima for the accumulators, and the row's ineq_viol / eq_viol columns themselves (gi / he) for the report.
@@ -179,9 +191,26 @@ __device__ __forceinline__ float2 eval_project(const ARGS& p, const typename ENV
     else return ENV::project(p.act, c, obs, i, ap, 0.0f, 0, k);
 }
 
-template <class ENV, int EIN, int H, int RT, int REC, int CON, int NOISE, int BUD = 0>
-__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON, NOISE, BUD>::type p, typename ENV::Consts c) {
+// POL = 1: the workgroup's 16 * RT lanes belong to ONE group g = row0 / group_lanes (group_lanes is a multiple of 64), a
+// function of blockIdx alone that is pinned to a scalar register; the workgroup runs the loop on a copy of the descriptor
+// whose non-NULL pointers are advanced by g * policy_stride floats -- scalar adds in front of the loop, nothing per policy
+// in a vector register.  A lane is `mine` only inside its group's first `episodes` lanes: padding lanes are never live, so
+// they never step, never write a row and never keep the workgroup alive (an all-padding workgroup leaves at the first
+// __syncthreads_or); their env rows are staged like any lane's and their outputs dropped.
+__device__ __forceinline__ const float* policy_ptr(const float* p, size_t off) { return p ? p + off : p; }
+__device__ __forceinline__ Mlp policy_of_group(const Mlp& a, int g, int policy_stride) {
+    const size_t off = (size_t)g * (size_t)policy_stride;
+    Mlp m = a;
+    m.Ws = policy_ptr(a.Ws, off); m.bs = policy_ptr(a.bs, off); m.Wa = policy_ptr(a.Wa, off); m.ba = policy_ptr(a.ba, off);
+    m.W0 = policy_ptr(a.W0, off); m.b0 = policy_ptr(a.b0, off); m.W1 = policy_ptr(a.W1, off); m.b1 = policy_ptr(a.b1, off);
+    m.W1b = policy_ptr(a.W1b, off); m.b1b = policy_ptr(a.b1b, off);
+    return m;
+}
+
+template <class ENV, int EIN, int H, int RT, int REC, int CON, int NOISE, int BUD = 0, int POL = 0>
+__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON, NOISE, BUD, POL>::type p, typename ENV::Consts c) {
     static_assert(!BUD || (!REC && !NOISE), "per-lane budgets: no record, no observation noise");
+    static_assert(!POL || (!REC && !NOISE && !BUD), "an actor per group: no record, no observation noise, one budget");
     typedef TileLds<EIN, RT, 8, 8> Lds;                          // 16 * RT lanes per workgroup; OBS <= 8
     __shared__ Lds lds;
     constexpr int kInS = Lds::kS;
@@ -190,14 +219,21 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
     const int tid = threadIdx.x;
     const int n = p.step.n;
     const int i = row0 + tid;
-    const bool mine = tid < kLanes && i < n;
+    bool mine = tid < kLanes && i < n;
+    Mlp group_actor;
+    if constexpr (POL) {
+        const int g = __builtin_amdgcn_readfirstlane(row0 / p.group_lanes);
+        mine = mine && i - g * p.group_lanes < p.episodes;
+        group_actor = policy_of_group(p.actor, g, p.policy_stride);
+    }
+    const Mlp& actor = POL ? group_actor : p.actor;
     for (int s = p.t0; s < p.t0 + p.steps; ++s) {
         // a lane's state is read from its accumulator row at every step (nothing of it stays live across the MFMA loops)
         const bool live = mine && (s == 0 || (__float_as_int(p.acc[(size_t)i * RPO_EVAL_LEN + 7]) & RPO_EVAL_ALIVE));
         if (!__syncthreads_or(live)) return;                     // (also the barrier in front of the LDS tiles' reuse)
         EvalEnv<ENV>::stage(p.step, row0, kLanes, lds.in_s, kInS);
         if constexpr (NOISE) stage_noise<ENV>(p, row0, kLanes, n, s, lds.in_s, kInS);
-        mlp_tile_forward<EIN, H, RT, Lds>(p.actor, lds, row0, n, nullptr, nullptr, p.gauss ? 0 : 1, p.scale, p.base);
+        mlp_tile_forward<EIN, H, RT, Lds>(actor, lds, row0, n, nullptr, nullptr, p.gauss ? 0 : 1, p.scale, p.base);
         if (live) {
             float ap = lds.out[tid * 2];
             if (p.gauss) ap = rpo_head_dev::gauss_head_row(ap, lds.out[tid * 2 + 1], 0.0f, p.scale, p.base, p.act.box_lo,
@@ -223,15 +259,15 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
     }
 }
 
-template <class ENV, int REC, int CON, int NOISE = 0, int BUD = 0>
-int launch_eval(const typename EvalArgsOf<ENV, CON, NOISE, BUD>::type& args, const typename ENV::Consts& c, int n, void* stream) {
+template <class ENV, int REC, int CON, int NOISE = 0, int BUD = 0, int POL = 0>
+int launch_eval(const typename EvalArgsOf<ENV, CON, NOISE, BUD, POL>::type& args, const typename ENV::Consts& c, int n, void* stream) {
     // the rollout's tile rule (fused.hip launch_rollout): 64 lanes per workgroup once that still fills the chip.  E = 128
     // only: the E = 256 instance spills (~150 bytes of scratch per lane) -- such actors evaluate on the stepwise path.
     if (args.actor.E != 128) return RPO_ERR_ARG;
     if (n >= 64 * 192) {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON, NOISE, BUD>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON, NOISE, BUD, POL>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     } else {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON, NOISE, BUD>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON, NOISE, BUD, POL>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     }
     RPO_LAUNCH_CHECK();
     return 0;
@@ -261,11 +297,31 @@ int check_eval_lanes(const EvalLanes& l) {
     return (reinterpret_cast<uintptr_t>(l.steps) | reinterpret_cast<uintptr_t>(l.lr)) % 4 ? RPO_ERR_ARG : 0;
 }
 
+// The groups of the *_evaluate_policies entry points (checked before any HIP call).
+struct EvalGroups {
+    int policy_stride, group_lanes, episodes;
+};
+int check_eval_groups(const EvalGroups& g, int n) {
+    if (g.policy_stride <= 0 || g.policy_stride % 4 || g.group_lanes <= 0 || g.group_lanes % 64) return RPO_ERR_ARG;
+    if (g.episodes < 1 || g.episodes > g.group_lanes || n < g.group_lanes || n % g.group_lanes) return RPO_ERR_ARG;
+    return 0;
+}
+
 // rec / con of the entry points -> the instance; con == NULL: the launches of rpo_<env>_evaluate[_record] as they were;
-// noise != NULL: the NOISE = 1 instances; lanes != NULL: the BUD = 1 instances (no record, no noise: checked by the callers)
+// noise != NULL: the NOISE = 1 instances; lanes != NULL: the BUD = 1 instances (no record, no noise: checked by the callers);
+// groups != NULL: the POL = 1 instances (no record, no noise, no lanes: checked by the callers)
 template <class ENV>
 int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, int rec, float* con, void* stream,
-                    const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr) {
+                    const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr) {
+    if (groups) {
+        EvalPolArgs<ENV> pa{};
+        static_cast<EvalArgs<ENV>&>(pa) = args;
+        pa.con = con;
+        pa.policy_stride = groups->policy_stride;
+        pa.group_lanes = groups->group_lanes;
+        pa.episodes = groups->episodes;
+        return con ? launch_eval<ENV, 0, 1, 0, 0, 1>(pa, c, n, stream) : launch_eval<ENV, 0, 0, 0, 0, 1>(pa, c, n, stream);
+    }
     if (lanes) {
         EvalBudArgs<ENV> ba{};
         static_cast<EvalArgs<ENV>&>(ba) = args;
@@ -600,7 +656,7 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, const float* consts_host,
                       int partial, int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows,
                       int trace_steps, int with_con, float* con, void* stream, const EvalNoise* noise = nullptr,
-                      const EvalLanes* lanes = nullptr) {
+                      const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (noise)
@@ -609,6 +665,10 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     if (lanes) {
         if (int e = check_eval_lanes(*lanes)) return e;
         if (rec || noise) return RPO_ERR_ARG;
+    }
+    if (groups) {
+        if (int e = check_eval_groups(*groups, n_envs)) return e;
+        if (rec || noise || lanes) return RPO_ERR_ARG;
     }
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
@@ -626,14 +686,15 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                                        max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
-    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes);
+    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups);
 }
 
 int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal, float* obs,
                       float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps,
                       float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                       int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows, int trace_steps,
-                      int with_con, float* con, void* stream, const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr) {
+                      int with_con, float* con, void* stream, const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr,
+                      const EvalGroups* groups = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (noise)
@@ -642,6 +703,10 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     if (lanes) {
         if (int e = check_eval_lanes(*lanes)) return e;
         if (rec || noise) return RPO_ERR_ARG;
+    }
+    if (groups) {
+        if (int e = check_eval_groups(*groups, n_envs)) return e;
+        if (rec || noise || lanes) return RPO_ERR_ARG;
     }
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
@@ -658,7 +723,7 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
     const PendEnv::Consts c{0};
-    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes);
+    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups);
 }
 
 }  // namespace
@@ -816,6 +881,29 @@ int rpo_pendulum_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float sc
     return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                              steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
                              trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, nullptr, &lanes);
+}
+
+int rpo_cartsafe_evaluate_policies(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                   float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc,
+                                   int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
+                                   float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
+                                   float viol_thresh, float* con, int policy_stride, int group_lanes, int episodes,
+                                   void* stream) {
+    const EvalGroups groups{policy_stride, group_lanes, episodes};
+    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
+                             viol_thresh, 0, nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, &groups);
+}
+
+int rpo_pendulum_evaluate_policies(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
+                                   float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                   float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                   float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* con,
+                                   int policy_stride, int group_lanes, int episodes, void* stream) {
+    const EvalGroups groups{policy_stride, group_lanes, episodes};
+    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
+                             nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, &groups);
 }
 
 int rpo_eval_obs_noise(int n, const float* obs, int obs_stride, int obs_dim, const float* sigma, unsigned long long seed,

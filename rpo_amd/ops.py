@@ -353,6 +353,26 @@ def _eval_lanes(lane_steps, lane_lr, n):
     return _p(lane_steps, torch.int32), _p(lane_lr)
 
 
+POLICY_GROUP_ALIGN = 64      # lanes of a policy group of ``evaluate_policies`` are padded to whole 64-lane tiles
+
+
+def _eval_policies(actor_desc, bank, n, group_lanes, episodes):
+    """The trailing arguments (policy_stride, group_lanes, episodes) of rpo_<env>_evaluate_policies.  ``bank``: float32
+    [P, stride] on the device, contiguous; ``actor_desc`` describes policy 0, every tensor of it inside bank[0] (the kernels add
+    g * stride to every pointer: a descriptor over other memory would be read out of bounds); n == P * group_lanes lanes."""
+    if bank.dim() != 2 or not bank.is_contiguous() or bank.dtype != torch.float32:
+        raise RpoHipError("evaluate_policies: the bank must be a contiguous float32 [P, stride] tensor, got %s %s"
+                          % (bank.dtype, tuple(bank.shape)))
+    P, stride = int(bank.shape[0]), int(bank.shape[1])
+    lo = _p(bank).value
+    for key, t in actor_desc.tensors.items():
+        if t is not None and not (lo <= t.data_ptr() and t.data_ptr() + 4 * t.numel() <= lo + 4 * stride and t.is_contiguous()):
+            raise RpoHipError("evaluate_policies: tensor %s of the descriptor does not lie inside policy 0 of the bank" % key)
+    if group_lanes <= 0 or n != P * group_lanes:
+        raise RpoHipError("evaluate_policies: %d lanes are not %d policies x %d lanes" % (n, P, group_lanes))
+    return stride, int(group_lanes), int(episodes)
+
+
 CURVE_LEN = CONST["RPO_CURVE_LEN"]
 CURVE_WS = CONST["RPO_CURVE_WS"]
 
@@ -505,6 +525,22 @@ class CartSafeKernels(object):
             box_hi, 0, 0.0, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh, None, 0, 0,
             None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), sp, lp, _stream()),
             "rpo_cartsafe_evaluate_budgets")
+
+    def evaluate_policies(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                          steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, bank,
+                          group_lanes, episodes, con=None):
+        """``evaluate`` with an actor per group of lanes (rpo_cartsafe_evaluate_policies): bank float32 [P, stride] on the
+        device, actor_desc over bank[0]; n = P x group_lanes lanes, the first ``episodes`` of every group live, the others
+        padding that is never written; con as there; no record, no noise."""
+        net = actor_desc.net_struct()
+        n = internal.shape[0]
+        tail = _eval_policies(actor_desc, bank, n, group_lanes, episodes)
+        check(_lib.load().rpo_cartsafe_evaluate_policies(
+            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
+            _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0), int(steps), box_lo,
+            box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh,
+            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
+            "rpo_cartsafe_evaluate_policies")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):
@@ -782,6 +818,22 @@ class PendulumKernels(object):
             int(steps), box_lo, box_hi, 0, 0.0, corr_eps, corr_momentum, max_episode_steps, viol_thresh, None, 0, 0,
             None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), sp, lp, _stream()),
             "rpo_pendulum_evaluate_budgets")
+
+    def evaluate_policies(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                          steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, bank,
+                          group_lanes, episodes, con=None):
+        """``evaluate`` with an actor per group of lanes (rpo_pendulum_evaluate_policies): bank float32 [P, stride] on the
+        device, actor_desc over bank[0]; n = P x group_lanes lanes, the first ``episodes`` of every group live, the others
+        padding that is never written; con as there; no record, no noise."""
+        net = actor_desc.net_struct()
+        n = internal.shape[0]
+        tail = _eval_policies(actor_desc, bank, n, group_lanes, episodes)
+        check(_lib.load().rpo_pendulum_evaluate_policies(
+            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action), _p(ep_len, torch.int32),
+            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0),
+            int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
+            "rpo_pendulum_evaluate_policies")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):

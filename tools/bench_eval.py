@@ -8,6 +8,7 @@
     python tools/bench_eval.py --constraints [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_constraints_bench.json]
     python tools/bench_eval.py --obs-noise [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_noise_bench.json]
     python tools/bench_eval.py --budgets [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_budgets_bench.json]
+    python tools/bench_eval.py --policies [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_policies_bench.json]
 
 Per configuration (cart-RPODDPG, cart-RPOSAC, pendulum-RPODDPG: fused; EVOPF-RPODDPG: stepwise only) a trainer with
 bench.py's hyper-parameters is trained for a few vector steps (a policy that has left its initialisation), then:
@@ -34,6 +35,10 @@ wall time, read-backs included).  Fused cart-RPODDPG and pendulum-RPOSAC at --si
 (where evaluate_budgets() runs those 8 calls itself: the ratio there measures only its bookkeeping).  Reported per size: the two
 legs, the ratio sweep / eight calls, and the sweep against ONE evaluate() call at the largest budget (the claim to test:
 about one call's time while B x episodes lanes do not fill the chip).
+--policies: ONE evaluate_policies() call with P = 8 distinct actor spans (the live actor and 7 seeded perturbations of it)
+against the 8 evaluate() calls under using_policy() it is defined by and against ONE plain evaluate(), in ONE build, by the same
+method.  Fused cart-RPODDPG and pendulum-RPOSAC at --sizes episodes.  Reported per size: the three legs, the ratios sweep / eight
+calls and sweep / one call, and the padded lanes of the launch.
 Every call ends with a host read of the results (evaluate()'s .cpu(), eval()'s), so wall times include the device work.
 Run each GPU step under its own time limit (timeout -k 10 ...).
 """
@@ -206,6 +211,42 @@ def budgets_bench(a, sizes):
     return line
 
 
+def policies_bench(a, sizes):
+    line = dict(tool="bench_eval --policies", device=torch.cuda.get_device_name(0), reps=a.reps, configs={})
+    for workload in ("cart_ddpg", "pen_sac"):
+        tr = trainer(workload)
+        live = tr.policy_params()
+        gen = torch.Generator(device="cpu").manual_seed(7)
+        policies = [None] + [live * (1.0 + 0.05 * torch.randn(live.numel(), generator=gen).to(live.device)) for _ in range(7)]
+        row = {}
+        for n in sizes:
+            def eight():
+                out = []
+                for p in policies:
+                    with tr.using_policy(p):
+                        out.append(tr.evaluate(n, seed=5))
+                return out
+            legs = {"evaluate_policies": lambda: tr.evaluate_policies(policies, n, seed=5),
+                    "eight_evaluate_calls": eight,
+                    "one_evaluate_call": lambda: tr.evaluate(n, seed=5)}
+            res = alternating(legs, a.reps)
+            s, calls = legs["evaluate_policies"](), eight()
+            assert s.path == "fused"
+            for g, r in enumerate(calls):                        # faster and different is not faster: the same bits
+                assert all(getattr(s[g], f).tobytes() == getattr(r, f).tobytes() for f in r.FIELDS), (workload, n, g)
+            res.update(ratio_to_eight_calls=res["evaluate_policies"]["median_s"] / res["eight_evaluate_calls"]["median_s"],
+                       ratio_to_one_call=res["evaluate_policies"]["median_s"] / res["one_evaluate_call"]["median_s"],
+                       policies=len(policies), lanes=len(policies) * ((n + 63) // 64 * 64), horizon=s.horizon, path=s.path,
+                       env_steps=int(s.length.sum()), violation_rate=s.violation_rate().tolist(),
+                       ret_mean=s.ret_mean().tolist())
+            row[str(n)] = res
+            del s, calls
+        line["configs"][workload] = row
+        del tr
+        torch.cuda.empty_cache()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -215,12 +256,13 @@ def main():
     ap.add_argument("--constraints", action="store_true")
     ap.add_argument("--obs-noise", action="store_true")
     ap.add_argument("--budgets", action="store_true")
+    ap.add_argument("--policies", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sizes = [int(x) for x in a.sizes.split(",") if x]
-    if a.record or a.constraints or a.obs_noise or a.budgets:
+    if a.record or a.constraints or a.obs_noise or a.budgets or a.policies:
         small = [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes
-        bench = budgets_bench if a.budgets else noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
+        bench = policies_bench if a.policies else budgets_bench if a.budgets else noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
         s = json.dumps(bench(a, small))
         print(s)
         if a.out:
