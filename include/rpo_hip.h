@@ -998,6 +998,35 @@ int rpo_pendulum_evaluate_policies(const rpo_mlp* actor_host, int gauss, float s
                                    float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* con,
                                    int policy_stride, int group_lanes, int episodes, void* stream);
 
+/* The noisy launches with a sigma PER GROUP of lanes (RPOTrainerBase.evaluate_noise): S noise levels on the same episodes AND
+ * the same draws in one launch sequence.  The n_envs lanes are S groups of group_lanes lanes, group-major; lane
+ * g * group_lanes + e is episode e under level g: its actor and projection read o[q] + sigma_table[8 g + q] * z(e, s, q) with
+ * the z of rpo_<env>_evaluate_noisy keyed by the EPISODE e within the group, not by the lane -- every level sees the draw that
+ * rpo_<env>_evaluate_noisy on an episodes-lane env hands its lane e (common random numbers).  sigma_table: a DEVICE table
+ * [S, 8] of floats >= 0, zero beyond the env's 6 | 5 observation columns, 4-byte aligned; a zero entry is not drawn and keeps
+ * the column's bits, so an all-zero row is the clean evaluation (NULL: RPO_ERR_NULL; misaligned: RPO_ERR_ARG; the values are on
+ * the device and are the caller's to check).  Of every group the first `episodes` lanes are live; the others are padding:
+ * they are never stepped, never drawn for, never keep a workgroup alive, and their rows of acc, con, action and of the env
+ * arrays are neither read into a result nor written.  group_lanes: > 0 and a multiple of 64 (no workgroup's lanes belong to
+ * two levels); 1 <= episodes <= group_lanes; n_envs a whole multiple of group_lanes (RPO_ERR_ARG otherwise, before any HIP
+ * call).  The arguments are those of rpo_<env>_evaluate_constraints without a trace and with con optional (NULL: no report);
+ * no record, one budget, one actor.  The env steps the TRUE state, as in rpo_<env>_evaluate_noisy.  Lanes never read one
+ * another, so rows [g * group_lanes, g * group_lanes + episodes) are
+ * == rpo_<env>_evaluate_noisy of the episodes-lane env with sigma = sigma_table[8 g ..] and the same noise_seed (an all-zero
+ *    row: rpo_<env>_evaluate[_constraints]), bit for bit, for every g. */
+int rpo_cartsafe_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                      float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                      float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                      float corr_eps, float corr_momentum, const float* consts_host, int partial,
+                                      int max_episode_steps, float viol_thresh, float* con, const float* sigma_table,
+                                      unsigned long long noise_seed, int group_lanes, int episodes, void* stream);
+int rpo_pendulum_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs,
+                                      float* internal, float* obs, float* action, int* ep_len, float* ep_ret,
+                                      unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
+                                      float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                                      int max_episode_steps, float viol_thresh, float* con, const float* sigma_table,
+                                      unsigned long long noise_seed, int group_lanes, int episodes, void* stream);
+
 /* The stepwise form of the noise (any env): out[i, q] = obs[i, q] + sigma[q] * z(i, step, q) for i < n, q < obs_dim, with the
  * draw and the arithmetic above (== per column q with sigma[q] != 0: rpo_philox_normal(n, ., seed, 0, step,
  * RPO_STREAM_EVAL_OBS + 0x100 * q, NULL), then the unfused multiply and add); a column with sigma[q] == 0 is copied.  obs

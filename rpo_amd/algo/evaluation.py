@@ -46,6 +46,13 @@ as P x padded lanes of one launch sequence (``rpo_<env>_evaluate_policies``: the
 group's actor out of the bank); every other configuration runs the P calls ("sweep").  The live actor is never written on the
 fused path and is back bit for bit after the sweep path.
 
+Noise sweeps (``evaluate_noise(episodes, obs_noise=[0, 0.01, 0.05, [...]])`` -> ``NoiseSweep``): S sensor-noise levels on the SAME
+initial states AND the same draws, group g being bit for bit the ``evaluate()`` call with ``obs_noise=levels[g]`` and the shared
+seed -- ``evaluate()`` keys episode i's draw by (seed, i, step, column), so the S calls already share their z.  On the fused path
+the groups run side by side, each padded to whole 64-lane tiles, as S x padded lanes of one launch sequence
+(``rpo_<env>_evaluate_noise_sweep``: the fused kernel's NSW instances read their group's sigma out of a device table and key the
+draw by the episode within the group, not by the lane); every other configuration runs the S calls ("sweep").
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
 does not record trajectories and produces no per-constraint reports.  With the trainer argument ``keep_best`` every point's
@@ -509,7 +516,8 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     return res
 
 
-def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None, lanes=None, groups=None):
+def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None, lanes=None, groups=None,
+               levels=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
     trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
@@ -519,7 +527,9 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
     kernels' ``evaluate`` gets no such keyword.  ``lanes``: (eval_steps int32 [n], eval_lr float32 [n]) on the device, the budget
     and step size of every lane in place of ``budget`` (rpo_<env>_evaluate_budgets; con only, neither trace nor noise).
     ``groups``: (bank [P, span], group_lanes, episodes) with ``desc`` over bank[0]: an actor per group of lanes
-    (rpo_<env>_evaluate_policies; con only, neither trace nor noise nor lanes)."""
+    (rpo_<env>_evaluate_policies; con only, neither trace nor noise nor lanes).  ``levels``: (sigma_table [S, 8] on the device,
+    seed, group_lanes, episodes): a noise level per group of lanes (rpo_<env>_evaluate_noise_sweep; con only, none of the
+    others)."""
     n = v.n
     eval_steps = tr.eval_steps if budget[0] is None else budget[0]
     eval_lr = tr.eval_lr if budget[1] is None else budget[1]
@@ -548,6 +558,15 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
                                          v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
                                          tr._box_hi, eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
                                          v.viol_thresh, *groups, **kw)
+        return
+    if levels is not None:
+        if trace is not None or noise is not None:
+            raise ValueError("noise levels per group run without a record and without a sigma of the whole launch")
+        for t0 in range(0, H, steps):
+            tr.kernels.evaluate_noise_sweep(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs,
+                                            v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0),
+                                            tr._box_lo, tr._box_hi, eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum,
+                                            v.max_episode_steps, v.viol_thresh, *levels, **kw)
         return
     for t0 in range(0, H, steps):
         tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
@@ -595,11 +614,12 @@ def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, nois
 
 # ------------------------------------------------------------------------------------------------ budget sweeps
 MAX_BUDGETS = 64
+Paired = collections.namedtuple("Paired", "mean stderr n")
 _FUSED_BUDGET_LANES = 1 << 24                                    # B x episodes lanes of one fused launch; beyond: "sweep"
 
 
 class ResultSweep(object):
-    """What ``BudgetSweep`` and ``PolicySweep`` share: G ``EvalResult``s of the same episodes (``sweep[g]`` is ``results[g]``)
+    """What ``BudgetSweep``, ``PolicySweep`` and ``NoiseSweep`` share: G ``EvalResult``s of the same episodes (``sweep[g]`` is ``results[g]``)
     and their fields stacked into [G, episodes] arrays whose rows ARE the results' arrays (one memory)."""
 
     def _stack(self, results):
@@ -633,6 +653,14 @@ class ResultSweep(object):
     def ret_mean(self):
         """Per group: the mean return over the episodes [G]."""
         return self.ret.mean(axis=1)
+
+    def paired(self, a, b):
+        """The paired comparison of groups a and b: ``Paired(mean, stderr, n)`` of the per-episode return difference
+        ``ret[a] - ret[b]`` (episode e of both started from the same state); stderr: the sample standard deviation (n - 1)
+        over sqrt(n), NaN for n = 1."""
+        d = self.ret[a] - self.ret[b]
+        n = d.shape[0]
+        return Paired(float(d.mean()), float(d.std(ddof=1) / math.sqrt(n)) if n > 1 else float("nan"), n)
 
 
 class BudgetSweep(ResultSweep):
@@ -751,7 +779,6 @@ def evaluate_budgets(tr, episodes=10, eval_steps=None, eval_lr=None, horizon=Non
 # ------------------------------------------------------------------------------------------------ policy sweeps
 MAX_POLICIES = 64
 _FUSED_POLICY_LANES = 1 << 24                                    # P x padded lanes of one fused launch; beyond: "sweep"
-Paired = collections.namedtuple("Paired", "mean stderr n")
 
 
 class PolicySweep(ResultSweep):
@@ -769,14 +796,6 @@ class PolicySweep(ResultSweep):
             raise ValueError("PolicySweep: %d results for %d names" % (len(results), len(self.names)))
         self._stack(results)
         self.path = path
-
-    def paired(self, a, b):
-        """The paired comparison of policies a and b: ``Paired(mean, stderr, n)`` of the per-episode return difference
-        ``ret[a] - ret[b]`` (episode e of both started from the same state); stderr: the sample standard deviation (n - 1)
-        over sqrt(n), NaN for n = 1."""
-        d = self.ret[a] - self.ret[b]
-        n = d.shape[0]
-        return Paired(float(d.mean()), float(d.std(ddof=1) / math.sqrt(n)) if n > 1 else float("nan"), n)
 
     def best(self, max_rate=0.0):
         """The index ``keep_best`` would hold after seeing the groups in order (``keep_best_wins`` of csrc/eval_dev.h on the
@@ -970,6 +989,125 @@ def evaluate_policies(tr, policies, episodes=10, seed=None, horizon=None, init_s
                                                          getattr(tr.base_env, "eq_names", None))
         results.append(res)
     return PolicySweep(results, names, "fused")
+
+
+# ------------------------------------------------------------------------------------------------ noise sweeps
+MAX_NOISE_LEVELS = 64
+_FUSED_NOISE_LANES = 1 << 24                                     # S x padded lanes of one fused launch; beyond: "sweep"
+
+
+class NoiseSweep(ResultSweep):
+    """The result of ``evaluate_noise()``: S sensor-noise levels evaluated on the same initial states and the same draws.
+
+    ``levels``: float32 [S, obs_dim], the sigma vector of every level in the caller's order (None: zeros; a number: broadcast);
+    ``results``: S ``EvalResult``s (``sweep[g]`` is ``results[g]``), each what ``evaluate(obs_noise=levels[g])`` with the shared
+    seed returns, with ``obs_noise = levels[g]``.  ``ret``, ``length``, ``mean_ineq``, ``mean_eq``, ``max_ineq``, ``max_eq``,
+    ``viol_steps``, ``proj_iters`` (also ``iters``), ``nonfinite``: [S, episodes] arrays whose rows ARE the results' arrays (one
+    memory).  ``path``: "fused" (one launch sequence over S x padded lanes) or "sweep" (S ``evaluate()`` calls).  ``seed``,
+    ``horizon``: the shared ones."""
+
+    def __init__(self, results, levels, path):
+        results = list(results)
+        self.levels = np.array(levels, dtype=np.float32)
+        if not results or self.levels.ndim != 2 or len(results) != self.levels.shape[0]:
+            raise ValueError("NoiseSweep: %d results for levels of shape %s" % (len(results), self.levels.shape))
+        self._stack(results)
+        for g, r in enumerate(self.results):
+            r.obs_noise = self.levels[g]
+        self.path = path
+
+    def tolerance(self, max_rate=0.0):
+        """The index of the last level, in the order given, of the longest prefix of levels whose ``violation_rate()`` are all
+        <= ``max_rate`` (with increasing levels: the largest noise the policy is still safe under); -1 if level 0 already
+        exceeds it.  A level behind the first failing one does not count, whatever its rate."""
+        bad = np.flatnonzero(~(self.violation_rate() <= max_rate))
+        return (int(bad[0]) if bad.size else len(self)) - 1
+
+    def __repr__(self):
+        return "NoiseSweep(levels=%s, episodes=%d, path=%s, return=%s, violation_rate=%s)" % (
+            np.array2string(self.levels.max(axis=1), precision=4), self.episodes, self.path,
+            np.array2string(self.ret_mean(), precision=4), np.array2string(self.violation_rate(), precision=4))
+
+
+def check_noise_levels(obs_noise, obs_dim):
+    """``obs_noise`` of evaluate_noise() -> the float32 levels [S, obs_dim]: a non-empty sequence of at most
+    ``MAX_NOISE_LEVELS`` entries, each what ``check_obs_noise`` takes (None: zeros); ValueError otherwise, naming the index of an
+    offending entry."""
+    what = "evaluate_noise"
+    if obs_noise is None or isinstance(obs_noise, (str, bytes)) or not hasattr(obs_noise, "__len__") or \
+            (isinstance(obs_noise, (np.ndarray, torch.Tensor)) and obs_noise.ndim == 0):
+        raise ValueError("%s: obs_noise must be a sequence of 1 to %d noise levels, got %r" % (what, MAX_NOISE_LEVELS, obs_noise))
+    entries = list(obs_noise)
+    if not 1 <= len(entries) <= MAX_NOISE_LEVELS:
+        raise ValueError("%s: obs_noise must hold 1 to %d noise levels, got %d" % (what, MAX_NOISE_LEVELS, len(entries)))
+    levels = np.zeros((len(entries), obs_dim), dtype=np.float32)
+    for g, entry in enumerate(entries):
+        try:
+            sigma = check_obs_noise(entry, obs_dim)
+        except ValueError as e:
+            raise ValueError("%s: obs_noise[%d]: %s" % (what, g, e))
+        if sigma is not None:
+            levels[g] = sigma
+    return levels
+
+
+def evaluate_noise(tr, episodes=10, obs_noise=None, horizon=None, seed=None, init_states=None, constraints=False):
+    """See ``RPOTrainerBase.evaluate_noise``."""
+    k = tr.kernels
+    levels = check_noise_levels(obs_noise, k.obs_dim)
+    n = check_episodes(episodes, "evaluate_noise: episodes")
+    want_con = check_constraints(constraints)
+    S = levels.shape[0]
+    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
+        raise ValueError("evaluate_noise: horizon must be an integer >= 1, got %r" % (horizon,))
+    H = int(horizon) if horizon is not None else default_horizon(tr)
+    if H >= 1 << 24:
+        raise ValueError("evaluate_noise: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
+    if init_states is not None:
+        init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
+        if tuple(init_states.shape) != (n, k.internal_dim):
+            raise ValueError("evaluate_noise: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
+                             % (n, k.internal_dim, tuple(init_states.shape)))
+    seed = fresh_seed(tr) if seed is None else int(seed)         # ONE seed (and one tick of the call counter) for all levels
+    GL = (n + hip_ops.POLICY_GROUP_ALIGN - 1) // hip_ops.POLICY_GROUP_ALIGN * hip_ops.POLICY_GROUP_ALIGN
+    fused = bool(fused_ok(tr) and hasattr(k, "evaluate_noise_sweep") and tr.schedule.get("fused_noise_sweep", 1)
+                 and S * GL <= _FUSED_NOISE_LANES)
+    if not fused:
+        results = [evaluate(tr, episodes=n, horizon=H, seed=seed, init_states=init_states, constraints=want_con,
+                            obs_noise=levels[g]) for g in range(S)]
+        return NoiseSweep(results, levels, "sweep")
+    dev = tr.device
+    make = dict(seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev, stats_cap=2,
+                viol_thresh=tr.vec.viol_thresh)
+    v = tr.base_env.make_vec(n, **make)                          # the initial states of evaluate(): reset, then the injection
+    v.reset()
+    if init_states is not None:
+        v.set_internal(init_states)
+    with torch.no_grad():
+        # S copies of the initial states, group-major, every group padded to GL lanes: lane g * GL + e is episode e under
+        # level g; internal AND obs are tiled, as in evaluate_policies().  The padding lanes keep the new env's rows: the
+        # kernel neither steps nor writes them
+        big = tr.base_env.make_vec(S * GL, **make)
+        big.internal.view(S, GL, -1)[:, :n].copy_(v.internal)
+        if big.obs is not big.internal:
+            big.obs.view(S, GL, -1)[:, :n].copy_(v.obs)
+        table = np.zeros((S, 8), dtype=np.float32)               # sigma[S, 8], zero beyond obs_dim
+        table[:, :k.obs_dim] = levels
+        table = torch.from_numpy(table).to(dev)
+        acc = torch.zeros(S * GL, 8, device=dev)
+        con = torch.zeros(S * GL, hip_ops.con_width(k.ineq_num, k.eq_num), device=dev) if want_con else None
+        _run_fused(tr, big, acc, H, con=con, levels=(table, seed, GL, n))
+    acc_host = acc.cpu().numpy().reshape(S, GL, 8)
+    con_host = con.cpu().numpy().reshape(S, GL, -1) if want_con else None
+    results = []
+    for g in range(S):
+        res = EvalResult(acc_host[g, :n], "fused", H, seed)
+        if want_con:
+            res.constraints = ConstraintReport.from_rows(con_host[g, :n], k.ineq_num, k.eq_num, res.length, big.viol_thresh,
+                                                         getattr(tr.base_env, "ineq_names", None),
+                                                         getattr(tr.base_env, "eq_names", None))
+        results.append(res)
+    return NoiseSweep(results, levels, "fused")
 
 
 # ------------------------------------------------------------------------------------------------ evaluation curves

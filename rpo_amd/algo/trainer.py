@@ -1587,6 +1587,35 @@ class RPOTrainerBase(object):
         return evaluate_policies(self, policies, episodes=episodes, seed=seed, horizon=horizon, init_states=init_states,
                                  constraints=constraints, names=names)
 
+    def evaluate_noise(self, episodes=10, obs_noise=None, horizon=None, seed=None, init_states=None, constraints=False):
+        """Evaluate the current policy under S sensor-noise levels on the SAME episodes and the SAME draws -> ``NoiseSweep``:
+        the violation rate and the return against the noise level, and the largest level the policy is still safe under.
+        ``obs_noise``: a non-empty sequence of 1 to 64 levels, each whatever ``evaluate(obs_noise=)`` accepts -- None, a
+        number >= 0 or ``obs_dim`` numbers >= 0 -- and validated like it (the ValueError names the offending index);
+        ``episodes``, ``horizon``, ``seed``, ``init_states`` ([episodes, internal_dim], shared by all levels) and
+        ``constraints`` are ``evaluate()``'s and validated like them.  Definition: group g is, bit for bit,
+        ``evaluate(episodes, horizon, seed=seed, init_states=init_states, constraints=constraints, obs_noise=levels[g])``;
+        ``seed=None`` draws ONE seed as ``evaluate()`` does (one tick of its call counter).  ``evaluate()`` keys episode i's
+        draw by (seed, i, step, column), so level g on episode e sees the same ``z(e, s, q)`` as every other level, scaled by
+        its own sigma (common random numbers: a paired comparison, not S unrelated samples), and a level that is None, 0 or
+        all zeros gives the clean evaluation's bits.  ``sweep.levels`` is float32 [S, obs_dim]; ``sweep.results[g]`` /
+        ``sweep[g]`` are the S ``EvalResult``s with ``obs_noise = levels[g]``; ``sweep.ret``, ``.length``, ``.viol_steps``,
+        ``.max_ineq``, ``.iters`` ... are [S, episodes] arrays over the same memory; ``sweep.violation_rate()`` and
+        ``sweep.ret_mean()`` are [S]; ``sweep.paired(a, b)`` is (mean, stderr, n) of the per-episode return difference
+        ``ret[a] - ret[b]``; ``sweep.tolerance(max_rate=0.0)`` is the index of the last level of the longest prefix, in the
+        order given, whose levels all have a violation rate <= ``max_rate`` (-1 if level 0 already exceeds it).
+        ``sweep.path``: "fused" -- where ``evaluate()`` takes its fused path (schedule ``fused_noise_sweep=0`` switches it
+        off), the groups, each padded to whole 64-lane tiles, run as S x padded lanes of ONE launch sequence whose
+        workgroups read their group's sigma out of a device table and key the draw by the episode within the group: one
+        vector env, one read-back -- or "sweep": EVOPF-v0, the Lagrangian baselines, 256-wide actors, ``fused_mlp=0``, the
+        oracle backend and more than 2^24 padded lanes run the S calls of the definition.  No ``record=``, ``eval_steps=`` or
+        ``eval_lr=``: call ``evaluate()`` per level for those.  ValueError, before anything is allocated and without a tick
+        of the call counter: no or more than 64 levels, a level of another length, a negative or non-finite sigma.  No
+        trainer state changes, as for ``evaluate()``.  See rpo_amd/algo/evaluation.py."""
+        from .evaluation import evaluate_noise
+        return evaluate_noise(self, episodes=episodes, obs_noise=obs_noise, horizon=horizon, seed=seed, init_states=init_states,
+                              constraints=constraints)
+
     def act(self, obs, eval_steps=None, eval_lr=None, residuals=True, out=None, form=0, profile=False):
         """The policy's projected actions for caller-supplied observations -> ``ActResult`` (torch tensors on the trainer's
         device, nothing waits for the device): ``action`` [n, action_dim], the completed + projected action ``eval()`` would

@@ -16,6 +16,9 @@
 //                        budget and step size per lane, so B budgets x episodes run side by side in one launch.
 //   (no kernel)          evaluate_policies(): the fused kernel's POL = 1 instances (rpo_<env>_evaluate_policies) run every group of
 //                        group_lanes lanes on an actor of its own out of a bank, so P policies x episodes run in one launch.
+//   (no kernel)          evaluate_noise(): the fused kernel's NSW = 1 instances (rpo_<env>_evaluate_noise_sweep) run every group of
+//                        group_lanes lanes under a sigma of its own out of a table and key the draw by the episode within the
+//                        group, so S noise levels x episodes run in one launch on the same z.
 //   summarize_*_kernel   the accumulator rows of a finished evaluation -> one row of an evaluation curve (rpo_eval_summarize).
 //   keep_best_*_kernel   that row against the incumbent's on the device, and the predicated copy of the actor's parameters
 //                        (rpo_eval_keep_best; the criterion is eval_dev.h: keep_best_wins).
@@ -82,11 +85,22 @@ struct EvalPolArgs : EvalConArgs<ENV> {
     int group_lanes;              // lanes per policy, padding included: a multiple of 64; n = P * group_lanes
     int episodes;                 // live lanes per group: 1 <= episodes <= group_lanes
 };
-template <class ENV, int CON, int NOISE, int BUD = 0, int POL = 0> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
+// The NSW = 1 instances (evaluate_noise()) take the groups' sigma table, the key of the draw and the groups' geometry behind the
+// EvalConArgs arguments (con: NULL for their CON = 0 instances, which never read it); the NSW = 0 instances keep their parameter
+// types.
+template <class ENV>
+struct EvalNoiseSweepArgs : EvalConArgs<ENV> {
+    const float* sigma_table;     // [S, 8] on the device: group g's sigma per observation column, zeros beyond kObs
+    unsigned long long noise_seed;
+    int group_lanes;              // lanes per noise level, padding included: a multiple of 64; n = S * group_lanes
+    int episodes;                 // live lanes per group: 1 <= episodes <= group_lanes
+};
+template <class ENV, int CON, int NOISE, int BUD = 0, int POL = 0, int NSW = 0> struct EvalArgsOf { typedef EvalArgs<ENV> type; };
 template <class ENV> struct EvalArgsOf<ENV, 1, 0, 0, 0> { typedef EvalConArgs<ENV> type; };
 template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 1, 0, 0> { typedef EvalNoiseArgs<ENV> type; };
 template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 0, 1, 0> { typedef EvalBudArgs<ENV> type; };
 template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 0, 0, 1> { typedef EvalPolArgs<ENV> type; };
+template <class ENV, int CON> struct EvalArgsOf<ENV, CON, 1, 0, 0, 1> { typedef EvalNoiseSweepArgs<ENV> type; };
 
 // What one env step leaves for the statistics: reward, done and the violations of the transition row, without the row --
 // their maxima for the accumulators, and the row's ineq_viol / eq_viol columns themselves (gi / he) for the report.
@@ -181,6 +195,24 @@ __device__ __forceinline__ void stage_noise(const ARGS& p, int row0, int rows, i
     *o = rpo_eval_dev::rpo_eval_noisy_obs(*o, sigma, p.noise_seed, row0 + r, s, q);
 }
 
+// NSW = 1: the workgroup's lanes belong to ONE group g (a scalar, as under POL = 1).  The thread that staged element (r, q) reads
+// the group's sigma out of the table (sigma_table[8 g + q]) and keys the draw by the EPISODE within the group,
+// e = row0 + r - g * group_lanes, not by the lane: level g on episode e draws the z(e, s, q) every other level draws, and the
+// one evaluate(obs_noise=) draws for its lane e.  A padding lane (e >= episodes) is not drawn for.  As in stage_noise the draw
+// ends in the LDS word.
+template <class ENV, class ARGS>
+__device__ __forceinline__ void stage_noise_group(const ARGS& p, int row0, int rows, int g, int s, float* in_s, int stride) {
+    constexpr int kObs = EvalEnv<ENV>::kObs;
+    const int tid = threadIdx.x;
+    if (tid >= rows * kObs) return;
+    const int r = tid / kObs, q = tid - r * kObs;
+    const int e = row0 + r - g * p.group_lanes;
+    if (e >= p.episodes) return;
+    const float sigma = p.sigma_table[(size_t)g * 8 + q];
+    float* o = in_s + r * stride + q;
+    *o = rpo_eval_dev::rpo_eval_noisy_obs(*o, sigma, p.noise_seed, e, s, q);
+}
+
 // BUD = 1: a live lane reads its own budget and step size (p.lane_steps[i], p.lane_lr[i]) behind the forward and projects with
 // them in place of p.act.max_steps / p.act.corr_lr: two more VGPRs and a vector loop bound in a loop that rows of one wave
 // already leave at different iterations; everything else of p.act stays launch-uniform, nothing of it crosses the MFMA loops.
@@ -207,10 +239,11 @@ __device__ __forceinline__ Mlp policy_of_group(const Mlp& a, int g, int policy_s
     return m;
 }
 
-template <class ENV, int EIN, int H, int RT, int REC, int CON, int NOISE, int BUD = 0, int POL = 0>
-__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON, NOISE, BUD, POL>::type p, typename ENV::Consts c) {
+template <class ENV, int EIN, int H, int RT, int REC, int CON, int NOISE, int BUD = 0, int POL = 0, int NSW = 0>
+__global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<ENV, CON, NOISE, BUD, POL, NSW>::type p, typename ENV::Consts c) {
     static_assert(!BUD || (!REC && !NOISE), "per-lane budgets: no record, no observation noise");
     static_assert(!POL || (!REC && !NOISE && !BUD), "an actor per group: no record, no observation noise, one budget");
+    static_assert(!NSW || (NOISE && !REC && !BUD && !POL), "a sigma per group: the noisy instance, no record, one budget, one actor");
     typedef TileLds<EIN, RT, 8, 8> Lds;                          // 16 * RT lanes per workgroup; OBS <= 8
     __shared__ Lds lds;
     constexpr int kInS = Lds::kS;
@@ -226,13 +259,19 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
         mine = mine && i - g * p.group_lanes < p.episodes;
         group_actor = policy_of_group(p.actor, g, p.policy_stride);
     }
+    int noise_group = 0;                                         // NSW = 1: the workgroup's group, a scalar like POL's g
+    if constexpr (NSW) {
+        noise_group = __builtin_amdgcn_readfirstlane(row0 / p.group_lanes);
+        mine = mine && i - noise_group * p.group_lanes < p.episodes;
+    }
     const Mlp& actor = POL ? group_actor : p.actor;
     for (int s = p.t0; s < p.t0 + p.steps; ++s) {
         // a lane's state is read from its accumulator row at every step (nothing of it stays live across the MFMA loops)
         const bool live = mine && (s == 0 || (__float_as_int(p.acc[(size_t)i * RPO_EVAL_LEN + 7]) & RPO_EVAL_ALIVE));
         if (!__syncthreads_or(live)) return;                     // (also the barrier in front of the LDS tiles' reuse)
         EvalEnv<ENV>::stage(p.step, row0, kLanes, lds.in_s, kInS);
-        if constexpr (NOISE) stage_noise<ENV>(p, row0, kLanes, n, s, lds.in_s, kInS);
+        if constexpr (NSW) stage_noise_group<ENV>(p, row0, kLanes, noise_group, s, lds.in_s, kInS);
+        else if constexpr (NOISE) stage_noise<ENV>(p, row0, kLanes, n, s, lds.in_s, kInS);
         mlp_tile_forward<EIN, H, RT, Lds>(actor, lds, row0, n, nullptr, nullptr, p.gauss ? 0 : 1, p.scale, p.base);
         if (live) {
             float ap = lds.out[tid * 2];
@@ -259,15 +298,15 @@ __global__ __launch_bounds__(kFwdThreads) void eval_kernel(typename EvalArgsOf<E
     }
 }
 
-template <class ENV, int REC, int CON, int NOISE = 0, int BUD = 0, int POL = 0>
-int launch_eval(const typename EvalArgsOf<ENV, CON, NOISE, BUD, POL>::type& args, const typename ENV::Consts& c, int n, void* stream) {
+template <class ENV, int REC, int CON, int NOISE = 0, int BUD = 0, int POL = 0, int NSW = 0>
+int launch_eval(const typename EvalArgsOf<ENV, CON, NOISE, BUD, POL, NSW>::type& args, const typename ENV::Consts& c, int n, void* stream) {
     // the rollout's tile rule (fused.hip launch_rollout): 64 lanes per workgroup once that still fills the chip.  E = 128
     // only: the E = 256 instance spills (~150 bytes of scratch per lane) -- such actors evaluate on the stepwise path.
     if (args.actor.E != 128) return RPO_ERR_ARG;
     if (n >= 64 * 192) {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON, NOISE, BUD, POL>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 4, REC, CON, NOISE, BUD, POL, NSW>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     } else {
-        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON, NOISE, BUD, POL>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
+        hipLaunchKernelGGL((eval_kernel<ENV, 128, 256, 1, REC, CON, NOISE, BUD, POL, NSW>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c);
     }
     RPO_LAUNCH_CHECK();
     return 0;
@@ -307,12 +346,39 @@ int check_eval_groups(const EvalGroups& g, int n) {
     return 0;
 }
 
+// The noise levels of the *_evaluate_noise_sweep entry points (checked before any HIP call): the table is on the DEVICE, so its
+// values are the caller's to check.
+struct EvalNoiseGroups {
+    const float* sigma_table;
+    unsigned long long seed;
+    int group_lanes, episodes;
+};
+int check_eval_noise_groups(const EvalNoiseGroups& g, int n) {
+    if (!g.sigma_table) return RPO_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(g.sigma_table) % 4) return RPO_ERR_ARG;
+    if (g.group_lanes <= 0 || g.group_lanes % 64) return RPO_ERR_ARG;
+    if (g.episodes < 1 || g.episodes > g.group_lanes || n < g.group_lanes || n % g.group_lanes) return RPO_ERR_ARG;
+    return 0;
+}
+
 // rec / con of the entry points -> the instance; con == NULL: the launches of rpo_<env>_evaluate[_record] as they were;
 // noise != NULL: the NOISE = 1 instances; lanes != NULL: the BUD = 1 instances (no record, no noise: checked by the callers);
-// groups != NULL: the POL = 1 instances (no record, no noise, no lanes: checked by the callers)
+// groups != NULL: the POL = 1 instances (no record, no noise, no lanes: checked by the callers); sweep != NULL: the NSW = 1
+// instances (no record, none of the others: checked by the callers)
 template <class ENV>
 int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, int rec, float* con, void* stream,
-                    const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr) {
+                    const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr,
+                    const EvalNoiseGroups* sweep = nullptr) {
+    if (sweep) {
+        EvalNoiseSweepArgs<ENV> sa{};
+        static_cast<EvalArgs<ENV>&>(sa) = args;
+        sa.con = con;
+        sa.sigma_table = sweep->sigma_table;
+        sa.noise_seed = sweep->seed;
+        sa.group_lanes = sweep->group_lanes;
+        sa.episodes = sweep->episodes;
+        return con ? launch_eval<ENV, 0, 1, 1, 0, 0, 1>(sa, c, n, stream) : launch_eval<ENV, 0, 0, 1, 0, 0, 1>(sa, c, n, stream);
+    }
     if (groups) {
         EvalPolArgs<ENV> pa{};
         static_cast<EvalArgs<ENV>&>(pa) = args;
@@ -656,7 +722,8 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, const float* consts_host,
                       int partial, int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows,
                       int trace_steps, int with_con, float* con, void* stream, const EvalNoise* noise = nullptr,
-                      const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr) {
+                      const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr,
+                      const EvalNoiseGroups* sweep = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (noise)
@@ -669,6 +736,10 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     if (groups) {
         if (int e = check_eval_groups(*groups, n_envs)) return e;
         if (rec || noise || lanes) return RPO_ERR_ARG;
+    }
+    if (sweep) {
+        if (int e = check_eval_noise_groups(*sweep, n_envs)) return e;
+        if (rec || noise || lanes || groups) return RPO_ERR_ARG;
     }
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
@@ -686,7 +757,7 @@ int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                                        max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
-    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups);
+    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups, sweep);
 }
 
 int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal, float* obs,
@@ -694,7 +765,7 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
                       float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                       int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows, int trace_steps,
                       int with_con, float* con, void* stream, const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr,
-                      const EvalGroups* groups = nullptr) {
+                      const EvalGroups* groups = nullptr, const EvalNoiseGroups* sweep = nullptr) {
     if (!actor_host) return RPO_ERR_NULL;
     if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
     if (noise)
@@ -707,6 +778,10 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     if (groups) {
         if (int e = check_eval_groups(*groups, n_envs)) return e;
         if (rec || noise || lanes) return RPO_ERR_ARG;
+    }
+    if (sweep) {
+        if (int e = check_eval_noise_groups(*sweep, n_envs)) return e;
+        if (rec || noise || lanes || groups) return RPO_ERR_ARG;
     }
     if (rec)
         if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
@@ -723,7 +798,7 @@ int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float b
     args.trace = rec ? trace : nullptr;
     args.trace_rows = rec ? trace_rows : 0;
     const PendEnv::Consts c{0};
-    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups);
+    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups, sweep);
 }
 
 }  // namespace
@@ -904,6 +979,30 @@ int rpo_pendulum_evaluate_policies(const rpo_mlp* actor_host, int gauss, float s
     return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                              steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
                              nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, &groups);
+}
+
+int rpo_cartsafe_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
+                                      float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
+                                      float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
+                                      float corr_eps, float corr_momentum, const float* consts_host, int partial,
+                                      int max_episode_steps, float viol_thresh, float* con, const float* sigma_table,
+                                      unsigned long long noise_seed, int group_lanes, int episodes, void* stream) {
+    const EvalNoiseGroups sweep{sigma_table, noise_seed, group_lanes, episodes};
+    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
+                             viol_thresh, 0, nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, nullptr, &sweep);
+}
+
+int rpo_pendulum_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs,
+                                      float* internal, float* obs, float* action, int* ep_len, float* ep_ret,
+                                      unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
+                                      float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                                      int max_episode_steps, float viol_thresh, float* con, const float* sigma_table,
+                                      unsigned long long noise_seed, int group_lanes, int episodes, void* stream) {
+    const EvalNoiseGroups sweep{sigma_table, noise_seed, group_lanes, episodes};
+    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
+                             nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, nullptr, &sweep);
 }
 
 int rpo_eval_obs_noise(int n, const float* obs, int obs_stride, int obs_dim, const float* sigma, unsigned long long seed,

@@ -373,6 +373,19 @@ def _eval_policies(actor_desc, bank, n, group_lanes, episodes):
     return stride, int(group_lanes), int(episodes)
 
 
+def _eval_noise_sweep(sigma_table, seed, n, group_lanes, episodes):
+    """The trailing arguments (sigma_table, noise_seed, group_lanes, episodes) of rpo_<env>_evaluate_noise_sweep.
+    ``sigma_table``: float32 [S, 8] on the device, contiguous (the kernels index it by group: a smaller one would be read out
+    of bounds); n == S * group_lanes lanes."""
+    if sigma_table.dim() != 2 or sigma_table.shape[1] != 8 or not sigma_table.is_contiguous() or sigma_table.dtype != torch.float32:
+        raise RpoHipError("evaluate_noise_sweep: the sigma table must be a contiguous float32 [S, 8] tensor, got %s %s"
+                          % (sigma_table.dtype, tuple(sigma_table.shape)))
+    S = int(sigma_table.shape[0])
+    if group_lanes <= 0 or n != S * group_lanes:
+        raise RpoHipError("evaluate_noise_sweep: %d lanes are not %d noise levels x %d lanes" % (n, S, group_lanes))
+    return _p(sigma_table), int(seed), int(group_lanes), int(episodes)
+
+
 CURVE_LEN = CONST["RPO_CURVE_LEN"]
 CURVE_WS = CONST["RPO_CURVE_WS"]
 
@@ -541,6 +554,22 @@ class CartSafeKernels(object):
             box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh,
             None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
             "rpo_cartsafe_evaluate_policies")
+
+    def evaluate_noise_sweep(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                             sigma_table, seed, group_lanes, episodes, con=None):
+        """``evaluate`` with a noise level per group of lanes (rpo_cartsafe_evaluate_noise_sweep): sigma_table float32 [S, 8] on
+        the device, the draw keyed by ``seed`` and the episode within the group; n = S x group_lanes lanes, the first
+        ``episodes`` of every group live, the others padding that is never written; con as there; no record."""
+        net = actor_desc.net_struct()
+        n = internal.shape[0]
+        tail = _eval_noise_sweep(sigma_table, seed, n, group_lanes, episodes)
+        check(_lib.load().rpo_cartsafe_evaluate_noise_sweep(
+            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
+            _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0), int(steps), box_lo,
+            box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh,
+            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
+            "rpo_cartsafe_evaluate_noise_sweep")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):
@@ -834,6 +863,22 @@ class PendulumKernels(object):
             int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
             None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
             "rpo_pendulum_evaluate_policies")
+
+    def evaluate_noise_sweep(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                             sigma_table, seed, group_lanes, episodes, con=None):
+        """``evaluate`` with a noise level per group of lanes (rpo_pendulum_evaluate_noise_sweep): sigma_table float32 [S, 8]
+        on the device, the draw keyed by ``seed`` and the episode within the group; n = S x group_lanes lanes, the first
+        ``episodes`` of every group live, the others padding that is never written; con as there; no record."""
+        net = actor_desc.net_struct()
+        n = internal.shape[0]
+        tail = _eval_noise_sweep(sigma_table, seed, n, group_lanes, episodes)
+        check(_lib.load().rpo_pendulum_evaluate_noise_sweep(
+            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action), _p(ep_len, torch.int32),
+            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0),
+            int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
+            "rpo_pendulum_evaluate_noise_sweep")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):

@@ -9,6 +9,7 @@
     python tools/bench_eval.py --obs-noise [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_noise_bench.json]
     python tools/bench_eval.py --budgets [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_budgets_bench.json]
     python tools/bench_eval.py --policies [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_policies_bench.json]
+    python tools/bench_eval.py --noise-sweep [--reps R] [--sizes 10,1024,65536] [--out profiles/eval_noise_sweep_bench.json]
 
 Per configuration (cart-RPODDPG, cart-RPOSAC, pendulum-RPODDPG: fused; EVOPF-RPODDPG: stepwise only) a trainer with
 bench.py's hyper-parameters is trained for a few vector steps (a policy that has left its initialisation), then:
@@ -39,6 +40,11 @@ about one call's time while B x episodes lanes do not fill the chip).
 against the 8 evaluate() calls under using_policy() it is defined by and against ONE plain evaluate(), in ONE build, by the same
 method.  Fused cart-RPODDPG and pendulum-RPOSAC at --sizes episodes.  Reported per size: the three legs, the ratios sweep / eight
 calls and sweep / one call, and the padded lanes of the launch.
+--noise-sweep: ONE evaluate_noise() call with S = 8 noise levels (0, 0.005, 0.01, 0.02, 0.05, 0.1, 0.2 and a per-column vector;
+EVOPF-v0: a thousandth of them) against the 8 evaluate(obs_noise=) calls it is defined by and against ONE such call (sigma
+0.05), in ONE build, by the same method.  Fused cart-RPODDPG and pendulum-RPOSAC at --sizes episodes, stepwise EVOPF-RPODDPG at
+10 (where evaluate_noise() runs those 8 calls itself: the ratio there measures only its bookkeeping).  Reported per size: the
+three legs, the ratios sweep / eight calls and sweep / one call, and the padded lanes of the launch.
 Every call ends with a host read of the results (evaluate()'s .cpu(), eval()'s), so wall times include the device work.
 Run each GPU step under its own time limit (timeout -k 10 ...).
 """
@@ -247,6 +253,36 @@ def policies_bench(a, sizes):
     return line
 
 
+def noise_sweep_bench(a, sizes):
+    line = dict(tool="bench_eval --noise-sweep", device=torch.cuda.get_device_name(0), reps=a.reps, configs={})
+    for workload, has_fused in (("cart_ddpg", True), ("pen_sac", True), ("evopf_ddpg", False)):
+        tr = trainer(workload)
+        unit = 1.0 if has_fused else 1e-3
+        O = tr.kernels.obs_dim
+        levels = [unit * x for x in (0.0, 0.005, 0.01, 0.02, 0.05, 0.1, 0.2)] + [[unit * 0.05 * (q % 2) for q in range(O)]]
+        row = {}
+        for n in (sizes if has_fused else [10]):
+            legs = {"evaluate_noise": lambda: tr.evaluate_noise(n, obs_noise=levels, seed=5),
+                    "eight_evaluate_calls": lambda: [tr.evaluate(n, seed=5, obs_noise=lv) for lv in levels],
+                    "one_evaluate_call": lambda: tr.evaluate(n, seed=5, obs_noise=levels[4])}
+            res = alternating(legs, a.reps)
+            s, calls = legs["evaluate_noise"](), legs["eight_evaluate_calls"]()
+            assert s.path == ("fused" if has_fused else "sweep")
+            for g, r in enumerate(calls):                        # faster and different is not faster: the same bits
+                assert all(getattr(s[g], f).tobytes() == getattr(r, f).tobytes() for f in r.FIELDS), (workload, n, g)
+            res.update(ratio_to_eight_calls=res["evaluate_noise"]["median_s"] / res["eight_evaluate_calls"]["median_s"],
+                       ratio_to_one_call=res["evaluate_noise"]["median_s"] / res["one_evaluate_call"]["median_s"],
+                       levels=s.levels.tolist(), lanes=len(levels) * ((n + 63) // 64 * 64), horizon=s.horizon, path=s.path,
+                       env_steps=int(s.length.sum()), violation_rate=s.violation_rate().tolist(), ret_mean=s.ret_mean().tolist(),
+                       tolerance=s.tolerance())
+            row[str(n)] = res
+            del s, calls
+        line["configs"][workload] = row
+        del tr
+        torch.cuda.empty_cache()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -257,12 +293,13 @@ def main():
     ap.add_argument("--obs-noise", action="store_true")
     ap.add_argument("--budgets", action="store_true")
     ap.add_argument("--policies", action="store_true")
+    ap.add_argument("--noise-sweep", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sizes = [int(x) for x in a.sizes.split(",") if x]
-    if a.record or a.constraints or a.obs_noise or a.budgets or a.policies:
+    if a.record or a.constraints or a.obs_noise or a.budgets or a.policies or a.noise_sweep:
         small = [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes
-        bench = policies_bench if a.policies else budgets_bench if a.budgets else noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
+        bench = noise_sweep_bench if a.noise_sweep else policies_bench if a.policies else budgets_bench if a.budgets else noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
         s = json.dumps(bench(a, small))
         print(s)
         if a.out:
