@@ -406,11 +406,16 @@ int rpo_td_huber(int n, const float* q1, const float* q2, const float* qn1, cons
  * ------------------------------------------------------------------------------------------------------------- */
 
 /* d(-min(q1, q2))/dq scaled (the actor loss of RPOSAC, rpo_sac.py:335): the smaller one takes the gradient, ties are split like
- * torch.min's backward: w = [q1 < q2] + 0.5 [q1 == q2]; dq1 = w * scale, dq2 = (1 - w) * scale. */
+ * torch.min's backward: w = [q1 < q2] + 0.5 [q1 == q2]; dq1 = w * scale, dq2 = (1 - w) * scale (exact: w is 0, 0.5 or 1;
+ * +0.0 == -0.0 and inf == inf are ties).  A NaN on either side, or both, makes both comparisons false: dq1 = 0, dq2 = scale.
+ * That deviates from torch: torch.minimum's backward hands BOTH inputs the full gradient there, dq1 = dq2 = scale. */
 int rpo_min_q_bwd(int n, const float* q1, const float* q2, float scale, float* dq1, float* dq2, void* stream);
 
 /* max_out[0] = max(max_out[0], max_i |x_i|) -- the "inf" norm of clip_grad_norm_ (rpo_ddpg.py:180,193).
- * max_out must hold a non-negative float (0 before the first call of an update). */
+ * max_out must hold a non-negative float (0 before the first call of an update).  x must be 16-byte aligned.
+ * NaN: fmaxf drops a NaN operand, so the norm is the maximum over the elements that are NOT NaN (torch's norm would be NaN and
+ * poison every element through the clip coefficient).  rpo_adam_step* then turns exactly the NaN element's exp_avg, exp_avg_sq
+ * and parameter into NaN and steps every other element with the norm of the finite ones. */
 int rpo_absmax(long long n, const float* x, float* max_out, void* stream);
 /* The same into a gradmax buffer [RPO_GRADMAX_LEN]: workgroup b maxes into slot b % 16 (the norm is the maximum over the
  * slots, as rpo_adam_step* read it) -- a wide launch does not queue its atomics on one word. */
@@ -434,7 +439,16 @@ int rpo_absmax_slots(long long n, const float* x, float* gradmax, void* stream);
  *   5.8 us launch, 4.7 us with 270 workgroups); 9 per sub-counter + 16 on the top word are not.
  *   prepared = 1: the caller's previous launch did the bookkeeping (rpo_split_update.prep_step: step_dev[0] already holds
  *   THIS step, the cache its corrections) -- the launch is then purely elementwise: it neither counts its workgroups in
- *   nor touches step_dev, gradmax (reset by the next rpo_split_critic_fwd_a, gradmax_reset) or `clock`. */
+ *   nor touches step_dev, gradmax (reset by the next rpo_split_critic_fwd_a, gradmax_reset) or `clock`.
+ *   Words of step_dev a launch may write: 0-7 (step, cached step, arrival word, the two doubles) and 32 k + 32, 32 k + 33 for
+ *   k < 16 (the sub-counters); no other word of the 544 is read or written.  Of gradmax only the 16 words [32 j] are.
+ *   Scalars: lr, betas, eps, weight_decay, tau arrive as float.  1 - beta and 1 - tau are formed in float32 FROM the float, and
+ *   the bias corrections in double from the float32 betas.  torch.optim.Adam hands its float32 ops float32(1 - beta) and takes
+ *   the corrections from the double betas: for beta2 = 0.999 the two 1 - beta2 differ by 1.3e-5 relative, which one step does not
+ *   show (0.11 eps32 of g^2 in exp_avg_sq) and thousands of steps build up to 1.3e-5 of exp_avg_sq (108 eps32; 6e-6 of the
+ *   denominator); sqrt(1 - beta2^t) differs by up to 6.4e-6 (t = 1; 3.7e-6 at t = 1000, nothing once beta2^t is gone).  Harmless
+ *   for learning; the cure is double scalars through this ABI (tests/optim_f64.py).
+ *   clamp_min0 is fmaxf(p, 0): a NaN parameter comes out as 0 (torch's clamp_ keeps NaN) while its exp_avg / exp_avg_sq stay NaN. */
 int rpo_adam_step(long long n, float* param, float* grad, float* exp_avg, float* exp_avg_sq, int* step_dev,
                   float lr, float beta1, float beta2, float eps, float weight_decay, int maximize, float clip_thres,
                   float* gradmax, int reset_gradmax, int zero_grad, int clamp_min0, float* target, float tau,

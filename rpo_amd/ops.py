@@ -199,7 +199,8 @@ class _AdamSegStruct(ctypes.Structure):
 
 def adam_step_multi(segs, clock=None, prepared=False):
     """One launch for up to four non-overlapping optimiser slices (rpo_adam_step_multi).  Each entry is a dict with the
-    keyword arguments of ``adam_step`` (+ ``target2`` / ``n2``), or ``dict(polyak_only=True, param=, target=, tau=)``."""
+    keyword arguments of ``adam_step`` (+ ``target2`` / ``n2``), or ``dict(polyak_only=True, param=, target=, tau=)``.
+    ``prepared`` holds for every stepped slice unless its entry carries a ``prepared`` of its own (the C struct's is per slice)."""
     arr = (_AdamSegStruct * len(segs))()
     vp = lambda t, dt=torch.float32: None if t is None else _p(t, dt).value                      # noqa: E731
     for a, g in zip(arr, segs):
@@ -216,7 +217,7 @@ def adam_step_multi(segs, clock=None, prepared=False):
         a.weight_decay, a.maximize, a.clip_thres = g.get("weight_decay", 0.0), int(g.get("maximize", False)), g.get("clip_thres", 0.0)
         a.gradmax, a.reset_gradmax = vp(g.get("gradmax")), int(g.get("reset_gradmax", True))
         a.zero_grad, a.clamp_min0 = int(g.get("zero_grad", False)), int(g.get("clamp_min0", False))
-        a.prepared = int(bool(prepared))
+        a.prepared = int(bool(g.get("prepared", prepared)))
     check(_lib.load().rpo_adam_step_multi(len(segs), arr, _p(clock, torch.int64, allow_none=True), _stream()),
           "rpo_adam_step_multi")
 
