@@ -276,6 +276,17 @@ int rpo_cartsafe_reset(int n_envs, float* state, int* ep_len, float* ep_ret, con
  *   rows       replay ring (may be NULL: no scatter); ring row = (t % cap_steps) * n_envs + lane, t = ctrl[RPO_CTRL_T]
  *   stats      [stats_cap, RPO_STATS_SUB, RPO_STATS_LEN] (may be NULL)
  *   ctrl       int64[RPO_CTRL_LEN]; ctrl[RPO_CTRL_T] is incremented when the launch finishes
+ * Pinned by tests/test_envs_f64_gpu.py (float64 restatement: tests/envs_f64.py):
+ *   done       is the reference's float64 test of the STORED float32 next state: x > 2.4, theta > 12 deg (cartpole.py:208-213).
+ *              2.4f and 0.20943952f lie above those thresholds; the kernel compares with the largest floats not above them, so a
+ *              next x of exactly 2.4f (or theta of 0.20943952f) terminates, as it does in the reference.
+ *   np.sign    (cartpole.py:184) is taken of the FLOAT32 product n_c * x_dot: x_dot = +-0 gives sign 0 (both friction terms
+ *              vanish), and so does a product that underflows to 0 -- |n_c x_dot| < 2^-150, e.g. the smallest denormal x_dot
+ *              under |n_c| < 1/2 -- where the float64 product keeps its sign.  Denormals are not flushed otherwise.
+ *   non-finite a NaN action or a non-finite next state sets ctrl[RPO_CTRL_NONFINITE] = t + 1 once (sticky; nothing is written
+ *              with ctrl = NULL); the row's outputs are non-finite where float64 gives that, every other row keeps its bits.
+ *   alignment  state / rows that are 8- but not 16-byte aligned take a per-lane path with the same bits; the 8 padding floats of
+ *              a ring row are written as zeros by whole-tile launches and left untouched otherwise.
  */
 int rpo_cartsafe_step(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count,
                       float* rows, long long cap_steps, float* stats, int stats_cap, long long* ctrl,
@@ -292,6 +303,11 @@ int rpo_cartsafe_step(int n_envs, float* state, const float* action, int* ep_len
  *   iters    [n]     out (may be NULL): GRG iterations taken by the lane
  *   eps_t = max(eps_end, eps_start - eps_decay * t) (PDDDPG_PA.eps_decay, ddpg_pa.py:118-119), t = ctrl[RPO_CTRL_T]
  *   (ctrl may be NULL: t = 0).  stats may be NULL.
+ * Pinned by tests/test_envs_f64_gpu.py: the other component is completed from the NOISED and clipped basic action; the masks
+ * are strict (a_p G_r[i] - d_r[i] > 0: a basic action ON the box, 10 * 1 - 10 = 0, does not select its row); the first iteration
+ * is unconditional and the loop then stops as soon as neither |eq_resid| nor max ineq_resid exceeds corr_eps.  A NaN basic action
+ * passes through the clip and the loop as NaN and stops after ONE iteration (iters = 1 for max_steps >= 1): NaN compares false
+ * with corr_eps, in torch.max(...) > corr_eps of the reference's loop as well.
  */
 int rpo_cartsafe_act_project(int n, const float* ap_raw, const float* noise, float* action, int* iters,
                              int noise_mode, float eps_start, float eps_end, float eps_decay, float box_lo,
@@ -327,7 +343,13 @@ int rpo_pendulum_reset(int n_envs, float* internal, float* obs, int* ep_len, flo
 
 /* pendulum.py:80-128 + TimeLimit + scatter + auto-reset.  internal [n,4] in/out; obs [n,5] out (may be NULL): the
  * next observation, or the reset observation where done.  The pre-step observation stored in the transition row is
- * recomputed from `internal` (it is bit-identical to what a previous launch wrote to `obs`). */
+ * recomputed from `internal` (it is bit-identical to what a previous launch wrote to `obs`).
+ * Pinned by tests/test_envs_f64_gpu.py (tests/envs_f64.py): done is the reference's float64 test of the STORED next state
+ * (l <= 0.5, l >= 1.5, |theta| >= pi / 12: pi/12f lies above pi / 12 and the tests are >= / <=, so the float32 comparison IS that
+ * test; equality terminates); theta is stepped with the UN-clipped next theta_dot and the speed clip at +-8 follows; the reward's
+ * |angle_normalize(theta)| is |theta| exactly for -pi < theta < pi and ((theta + pi) mod 2 pi) - pi outside; the violations are
+ * those of the un-clipped action; the Lagrangian's mask g > 0 is strict (g = 0 gives gradient 0 exactly); non-finite rows as in
+ * rpo_cartsafe_step; a NaN basic action in rpo_pendulum_act_project as in rpo_cartsafe_act_project. */
 int rpo_pendulum_step(int n_envs, float* internal, float* obs, const float* action, int* ep_len, float* ep_ret,
                       unsigned* ep_count, float* rows, long long cap_steps, float* stats, int stats_cap,
                       long long* ctrl, int max_episode_steps, int auto_reset, float viol_thresh,

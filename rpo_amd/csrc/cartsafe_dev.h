@@ -29,7 +29,11 @@ constexpr float kGravity = 9.8f, kMassPole = 0.1f, kTotalMass = 1.1f, kLength = 
 constexpr float kPoleMassLength = 0.05f, kTau = 0.02f, kMuC = 0.1f, kMuP = 0.01f;
 constexpr float kCosD0 = 0.5000000000000001f, kCosD1 = 0.8660254037844387f;   // cos(pi/3), cos(-pi/6)
 constexpr float kSinD0 = 0.8660254037844386f, kSinD1 = -0.5f;                 // sin(pi/3), sin(-pi/6)
-constexpr float kThetaThreshold = 0.20943951023931953f, kXThreshold = 2.4f;   // 12 deg, cartpole.py:88-89
+// Termination thresholds, cartpole.py:88-89,208-213: 12 deg and 2.4 as the reference compares them -- in float64 -- with the stored
+// float32 state.  The rounded constants 0.20943952f and 2.4f lie ABOVE the float64 thresholds, so a next x of exactly 2.4f
+// (> 2.4: terminated in the reference) passed `x > 2.4f`.  For a float32 x, x > 2.4 <=> x > the largest float32 not above 2.4
+// (and x < -2.4 <=> x < its negative): these are those two floats, 0x3E56774F and 0x40199999.
+constexpr float kThetaThreshold = 0.2094395011663437f, kXThreshold = 2.3999998569488525f;
 constexpr float kActMax = 10.0f, kResetLo = -0.05f, kResetSpan = 0.1f;
 
 __device__ __forceinline__ void eq_ineq(const CartConsts& c, float a0, float a1, float& h, float (&g)[6]) {

@@ -8,7 +8,9 @@ namespace rpo_pend_dev {
 constexpr float kMaxSpeed = 8.0f, kMaxTorque = 6.0f, kMaxSum = 32.0f, kDt = 0.05f, kG = 10.0f, kM = 0.5f;
 constexpr float kK = 1.0f, kL0 = 1.0f, kMDt = 10.0f;   // m / dt
 constexpr float kPi = 3.14159265358979323846f, kTwoPi = 6.28318530717958647692f;
-constexpr float kThetaLim = 0.26179938779914943654f;   // pi / 12
+// pi / 12 (pendulum.py:124).  The tests are >= / <= and the float32 constant lies ABOVE pi / 12: for a float32 v, v >= pi/12 <=>
+// v >= kThetaLim, the reference's float64 comparison of the stored state exactly (0.5 and 1.5 are floats).
+constexpr float kThetaLim = 0.26179938779914943654f;
 // reset box, pendulum.py:131-132 (float32 arrays in the reference)
 __device__ constexpr float kResetLo[4] = {-0.26179938779914943654f, -1.0f, 0.95f, -0.05f};
 __device__ constexpr float kResetHi[4] = {0.26179938779914943654f, 1.0f, 1.05f, 0.05f};
@@ -81,9 +83,15 @@ __device__ __forceinline__ void pend_lane(const StepArgs& p, int i, float4 s, fl
     const float fx = fminf(fmaxf(a.x, -kMaxTorque), kMaxTorque), fy = fminf(fmaxf(a.y, -kMaxTorque), kMaxTorque);
     const float fth = -fy * sn + fx * cs;
     const float fl = fy * cs + fx * sn;
-    float an = fmodf(th + kPi, kTwoPi);                                      // angle_normalize :367-368
-    if (an < 0.0f) an += kTwoPi;
-    const float costs = fabsf(an - kPi);
+    // |angle_normalize(th)| :106,367-368.  For -pi < th < pi it IS |th|, exactly; fmodf(th + pi, 2 pi) - pi rounds th + pi first and
+    // drops th's low bits near upright (~100 eps32 of the reward on the reset box).  Every float32 strictly inside (-kPi, kPi) lies
+    // inside (-pi, pi); the wrap is kept for the rest.
+    float costs = fabsf(th);
+    if (!(costs < kPi)) {
+        float an = fmodf(th + kPi, kTwoPi);
+        if (an < 0.0f) an += kTwoPi;
+        costs = fabsf(an - kPi);
+    }
     const float thacc = (fth - kM * (kG * sn + 2.0f * ldot * thdot)) / (l * kM);
     const float lacc = (fl - kM * kG * cs + kM * l * thdot * thdot - kK * (l - kL0)) / kM;
     float nthdot = thdot + thacc * kDt;
