@@ -458,6 +458,47 @@ def fresh_seed(tr):
     return int(((tr.seed ^ 0xE7A1E7A1) + 0x9E3779B97F4A7C15 * (calls + 1)) & (2 ** 63 - 1))
 
 
+def check_horizon(tr, horizon, what="evaluate"):
+    """``horizon`` of the evaluate*() calls -> the number of env steps (None: ``default_horizon``); ValueError otherwise."""
+    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
+        raise ValueError("%s: horizon must be an integer >= 1, got %r" % (what, horizon))
+    H = int(horizon) if horizon is not None else default_horizon(tr)
+    if H >= 1 << 24:
+        raise ValueError("%s: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % (what, H))
+    return H
+
+
+def check_init_states(tr, init_states, n, what="evaluate"):
+    """``init_states`` of the evaluate*() calls -> None or the float32 tensor [n, internal_dim] on the trainer's device."""
+    if init_states is None:
+        return None
+    init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
+    if tuple(init_states.shape) != (n, tr.kernels.internal_dim):
+        raise ValueError("%s: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
+                         % (what, n, tr.kernels.internal_dim, tuple(init_states.shape)))
+    return init_states
+
+
+def _make_vec(tr, n, seed):
+    return tr.base_env.make_vec(n, seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=tr.device,
+                                stats_cap=2, viol_thresh=tr.vec.viol_thresh)
+
+
+def _initial_env(tr, n, seed, init_states):
+    """The initial env of ``evaluate()``: n lanes reset under ``seed``, then the injection of ``init_states``."""
+    v = _make_vec(tr, n, seed)
+    v.reset()
+    if init_states is not None:
+        v.set_internal(init_states)
+    return v
+
+
+def _constraint_report(tr, con, length, viol_thresh):
+    """``ConstraintReport`` of the rows ``con`` (numpy, [n, W]) with the env's names of the constraints."""
+    return ConstraintReport.from_rows(con, tr.kernels.ineq_num, tr.kernels.eq_num, length, viol_thresh,
+                                      getattr(tr.base_env, "ineq_names", None), getattr(tr.base_env, "eq_names", None))
+
+
 def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
              constraints=False, obs_noise=None):
     """See ``RPOTrainerBase.evaluate``."""
@@ -468,11 +509,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
         sigma = None
     budget = (None, None) if eval_steps is None and eval_lr is None else check_budget(tr, eval_steps, eval_lr)
     R = check_record(record, n)
-    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
-        raise ValueError("evaluate: horizon must be an integer >= 1, got %r" % (horizon,))
-    H = int(horizon) if horizon is not None else default_horizon(tr)
-    if H >= 1 << 24:
-        raise ValueError("evaluate: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
+    H = check_horizon(tr, horizon)
     k = tr.kernels
     fused = fused_ok(tr)
     dims = (k.obs_dim, k.partial_dim if fused else tr._eval_proposal_dim(), k.action_dim)
@@ -482,54 +519,45 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
             raise ValueError("evaluate: record=%r needs a trace buffer of %d bytes (horizon %d x %d episodes x %d floats), above "
                              "the cap of %d bytes; record fewer episodes (record=k)"
                              % (record, nbytes, H, R, hip_ops.trace_layout(*dims)[1], hip_ops.TRACE_MAX_BYTES))
-    if init_states is not None:
-        init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
-        if tuple(init_states.shape) != (n, k.internal_dim):
-            raise ValueError("evaluate: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
-                             % (n, k.internal_dim, tuple(init_states.shape)))
+    init_states = check_init_states(tr, init_states, n)
     seed = fresh_seed(tr) if seed is None else int(seed)
-    v = tr.base_env.make_vec(n, seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=tr.device,
-                             stats_cap=2, viol_thresh=tr.vec.viol_thresh)
-    v.reset()
-    if init_states is not None:
-        v.set_internal(init_states)
+    v = _initial_env(tr, n, seed, init_states)
     acc = torch.zeros(n, 8, device=tr.device)
     # the record: zeroed here (the kernels write live lanes' rows only and never clear it), [step, episode, W]
     trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
     # the per-constraint report: step 0 writes every row from scratch, nothing to clear
     con = torch.empty(n, hip_ops.con_width(k.ineq_num, k.eq_num), device=tr.device) if want_con else None
     noise = {} if sigma is None else dict(noise=(sigma, seed))   # keyed by the evaluation's seed, like the reset stream
+    path, run = ("fused", _run_fused) if fused else ("stepwise", _run_stepwise)
     with torch.no_grad():
-        if fused:
-            path = "fused"
-            _run_fused(tr, v, acc, H, trace=trace, budget=budget, con=con, **noise)
-        else:
-            path = "stepwise"
-            _run_stepwise(tr, v, acc, H, trace=trace, budget=budget, con=con, **noise)
+        run(tr, v, acc, H, trace=trace, budget=budget, con=con, **noise)
     res = EvalResult(acc.cpu().numpy(), path, H, seed, obs_noise=sigma)
     if want_con:
-        res.constraints = ConstraintReport.from_rows(con.cpu().numpy(), k.ineq_num, k.eq_num, res.length, v.viol_thresh,
-                                                     getattr(tr.base_env, "ineq_names", None),
-                                                     getattr(tr.base_env, "eq_names", None))
+        res.constraints = _constraint_report(tr, con.cpu().numpy(), res.length, v.viol_thresh)
     if R:
         res.trajectory = EvalTrajectory.from_trace(trace.cpu().numpy(), dims, res.length[:R], v.viol_thresh)
     return res
 
 
-def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None, lanes=None, groups=None,
-               levels=None):
+#: the env kernels' method of a ``variant`` of _run_fused -> what is said to a record or a noise next to it
+_VARIANT_REFUSALS = {"evaluate_budgets": "per-lane budgets run without a record and without observation noise",
+                     "evaluate_policies": "policy groups run without a record and without observation noise",
+                     "evaluate_noise_sweep": "noise levels per group run without a record and without a sigma of the whole launch"}
+
+
+def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=None, noise=None, variant=None):
     """ceil(H / steps) launches of rpo_<env>_evaluate, enqueued back to back.  steps: RPO_EVAL_LANE_STEPS lane-steps per launch
     (4 steps at 2^20 lanes, one launch for the whole horizon up to ~8000 lanes).  ``desc``: another actor descriptor than the
     trainer's (the curve's parameter snapshot).  ``trace``: the zeroed record [H, R, W] every launch continues
     (rpo_<env>_evaluate_record).  ``budget``: evaluate()'s per-call (eval_steps, eval_lr), None: the trainer's.  ``con``: the
     per-constraint report [n, W] every launch continues (rpo_<env>_evaluate_constraints).  ``noise``: (sigma float32 numpy
     [obs_dim], seed) of ``obs_noise=`` (rpo_<env>_evaluate_noisy; the draw is keyed by the absolute step t0 + s); None: the
-    kernels' ``evaluate`` gets no such keyword.  ``lanes``: (eval_steps int32 [n], eval_lr float32 [n]) on the device, the budget
-    and step size of every lane in place of ``budget`` (rpo_<env>_evaluate_budgets; con only, neither trace nor noise).
-    ``groups``: (bank [P, span], group_lanes, episodes) with ``desc`` over bank[0]: an actor per group of lanes
-    (rpo_<env>_evaluate_policies; con only, neither trace nor noise nor lanes).  ``levels``: (sigma_table [S, 8] on the device,
-    seed, group_lanes, episodes): a noise level per group of lanes (rpo_<env>_evaluate_noise_sweep; con only, none of the
-    others)."""
+    kernels' ``evaluate`` gets no such keyword.  ``variant``: (the env kernels' method, its arguments behind viol_thresh...) of a
+    sweep in place of ``evaluate`` -- one at most by construction, con only, neither trace nor noise:
+    ("evaluate_budgets",) with ``budget`` = (eval_steps int32 [n], eval_lr float32 [n]) on the device, the budget and step size
+    of every lane (rpo_<env>_evaluate_budgets); ("evaluate_policies", bank [P, span], group_lanes, episodes) with ``desc`` over
+    bank[0]: an actor per group of lanes (rpo_<env>_evaluate_policies); ("evaluate_noise_sweep", sigma_table [S, 8] on the
+    device, seed, group_lanes, episodes): a noise level per group of lanes (rpo_<env>_evaluate_noise_sweep)."""
     n = v.n
     eval_steps = tr.eval_steps if budget[0] is None else budget[0]
     eval_lr = tr.eval_lr if budget[1] is None else budget[1]
@@ -541,37 +569,14 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
         kw["con"] = con
     if noise is not None:
         kw["noise"] = noise
-    if lanes is not None:
-        if trace is not None or noise is not None:
-            raise ValueError("per-lane budgets run without a record and without observation noise")
-        for t0 in range(0, H, steps):
-            tr.kernels.evaluate_budgets(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs,
-                                        v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
-                                        tr._box_hi, lanes[0], lanes[1], tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
-                                        v.viol_thresh, **kw)
-        return
-    if groups is not None:
-        if trace is not None or noise is not None:
-            raise ValueError("policy groups run without a record and without observation noise")
-        for t0 in range(0, H, steps):
-            tr.kernels.evaluate_policies(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs,
-                                         v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
-                                         tr._box_hi, eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
-                                         v.viol_thresh, *groups, **kw)
-        return
-    if levels is not None:
-        if trace is not None or noise is not None:
-            raise ValueError("noise levels per group run without a record and without a sigma of the whole launch")
-        for t0 in range(0, H, steps):
-            tr.kernels.evaluate_noise_sweep(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs,
-                                            v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0),
-                                            tr._box_lo, tr._box_hi, eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum,
-                                            v.max_episode_steps, v.viol_thresh, *levels, **kw)
-        return
-    for t0 in range(0, H, steps):
-        tr.kernels.evaluate(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs, v.action,
-                            v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo, tr._box_hi,
-                            eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps, v.viol_thresh, **kw)
+    method, *tail = ("evaluate",) if variant is None else variant
+    if variant is not None and (trace is not None or noise is not None):
+        raise ValueError(_VARIANT_REFUSALS[method])
+    for t0 in range(0, H, steps):                                # (the method is looked up at every launch)
+        getattr(tr.kernels, method)(desc, tr._gauss_policy, scale, base, v.internal, None if v.obs is v.internal else v.obs,
+                                    v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
+                                    tr._box_hi, eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
+                                    v.viol_thresh, *tail, **kw)
 
 
 def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, noise=None):
@@ -612,6 +617,45 @@ def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, nois
         update(rows, k.cols, iters, i, v.viol_thresh, acc)
 
 
+# ------------------------------------------------------------------------------------------------ sweeps: shared
+def _padded(n):
+    """n episodes of a group padded to whole 64-lane tiles."""
+    return (n + hip_ops.POLICY_GROUP_ALIGN - 1) // hip_ops.POLICY_GROUP_ALIGN * hip_ops.POLICY_GROUP_ALIGN
+
+
+def _tile_groups(tr, v, seed, G, want_con, GL=None):
+    """(env, acc, con) of G copies of the initial env ``v``, group-major: lane g * GL + e is episode e of group g.  internal AND
+    obs are tiled (SpringPendulum's injected observation comes from torch's cos / sin: recomputing it here would not be
+    evaluate()'s bits); the bookkeeping of the new env is zero, like the reset one's.  GL None: the groups are not padded and
+    con is left to step 0, which writes every row; else every group has GL >= n lanes, the padding lanes keep the new env's rows
+    (the kernel neither steps nor writes them) and con is zeroed."""
+    n = v.n
+    lanes = n if GL is None else GL
+    big = _make_vec(tr, G * lanes, seed)
+    big.internal.view(G, lanes, -1)[:, :n].copy_(v.internal)
+    if big.obs is not big.internal:
+        big.obs.view(G, lanes, -1)[:, :n].copy_(v.obs)
+    acc = torch.zeros(G * lanes, 8, device=tr.device)
+    con = None
+    if want_con:
+        con = (torch.empty if GL is None else torch.zeros)(G * lanes, hip_ops.con_width(tr.kernels.ineq_num, tr.kernels.eq_num),
+                                                           device=tr.device)
+    return big, acc, con
+
+
+def _group_results(tr, acc, con, G, n, H, seed, viol_thresh):
+    """The G ``EvalResult``s (path "fused") of the first n lanes of every group of acc [G * GL, 8] / con [G * GL, W] or None."""
+    acc_host = acc.cpu().numpy().reshape(G, -1, 8)
+    con_host = None if con is None else con.cpu().numpy().reshape(G, acc_host.shape[1], -1)
+    results = []
+    for g in range(G):
+        res = EvalResult(acc_host[g, :n], "fused", H, seed)
+        if con is not None:
+            res.constraints = _constraint_report(tr, con_host[g, :n], res.length, viol_thresh)
+        results.append(res)
+    return results
+
+
 # ------------------------------------------------------------------------------------------------ budget sweeps
 MAX_BUDGETS = 64
 Paired = collections.namedtuple("Paired", "mean stderr n")
@@ -622,8 +666,8 @@ class ResultSweep(object):
     """What ``BudgetSweep``, ``PolicySweep`` and ``NoiseSweep`` share: G ``EvalResult``s of the same episodes (``sweep[g]`` is ``results[g]``)
     and their fields stacked into [G, episodes] arrays whose rows ARE the results' arrays (one memory)."""
 
-    def _stack(self, results):
-        self.results = list(results)
+    def _stack(self, results, path):
+        self.results, self.path = list(results), path
         if not self.results:
             raise ValueError("%s: no results" % type(self).__name__)
         if len(set(r.episodes for r in self.results)) != 1:
@@ -679,8 +723,7 @@ class BudgetSweep(ResultSweep):
         if not results or not len(results) == len(self.eval_steps) == len(self.eval_lr):
             raise ValueError("BudgetSweep: %d results for %d budgets and %d step sizes"
                              % (len(results), len(self.eval_steps), len(self.eval_lr)))
-        self._stack(results)
-        self.path = path
+        self._stack(results, path)
 
     def budget(self, max_rate=0.0):
         """The smallest ``eval_steps[g]`` whose ``violation_rate()[g]`` is <= ``max_rate``; None if no budget of the sweep is."""
@@ -725,55 +768,22 @@ def evaluate_budgets(tr, episodes=10, eval_steps=None, eval_lr=None, horizon=Non
         raise ValueError("evaluate_budgets needs a trainer that projects (RPODDPG / RPOSAC); %s has no projection" % type(tr).__name__)
     steps, lrs = check_budgets(tr, eval_steps, eval_lr)
     B = len(steps)
-    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
-        raise ValueError("evaluate_budgets: horizon must be an integer >= 1, got %r" % (horizon,))
-    H = int(horizon) if horizon is not None else default_horizon(tr)
-    if H >= 1 << 24:
-        raise ValueError("evaluate_budgets: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
-    k = tr.kernels
-    if init_states is not None:
-        init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
-        if tuple(init_states.shape) != (n, k.internal_dim):
-            raise ValueError("evaluate_budgets: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
-                             % (n, k.internal_dim, tuple(init_states.shape)))
+    H = check_horizon(tr, horizon, "evaluate_budgets")
+    init_states = check_init_states(tr, init_states, n, "evaluate_budgets")
     seed = fresh_seed(tr) if seed is None else int(seed)         # ONE seed (and one tick of the call counter) for all budgets
-    fused = bool(fused_ok(tr) and hasattr(k, "evaluate_budgets") and tr.schedule.get("fused_budgets", 1)
+    fused = bool(fused_ok(tr) and hasattr(tr.kernels, "evaluate_budgets") and tr.schedule.get("fused_budgets", 1)
                  and B * n <= _FUSED_BUDGET_LANES)
     if not fused:
         results = [evaluate(tr, episodes=n, horizon=H, seed=seed, init_states=init_states, eval_steps=b, eval_lr=lr,
                             constraints=want_con) for b, lr in zip(steps, lrs)]
         return BudgetSweep(results, steps, lrs, "sweep")
-    dev = tr.device
-    make = dict(seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev, stats_cap=2,
-                viol_thresh=tr.vec.viol_thresh)
-    v = tr.base_env.make_vec(n, **make)                          # the initial states of evaluate(): reset, then the injection
-    v.reset()
-    if init_states is not None:
-        v.set_internal(init_states)
-    # B copies, group-major: lane g * n + e is episode e under budget g.  internal AND obs are tiled (SpringPendulum's injected
-    # observation comes from torch's cos / sin: recomputing it here would not be evaluate()'s bits); the bookkeeping of the
-    # new env is zero, like the reset one's
-    big = tr.base_env.make_vec(B * n, **make)
-    big.internal.view(B, n, -1).copy_(v.internal)
-    if big.obs is not big.internal:
-        big.obs.view(B, n, -1).copy_(v.obs)
-    lanes = (torch.tensor(steps, dtype=torch.int32, device=dev).repeat_interleave(n),
-             torch.tensor(lrs, dtype=torch.float32, device=dev).repeat_interleave(n))
-    acc = torch.zeros(B * n, 8, device=dev)
-    con = torch.empty(B * n, hip_ops.con_width(k.ineq_num, k.eq_num), device=dev) if want_con else None
+    # B unpadded groups: lane g * n + e is episode e under budget g
+    big, acc, con = _tile_groups(tr, _initial_env(tr, n, seed, init_states), seed, B, want_con)
+    lanes = (torch.tensor(steps, dtype=torch.int32, device=tr.device).repeat_interleave(n),
+             torch.tensor(lrs, dtype=torch.float32, device=tr.device).repeat_interleave(n))
     with torch.no_grad():
-        _run_fused(tr, big, acc, H, con=con, lanes=lanes)
-    acc_host = acc.cpu().numpy().reshape(B, n, 8)
-    con_host = con.cpu().numpy().reshape(B, n, -1) if want_con else None
-    results = []
-    for g in range(B):
-        res = EvalResult(acc_host[g], "fused", H, seed)
-        if want_con:
-            res.constraints = ConstraintReport.from_rows(con_host[g], k.ineq_num, k.eq_num, res.length, big.viol_thresh,
-                                                         getattr(tr.base_env, "ineq_names", None),
-                                                         getattr(tr.base_env, "eq_names", None))
-        results.append(res)
-    return BudgetSweep(results, steps, lrs, "fused")
+        _run_fused(tr, big, acc, H, budget=lanes, con=con, variant=("evaluate_budgets",))
+    return BudgetSweep(_group_results(tr, acc, con, B, n, H, seed, big.viol_thresh), steps, lrs, "fused")
 
 
 # ------------------------------------------------------------------------------------------------ policy sweeps
@@ -794,8 +804,7 @@ class PolicySweep(ResultSweep):
         results, self.names = list(results), tuple(str(x) for x in names)
         if not results or len(results) != len(self.names):
             raise ValueError("PolicySweep: %d results for %d names" % (len(results), len(self.names)))
-        self._stack(results)
-        self.path = path
+        self._stack(results, path)
 
     def best(self, max_rate=0.0):
         """The index ``keep_best`` would hold after seeing the groups in order (``keep_best_wins`` of csrc/eval_dev.h on the
@@ -915,21 +924,28 @@ def check_policies(tr, policies, names):
     return flat, rng, spans, list(names)
 
 
-def policy_bank(tr, spans):
-    """(bank, descriptor) of the fused path: the P spans (None: the live actor's) side by side in one device tensor
-    [P, span] -- the span is a multiple of 4 floats by FlatParams' padding, so every policy's tensors keep the alignment of
-    the live ones -- and ONE ``MlpDesc`` over policy 0, built as ``CurveRunner._alloc`` builds its snapshot's."""
-    flat, (lo, hi) = actor_span(tr, "evaluate_policies()")
-    live, d = flat.param((lo, hi)), tr.fused.descs["actor"]
-    bank = torch.empty(len(spans), hi - lo, device=tr.device)
-    for g, src in enumerate(spans):
-        bank[g].copy_(live if src is None else src)
+def actor_desc_over(tr, buf):
+    """The fused actor's ``MlpDesc`` over ``buf``: a float32 vector laid out like the actor's span of the flat parameter buffer
+    (every tensor at its offset in the span)."""
+    flat, d = tr.agent.flat, tr.fused.descs["actor"]
     tensors = {}
     for key, p in d.tensors.items():
         if p is not None:
-            off = flat.offset[id(p)] - lo
-            tensors[key] = bank[0, off:off + p.numel()].view(p.shape)
-    return bank, tr.backend.MlpDesc(tensors, d.S, d.A, d.E, d.H, d.n_out, d.cat, head_dim=d.head_dim)
+            off = flat.offset[id(p)] - flat.actor_range[0]
+            tensors[key] = buf[off:off + p.numel()].view(p.shape)
+    return tr.backend.MlpDesc(tensors, d.S, d.A, d.E, d.H, d.n_out, d.cat, head_dim=d.head_dim)
+
+
+def policy_bank(tr, spans):
+    """(bank, descriptor) of the fused path: the P spans (None: the live actor's) side by side in one device tensor
+    [P, span] -- the span is a multiple of 4 floats by FlatParams' padding, so every policy's tensors keep the alignment of
+    the live ones -- and ONE ``MlpDesc`` over policy 0 (``actor_desc_over``)."""
+    flat, (lo, hi) = actor_span(tr, "evaluate_policies()")
+    live = flat.param((lo, hi))
+    bank = torch.empty(len(spans), hi - lo, device=tr.device)
+    for g, src in enumerate(spans):
+        bank[g].copy_(live if src is None else src)
+    return bank, actor_desc_over(tr, bank[0])
 
 
 def evaluate_policies(tr, policies, episodes=10, seed=None, horizon=None, init_states=None, constraints=False, names=None):
@@ -938,20 +954,11 @@ def evaluate_policies(tr, policies, episodes=10, seed=None, horizon=None, init_s
     n = check_episodes(episodes, "evaluate_policies: episodes")
     want_con = check_constraints(constraints)
     P = len(spans)
-    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
-        raise ValueError("evaluate_policies: horizon must be an integer >= 1, got %r" % (horizon,))
-    H = int(horizon) if horizon is not None else default_horizon(tr)
-    if H >= 1 << 24:
-        raise ValueError("evaluate_policies: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
-    k = tr.kernels
-    if init_states is not None:
-        init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
-        if tuple(init_states.shape) != (n, k.internal_dim):
-            raise ValueError("evaluate_policies: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
-                             % (n, k.internal_dim, tuple(init_states.shape)))
+    H = check_horizon(tr, horizon, "evaluate_policies")
+    init_states = check_init_states(tr, init_states, n, "evaluate_policies")
     seed = fresh_seed(tr) if seed is None else int(seed)         # ONE seed (and one tick of the call counter) for all policies
-    GL = (n + hip_ops.POLICY_GROUP_ALIGN - 1) // hip_ops.POLICY_GROUP_ALIGN * hip_ops.POLICY_GROUP_ALIGN
-    fused = bool(fused_ok(tr) and hasattr(k, "evaluate_policies") and tr.schedule.get("fused_policies", 1)
+    GL = _padded(n)
+    fused = bool(fused_ok(tr) and hasattr(tr.kernels, "evaluate_policies") and tr.schedule.get("fused_policies", 1)
                  and P * GL <= _FUSED_POLICY_LANES)
     if not fused:
         results = []
@@ -959,36 +966,13 @@ def evaluate_policies(tr, policies, episodes=10, seed=None, horizon=None, init_s
             with using_policy(tr, src):
                 results.append(evaluate(tr, episodes=n, horizon=H, seed=seed, init_states=init_states, constraints=want_con))
         return PolicySweep(results, names, "sweep")
-    dev = tr.device
-    make = dict(seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev, stats_cap=2,
-                viol_thresh=tr.vec.viol_thresh)
-    v = tr.base_env.make_vec(n, **make)                          # the initial states of evaluate(): reset, then the injection
-    v.reset()
-    if init_states is not None:
-        v.set_internal(init_states)
+    v = _initial_env(tr, n, seed, init_states)
     with torch.no_grad():
         bank, desc = policy_bank(tr, spans)
-        # P copies of the initial states, group-major, every group padded to GL lanes: lane g * GL + e is episode e under
-        # policy g; internal AND obs are tiled, as in evaluate_budgets().  The padding lanes keep the new env's rows: the
-        # kernel neither steps nor writes them
-        big = tr.base_env.make_vec(P * GL, **make)
-        big.internal.view(P, GL, -1)[:, :n].copy_(v.internal)
-        if big.obs is not big.internal:
-            big.obs.view(P, GL, -1)[:, :n].copy_(v.obs)
-        acc = torch.zeros(P * GL, 8, device=dev)
-        con = torch.zeros(P * GL, hip_ops.con_width(k.ineq_num, k.eq_num), device=dev) if want_con else None
-        _run_fused(tr, big, acc, H, desc=desc, con=con, groups=(bank, GL, n))
-    acc_host = acc.cpu().numpy().reshape(P, GL, 8)
-    con_host = con.cpu().numpy().reshape(P, GL, -1) if want_con else None
-    results = []
-    for g in range(P):
-        res = EvalResult(acc_host[g, :n], "fused", H, seed)
-        if want_con:
-            res.constraints = ConstraintReport.from_rows(con_host[g, :n], k.ineq_num, k.eq_num, res.length, big.viol_thresh,
-                                                         getattr(tr.base_env, "ineq_names", None),
-                                                         getattr(tr.base_env, "eq_names", None))
-        results.append(res)
-    return PolicySweep(results, names, "fused")
+        # P groups padded to GL lanes: lane g * GL + e is episode e under policy g
+        big, acc, con = _tile_groups(tr, v, seed, P, want_con, GL)
+        _run_fused(tr, big, acc, H, desc=desc, con=con, variant=("evaluate_policies", bank, GL, n))
+    return PolicySweep(_group_results(tr, acc, con, P, n, H, seed, big.viol_thresh), names, "fused")
 
 
 # ------------------------------------------------------------------------------------------------ noise sweeps
@@ -1011,10 +995,9 @@ class NoiseSweep(ResultSweep):
         self.levels = np.array(levels, dtype=np.float32)
         if not results or self.levels.ndim != 2 or len(results) != self.levels.shape[0]:
             raise ValueError("NoiseSweep: %d results for levels of shape %s" % (len(results), self.levels.shape))
-        self._stack(results)
+        self._stack(results, path)
         for g, r in enumerate(self.results):
             r.obs_noise = self.levels[g]
-        self.path = path
 
     def tolerance(self, max_rate=0.0):
         """The index of the last level, in the order given, of the longest prefix of levels whose ``violation_rate()`` are all
@@ -1058,56 +1041,25 @@ def evaluate_noise(tr, episodes=10, obs_noise=None, horizon=None, seed=None, ini
     n = check_episodes(episodes, "evaluate_noise: episodes")
     want_con = check_constraints(constraints)
     S = levels.shape[0]
-    if horizon is not None and (isinstance(horizon, bool) or int(horizon) != horizon or horizon < 1):
-        raise ValueError("evaluate_noise: horizon must be an integer >= 1, got %r" % (horizon,))
-    H = int(horizon) if horizon is not None else default_horizon(tr)
-    if H >= 1 << 24:
-        raise ValueError("evaluate_noise: horizon must be below 2^24 (lengths are counted exactly in float32), got %d" % H)
-    if init_states is not None:
-        init_states = torch.as_tensor(init_states, dtype=torch.float32, device=tr.device)
-        if tuple(init_states.shape) != (n, k.internal_dim):
-            raise ValueError("evaluate_noise: init_states must be [episodes, internal_dim] = [%d, %d], got %s"
-                             % (n, k.internal_dim, tuple(init_states.shape)))
+    H = check_horizon(tr, horizon, "evaluate_noise")
+    init_states = check_init_states(tr, init_states, n, "evaluate_noise")
     seed = fresh_seed(tr) if seed is None else int(seed)         # ONE seed (and one tick of the call counter) for all levels
-    GL = (n + hip_ops.POLICY_GROUP_ALIGN - 1) // hip_ops.POLICY_GROUP_ALIGN * hip_ops.POLICY_GROUP_ALIGN
+    GL = _padded(n)
     fused = bool(fused_ok(tr) and hasattr(k, "evaluate_noise_sweep") and tr.schedule.get("fused_noise_sweep", 1)
                  and S * GL <= _FUSED_NOISE_LANES)
     if not fused:
         results = [evaluate(tr, episodes=n, horizon=H, seed=seed, init_states=init_states, constraints=want_con,
                             obs_noise=levels[g]) for g in range(S)]
         return NoiseSweep(results, levels, "sweep")
-    dev = tr.device
-    make = dict(seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev, stats_cap=2,
-                viol_thresh=tr.vec.viol_thresh)
-    v = tr.base_env.make_vec(n, **make)                          # the initial states of evaluate(): reset, then the injection
-    v.reset()
-    if init_states is not None:
-        v.set_internal(init_states)
+    v = _initial_env(tr, n, seed, init_states)
     with torch.no_grad():
-        # S copies of the initial states, group-major, every group padded to GL lanes: lane g * GL + e is episode e under
-        # level g; internal AND obs are tiled, as in evaluate_policies().  The padding lanes keep the new env's rows: the
-        # kernel neither steps nor writes them
-        big = tr.base_env.make_vec(S * GL, **make)
-        big.internal.view(S, GL, -1)[:, :n].copy_(v.internal)
-        if big.obs is not big.internal:
-            big.obs.view(S, GL, -1)[:, :n].copy_(v.obs)
+        # S groups padded to GL lanes: lane g * GL + e is episode e under level g
+        big, acc, con = _tile_groups(tr, v, seed, S, want_con, GL)
         table = np.zeros((S, 8), dtype=np.float32)               # sigma[S, 8], zero beyond obs_dim
         table[:, :k.obs_dim] = levels
-        table = torch.from_numpy(table).to(dev)
-        acc = torch.zeros(S * GL, 8, device=dev)
-        con = torch.zeros(S * GL, hip_ops.con_width(k.ineq_num, k.eq_num), device=dev) if want_con else None
-        _run_fused(tr, big, acc, H, con=con, levels=(table, seed, GL, n))
-    acc_host = acc.cpu().numpy().reshape(S, GL, 8)
-    con_host = con.cpu().numpy().reshape(S, GL, -1) if want_con else None
-    results = []
-    for g in range(S):
-        res = EvalResult(acc_host[g, :n], "fused", H, seed)
-        if want_con:
-            res.constraints = ConstraintReport.from_rows(con_host[g, :n], k.ineq_num, k.eq_num, res.length, big.viol_thresh,
-                                                         getattr(tr.base_env, "ineq_names", None),
-                                                         getattr(tr.base_env, "eq_names", None))
-        results.append(res)
-    return NoiseSweep(results, levels, "fused")
+        table = torch.from_numpy(table).to(tr.device)
+        _run_fused(tr, big, acc, H, con=con, variant=("evaluate_noise_sweep", table, seed, GL, n))
+    return NoiseSweep(_group_results(tr, acc, con, S, n, H, seed, big.viol_thresh), levels, "fused")
 
 
 # ------------------------------------------------------------------------------------------------ evaluation curves
@@ -1308,8 +1260,7 @@ class CurveRunner(object):
 
     def _alloc(self):
         tr, dev = self.tr, self.tr.device
-        self.v = tr.base_env.make_vec(self.n, seed=0, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=dev,
-                                      stats_cap=2, viol_thresh=tr.vec.viol_thresh)
+        self.v = _make_vec(tr, self.n, 0)
         self.acc = torch.zeros(self.n, 8, device=dev)
         self.ring = torch.zeros(_CURVE_RING, CURVE_LEN, dtype=torch.float64, device=dev)
         self.ws = torch.zeros(_CURVE_WS, dtype=torch.float64, device=dev)
@@ -1319,14 +1270,8 @@ class CurveRunner(object):
         if self.overlap:
             flat = tr.agent.flat
             lo, hi = flat.actor_range
-            d = tr.fused.descs["actor"]
             self.src, self.snap = flat.param(flat.actor_range), torch.zeros(hi - lo, device=dev)
-            tensors = {}
-            for key, p in d.tensors.items():
-                if p is not None:
-                    off = flat.offset[id(p)] - lo
-                    tensors[key] = self.snap[off:off + p.numel()].view(p.shape)
-            self.desc = tr.backend.MlpDesc(tensors, d.S, d.A, d.E, d.H, d.n_out, d.cat, head_dim=d.head_dim)
+            self.desc = actor_desc_over(tr, self.snap)
             self.step_word = torch.zeros(1, dtype=torch.int64, device=dev)
             self.stream = torch.cuda.Stream()
         if self.keep_rate is not None:

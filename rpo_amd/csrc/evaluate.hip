@@ -361,54 +361,77 @@ int check_eval_noise_groups(const EvalNoiseGroups& g, int n) {
     return 0;
 }
 
-// rec / con of the entry points -> the instance; con == NULL: the launches of rpo_<env>_evaluate[_record] as they were;
-// noise != NULL: the NOISE = 1 instances; lanes != NULL: the BUD = 1 instances (no record, no noise: checked by the callers);
-// groups != NULL: the POL = 1 instances (no record, no noise, no lanes: checked by the callers); sweep != NULL: the NSW = 1
-// instances (no record, none of the others: checked by the callers)
+// What every rpo_<env>_evaluate* entry point takes (the EVAL_COMMON list at the entry points fills it in this order).  CartSafe's
+// observation IS its state: obs = state there; SpringPendulum has no constants: consts_host = NULL.
+struct EvalCommon {
+    const rpo_mlp* actor_host;
+    void* stream;
+    int gauss, n, t0, steps, max_steps, max_episode_steps, partial;
+    float scale, base, box_lo, box_hi, corr_lr, corr_eps, corr_momentum, viol_thresh;
+    float *state, *obs, *action, *ep_ret, *acc;
+    int* ep_len;
+    unsigned* ep_count;
+    long long* ctrl;
+    const float* consts_host;
+};
+
+// What an entry point adds to rpo_<env>_evaluate; value-initialised: nothing.  One variant at most, by construction.
+enum EvalVariant { kEvalPlain, kEvalNoisy, kEvalBudgets, kEvalPolicies, kEvalNoiseSweep };   // from kEvalBudgets on: no record
+struct EvalOpts {
+    int rec, with_con;            // the entry point takes a record / a report at all: a NULL one is then RPO_ERR_NULL
+    float *trace, *con;
+    int trace_rows, trace_steps;
+    EvalVariant variant;          // which of the four below counts
+    EvalNoise noise;              // -> the NOISE = 1 instances
+    EvalLanes lanes;              // -> the BUD = 1 instances
+    EvalGroups groups;            // -> the POL = 1 instances
+    EvalNoiseGroups sweep;        // -> the NSW = 1 instances
+};
+
+// The instance's arguments: the base copied, con set (NULL for the CON = 0 instances, which never read it), the rest zero.
+template <class ARGS, class ENV>
+ARGS eval_args_of(const EvalArgs<ENV>& args, float* con) {
+    ARGS a{};
+    static_cast<EvalArgs<ENV>&>(a) = args;
+    a.con = con;
+    return a;
+}
+
+// The options of the entry points -> the instance; no report: the launches of rpo_<env>_evaluate[_record] as they were.
 template <class ENV>
-int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, int rec, float* con, void* stream,
-                    const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr,
-                    const EvalNoiseGroups* sweep = nullptr) {
-    if (sweep) {
-        EvalNoiseSweepArgs<ENV> sa{};
-        static_cast<EvalArgs<ENV>&>(sa) = args;
-        sa.con = con;
-        sa.sigma_table = sweep->sigma_table;
-        sa.noise_seed = sweep->seed;
-        sa.group_lanes = sweep->group_lanes;
-        sa.episodes = sweep->episodes;
+int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, int n, const EvalOpts& o, void* stream) {
+    const int rec = o.rec;
+    float* con = o.with_con ? o.con : nullptr;
+    if (o.variant == kEvalNoiseSweep) {
+        auto sa = eval_args_of<EvalNoiseSweepArgs<ENV>>(args, con);
+        sa.sigma_table = o.sweep.sigma_table;
+        sa.noise_seed = o.sweep.seed;
+        sa.group_lanes = o.sweep.group_lanes;
+        sa.episodes = o.sweep.episodes;
         return con ? launch_eval<ENV, 0, 1, 1, 0, 0, 1>(sa, c, n, stream) : launch_eval<ENV, 0, 0, 1, 0, 0, 1>(sa, c, n, stream);
     }
-    if (groups) {
-        EvalPolArgs<ENV> pa{};
-        static_cast<EvalArgs<ENV>&>(pa) = args;
-        pa.con = con;
-        pa.policy_stride = groups->policy_stride;
-        pa.group_lanes = groups->group_lanes;
-        pa.episodes = groups->episodes;
+    if (o.variant == kEvalPolicies) {
+        auto pa = eval_args_of<EvalPolArgs<ENV>>(args, con);
+        pa.policy_stride = o.groups.policy_stride;
+        pa.group_lanes = o.groups.group_lanes;
+        pa.episodes = o.groups.episodes;
         return con ? launch_eval<ENV, 0, 1, 0, 0, 1>(pa, c, n, stream) : launch_eval<ENV, 0, 0, 0, 0, 1>(pa, c, n, stream);
     }
-    if (lanes) {
-        EvalBudArgs<ENV> ba{};
-        static_cast<EvalArgs<ENV>&>(ba) = args;
-        ba.con = con;
-        ba.lane_steps = lanes->steps;
-        ba.lane_lr = lanes->lr;
+    if (o.variant == kEvalBudgets) {
+        auto ba = eval_args_of<EvalBudArgs<ENV>>(args, con);
+        ba.lane_steps = o.lanes.steps;
+        ba.lane_lr = o.lanes.lr;
         return con ? launch_eval<ENV, 0, 1, 0, 1>(ba, c, n, stream) : launch_eval<ENV, 0, 0, 0, 1>(ba, c, n, stream);
     }
-    if (noise) {
-        EvalNoiseArgs<ENV> na{};
-        static_cast<EvalArgs<ENV>&>(na) = args;
-        na.con = con;
-        for (int q = 0; q < noise->len; ++q) na.sigma[q] = noise->sigma_host[q];
-        na.noise_seed = noise->seed;
+    if (o.variant == kEvalNoisy) {
+        auto na = eval_args_of<EvalNoiseArgs<ENV>>(args, con);
+        for (int q = 0; q < o.noise.len; ++q) na.sigma[q] = o.noise.sigma_host[q];
+        na.noise_seed = o.noise.seed;
         if (!con) return rec ? launch_eval<ENV, 1, 0, 1>(na, c, n, stream) : launch_eval<ENV, 0, 0, 1>(na, c, n, stream);
         return rec ? launch_eval<ENV, 1, 1, 1>(na, c, n, stream) : launch_eval<ENV, 0, 1, 1>(na, c, n, stream);
     }
     if (!con) return rec ? launch_eval<ENV, 1, 0>(args, c, n, stream) : launch_eval<ENV, 0, 0>(args, c, n, stream);
-    EvalConArgs<ENV> ca;
-    static_cast<EvalArgs<ENV>&>(ca) = args;
-    ca.con = con;
+    const auto ca = eval_args_of<EvalConArgs<ENV>>(args, con);
     return rec ? launch_eval<ENV, 1, 1>(ca, c, n, stream) : launch_eval<ENV, 0, 1>(ca, c, n, stream);
 }
 
@@ -715,90 +738,64 @@ __global__ __launch_bounds__(RPO_BLOCK) void keep_best_copy_kernel(long long n, 
     for (long long i = head + 4 * n4 + tid; i < n; i += stride) best[i] = src[i];
 }
 
-// rpo_cartsafe_evaluate (rec = 0: trace arguments unused), rpo_cartsafe_evaluate_record (rec = 1) and
-// rpo_cartsafe_evaluate_constraints (with_con = 1; rec = whether it got a trace)
-int cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state, float* action,
-                      int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, float box_lo,
-                      float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, const float* consts_host,
-                      int partial, int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows,
-                      int trace_steps, int with_con, float* con, void* stream, const EvalNoise* noise = nullptr,
-                      const EvalLanes* lanes = nullptr, const EvalGroups* groups = nullptr,
-                      const EvalNoiseGroups* sweep = nullptr) {
-    if (!actor_host) return RPO_ERR_NULL;
-    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
-    if (noise)
-        if (int e = check_eval_noise(*noise, 6)) return e;
-    if (!state || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
-    if (lanes) {
-        if (int e = check_eval_lanes(*lanes)) return e;
-        if (rec || noise) return RPO_ERR_ARG;
-    }
-    if (groups) {
-        if (int e = check_eval_groups(*groups, n_envs)) return e;
-        if (rec || noise || lanes) return RPO_ERR_ARG;
-    }
-    if (sweep) {
-        if (int e = check_eval_noise_groups(*sweep, n_envs)) return e;
-        if (rec || noise || lanes || groups) return RPO_ERR_ARG;
-    }
-    if (rec)
-        if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
-    if (with_con)
-        if (int e = check_eval_con(con)) return e;
-    EvalArgs<CartEnv> args{};
-    args.actor = to_dev(actor_host);
-    if (int e = check_eval_actor(args.actor, 6, gauss)) return e;
-    rpo_cart_dev::CartConsts c;
-    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
-    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
-    args.act = rpo_cart_dev::ActArgs{n_envs, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, box_lo, box_hi,
-                                     max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    args.step = rpo_cart_dev::StepArgs{n_envs, state, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
-                                       max_episode_steps, 0, viol_thresh, 0ull, 0u, 0};
-    args.trace = rec ? trace : nullptr;
-    args.trace_rows = rec ? trace_rows : 0;
-    return launch_eval_any<CartEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups, sweep);
+// Host side of the entry points: what the two envs differ in beyond EvalEnv<ENV>::kObs, overloaded on the env's types -- loading
+// the constants and building ActArgs / StepArgs (projection: RPO_NOISE_NONE; step: rows = NULL, auto_reset = 0).
+int eval_consts(rpo_cart_dev::CartConsts& c, const EvalCommon& q) { return rpo_cart_dev::load_consts(c, q.consts_host, q.partial); }
+int eval_consts(PendEnv::Consts& c, const EvalCommon&) { c.unused = 0; return 0; }
+
+void eval_env_args(const EvalCommon& q, rpo_cart_dev::ActArgs& act, rpo_cart_dev::StepArgs& step) {
+    act = rpo_cart_dev::ActArgs{q.n, nullptr, nullptr, q.action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, q.box_lo, q.box_hi,
+                                q.max_steps, q.corr_lr, q.corr_eps, q.corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    step = rpo_cart_dev::StepArgs{q.n, q.state, q.action, q.ep_len, q.ep_ret, q.ep_count, nullptr, 1, nullptr, 0, q.ctrl,
+                                  q.max_episode_steps, 0, q.viol_thresh, 0ull, 0u, 0};
+}
+void eval_env_args(const EvalCommon& q, rpo_pend_dev::ActArgs& act, rpo_pend_dev::StepArgs& step) {
+    act = rpo_pend_dev::ActArgs{q.n, nullptr, 5, nullptr, nullptr, q.action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, q.box_lo,
+                                q.box_hi, q.max_steps, q.corr_lr, q.corr_eps, q.corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    step = rpo_pend_dev::StepArgs{q.n, q.state, q.obs, q.action, q.ep_len, q.ep_ret, q.ep_count, nullptr, 1, nullptr, 0, q.ctrl,
+                                  q.max_episode_steps, 0, q.viol_thresh, 0ull, 0u};
 }
 
-int pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal, float* obs,
-                      float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps,
-                      float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
-                      int max_episode_steps, float viol_thresh, int rec, float* trace, int trace_rows, int trace_steps,
-                      int with_con, float* con, void* stream, const EvalNoise* noise = nullptr, const EvalLanes* lanes = nullptr,
-                      const EvalGroups* groups = nullptr, const EvalNoiseGroups* sweep = nullptr) {
-    if (!actor_host) return RPO_ERR_NULL;
-    if (int e = check_eval_range(n_envs, t0, steps, max_episode_steps, max_steps)) return e;
-    if (noise)
-        if (int e = check_eval_noise(*noise, 5)) return e;
-    if (!internal || !obs || !action || !ep_len || !ep_ret || !ep_count || !acc) return RPO_ERR_NULL;
-    if (lanes) {
-        if (int e = check_eval_lanes(*lanes)) return e;
-        if (rec || noise) return RPO_ERR_ARG;
-    }
-    if (groups) {
-        if (int e = check_eval_groups(*groups, n_envs)) return e;
-        if (rec || noise || lanes) return RPO_ERR_ARG;
-    }
-    if (sweep) {
-        if (int e = check_eval_noise_groups(*sweep, n_envs)) return e;
-        if (rec || noise || lanes || groups) return RPO_ERR_ARG;
-    }
-    if (rec)
-        if (int e = check_eval_trace(trace, n_envs, trace_rows, trace_steps, t0, steps)) return e;
-    if (with_con)
-        if (int e = check_eval_con(con)) return e;
-    EvalArgs<PendEnv> args{};
-    args.actor = to_dev(actor_host);
-    if (int e = check_eval_actor(args.actor, 5, gauss)) return e;
-    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.t0 = t0; args.steps = steps; args.acc = acc;
-    args.act = rpo_pend_dev::ActArgs{n_envs, nullptr, 5, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
-                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    args.step = rpo_pend_dev::StepArgs{n_envs, internal, obs, action, ep_len, ep_ret, ep_count, nullptr, 1, nullptr, 0, ctrl,
-                                       max_episode_steps, 0, viol_thresh, 0ull, 0u};
-    args.trace = rec ? trace : nullptr;
-    args.trace_rows = rec ? trace_rows : 0;
-    const PendEnv::Consts c{0};
-    return launch_eval_any<PendEnv>(args, c, n_envs, rec, with_con ? con : nullptr, stream, noise, lanes, groups, sweep);
+// Every rpo_<env>_evaluate* entry point: the validation in one order, then the launch.
+template <class ENV>
+int evaluate_entry(const EvalCommon& q, const EvalOpts& o) {
+    constexpr int kObs = EvalEnv<ENV>::kObs;
+    if (!q.actor_host) return RPO_ERR_NULL;
+    if (int e = check_eval_range(q.n, q.t0, q.steps, q.max_episode_steps, q.max_steps)) return e;
+    if (o.variant == kEvalNoisy)
+        if (int e = check_eval_noise(o.noise, kObs)) return e;
+    if (!q.state || !q.obs || !q.action || !q.ep_len || !q.ep_ret || !q.ep_count || !q.acc) return RPO_ERR_NULL;
+    if (int e = o.variant == kEvalBudgets      ? check_eval_lanes(o.lanes)
+                : o.variant == kEvalPolicies   ? check_eval_groups(o.groups, q.n)
+                : o.variant == kEvalNoiseSweep ? check_eval_noise_groups(o.sweep, q.n)
+                                               : 0)
+        return e;
+    // which variants exclude each other (the host's statement of eval_kernel's static_asserts): EvalOpts holds one variant at
+    // most, and per-lane budgets, policy groups and noise groups run without a record
+    if (o.rec && o.variant >= kEvalBudgets) return RPO_ERR_ARG;
+    if (o.rec)
+        if (int e = check_eval_trace(o.trace, q.n, o.trace_rows, o.trace_steps, q.t0, q.steps)) return e;
+    if (o.with_con)
+        if (int e = check_eval_con(o.con)) return e;
+    EvalArgs<ENV> args{};
+    args.actor = to_dev(q.actor_host);
+    if (int e = check_eval_actor(args.actor, kObs, q.gauss)) return e;
+    typename ENV::Consts c;
+    if (int e = eval_consts(c, q)) return e;
+    args.scale = q.scale; args.base = q.base; args.gauss = q.gauss ? 1 : 0; args.t0 = q.t0; args.steps = q.steps; args.acc = q.acc;
+    eval_env_args(q, args.act, args.step);
+    args.trace = o.rec ? o.trace : nullptr;
+    args.trace_rows = o.rec ? o.trace_rows : 0;
+    return launch_eval_any<ENV>(args, c, q.n, o, q.stream);
+}
+
+// The record and the report where the caller handed one over (the arguments of the entry points from _constraints on).
+EvalOpts eval_opts(float* trace, int trace_rows, int trace_steps, float* con, EvalVariant variant = kEvalPlain) {
+    EvalOpts o{};
+    o.rec = trace ? 1 : 0; o.trace = trace; o.trace_rows = trace_rows; o.trace_steps = trace_steps;
+    o.with_con = con ? 1 : 0; o.con = con;
+    o.variant = variant;
+    return o;
 }
 
 }  // namespace
@@ -849,14 +846,19 @@ int rpo_eval_keep_best(long long n_params, const float* src, float* best, const 
     return 0;
 }
 
+// The arguments every rpo_<env>_evaluate* entry point declares under these names, in EvalCommon's order.
+#define EVAL_COMMON(STATE, OBS, CONSTS, PARTIAL)                                                                                  \
+    EvalCommon{actor_host, stream, gauss, n_envs, t0, steps, max_steps, max_episode_steps, PARTIAL, scale, base, box_lo, box_hi,  \
+               corr_lr, corr_eps, corr_momentum, viol_thresh, STATE, OBS, action, ep_ret, acc, ep_len, ep_count, ctrl, CONSTS}
+#define EVAL_CART EVAL_COMMON(state, state, consts_host, partial)
+#define EVAL_PEND EVAL_COMMON(internal, obs, nullptr, 0)
+
 int rpo_cartsafe_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
                           float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl, float* acc, int t0,
                           int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
                           float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
                           float viol_thresh, void* stream) {
-    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, 0, nullptr, 0, 0, 0, nullptr, stream);
+    return evaluate_entry<CartEnv>(EVAL_CART, EvalOpts{});
 }
 
 int rpo_cartsafe_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -864,18 +866,16 @@ int rpo_cartsafe_evaluate_record(const rpo_mlp* actor_host, int gauss, float sca
                                  int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps,
                                  float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
                                  float viol_thresh, float* trace, int trace_rows, int trace_steps, void* stream) {
-    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, 1, trace, trace_rows, trace_steps, 0, nullptr, stream);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, nullptr);
+    o.rec = 1;
+    return evaluate_entry<CartEnv>(EVAL_CART, o);
 }
 
 int rpo_pendulum_evaluate(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
                           float* obs, float* action, int* ep_len, float* ep_ret, unsigned* ep_count, long long* ctrl,
                           float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
                           float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, void* stream) {
-    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
-                             nullptr, 0, 0, 0, nullptr, stream);
+    return evaluate_entry<PendEnv>(EVAL_PEND, EvalOpts{});
 }
 
 int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
@@ -883,9 +883,9 @@ int rpo_pendulum_evaluate_record(const rpo_mlp* actor_host, int gauss, float sca
                                  float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
                                  float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
                                  int trace_rows, int trace_steps, void* stream) {
-    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 1,
-                             trace, trace_rows, trace_steps, 0, nullptr, stream);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, nullptr);
+    o.rec = 1;
+    return evaluate_entry<PendEnv>(EVAL_PEND, o);
 }
 
 int rpo_cartsafe_evaluate_constraints(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -894,9 +894,9 @@ int rpo_cartsafe_evaluate_constraints(const rpo_mlp* actor_host, int gauss, floa
                                       float corr_eps, float corr_momentum, const float* consts_host, int partial,
                                       int max_episode_steps, float viol_thresh, float* trace, int trace_rows, int trace_steps,
                                       float* con, void* stream) {
-    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, trace ? 1 : 0, trace, trace_rows, trace_steps, 1, con, stream);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, con);
+    o.with_con = 1;
+    return evaluate_entry<CartEnv>(EVAL_CART, o);
 }
 
 int rpo_pendulum_evaluate_constraints(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs,
@@ -905,9 +905,9 @@ int rpo_pendulum_evaluate_constraints(const rpo_mlp* actor_host, int gauss, floa
                                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                                       int max_episode_steps, float viol_thresh, float* trace, int trace_rows, int trace_steps,
                                       float* con, void* stream) {
-    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-                             trace ? 1 : 0, trace, trace_rows, trace_steps, 1, con, stream);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, con);
+    o.with_con = 1;
+    return evaluate_entry<PendEnv>(EVAL_PEND, o);
 }
 
 int rpo_cartsafe_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -916,10 +916,9 @@ int rpo_cartsafe_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scal
                                 float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
                                 float viol_thresh, float* trace, int trace_rows, int trace_steps, float* con,
                                 const float* sigma_host, int sigma_len, unsigned long long noise_seed, void* stream) {
-    const EvalNoise noise{sigma_host, sigma_len, noise_seed};
-    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, &noise);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, con, kEvalNoisy);
+    o.noise = EvalNoise{sigma_host, sigma_len, noise_seed};
+    return evaluate_entry<CartEnv>(EVAL_CART, o);
 }
 
 int rpo_pendulum_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
@@ -928,10 +927,9 @@ int rpo_pendulum_evaluate_noisy(const rpo_mlp* actor_host, int gauss, float scal
                                 float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
                                 int trace_rows, int trace_steps, float* con, const float* sigma_host, int sigma_len,
                                 unsigned long long noise_seed, void* stream) {
-    const EvalNoise noise{sigma_host, sigma_len, noise_seed};
-    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-                             trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, &noise);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, con, kEvalNoisy);
+    o.noise = EvalNoise{sigma_host, sigma_len, noise_seed};
+    return evaluate_entry<PendEnv>(EVAL_PEND, o);
 }
 
 int rpo_cartsafe_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -940,10 +938,9 @@ int rpo_cartsafe_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float sc
                                   float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
                                   float viol_thresh, float* trace, int trace_rows, int trace_steps, float* con,
                                   const int* lane_steps, const float* lane_lr, void* stream) {
-    const EvalLanes lanes{lane_steps, lane_lr};
-    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, nullptr, &lanes);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, con, kEvalBudgets);
+    o.lanes = EvalLanes{lane_steps, lane_lr};
+    return evaluate_entry<CartEnv>(EVAL_CART, o);
 }
 
 int rpo_pendulum_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
@@ -952,10 +949,9 @@ int rpo_pendulum_evaluate_budgets(const rpo_mlp* actor_host, int gauss, float sc
                                   float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* trace,
                                   int trace_rows, int trace_steps, float* con, const int* lane_steps, const float* lane_lr,
                                   void* stream) {
-    const EvalLanes lanes{lane_steps, lane_lr};
-    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-                             trace ? 1 : 0, trace, trace_rows, trace_steps, con ? 1 : 0, con, stream, nullptr, &lanes);
+    EvalOpts o = eval_opts(trace, trace_rows, trace_steps, con, kEvalBudgets);
+    o.lanes = EvalLanes{lane_steps, lane_lr};
+    return evaluate_entry<PendEnv>(EVAL_PEND, o);
 }
 
 int rpo_cartsafe_evaluate_policies(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -964,10 +960,9 @@ int rpo_cartsafe_evaluate_policies(const rpo_mlp* actor_host, int gauss, float s
                                    float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
                                    float viol_thresh, float* con, int policy_stride, int group_lanes, int episodes,
                                    void* stream) {
-    const EvalGroups groups{policy_stride, group_lanes, episodes};
-    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, 0, nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, &groups);
+    EvalOpts o = eval_opts(nullptr, 0, 0, con, kEvalPolicies);
+    o.groups = EvalGroups{policy_stride, group_lanes, episodes};
+    return evaluate_entry<CartEnv>(EVAL_CART, o);
 }
 
 int rpo_pendulum_evaluate_policies(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
@@ -975,10 +970,9 @@ int rpo_pendulum_evaluate_policies(const rpo_mlp* actor_host, int gauss, float s
                                    float* acc, int t0, int steps, float box_lo, float box_hi, int max_steps, float corr_lr,
                                    float corr_eps, float corr_momentum, int max_episode_steps, float viol_thresh, float* con,
                                    int policy_stride, int group_lanes, int episodes, void* stream) {
-    const EvalGroups groups{policy_stride, group_lanes, episodes};
-    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
-                             nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, &groups);
+    EvalOpts o = eval_opts(nullptr, 0, 0, con, kEvalPolicies);
+    o.groups = EvalGroups{policy_stride, group_lanes, episodes};
+    return evaluate_entry<PendEnv>(EVAL_PEND, o);
 }
 
 int rpo_cartsafe_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -987,10 +981,9 @@ int rpo_cartsafe_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, floa
                                       float corr_eps, float corr_momentum, const float* consts_host, int partial,
                                       int max_episode_steps, float viol_thresh, float* con, const float* sigma_table,
                                       unsigned long long noise_seed, int group_lanes, int episodes, void* stream) {
-    const EvalNoiseGroups sweep{sigma_table, noise_seed, group_lanes, episodes};
-    return cartsafe_evaluate(actor_host, gauss, scale, base, n_envs, state, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                             box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, consts_host, partial, max_episode_steps,
-                             viol_thresh, 0, nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, nullptr, &sweep);
+    EvalOpts o = eval_opts(nullptr, 0, 0, con, kEvalNoiseSweep);
+    o.sweep = EvalNoiseGroups{sigma_table, noise_seed, group_lanes, episodes};
+    return evaluate_entry<CartEnv>(EVAL_CART, o);
 }
 
 int rpo_pendulum_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs,
@@ -999,10 +992,9 @@ int rpo_pendulum_evaluate_noise_sweep(const rpo_mlp* actor_host, int gauss, floa
                                       float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                                       int max_episode_steps, float viol_thresh, float* con, const float* sigma_table,
                                       unsigned long long noise_seed, int group_lanes, int episodes, void* stream) {
-    const EvalNoiseGroups sweep{sigma_table, noise_seed, group_lanes, episodes};
-    return pendulum_evaluate(actor_host, gauss, scale, base, n_envs, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, 0,
-                             nullptr, 0, 0, con ? 1 : 0, con, stream, nullptr, nullptr, nullptr, &sweep);
+    EvalOpts o = eval_opts(nullptr, 0, 0, con, kEvalNoiseSweep);
+    o.sweep = EvalNoiseGroups{sigma_table, noise_seed, group_lanes, episodes};
+    return evaluate_entry<PendEnv>(EVAL_PEND, o);
 }
 
 int rpo_eval_obs_noise(int n, const float* obs, int obs_stride, int obs_dim, const float* sigma, unsigned long long seed,

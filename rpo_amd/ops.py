@@ -439,7 +439,92 @@ def _act_profile(profile, n, steps):
 
 # =================================================================================================== env kernel sets
 
-class CartSafeKernels(object):
+class _FusedEvaluate(object):
+    """The ``evaluate*`` methods of the env kernel classes that have the fused evaluation kernel (rpo_<env>_evaluate*, rpo_amd/
+    csrc/evaluate.hip).  The class says what its entry points differ in: ``_eval_env`` (the <env> of the symbols),
+    ``_eval_state(internal, obs)`` (the state pointers behind n_envs) and ``_eval_consts()`` (the arguments in front of
+    max_episode_steps)."""
+
+    def _eval_args(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                   box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh):
+        """The arguments every entry point starts with (the byref keeps the actor's struct alive over the call)."""
+        n = internal.shape[0]
+        return (ctypes.byref(actor_desc.net_struct()), int(gauss), scale, base, n, *self._eval_state(internal, obs), _p(action),
+                _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
+                _eval_acc(acc, n), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
+                *self._eval_consts(), max_episode_steps, viol_thresh)
+
+    def _eval_launch(self, variant, *args):
+        name = "rpo_%s_%s" % (self._eval_env, variant)
+        check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+    def _eval_trace(self, trace, n):
+        if trace is None:
+            return None, 0, 0
+        return _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
+
+    def _eval_con(self, con, n):
+        return None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num))
+
+    def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
+                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None,
+                 con=None, noise=None):
+        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_<env>_evaluate); acc [n, EVAL_LEN].
+        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_<env>_evaluate_record).
+        con [n, con_width]: the per-constraint report, with or without a trace (rpo_<env>_evaluate_constraints).
+        noise (sigma, seed): observation noise, sigma a host float32 [obs_dim], with or without trace and con
+        (rpo_<env>_evaluate_noisy)."""
+        n = internal.shape[0]
+        args = self._eval_args(actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                               steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh)
+        if noise is not None:
+            tr = self._eval_trace(trace, n)
+            sigma, tail = _eval_noise(noise, self.obs_dim)       # (sigma: kept alive over the call that copies it)
+            self._eval_launch("evaluate_noisy", *args, *tr, self._eval_con(con, n), *tail)
+        elif con is not None:
+            self._eval_launch("evaluate_constraints", *args, *self._eval_trace(trace, n), self._eval_con(con, n))
+        elif trace is None:
+            self._eval_launch("evaluate", *args)
+        else:
+            self._eval_launch("evaluate_record", *args, *self._eval_trace(trace, n))
+
+    def evaluate_budgets(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                         steps, box_lo, box_hi, lane_steps, lane_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                         con=None):
+        """``evaluate`` with a projection budget per lane (rpo_<env>_evaluate_budgets): lane_steps int32 [n] / lane_lr
+        float32 [n] on the device in place of max_steps / corr_lr; con as there; no record, no noise."""
+        n = internal.shape[0]
+        tail = _eval_lanes(lane_steps, lane_lr, n)
+        args = self._eval_args(actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                               steps, box_lo, box_hi, 0, 0.0, corr_eps, corr_momentum, max_episode_steps, viol_thresh)
+        self._eval_launch("evaluate_budgets", *args, None, 0, 0, self._eval_con(con, n), *tail)
+
+    def evaluate_policies(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                          steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, bank,
+                          group_lanes, episodes, con=None):
+        """``evaluate`` with an actor per group of lanes (rpo_<env>_evaluate_policies): bank float32 [P, stride] on the
+        device, actor_desc over bank[0]; n = P x group_lanes lanes, the first ``episodes`` of every group live, the others
+        padding that is never written; con as there; no record, no noise."""
+        n = internal.shape[0]
+        tail = _eval_policies(actor_desc, bank, n, group_lanes, episodes)
+        args = self._eval_args(actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                               steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh)
+        self._eval_launch("evaluate_policies", *args, self._eval_con(con, n), *tail)
+
+    def evaluate_noise_sweep(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
+                             sigma_table, seed, group_lanes, episodes, con=None):
+        """``evaluate`` with a noise level per group of lanes (rpo_<env>_evaluate_noise_sweep): sigma_table float32 [S, 8] on
+        the device, the draw keyed by ``seed`` and the episode within the group; n = S x group_lanes lanes, the first
+        ``episodes`` of every group live, the others padding that is never written; con as there; no record."""
+        n = internal.shape[0]
+        tail = _eval_noise_sweep(sigma_table, seed, n, group_lanes, episodes)
+        args = self._eval_args(actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
+                               steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh)
+        self._eval_launch("evaluate_noise_sweep", *args, self._eval_con(con, n), *tail)
+
+
+class CartSafeKernels(_FusedEvaluate):
     """HIP kernels of CartSafe-v0.  ``consts`` is the float32[35] table of include/rpo_hip.h (RPO_CART_CONSTS_LEN)."""
 
     name = "CartSafe-v0"
@@ -459,6 +544,14 @@ class CartSafeKernels(object):
     @property
     def _cptr(self):
         return _host_ptr(self.consts)
+
+    _eval_env = "cartsafe"
+
+    def _eval_state(self, internal, obs):
+        return (_p(internal),)
+
+    def _eval_consts(self):
+        return self._cptr, self.partial
 
     def reset(self, internal, obs, ep_len, ep_ret, ep_count, seed, env_id_base):
         # the observation IS the internal state for this env: `obs` aliases `internal`
@@ -495,82 +588,6 @@ class CartSafeKernels(object):
             eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr,
             self.partial, max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, int(defer_clock), _stream()),
             "rpo_cartsafe_rollout")
-
-    def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None,
-                 con=None, noise=None):
-        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_cartsafe_evaluate); acc [n, EVAL_LEN].
-        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_cartsafe_evaluate_record).
-        con [n, con_width]: the per-constraint report, with or without a trace (rpo_cartsafe_evaluate_constraints).
-        noise (sigma, seed): observation noise, sigma a host float32 [obs_dim], with or without trace and con
-        (rpo_cartsafe_evaluate_noisy)."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32),
-                _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n),
-                int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
-                max_episode_steps, viol_thresh)
-        if noise is not None:
-            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
-            sigma, tail = _eval_noise(noise, self.obs_dim)       # (sigma: kept alive over the call that copies it)
-            check(_lib.load().rpo_cartsafe_evaluate_noisy(*args, *tr, None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)),
-                                                    *tail, _stream()), "rpo_cartsafe_evaluate_noisy")
-        elif con is not None:
-            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
-            check(_lib.load().rpo_cartsafe_evaluate_constraints(*args, *tr, _con(con, n, con_width(self.ineq_num, self.eq_num)),
-                                                                _stream()), "rpo_cartsafe_evaluate_constraints")
-        elif trace is None:
-            check(_lib.load().rpo_cartsafe_evaluate(*args, _stream()), "rpo_cartsafe_evaluate")
-        else:
-            tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
-            check(_lib.load().rpo_cartsafe_evaluate_record(*args, *tr, _stream()), "rpo_cartsafe_evaluate_record")
-
-    def evaluate_budgets(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                         steps, box_lo, box_hi, lane_steps, lane_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-                         con=None):
-        """``evaluate`` with a projection budget per lane (rpo_cartsafe_evaluate_budgets): lane_steps int32 [n] / lane_lr
-        float32 [n] on the device in place of max_steps / corr_lr; con as there; no record, no noise."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        sp, lp = _eval_lanes(lane_steps, lane_lr, n)
-        check(_lib.load().rpo_cartsafe_evaluate_budgets(
-            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
-            _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0), int(steps), box_lo,
-            box_hi, 0, 0.0, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh, None, 0, 0,
-            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), sp, lp, _stream()),
-            "rpo_cartsafe_evaluate_budgets")
-
-    def evaluate_policies(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                          steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, bank,
-                          group_lanes, episodes, con=None):
-        """``evaluate`` with an actor per group of lanes (rpo_cartsafe_evaluate_policies): bank float32 [P, stride] on the
-        device, actor_desc over bank[0]; n = P x group_lanes lanes, the first ``episodes`` of every group live, the others
-        padding that is never written; con as there; no record, no noise."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        tail = _eval_policies(actor_desc, bank, n, group_lanes, episodes)
-        check(_lib.load().rpo_cartsafe_evaluate_policies(
-            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
-            _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0), int(steps), box_lo,
-            box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh,
-            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
-            "rpo_cartsafe_evaluate_policies")
-
-    def evaluate_noise_sweep(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-                             sigma_table, seed, group_lanes, episodes, con=None):
-        """``evaluate`` with a noise level per group of lanes (rpo_cartsafe_evaluate_noise_sweep): sigma_table float32 [S, 8] on
-        the device, the draw keyed by ``seed`` and the episode within the group; n = S x group_lanes lanes, the first
-        ``episodes`` of every group live, the others padding that is never written; con as there; no record."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        tail = _eval_noise_sweep(sigma_table, seed, n, group_lanes, episodes)
-        check(_lib.load().rpo_cartsafe_evaluate_noise_sweep(
-            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
-            _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0), int(steps), box_lo,
-            box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, max_episode_steps, viol_thresh,
-            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
-            "rpo_cartsafe_evaluate_noise_sweep")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):
@@ -759,7 +776,7 @@ class EvopfKernels(object):
     fused_adds = True      # complete_bwd(grad_action2=...) and lagrangian(overwrite=...) exist: no torch launches between them
 
 
-class PendulumKernels(object):
+class PendulumKernels(_FusedEvaluate):
     """HIP kernels of SpringPendulum-v0."""
 
     name = "SpringPendulum-v0"
@@ -769,6 +786,13 @@ class PendulumKernels(object):
     cols = dict(state=(0, 5), action=(5, 7), next_state=(7, 12), reward=(12, 13), done=(13, 14), eq_viol=(14, 15),
                 ineq_viol=(15, 16))
     partial = 0
+    _eval_env = "pendulum"
+
+    def _eval_state(self, internal, obs):
+        return _p(internal), _p(obs)
+
+    def _eval_consts(self):
+        return ()
 
     def reset(self, internal, obs, ep_len, ep_ret, ep_count, seed, env_id_base):
         check(_lib.load().rpo_pendulum_reset(internal.shape[0], _p(internal), _p(obs, allow_none=True),
@@ -804,82 +828,6 @@ class PendulumKernels(object):
             noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
             max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, int(defer_clock), _stream()),
             "rpo_pendulum_rollout")
-
-    def evaluate(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
-                 box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, trace=None,
-                 con=None, noise=None):
-        """Env steps [t0, t0 + steps) of a policy evaluation in one launch (rpo_pendulum_evaluate); acc [n, EVAL_LEN].
-        trace [T, R, W] (zeroed by the caller): the per-step record of lanes 0..R-1 (rpo_pendulum_evaluate_record).
-        con [n, con_width]: the per-constraint report, with or without a trace (rpo_pendulum_evaluate_constraints).
-        noise (sigma, seed): observation noise, sigma a host float32 [obs_dim], with or without trace and con
-        (rpo_pendulum_evaluate_noisy)."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        args = (ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action),
-                _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
-                _eval_acc(acc, n), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps,
-                corr_momentum, max_episode_steps, viol_thresh)
-        if noise is not None:
-            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
-            sigma, tail = _eval_noise(noise, self.obs_dim)       # (sigma: kept alive over the call that copies it)
-            check(_lib.load().rpo_pendulum_evaluate_noisy(*args, *tr, None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)),
-                                                    *tail, _stream()), "rpo_pendulum_evaluate_noisy")
-        elif con is not None:
-            tr = (None, 0, 0) if trace is None else _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
-            check(_lib.load().rpo_pendulum_evaluate_constraints(*args, *tr, _con(con, n, con_width(self.ineq_num, self.eq_num)),
-                                                                _stream()), "rpo_pendulum_evaluate_constraints")
-        elif trace is None:
-            check(_lib.load().rpo_pendulum_evaluate(*args, _stream()), "rpo_pendulum_evaluate")
-        else:
-            tr = _trace(trace, n, trace_layout(self.obs_dim, self.partial_dim, self.action_dim)[1])
-            check(_lib.load().rpo_pendulum_evaluate_record(*args, *tr, _stream()), "rpo_pendulum_evaluate_record")
-
-    def evaluate_budgets(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                         steps, box_lo, box_hi, lane_steps, lane_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-                         con=None):
-        """``evaluate`` with a projection budget per lane (rpo_pendulum_evaluate_budgets): lane_steps int32 [n] / lane_lr
-        float32 [n] on the device in place of max_steps / corr_lr; con as there; no record, no noise."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        sp, lp = _eval_lanes(lane_steps, lane_lr, n)
-        check(_lib.load().rpo_pendulum_evaluate_budgets(
-            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action), _p(ep_len, torch.int32),
-            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0),
-            int(steps), box_lo, box_hi, 0, 0.0, corr_eps, corr_momentum, max_episode_steps, viol_thresh, None, 0, 0,
-            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), sp, lp, _stream()),
-            "rpo_pendulum_evaluate_budgets")
-
-    def evaluate_policies(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                          steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, bank,
-                          group_lanes, episodes, con=None):
-        """``evaluate`` with an actor per group of lanes (rpo_pendulum_evaluate_policies): bank float32 [P, stride] on the
-        device, actor_desc over bank[0]; n = P x group_lanes lanes, the first ``episodes`` of every group live, the others
-        padding that is never written; con as there; no record, no noise."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        tail = _eval_policies(actor_desc, bank, n, group_lanes, episodes)
-        check(_lib.load().rpo_pendulum_evaluate_policies(
-            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action), _p(ep_len, torch.int32),
-            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0),
-            int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
-            "rpo_pendulum_evaluate_policies")
-
-    def evaluate_noise_sweep(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
-                             steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-                             sigma_table, seed, group_lanes, episodes, con=None):
-        """``evaluate`` with a noise level per group of lanes (rpo_pendulum_evaluate_noise_sweep): sigma_table float32 [S, 8]
-        on the device, the draw keyed by ``seed`` and the episode within the group; n = S x group_lanes lanes, the first
-        ``episodes`` of every group live, the others padding that is never written; con as there; no record."""
-        net = actor_desc.net_struct()
-        n = internal.shape[0]
-        tail = _eval_noise_sweep(sigma_table, seed, n, group_lanes, episodes)
-        check(_lib.load().rpo_pendulum_evaluate_noise_sweep(
-            ctypes.byref(net), int(gauss), scale, base, n, _p(internal), _p(obs), _p(action), _p(ep_len, torch.int32),
-            _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0),
-            int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
-            None if con is None else _con(con, n, con_width(self.ineq_num, self.eq_num)), *tail, _stream()),
-            "rpo_pendulum_evaluate_noise_sweep")
 
     def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
                    max_steps, corr_lr, corr_eps, corr_momentum, form=0):
