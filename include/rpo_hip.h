@@ -236,7 +236,10 @@ int rpo_abi_version(void);
                                       projection (<= 512 rows) on XCDs 0-1 and a rollout projection on XCDs 2-7 (block b runs on XCD b % 8:
                                       the grid is padded and the other XCDs' workgroups leave at once), so that the two launches that
                                       overlap in the training windows never share a SIMD.  Measured: DESIGN.md 4b */
-#define RPO_TUNE_COUNT 9
+#define RPO_TUNE_FWD_BF16X3 9      /* EXPERIMENT (default 0 = off): 1: the streaming forward (where RPO_TUNE_FWD_STREAM
+                                      applies, nowhere else) runs its hidden layer as a 3 x bf16 split of both operands on
+                                      v_mfma_f32_16x16x32_bf16 (mlp_stream_bf16x3.h): f32-accurate, NOT bit-equal to the exact form */
+#define RPO_TUNE_COUNT 10
 int rpo_tuning(int key, int value);
 
 /* ---------------------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@
 #include "mlp_gemm.h"
 #include "mlp_tile.h"
 #include "mlp_stream.h"
+#include "mlp_stream_bf16x3.h"
 
 namespace {
 
@@ -86,6 +87,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void mlp_forward_stream_kernel(Fwd
     mlp_forward_stream_body<256, NW>(p);
 }
 
+// The same launch with the hidden layer as a 3 x bf16 split on the bf16 matrix pipe (mlp_stream_bf16x3.h; opt-in).
+template <int NW>
+__global__ __launch_bounds__(NW * 64, NW / 4) void mlp_forward_stream_bf16x3_kernel(FwdArgs4 p) {
+    mlp_forward_stream_bf16x3_body<NW>(p);
+}
+
 static int stream_cus() { return rpo_cu_count(); }
 
 // the streaming forward applies: large n, every network of the launch 128 -> 256 with scalar heads and <= 11 inputs
@@ -105,6 +112,14 @@ static int launch_stream(const FwdArgs4& a, int count, int n, hipStream_t stream
     int gx = stream_cus() / count;                              // one persistent workgroup per CU (LDS: 150 KB each)
     if (gx < 1) gx = 1;
     if (gx > (tiles + nw - 1) / nw) gx = (tiles + nw - 1) / nw;
+    if (rpo_tune(RPO_TUNE_FWD_BF16X3) == 1) {                   // (read at launch: a captured graph keeps the form it was captured with)
+        gx = stream_cus() / count;                              // 12 waves per workgroup for either value of FWD_STREAM_WAVES
+        if (gx < 1) gx = 1;
+        if (gx > (tiles + 11) / 12) gx = (tiles + 11) / 12;
+        hipLaunchKernelGGL((mlp_forward_stream_bf16x3_kernel<12>), dim3(gx, count), dim3(12 * 64), 0, stream, a);
+        RPO_LAUNCH_CHECK();
+        return 0;
+    }
     if (nw == 16) hipLaunchKernelGGL((mlp_forward_stream_kernel<16>), dim3(gx, count), dim3(16 * 64), 0, stream, a);
     else hipLaunchKernelGGL((mlp_forward_stream_kernel<12>), dim3(gx, count), dim3(12 * 64), 0, stream, a);
     RPO_LAUNCH_CHECK();
