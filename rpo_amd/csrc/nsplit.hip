@@ -1823,8 +1823,14 @@ MlpGrad grad_dev(const rpo_mlp_grad* g) {
     return MlpGrad{g->Ws, g->bs, g->Wa, g->ba, g->W0, g->b0, g->W1, g->b1, g->W1b, g->b1b};
 }
 
-// Resolve and validate the parts of rpo_split_update a stage needs.  need: bit 0 policy net, 1 critics, 2 target
-// critics, 3 critic gradients, 4 actor gradients, 5 online actor (policy step).
+// What a stage asks to_args for
+enum : unsigned {
+    kNeedPolicy = 1u,                       // the network that proposes the next actions: actor (twin) or actor_target
+    kNeedCritics = 2u, kNeedTargets = 4u, kNeedCriticGrads = 8u, kNeedActorGrad = 16u,
+    kNeedActor = 32u,                       // the online actor (policy step, _pol roles, riding rollout)
+};
+
+// Resolve and validate the parts of rpo_split_update a stage needs (need: kNeed*).
 int to_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& c) {
     if (!u) return RPO_ERR_NULL;
     if (u->batch <= 0 || u->batch > kBwdMaxB || (u->env != 0 && u->env != 1)) return RPO_ERR_ARG;
@@ -1841,21 +1847,21 @@ int to_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& 
         m = to_dev(h);
         return (split_ok(m) && m.S == S && m.A == 2 && m.n_out == 1) ? 0 : (int)RPO_ERR_ARG;
     };
-    if (need & 1u) {
+    if (need & kNeedPolicy) {
         if (int e = u->twin ? ok_actor(u->actor, a.actor) : ok_actor(u->actor_target, a.actor_target)) return e;
     }
-    if (need & 32u) {
+    if (need & kNeedActor) {
         if (int e = ok_actor(u->actor, a.actor)) return e;
     }
-    if (need & 2u) {
+    if (need & kNeedCritics) {
         if (int e = ok_critic(u->critic1, a.critic[0])) return e;
         if (K == 2) if (int e = ok_critic(u->critic2, a.critic[1])) return e;
     }
-    if (need & 4u) {
+    if (need & kNeedTargets) {
         if (int e = ok_critic(u->critic_target1, a.critic_target[0])) return e;
         if (K == 2) if (int e = ok_critic(u->critic_target2, a.critic_target[1])) return e;
     }
-    if (need & 8u) {
+    if (need & kNeedCriticGrads) {
         if (!u->critic1_grad || (K == 2 && !u->critic2_grad)) return RPO_ERR_NULL;
         a.critic_grad[0] = grad_dev(u->critic1_grad);
         a.critic_grad[1] = grad_dev(u->critic2_grad);
@@ -1864,7 +1870,7 @@ int to_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& 
             if (!g.Ws || !g.bs || !g.Wa || !g.ba || !g.W0 || !g.b0 || !g.W1 || !g.b1) return RPO_ERR_NULL;
         }
     }
-    if (need & 16u) {
+    if (need & kNeedActorGrad) {
         if (!u->actor_grad) return RPO_ERR_NULL;
         a.actor_grad = grad_dev(u->actor_grad);
         const MlpGrad& g = a.actor_grad;
@@ -1897,240 +1903,109 @@ int to_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& 
     return 0;
 }
 
-}  // namespace
+// ---- the stages' kernels
+// A stage's kernel: its CartSafe and its SpringPendulum instantiation
+template <class C, class P> struct EnvKernels { C* cart; P* pend; };
+template <class C, class P> constexpr EnvKernels<C, P> env_kernels(C* cart, P* pend) { return EnvKernels<C, P>{cart, pend}; }
 
-extern "C" {
+// Every instantiation the stages launch, named once.  The compiler emits the kernels in the order of their first use, this
+// list: keep it, the code object's layout follows it.
+const auto kFwdA = env_kernels(split_critic_fwd_a_kernel<CartRow>, split_critic_fwd_a_kernel<PendRow>);
+const auto kFwdB = env_kernels(split_critic_fwd_b_kernel<CartRow, 1>, split_critic_fwd_b_kernel<PendRow, 0>);
+const auto kFront = split_critic_front_kernel<CartRow>;
+const auto kMid = split_critic_mid_kernel<PendRow>;
+const auto kPfront = split_critic_pfront_kernel<PendRow>;
+const auto kFwdBPol = env_kernels(split_critic_fwd_b_pol_kernel<CartRow, 1>, split_critic_fwd_b_pol_kernel<PendRow, 0>);
+const auto kProjectTall = split_pend_head_project_kernel<1>;
+const auto kBwdA = env_kernels(split_critic_bwd_a_kernel<CartRow>, split_critic_bwd_a_kernel<PendRow>);
+const auto kBwdB = env_kernels(split_critic_bwd_b_kernel<CartRow>, split_critic_bwd_b_kernel<PendRow>);
+const auto kFwdARide = env_kernels(split_critic_fwd_a_ride_kernel<CartRow>, split_critic_fwd_a_ride_kernel<PendRow>);
+const auto kFwdBRide = env_kernels(split_critic_fwd_b_ride_kernel<CartRow, 1>, split_critic_fwd_b_ride_kernel<PendRow, 0>);
+const auto kFrontRide = split_critic_front_ride_kernel<CartRow>;
+const auto kPfrontRide = split_critic_pfront_ride_kernel<PendRow>;
+const auto kMidRide = split_critic_mid_ride_kernel<PendRow>;
+const auto kBwdBRide = env_kernels(split_critic_bwd_b_ride_kernel<CartRow>, split_critic_bwd_b_ride_kernel<PendRow>);
+const auto kPolicyA = env_kernels(split_policy_a_kernel<CartRow>, split_policy_a_kernel<PendRow>);
+const auto kPolicyB = env_kernels(split_policy_b_kernel<CartPol>, split_policy_b_kernel<PendPol>);
+const auto kPolicyFront = env_kernels(split_policy_front_kernel<CartPol>, split_policy_front_kernel<PendPol>);
+const auto kPolicyD = env_kernels(split_policy_d_kernel<CartPol>, split_policy_d_kernel<PendPol>);
+const auto kPolicyE = env_kernels(split_policy_e_kernel<CartPol>, split_policy_e_kernel<PendPol>);
 
-int rpo_split_critic_fwd_a(const rpo_split_update* u, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 1u | 2u, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.rows || !a.batch_out || !a.ctrl || !a.part_pi || a.cap_steps <= 0 || a.n_envs <= 0) return RPO_ERR_NULL;
-    if (a.rollout_ctrl && a.rollout_stats && a.rollout_stats_cap <= 0) return RPO_ERR_ARG;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k]) return RPO_ERR_NULL;
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, 1 + K);
-    if (u->env == 0) hipLaunchKernelGGL(split_critic_fwd_a_kernel<CartRow>, grid, dim3(kNsThreads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(split_critic_fwd_a_kernel<PendRow>, grid, dim3(kNsThreads), 0, (hipStream_t)stream, a);
-    RPO_LAUNCH_CHECK();
-    return 0;
+// Launch and answer like RPO_LAUNCH_CHECK: 0 or the hipError_t
+template <class... P, class... A>
+int launch(void (*kernel)(P...), dim3 grid, int threads, size_t lds, void* stream, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, (hipStream_t)stream, args...);
+    return (int)hipGetLastError();
 }
 
-int rpo_split_critic_fwd_b(const rpo_split_update* u, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, (u && u->env == 0 ? 1u : 0u) | 4u, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.batch_out || !a.ctrl) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_qn[k]) return RPO_ERR_NULL;
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, K);
-    if (u->env == 0) {
-        if (!a.part_pi || (a.twin && !a.logp) || a.max_steps < 0) return RPO_ERR_NULL;
-        hipLaunchKernelGGL((split_critic_fwd_b_kernel<CartRow, 1>), grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c);
-    } else {
-        if (!a.next_actions) return RPO_ERR_NULL;
-        hipLaunchKernelGGL((split_critic_fwd_b_kernel<PendRow, 0>), grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c);
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+// The env dispatch: the CartSafe (env 0) or the SpringPendulum instantiation of a stage's kernel
+template <class C, class P, class... A>
+int launch_env(const EnvKernels<C, P>& k, int env, dim3 grid, int threads, void* stream, const A&... args) {
+    return env == 0 ? launch(k.cart, grid, threads, 0, stream, args...) : launch(k.pend, grid, threads, 0, stream, args...);
 }
 
-int rpo_xcc_probe(int gx, int gy, int gz, int threads, int* out, void* stream) {
-    if (gx <= 0 || gy <= 0 || gz <= 0 || threads <= 0 || threads > 1024) return RPO_ERR_ARG;
-    if (!out) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(xcc_probe_kernel, dim3(gx, gy, gz), dim3(threads), 0, (hipStream_t)stream, out);
-    RPO_LAUNCH_CHECK();
-    return 0;
+// ---- geometry
+int critics(const SplitArgs& a) { return a.twin ? 2 : 1; }
+int tiles(int B) { return (B + kRows - 1) / kRows; }
+dim3 slab_grid(const SplitArgs& a, int planes) { return dim3(kNsGroups, tiles(a.B), planes); }
+
+// planes behind a stage's own for the rider's lanes [lane_begin, lane_end): wg_tiles lane tiles per workgroup
+int ride_planes(const rpo_rollout_rider* r, int T, int wg_tiles) {
+    const int lane_wgs = ((r->lane_end - r->lane_begin + kRows - 1) / kRows + wg_tiles - 1) / wg_tiles;
+    return (lane_wgs + T - 1) / T;
 }
 
-int rpo_hw_probe(int gx, int gy, int gz, int threads, int lds_bytes, int spin, int* out, void* stream) {
-    if (gx <= 0 || gy <= 0 || gz <= 0 || threads <= 0 || threads > 1024 || lds_bytes < 4 || lds_bytes > 65536 || spin < 0) return RPO_ERR_ARG;
-    if (!out) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(hw_probe_kernel, dim3(gx, gy, gz), dim3(threads), lds_bytes, (hipStream_t)stream, out, spin);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-static int front_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& c) {
-    if (!u) return RPO_ERR_NULL;
-    if (u->env != 0) return RPO_ERR_ARG;
-    if (int e = to_args(u, 1u | 2u | 4u | need, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.rows || !a.batch_out || !a.ctrl || !a.part_pi || !a.tile_sync || a.cap_steps <= 0 || a.n_envs <= 0) return RPO_ERR_NULL;
-    if (a.rollout_ctrl && a.rollout_stats && a.rollout_stats_cap <= 0) return RPO_ERR_ARG;
-    if ((a.twin && !a.logp) || a.max_steps < 0 || !a.loss_partial) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k] || !a.part_qn[k] || !a.dq[k] || !a.dx0[k]) return RPO_ERR_NULL;
-    return 0;
-}
-
-static int front_launch(const rpo_split_update* u, int pol, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = front_args(u, pol ? 32u : 0u, a, c)) return e;
-    if (pol) {
-        if (u->shared_embedding) return RPO_ERR_ARG;              // the critic step would change the policy's first layer
-        if (!a.part_pol || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
-    }
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, 1 + 3 * (a.twin ? 2 : 1) + pol);
-    hipLaunchKernelGGL(split_critic_front_kernel<CartRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c, pol);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_critic_front(const rpo_split_update* u, void* stream) { return front_launch(u, 0, stream); }
-int rpo_split_critic_front_pol(const rpo_split_update* u, void* stream) { return front_launch(u, 1, stream); }
-
-static int mid_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& c) {
-    if (!u) return RPO_ERR_NULL;
-    if (u->env != 1) return RPO_ERR_ARG;
-    if (int e = to_args(u, 2u | 4u | need, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.batch_out || !a.ctrl || !a.next_actions || !a.tile_sync || !a.loss_partial || (a.twin && !a.logp)) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k] || !a.part_qn[k] || !a.dq[k] || !a.dx0[k]) return RPO_ERR_NULL;
-    return 0;
-}
-
-static int mid_launch(const rpo_split_update* u, int pol, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = mid_args(u, pol ? 32u : 0u, a, c)) return e;
-    if (pol) {
-        if (u->shared_embedding) return RPO_ERR_ARG;
-        if (!a.part_pol || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
-    }
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, 2 * (a.twin ? 2 : 1) + pol);
-    hipLaunchKernelGGL(split_critic_mid_kernel<PendRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c, pol);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-// SpringPendulum: fwd_a + projection + fwd_b + bwd_a as one launch (pfront_role)
-static int pfront_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& c) {
-    if (!u) return RPO_ERR_NULL;
-    if (u->env != 1) return RPO_ERR_ARG;
-    if (int e = to_args(u, 1u | 2u | 4u | need, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.rows || !a.batch_out || !a.ctrl || !a.part_pi || !a.next_actions || !a.tile_sync || !a.loss_partial || !u->proj_ws ||
-        (a.twin && !a.logp))
-        return RPO_ERR_NULL;
-    if (a.cap_steps <= 0 || a.n_envs <= 0 || a.B > 256 || a.max_steps < 0 || a.max_steps > kPmMaxSteps) return RPO_ERR_ARG;
-    if (((uintptr_t)u->proj_ws & 127u) || u->proj_store_mode < 0 || u->proj_store_mode > 2) return RPO_ERR_ARG;
-    if (a.rollout_ctrl && a.rollout_stats && a.rollout_stats_cap <= 0) return RPO_ERR_ARG;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k] || !a.part_qn[k] || !a.dq[k] || !a.dx0[k]) return RPO_ERR_NULL;
-    return 0;
-}
-
-static int pfront_launch(const rpo_split_update* u, int pol, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = pfront_args(u, pol ? 32u : 0u, a, c)) return e;
-    if (pol) {
-        if (u->shared_embedding) return RPO_ERR_ARG;
-        if (!a.part_pol || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
-    }
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, 2 + 3 * (a.twin ? 2 : 1) + pol);
-    hipLaunchKernelGGL(split_critic_pfront_kernel<PendRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c, pol, u->proj_ws,
-                       u->proj_store_mode);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_critic_pfront(const rpo_split_update* u, void* stream) { return pfront_launch(u, 0, stream); }
-int rpo_split_critic_pfront_pol(const rpo_split_update* u, void* stream) { return pfront_launch(u, 1, stream); }
-
-int rpo_split_critic_mid(const rpo_split_update* u, void* stream) { return mid_launch(u, 0, stream); }
-int rpo_split_critic_mid_pol(const rpo_split_update* u, void* stream) { return mid_launch(u, 1, stream); }
-
-int rpo_split_critic_fwd_b_pol(const rpo_split_update* u, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, (u && u->env == 0 ? 1u : 0u) | 4u | 32u, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (u->shared_embedding) return RPO_ERR_ARG;                  // the critic step would change the policy's first layer
-    if (!a.batch_out || !a.ctrl || !a.part_pol || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_qn[k]) return RPO_ERR_NULL;
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, K + 1);
-    if (u->env == 0) {
-        if (!a.part_pi || (a.twin && !a.logp) || a.max_steps < 0) return RPO_ERR_NULL;
-        hipLaunchKernelGGL((split_critic_fwd_b_pol_kernel<CartRow, 1>), grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c);
-    } else {
-        if (!a.next_actions) return RPO_ERR_NULL;
-        hipLaunchKernelGGL((split_critic_fwd_b_pol_kernel<PendRow, 0>), grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c);
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_pend_head_project(const rpo_split_update* u, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 1u, a, c)) return e;
-    if (u->env != 1 || a.max_steps < 0) return RPO_ERR_ARG;
-    if (!a.batch_out || !a.ctrl || !a.part_pi || !a.next_actions || (a.twin && !a.logp)) return RPO_ERR_NULL;
-    const size_t lds = ((size_t)a.B + 4) * sizeof(float);
-    static_assert(kPmWords == RPO_PROJ_WS_WORDS && kPmGaveUp == RPO_PROJ_WS_GAVE_UP, "workspace layout");
-    if (u->proj_ws && a.B <= 256 && a.max_steps <= kPmMaxSteps) {
-        if (((uintptr_t)u->proj_ws & 127u) || u->proj_store_mode < 0 || u->proj_store_mode > 2) return RPO_ERR_ARG;
-        hipLaunchKernelGGL(split_pend_head_project_multi_kernel, dim3(8 * ((a.B + kPmRows - 1) / kPmRows)), dim3(kThreads), 0,
-                           (hipStream_t)stream, a, u->proj_ws, u->proj_store_mode, (const float*)nullptr, (const float*)nullptr, 0);
-    } else if (a.B <= 256) {
-        hipLaunchKernelGGL(split_pend_head_project_wide_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-    } else {
-        const int threads = (a.B + RPO_WAVE - 1) / RPO_WAVE * RPO_WAVE;
-        hipLaunchKernelGGL(split_pend_head_project_kernel<1>, dim3(1), dim3(threads), lds, (hipStream_t)stream, a);
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_pendulum_project_batchref_ws(int n, const float* obs, int obs_stride, const float* ap, float* action, int* iters_out,
-                                     int max_steps, float corr_lr, float corr_eps, float corr_momentum,
-                                     unsigned long long* ws, int store_mode, void* stream) {
-    if (n <= 0 || n > 256 || max_steps < 0 || max_steps > kPmMaxSteps || obs_stride < RPO_PEND_OBS_DIM) return RPO_ERR_ARG;
-    if (!obs || !ap || !action || !ws) return RPO_ERR_NULL;
-    if (((uintptr_t)ws & 127u) || store_mode < 0 || store_mode > 2) return RPO_ERR_ARG;
-    SplitArgs a{};
-    a.B = n; a.next_actions = action; a.proj_iters = iters_out; a.max_steps = max_steps; a.corr_lr = corr_lr;
-    a.corr_eps = corr_eps; a.corr_momentum = corr_momentum;
-    hipLaunchKernelGGL(split_pend_head_project_multi_kernel, dim3(8 * ((n + kPmRows - 1) / kPmRows)), dim3(kThreads), 0, (hipStream_t)stream,
-                       a, ws, store_mode, ap, obs, obs_stride);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_critic_bwd_a(const rpo_split_update* u, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 2u | 4u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    if (!a.batch_out || !a.loss_partial || (a.twin && !a.logp)) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.part_qn[k] || !a.x0[k] || !a.h1[k] || !a.dq[k] || !a.dx0[k]) return RPO_ERR_NULL;
-    const int grid = K * T * kNsGroups;
-    if (u->env == 0) hipLaunchKernelGGL(split_critic_bwd_a_kernel<CartRow>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(split_critic_bwd_a_kernel<PendRow>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, a);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_critic_bwd_b(const rpo_split_update* u, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 2u | 8u, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.batch_out) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.dx0[k] || !a.dq[k] || !a.x0[k] || !a.h1[k]) return RPO_ERR_NULL;
+// bwd_b's own blocks: weight roles, first-layer blocks, and one for the bookkeeping if any is asked for
+int bwd_b_blocks(const SplitArgs& a) {
     const Mlp& m = a.critic[0];
-    const int blocks = kWeightBlocks + mlp_fl_blocks(m.E * (m.S + 1 + m.A + 1)) + ((a.prep_step || a.clock_out || a.updates_out) ? 1 : 0);
-    if (u->env == 0) hipLaunchKernelGGL(split_critic_bwd_b_kernel<CartRow>, dim3(blocks, K), dim3(kThreads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(split_critic_bwd_b_kernel<PendRow>, dim3(blocks, K), dim3(kThreads), 0, (hipStream_t)stream, a);
-    RPO_LAUNCH_CHECK();
+    return kWeightBlocks + mlp_fl_blocks(m.E * (m.S + 1 + m.A + 1)) + ((a.prep_step || a.clock_out || a.updates_out) ? 1 : 0);
+}
+
+// ---- predicates the stages share
+// the per-critic buffers a stage reads or writes
+enum : unsigned {
+    kBufQ = 1u, kBufSaved = 2u /* x0, h1 */, kBufQn = 4u, kBufDq = 8u, kBufDx0 = 16u,
+    kBufFwd = kBufQ | kBufSaved, kBufBwd = kBufSaved | kBufDq | kBufDx0, kBufAll = kBufFwd | kBufQn | kBufBwd,
+};
+bool critic_bufs(const SplitArgs& a, unsigned set) {
+    for (int k = 0; k < critics(a); ++k)
+        if (((set & kBufQ) && !a.part_q[k]) || ((set & kBufSaved) && (!a.x0[k] || !a.h1[k])) || ((set & kBufQn) && !a.part_qn[k]) ||
+            ((set & kBufDq) && !a.dq[k]) || ((set & kBufDx0) && !a.dx0[k]))
+            return false;
+    return true;
+}
+
+// the fused sampling's inputs; an empty ring or no lanes answer size_code (RPO_ERR_ARG in pfront, RPO_ERR_NULL elsewhere)
+int sample_check(const SplitArgs& a, int size_code) {
+    if (!a.rows) return RPO_ERR_NULL;
+    if (a.cap_steps <= 0 || a.n_envs <= 0) return size_code;
+    if (a.rollout_ctrl && a.rollout_stats && a.rollout_stats_cap <= 0) return RPO_ERR_ARG;
     return 0;
 }
 
-}  // extern "C"
+// An entry point's flavour: alone, with the policy step's first role (_pol), or with a rollout riding on it (_ride)
+enum Variant { kPlain, kPol, kRide };
+unsigned actor_need(Variant v) { return v == kPlain ? 0u : kNeedActor; }
 
-// ---- riding rollout stages
-namespace {
+// what a _pol entry adds, behind the checks of its stage
+int pol_check(const rpo_split_update* u, const SplitArgs& a, Variant v) {
+    if (v != kPol) return 0;
+    if (u->shared_embedding) return RPO_ERR_ARG;                  // the critic step would change the policy's first layer
+    return (a.part_pol && a.x0_a && a.h1_a) ? 0 : (int)RPO_ERR_NULL;
+}
 
+// The multi-workgroup projection: what it handles, and the rule for its workspace
+bool proj_multi_fits(int B, int max_steps) { return B <= 256 && max_steps <= kPmMaxSteps; }
+bool proj_ws_ok(const unsigned long long* ws, int store_mode) { return !((uintptr_t)ws & 127u) && store_mode >= 0 && store_mode <= 2; }
+
+int project_multi(const SplitArgs& a, unsigned long long* ws, int store_mode, const float* ap, const float* obs, int obs_stride,
+                  void* stream) {
+    if (!proj_ws_ok(ws, store_mode)) return RPO_ERR_ARG;
+    return launch(split_pend_head_project_multi_kernel, dim3(8 * ((a.B + kPmRows - 1) / kPmRows)), kThreads, 0, stream, a, ws,
+                  store_mode, ap, obs, obs_stride);
+}
+
+// ---- riding rollout
 int ride_check(const rpo_split_update* u, const rpo_rollout_rider* r) {
     if (!u || !r) return RPO_ERR_NULL;
     if (r->n_envs <= 0 || r->max_episode_steps <= 0 || r->max_steps < 0) return RPO_ERR_ARG;
@@ -2140,6 +2015,21 @@ int ride_check(const rpo_split_update* u, const rpo_rollout_rider* r) {
     if ((r->gauss != 0) != (u->twin != 0)) return RPO_ERR_ARG;          // u->actor is the rollout policy
     if (u->shared_embedding) return RPO_ERR_ARG;                         // the critic step would change the policy under the rollout
     return 0;
+}
+
+// forward stages: lanes [lane_begin, lane_end) of this launch
+int ride_range(const rpo_rollout_rider* r) {
+    if (r->lane_begin < 0 || r->lane_begin % kRows || r->lane_end < r->lane_begin || r->lane_end > r->n_envs ||
+        (r->lane_end % kRows && r->lane_end != r->n_envs))
+        return RPO_ERR_ARG;
+    return 0;
+}
+
+// A _ride entry's first checks, before anything about its stage
+int ride_checks(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, bool lanes) {
+    if (v != kRide) return 0;
+    if (int e = ride_check(u, r)) return e;
+    return lanes ? ride_range(r) : 0;
 }
 
 void ride_env(const rpo_rollout_rider* r, RideArgs<CartEnv>& o) {
@@ -2160,224 +2050,224 @@ void ride_env(const rpo_rollout_rider* r, RideArgs<PendEnv>& o) {
                                     r->viol_thresh, (uint64_t)r->seed, (uint32_t)r->env_id_base};
 }
 
-template <class ENV>
-RideArgs<ENV> ride_args(const SplitArgs& a, const rpo_rollout_rider* r) {
-    RideArgs<ENV> o{};
-    o.actor = a.actor; o.scale = r->scale; o.base = r->base; o.gauss = r->gauss ? 1 : 0; o.n = r->n_envs; o.part = r->part;
-    o.lane0 = r->lane_begin; o.lane1 = r->lane_end; o.defer_clock = r->defer_clock ? 1 : 0;
-    ride_env(r, o);
-    return o;
+// The rider as a launch argument: becomes the RideArgs of the env the launched kernel was instantiated for
+struct Ride {
+    const SplitArgs& a; const rpo_rollout_rider* r;
+    template <class ENV> operator RideArgs<ENV>() const {
+        RideArgs<ENV> o{};
+        o.actor = a.actor; o.scale = r->scale; o.base = r->base; o.gauss = r->gauss ? 1 : 0; o.n = r->n_envs; o.part = r->part;
+        o.lane0 = r->lane_begin; o.lane1 = r->lane_end; o.defer_clock = r->defer_clock ? 1 : 0;
+        ride_env(r, o);
+        return o;
+    }
+};
+
+// ---- the stage families: one body each; the exported symbols below forward to them
+int fwd_a(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, void* stream) {
+    SplitArgs a; CartConsts c;
+    if (int e = ride_checks(u, r, v, true)) return e;
+    if (int e = to_args(u, kNeedPolicy | kNeedCritics | actor_need(v), a, c)) return e;
+    if (!a.batch_out || !a.ctrl || !a.part_pi) return RPO_ERR_NULL;
+    if (int e = sample_check(a, RPO_ERR_NULL)) return e;
+    if (!critic_bufs(a, kBufFwd)) return RPO_ERR_NULL;
+    const int planes = 1 + critics(a);
+    if (v == kRide)                                               // two lane tiles per workgroup
+        return launch_env(kFwdARide, u->env, slab_grid(a, planes + ride_planes(r, tiles(a.B), 2)), kThreads, stream, a, Ride{a, r});
+    return launch_env(kFwdA, u->env, slab_grid(a, planes), kNsThreads, stream, a);
+}
+
+int fwd_b(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, void* stream) {
+    SplitArgs a; CartConsts c;
+    if (int e = ride_checks(u, r, v, true)) return e;
+    if (int e = to_args(u, (u && u->env == 0 ? kNeedPolicy : 0u) | kNeedTargets | actor_need(v), a, c)) return e;
+    if (int e = pol_check(u, a, v)) return e;
+    if (!a.batch_out || !a.ctrl || !critic_bufs(a, kBufQn)) return RPO_ERR_NULL;
+    if (u->env == 0 ? (!a.part_pi || (a.twin && !a.logp) || a.max_steps < 0) : !a.next_actions) return RPO_ERR_NULL;
+    const int planes = critics(a);
+    if (v == kRide)                                               // one lane tile per workgroup
+        return launch_env(kFwdBRide, u->env, slab_grid(a, planes + ride_planes(r, tiles(a.B), 1)), kNsThreads, stream, a, c, Ride{a, r});
+    if (v == kPol) return launch_env(kFwdBPol, u->env, slab_grid(a, planes + 1), kNsThreads, stream, a, c);
+    return launch_env(kFwdB, u->env, slab_grid(a, planes), kNsThreads, stream, a, c);
+}
+
+// front, mid and pfront serve one env, and say so before they look at the struct
+int fused_args(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, int env, unsigned need, SplitArgs& a, CartConsts& c) {
+    if (int e = ride_checks(u, r, v, true)) return e;
+    if (!u) return RPO_ERR_NULL;
+    if (u->env != env) return RPO_ERR_ARG;
+    return to_args(u, need | actor_need(v), a, c);
+}
+
+// their grid: the stage's own planes, then the _pol role's plane or the rider's (two lane tiles per workgroup)
+dim3 fused_grid(const SplitArgs& a, const rpo_rollout_rider* r, Variant v, int planes) {
+    return slab_grid(a, planes + (v == kRide ? ride_planes(r, tiles(a.B), 2) : (int)(v == kPol)));
+}
+
+// CartSafe: fwd_a + fwd_b + bwd_a as one launch
+int front(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, void* stream) {
+    SplitArgs a; CartConsts c;
+    if (int e = fused_args(u, r, v, 0, kNeedPolicy | kNeedCritics | kNeedTargets, a, c)) return e;
+    if (!a.batch_out || !a.ctrl || !a.part_pi || !a.tile_sync) return RPO_ERR_NULL;
+    if (int e = sample_check(a, RPO_ERR_NULL)) return e;
+    if ((a.twin && !a.logp) || a.max_steps < 0 || !a.loss_partial || !critic_bufs(a, kBufAll)) return RPO_ERR_NULL;
+    if (int e = pol_check(u, a, v)) return e;
+    const dim3 grid = fused_grid(a, r, v, 1 + 3 * critics(a));
+    if (v == kRide) return launch(kFrontRide, grid, kThreads, 0, stream, a, c, Ride{a, r});
+    return launch(kFront, grid, kThreads, 0, stream, a, c, (int)(v == kPol));
+}
+
+// SpringPendulum: fwd_b + bwd_a as one launch, behind the projection
+int mid(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, void* stream) {
+    SplitArgs a; CartConsts c;
+    if (int e = fused_args(u, r, v, 1, kNeedCritics | kNeedTargets, a, c)) return e;
+    if (!a.batch_out || !a.ctrl || !a.next_actions || !a.tile_sync || !a.loss_partial || (a.twin && !a.logp) || !critic_bufs(a, kBufAll))
+        return RPO_ERR_NULL;
+    if (int e = pol_check(u, a, v)) return e;
+    const dim3 grid = fused_grid(a, r, v, 2 * critics(a));
+    if (v == kRide) return launch(kMidRide, grid, kThreads, 0, stream, a, c, Ride{a, r});
+    return launch(kMid, grid, kThreads, 0, stream, a, c, (int)(v == kPol));
+}
+
+// SpringPendulum: fwd_a + projection + fwd_b + bwd_a as one launch (pfront_role)
+int pfront(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, void* stream) {
+    SplitArgs a; CartConsts c;
+    if (int e = fused_args(u, r, v, 1, kNeedPolicy | kNeedCritics | kNeedTargets, a, c)) return e;
+    if (!a.batch_out || !a.ctrl || !a.part_pi || !a.next_actions || !a.tile_sync || !a.loss_partial || !u->proj_ws || (a.twin && !a.logp))
+        return RPO_ERR_NULL;
+    if (int e = sample_check(a, RPO_ERR_ARG)) return e;
+    if (a.max_steps < 0 || !proj_multi_fits(a.B, a.max_steps) || !proj_ws_ok(u->proj_ws, u->proj_store_mode)) return RPO_ERR_ARG;
+    if (!critic_bufs(a, kBufAll)) return RPO_ERR_NULL;
+    if (int e = pol_check(u, a, v)) return e;
+    const dim3 grid = fused_grid(a, r, v, 2 + 3 * critics(a));
+    if (v == kRide) return launch(kPfrontRide, grid, kThreads, 0, stream, a, c, Ride{a, r}, u->proj_ws, u->proj_store_mode);
+    return launch(kPfront, grid, kThreads, 0, stream, a, c, (int)(v == kPol), u->proj_ws, u->proj_store_mode);
+}
+
+int bwd_b(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, void* stream) {
+    SplitArgs a; CartConsts c;
+    if (int e = ride_checks(u, r, v, false)) return e;
+    if (int e = to_args(u, kNeedCritics | kNeedCriticGrads | actor_need(v), a, c)) return e;
+    if (!a.batch_out || !critic_bufs(a, kBufBwd)) return RPO_ERR_NULL;
+    const int own = bwd_b_blocks(a);
+    if (v == kRide)                                               // the step of every lane behind the stage's own blocks
+        return launch_env(kBwdBRide, u->env, dim3(own + (r->n_envs + kThreads - 1) / kThreads, critics(a)), kThreads, stream, a, c,
+                          Ride{a, r}, own);
+    return launch_env(kBwdB, u->env, dim3(own, critics(a)), kThreads, stream, a);
+}
+
+// policy_b alone, or as the fused policy launch: [policy_a +] policy_b + policy_c + the first half of policy_d
+int policy_b(const rpo_split_update* u, int fused, int with_a, void* stream) {
+    SplitArgs a; CartConsts c;
+    if (int e = to_args(u, kNeedActor | kNeedCritics, a, c)) return e;
+    if (!a.batch_out || !a.ctrl || (!a.part_pi && !a.part_pol) || !a.nu || !a.noise_out || !a.actions || !a.g_act || !a.lag_partial ||
+        (a.twin ? (!a.raw || !a.logp) : !a.ap_det) || !critic_bufs(a, kBufFwd))
+        return RPO_ERR_NULL;
+    if (!fused) return launch_env(kPolicyB, u->env, slab_grid(a, critics(a)), kNsThreads, stream, a, c);
+    if (!a.tile_sync || !a.da_part || !critic_bufs(a, kBufDx0) || !a.dx0_a || !a.dout || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
+    return launch_env(kPolicyFront, u->env, slab_grid(a, with_a + 2 * critics(a) + 1), kThreads, stream, a, c, with_a);
 }
 
 }  // namespace
 
 extern "C" {
 
-// forward stages: lanes [lane_begin, lane_end) of this launch
-static int ride_range(const rpo_rollout_rider* r) {
-    if (r->lane_begin < 0 || r->lane_begin % kRows || r->lane_end < r->lane_begin || r->lane_end > r->n_envs ||
-        (r->lane_end % kRows && r->lane_end != r->n_envs))
-        return RPO_ERR_ARG;
-    return 0;
-}
+int rpo_split_critic_fwd_a(const rpo_split_update* u, void* stream) { return fwd_a(u, nullptr, kPlain, stream); }
+int rpo_split_critic_fwd_a_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) { return fwd_a(u, r, kRide, stream); }
 
-int rpo_split_critic_fwd_a_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) {
-    if (int e = ride_check(u, r)) return e;
-    if (int e = ride_range(r)) return e;
+int rpo_split_critic_fwd_b(const rpo_split_update* u, void* stream) { return fwd_b(u, nullptr, kPlain, stream); }
+int rpo_split_critic_fwd_b_pol(const rpo_split_update* u, void* stream) { return fwd_b(u, nullptr, kPol, stream); }
+int rpo_split_critic_fwd_b_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) { return fwd_b(u, r, kRide, stream); }
+
+int rpo_split_critic_front(const rpo_split_update* u, void* stream) { return front(u, nullptr, kPlain, stream); }
+int rpo_split_critic_front_pol(const rpo_split_update* u, void* stream) { return front(u, nullptr, kPol, stream); }
+int rpo_split_critic_front_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) { return front(u, r, kRide, stream); }
+
+int rpo_split_critic_mid(const rpo_split_update* u, void* stream) { return mid(u, nullptr, kPlain, stream); }
+int rpo_split_critic_mid_pol(const rpo_split_update* u, void* stream) { return mid(u, nullptr, kPol, stream); }
+int rpo_split_critic_mid_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) { return mid(u, r, kRide, stream); }
+
+int rpo_split_critic_pfront(const rpo_split_update* u, void* stream) { return pfront(u, nullptr, kPlain, stream); }
+int rpo_split_critic_pfront_pol(const rpo_split_update* u, void* stream) { return pfront(u, nullptr, kPol, stream); }
+int rpo_split_critic_pfront_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) { return pfront(u, r, kRide, stream); }
+
+int rpo_split_critic_bwd_b(const rpo_split_update* u, void* stream) { return bwd_b(u, nullptr, kPlain, stream); }
+int rpo_split_critic_bwd_b_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) { return bwd_b(u, r, kRide, stream); }
+
+int rpo_split_policy_b(const rpo_split_update* u, void* stream) { return policy_b(u, 0, 0, stream); }
+int rpo_split_policy_front(const rpo_split_update* u, void* stream) { return policy_b(u, 1, 1, stream); }
+int rpo_split_policy_front_bc(const rpo_split_update* u, void* stream) { return policy_b(u, 1, 0, stream); }
+
+int rpo_split_critic_bwd_a(const rpo_split_update* u, void* stream) {
     SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 1u | 2u | 32u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    if (!a.rows || !a.batch_out || !a.ctrl || !a.part_pi || a.cap_steps <= 0 || a.n_envs <= 0) return RPO_ERR_NULL;
-    if (a.rollout_ctrl && a.rollout_stats && a.rollout_stats_cap <= 0) return RPO_ERR_ARG;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k]) return RPO_ERR_NULL;
-    const int lane_wgs = ((r->lane_end - r->lane_begin + kRows - 1) / kRows + 1) / 2;      // two lane tiles per workgroup
-    const dim3 grid(kNsGroups, T, 1 + K + (lane_wgs + T - 1) / T);
-    if (u->env == 0)
-        hipLaunchKernelGGL(split_critic_fwd_a_ride_kernel<CartRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, ride_args<CartEnv>(a, r));
-    else
-        hipLaunchKernelGGL(split_critic_fwd_a_ride_kernel<PendRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, ride_args<PendEnv>(a, r));
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = to_args(u, kNeedCritics | kNeedTargets, a, c)) return e;
+    if (!a.batch_out || !a.loss_partial || (a.twin && !a.logp) || !critic_bufs(a, kBufAll)) return RPO_ERR_NULL;
+    return launch_env(kBwdA, u->env, dim3(critics(a) * tiles(a.B) * kNsGroups), kThreads, stream, a);
 }
 
-int rpo_split_critic_fwd_b_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) {
-    if (int e = ride_check(u, r)) return e;
-    if (int e = ride_range(r)) return e;
+int rpo_split_pend_head_project(const rpo_split_update* u, void* stream) {
     SplitArgs a; CartConsts c;
-    if (int e = to_args(u, (u->env == 0 ? 1u : 0u) | 4u | 32u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    if (!a.batch_out || !a.ctrl) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_qn[k]) return RPO_ERR_NULL;
-    const int lane_wgs = (r->lane_end - r->lane_begin + kRows - 1) / kRows;
-    const dim3 grid(kNsGroups, T, K + (lane_wgs + T - 1) / T);
-    if (u->env == 0) {
-        if (!a.part_pi || (a.twin && !a.logp) || a.max_steps < 0) return RPO_ERR_NULL;
-        hipLaunchKernelGGL((split_critic_fwd_b_ride_kernel<CartRow, 1>), grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c,
-                           ride_args<CartEnv>(a, r));
-    } else {
-        if (!a.next_actions) return RPO_ERR_NULL;
-        hipLaunchKernelGGL((split_critic_fwd_b_ride_kernel<PendRow, 0>), grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c,
-                           ride_args<PendEnv>(a, r));
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = to_args(u, kNeedPolicy, a, c)) return e;
+    if (u->env != 1 || a.max_steps < 0) return RPO_ERR_ARG;
+    if (!a.batch_out || !a.ctrl || !a.part_pi || !a.next_actions || (a.twin && !a.logp)) return RPO_ERR_NULL;
+    static_assert(kPmWords == RPO_PROJ_WS_WORDS && kPmGaveUp == RPO_PROJ_WS_GAVE_UP, "workspace layout");
+    if (u->proj_ws && proj_multi_fits(a.B, a.max_steps))
+        return project_multi(a, u->proj_ws, u->proj_store_mode, nullptr, nullptr, 0, stream);
+    if (a.B <= 256) return launch(split_pend_head_project_wide_kernel, dim3(1), 1024, 0, stream, a);
+    return launch(kProjectTall, dim3(1), (a.B + RPO_WAVE - 1) / RPO_WAVE * RPO_WAVE, ((size_t)a.B + 4) * sizeof(float), stream, a);
 }
 
-int rpo_split_critic_front_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) {
-    if (int e = ride_check(u, r)) return e;
-    if (int e = ride_range(r)) return e;
-    SplitArgs a; CartConsts c;
-    if (int e = front_args(u, 32u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    const int lane_wgs = ((r->lane_end - r->lane_begin + kRows - 1) / kRows + 1) / 2;      // two lane tiles per workgroup
-    const dim3 grid(kNsGroups, T, 1 + 3 * K + (lane_wgs + T - 1) / T);
-    hipLaunchKernelGGL(split_critic_front_ride_kernel<CartRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c,
-                       ride_args<CartEnv>(a, r));
-    RPO_LAUNCH_CHECK();
-    return 0;
+int rpo_pendulum_project_batchref_ws(int n, const float* obs, int obs_stride, const float* ap, float* action, int* iters_out,
+                                     int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                                     unsigned long long* ws, int store_mode, void* stream) {
+    if (n <= 0 || max_steps < 0 || !proj_multi_fits(n, max_steps) || obs_stride < RPO_PEND_OBS_DIM) return RPO_ERR_ARG;
+    if (!obs || !ap || !action || !ws) return RPO_ERR_NULL;
+    SplitArgs a{};
+    a.B = n; a.next_actions = action; a.proj_iters = iters_out; a.max_steps = max_steps; a.corr_lr = corr_lr;
+    a.corr_eps = corr_eps; a.corr_momentum = corr_momentum;
+    return project_multi(a, ws, store_mode, ap, obs, obs_stride, stream);
 }
-
-int rpo_split_critic_pfront_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) {
-    if (int e = ride_check(u, r)) return e;
-    if (int e = ride_range(r)) return e;
-    SplitArgs a; CartConsts c;
-    if (int e = pfront_args(u, 32u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    const int lane_wgs = ((r->lane_end - r->lane_begin + kRows - 1) / kRows + 1) / 2;      // two lane tiles per workgroup
-    const dim3 grid(kNsGroups, T, 2 + 3 * K + (lane_wgs + T - 1) / T);
-    hipLaunchKernelGGL(split_critic_pfront_ride_kernel<PendRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c,
-                       ride_args<PendEnv>(a, r), u->proj_ws, u->proj_store_mode);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_critic_mid_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) {
-    if (int e = ride_check(u, r)) return e;
-    if (int e = ride_range(r)) return e;
-    SplitArgs a; CartConsts c;
-    if (int e = mid_args(u, 32u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    const int lane_wgs = ((r->lane_end - r->lane_begin + kRows - 1) / kRows + 1) / 2;      // two lane tiles per workgroup
-    const dim3 grid(kNsGroups, T, 2 * K + (lane_wgs + T - 1) / T);
-    hipLaunchKernelGGL(split_critic_mid_ride_kernel<PendRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c,
-                       ride_args<PendEnv>(a, r));
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_critic_bwd_b_ride(const rpo_split_update* u, const rpo_rollout_rider* r, void* stream) {
-    if (int e = ride_check(u, r)) return e;
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 2u | 8u | 32u, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.batch_out) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.dx0[k] || !a.dq[k] || !a.x0[k] || !a.h1[k]) return RPO_ERR_NULL;
-    const Mlp& m = a.critic[0];
-    const int own = kWeightBlocks + mlp_fl_blocks(m.E * (m.S + 1 + m.A + 1)) + ((a.prep_step || a.clock_out || a.updates_out) ? 1 : 0);
-    const dim3 grid(own + (r->n_envs + kThreads - 1) / kThreads, K);
-    if (u->env == 0)
-        hipLaunchKernelGGL(split_critic_bwd_b_ride_kernel<CartRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c,
-                           ride_args<CartEnv>(a, r), own);
-    else
-        hipLaunchKernelGGL(split_critic_bwd_b_ride_kernel<PendRow>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c,
-                           ride_args<PendEnv>(a, r), own);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-}  // extern "C"
-
-extern "C" {
 
 int rpo_split_policy_a(const rpo_split_update* u, void* stream) {
     SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 32u, a, c)) return e;
+    if (int e = to_args(u, kNeedActor, a, c)) return e;
     if (!a.batch_out || (!a.part_pi && !a.part_pol) || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows);
-    if (u->env == 0) hipLaunchKernelGGL(split_policy_a_kernel<CartRow>, grid, dim3(kNsThreads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(split_policy_a_kernel<PendRow>, grid, dim3(kNsThreads), 0, (hipStream_t)stream, a);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_env(kPolicyA, u->env, dim3(kNsGroups, tiles(a.B)), kNsThreads, stream, a);
 }
-
-int rpo_split_policy_b(const rpo_split_update* u, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 32u | 2u, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.batch_out || !a.ctrl || (!a.part_pi && !a.part_pol) || !a.nu || !a.noise_out || !a.actions || !a.g_act || !a.lag_partial) return RPO_ERR_NULL;
-    if (a.twin ? (!a.raw || !a.logp) : !a.ap_det) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k]) return RPO_ERR_NULL;
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, K);
-    if (u->env == 0) hipLaunchKernelGGL(split_policy_b_kernel<CartPol>, grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c);
-    else hipLaunchKernelGGL(split_policy_b_kernel<PendPol>, grid, dim3(kNsThreads), 0, (hipStream_t)stream, a, c);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-static int policy_front_launch(const rpo_split_update* u, int with_a, void* stream) {
-    SplitArgs a; CartConsts c;
-    if (!u) return RPO_ERR_NULL;
-    if (int e = to_args(u, 32u | 2u, a, c)) return e;
-    const int K = a.twin ? 2 : 1;
-    if (!a.batch_out || !a.ctrl || (!a.part_pi && !a.part_pol) || !a.nu || !a.noise_out || !a.actions || !a.g_act || !a.lag_partial ||
-        !a.tile_sync || !a.da_part)
-        return RPO_ERR_NULL;
-    if (a.twin ? (!a.raw || !a.logp) : !a.ap_det) return RPO_ERR_NULL;
-    if (with_a && (!a.x0_a || !a.h1_a)) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k] || !a.dx0[k]) return RPO_ERR_NULL;
-    if (!a.dx0_a || !a.dout || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
-    const dim3 grid(kNsGroups, (a.B + kRows - 1) / kRows, with_a + 2 * K + 1);
-    if (u->env == 0) hipLaunchKernelGGL(split_policy_front_kernel<CartPol>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c, with_a);
-    else hipLaunchKernelGGL(split_policy_front_kernel<PendPol>, grid, dim3(kThreads), 0, (hipStream_t)stream, a, c, with_a);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int rpo_split_policy_front(const rpo_split_update* u, void* stream) { return policy_front_launch(u, 1, stream); }
-int rpo_split_policy_front_bc(const rpo_split_update* u, void* stream) { return policy_front_launch(u, 0, stream); }
 
 int rpo_split_policy_c(const rpo_split_update* u, void* stream) {
     SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 2u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    if (!a.da_part || !a.lag_partial || (a.twin && !a.logp)) return RPO_ERR_NULL;
-    for (int k = 0; k < K; ++k)
-        if (!a.part_q[k] || !a.x0[k] || !a.h1[k] || !a.dx0[k]) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(split_policy_c_kernel, dim3(K * T * kNsGroups), dim3(kThreads), 0, (hipStream_t)stream, a);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = to_args(u, kNeedCritics, a, c)) return e;
+    if (!a.da_part || !a.lag_partial || (a.twin && !a.logp) || !critic_bufs(a, kBufFwd | kBufDx0)) return RPO_ERR_NULL;
+    return launch(split_policy_c_kernel, dim3(critics(a) * tiles(a.B) * kNsGroups), kThreads, 0, stream, a);
 }
 
 int rpo_split_policy_d(const rpo_split_update* u, void* stream) {
     SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 32u | 16u, a, c)) return e;
-    const int K = a.twin ? 2 : 1, T = (a.B + kRows - 1) / kRows;
-    if (!a.batch_out || !a.ctrl || !a.da_part || !a.g_act || !a.noise_out || !a.x0_a || !a.h1_a || !a.dx0_a || !a.dout) return RPO_ERR_NULL;
-    if (a.twin ? !a.raw : !a.ap_det) return RPO_ERR_NULL;
-    if (a.shared_embedding)
-        for (int k = 0; k < K; ++k)
-            if (!a.dx0[k]) return RPO_ERR_NULL;
-    const int grid = T * kNsGroups;
-    if (u->env == 0) hipLaunchKernelGGL(split_policy_d_kernel<CartPol>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, a, c);
-    else hipLaunchKernelGGL(split_policy_d_kernel<PendPol>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, a, c);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = to_args(u, kNeedActor | kNeedActorGrad, a, c)) return e;
+    if (!a.batch_out || !a.ctrl || !a.da_part || !a.g_act || !a.noise_out || !a.x0_a || !a.h1_a || !a.dx0_a || !a.dout ||
+        (a.twin ? !a.raw : !a.ap_det) || (a.shared_embedding && !critic_bufs(a, kBufDx0)))
+        return RPO_ERR_NULL;
+    return launch_env(kPolicyD, u->env, dim3(tiles(a.B) * kNsGroups), kThreads, stream, a, c);
 }
 
 int rpo_split_policy_e(const rpo_split_update* u, void* stream) {
     SplitArgs a; CartConsts c;
-    if (int e = to_args(u, 32u | 16u, a, c)) return e;
+    if (int e = to_args(u, kNeedActor | kNeedActorGrad, a, c)) return e;
     if (!a.batch_out || !a.dx0_a || !a.lag_partial || !a.lag_out || !a.nu_grad || !a.dout || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
     const int fl_blocks = mlp_fl_blocks(a.actor.E * (a.actor.S + 1));
-    if (u->env == 0) hipLaunchKernelGGL(split_policy_e_kernel<CartPol>, dim3(kWeightBlocks + fl_blocks + 1), dim3(kThreads), 0, (hipStream_t)stream, a, fl_blocks);
-    else hipLaunchKernelGGL(split_policy_e_kernel<PendPol>, dim3(kWeightBlocks + fl_blocks + 1), dim3(kThreads), 0, (hipStream_t)stream, a, fl_blocks);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_env(kPolicyE, u->env, dim3(kWeightBlocks + fl_blocks + 1), kThreads, stream, a, fl_blocks);
+}
+
+int rpo_xcc_probe(int gx, int gy, int gz, int threads, int* out, void* stream) {
+    if (gx <= 0 || gy <= 0 || gz <= 0 || threads <= 0 || threads > 1024) return RPO_ERR_ARG;
+    if (!out) return RPO_ERR_NULL;
+    return launch(xcc_probe_kernel, dim3(gx, gy, gz), threads, 0, stream, out);
+}
+
+int rpo_hw_probe(int gx, int gy, int gz, int threads, int lds_bytes, int spin, int* out, void* stream) {
+    if (gx <= 0 || gy <= 0 || gz <= 0 || threads <= 0 || threads > 1024 || lds_bytes < 4 || lds_bytes > 65536 || spin < 0) return RPO_ERR_ARG;
+    if (!out) return RPO_ERR_NULL;
+    return launch(hw_probe_kernel, dim3(gx, gy, gz), threads, lds_bytes, stream, out, spin);
 }
 
 }  // extern "C"

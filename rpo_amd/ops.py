@@ -1262,8 +1262,12 @@ class SplitUpdate(object):
     """Arguments of the column-split update stages (rpo_split_*), built once per trainer: every pointer refers to a static
     device buffer, so the struct is reused for every launch (and every hipGraph capture)."""
 
-    STAGES = ("critic_fwd_a", "critic_fwd_b", "critic_front", "critic_front_pol", "critic_mid", "critic_mid_pol", "critic_pfront", "critic_pfront_pol", "critic_fwd_b_pol", "pend_head_project", "critic_bwd_a", "critic_bwd_b", "policy_a", "policy_b",
+    STAGES = ("critic_fwd_a", "critic_fwd_b", "critic_fwd_b_pol", "critic_front", "critic_front_pol", "critic_mid", "critic_mid_pol",
+              "critic_pfront", "critic_pfront_pol", "pend_head_project", "critic_bwd_a", "critic_bwd_b", "policy_a", "policy_b",
               "policy_c", "policy_d", "policy_e", "policy_front", "policy_front_bc")
+    RIDE_STAGES = ("critic_fwd_a", "critic_fwd_b", "critic_front", "critic_mid", "critic_pfront", "critic_bwd_b")   # run(stage, rider)
+    _DTYPES = dict(idx_out=torch.int64, idx_in=torch.int64, ctrl=torch.int64, rollout_ctrl=torch.int64, clock_out=torch.int64,
+                   updates_out=torch.int64, proj_ws=torch.int64, proj_iters=torch.int32, prep_step=torch.int32, tile_sync=torch.int32)
 
     def __init__(self, env_kernels, descs, twin, batch, fields):
         """descs: name -> MlpDesc for actor, actor_target (RPODDPG), critic1, critic2, critic_target1, critic_target2;
@@ -1292,14 +1296,10 @@ class SplitUpdate(object):
     def set(self, **fields):
         for k, v in fields.items():
             if isinstance(v, torch.Tensor):
-                dt = torch.int64 if k in ("idx_out", "idx_in", "ctrl", "rollout_ctrl", "clock_out", "updates_out") else \
-                    (torch.int32 if k in ("proj_iters", "prep_step", "tile_sync") else torch.float32)
-                if k == "proj_ws":
-                    dt = torch.int64
                 if k == "rows":                                     # the fused sampling reads rows at the compiled ring stride
                     _ring(v, self.ring_floats)
                 self._held[k] = v                                   # keeps the buffer alive while the struct points at it
-                setattr(self.st, k, _p(v, dt).value)
+                setattr(self.st, k, _p(v, self._DTYPES.get(k, torch.float32)).value)
             else:
                 self._held.pop(k, None)
                 setattr(self.st, k, v)

@@ -6,7 +6,7 @@ import sys
 
 import pytest
 
-from rpo_amd import _lib
+from rpo_amd import _lib, ops
 
 
 def test_header_parses():
@@ -86,14 +86,16 @@ def test_struct_layouts_match_the_compiler(tmp_path):
 
 def test_split_update_stages_validate_arguments():
     lib = _lib.load()
-    for stage in ("critic_fwd_a", "critic_fwd_b", "critic_fwd_b_pol", "pend_head_project", "critic_bwd_a", "critic_bwd_b", "policy_a",
-                  "policy_b", "policy_c", "policy_d", "policy_e", "critic_front", "critic_front_pol", "critic_mid", "critic_mid_pol",
-                  "critic_pfront", "critic_pfront_pol", "policy_front", "policy_front_bc"):
+    stages, ride_stages = ops.SplitUpdate.STAGES, ops.SplitUpdate.RIDE_STAGES
+    exported = {n: len(a) for n, a in _lib.PROTOTYPES.items() if n.startswith("rpo_split_")}      # (u, stream) | (u, rider, stream)
+    assert sorted("rpo_split_" + s for s in stages) == sorted(n for n, k in exported.items() if k == 2)
+    assert sorted("rpo_split_" + s + "_ride" for s in ride_stages) == sorted(n for n, k in exported.items() if k == 3)
+    for stage in stages:
         assert getattr(lib, "rpo_split_" + stage)(None, None) == _lib.CONST["RPO_ERR_NULL"]
     assert lib.rpo_xcc_probe(8, 16, 4, 256, None, None) == _lib.CONST["RPO_ERR_NULL"]
     assert lib.rpo_xcc_probe(0, 16, 4, 256, None, None) == _lib.CONST["RPO_ERR_ARG"]
-    for stage in ("critic_fwd_a_ride", "critic_fwd_b_ride", "critic_bwd_b_ride", "critic_front_ride", "critic_mid_ride", "critic_pfront_ride"):            # the riding rollout halves: both structs are required
-        assert getattr(lib, "rpo_split_" + stage)(None, None, None) == _lib.CONST["RPO_ERR_NULL"]
+    for stage in ride_stages:                                        # the riding rollout halves: both structs are required
+        assert getattr(lib, "rpo_split_" + stage + "_ride")(None, None, None) == _lib.CONST["RPO_ERR_NULL"]
     assert _lib.CONST["RPO_ABI_VERSION"] == 6
 
 

@@ -6,6 +6,8 @@ Tolerances: (1) 4 Adam steps of float32 MLPs on rocBLAS vs the reference's CPU G
 absolute, losses to 1e-4 relative.  (3) float32 env physics on the GPU vs float64 in the oracle, compounded over the
 iterations: parameters 2e-5 absolute, replay rows 2e-4.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -570,24 +572,28 @@ def test_pipelines_with_a_ragged_batch(hip, algo, envname, monkeypatch):
     np.testing.assert_allclose(a.buffer.rows.cpu().numpy(), b.buffer.rows.cpu().numpy(), rtol=0, atol=1e-5)
 
 
-@pytest.mark.parametrize("algo,envname", CASES[:4])
-def test_split_update_equals_row_tile_pipelines(hip, algo, envname, monkeypatch):
+@pytest.mark.parametrize("algo,envname,batch", [pytest.param(a, e, 256, id="%s-%s" % (a, e)) for a, e in CASES[:4]] +
+                         [("ddpg", "pendulum", 272), ("sac", "pendulum", 272)])
+def test_split_update_equals_row_tile_pipelines(hip, algo, envname, batch, monkeypatch):
     """The column-split update (rpo_split_*: 128 workgroups per network evaluation, head partials summed by the
-    consumer, TD prologue + on-the-fly dh in the backward) against the row-tile pipelines it replaces."""
+    consumer, TD prologue + on-the-fly dh in the backward) against the row-tile pipelines it replaces.  Batch 272 (17 row
+    tiles, SpringPendulum): one tile past the 256 rows of the wide projection kernel, the one-workgroup form of
+    rpo_split_pend_head_project that no other schedule test reaches."""
     dev = torch.device("cuda")
+    run = functools.partial(_run, batch_size=batch)
     monkeypatch.setenv("RPO_SCHEDULE", "split=0")
-    a = _run(algo, envname, hip, dev, 26, 300, use_graph=False)
+    a = run(algo, envname, hip, dev, 26, 300, use_graph=False)
     assert a._split_state() is None
     monkeypatch.setenv("RPO_SCHEDULE", "split=1")
-    b = _run(algo, envname, hip, dev, 26, 300, use_graph=False)
-    assert b._split_state() is not None
-    c = _run(algo, envname, hip, dev, 26, 300, use_graph=True)
+    b = run(algo, envname, hip, dev, 26, 300, use_graph=False)
+    assert b._split_state() is not None and int(b._split_state().st.batch) == batch
+    c = run(algo, envname, hip, dev, 26, 300, use_graph=True)
     assert torch.equal(b.agent.flat.data, c.agent.flat.data) and torch.equal(b.buffer.rows, c.buffer.rows)   # graph == eager
     # critic update: bit for bit (3 iterations: before the first policy step)
     monkeypatch.setenv("RPO_SCHEDULE", "split=0")
-    a3 = _run(algo, envname, hip, dev, 3, 300, use_graph=False)
+    a3 = run(algo, envname, hip, dev, 3, 300, use_graph=False)
     monkeypatch.setenv("RPO_SCHEDULE", "split=1")
-    b3 = _run(algo, envname, hip, dev, 3, 300, use_graph=False)
+    b3 = run(algo, envname, hip, dev, 3, 300, use_graph=False)
     assert torch.equal(a3.agent.flat.data, b3.agent.flat.data)
     assert torch.equal(a3.agent.critic_target_flat, b3.agent.critic_target_flat)
     assert torch.equal(a3.agent.critic_optim.exp_avg_sq, b3.agent.critic_optim.exp_avg_sq)
@@ -672,11 +678,18 @@ def test_ridden_rollout_equals_serial(hip, algo, envname, monkeypatch):
     assert f.agent.flat.sizes[1] > 0 and not f._ride_ok(True)
 
 
-@pytest.mark.parametrize("algo,envname,shared,ride", [
+_FRONT_CASES = [
     ("ddpg", "cart", True, "0"), ("ddpg", "cart", False, "0"), ("sac", "cart", False, "0"), ("sac", "cart", False, "1"),
     ("ddpg", "cart", False, "1"), ("sac", "pendulum", False, "0"), ("sac", "pendulum", False, "1"), ("ddpg", "pendulum", False, "1"),
-    ("ddpg", "pendulum", True, "0")])
-def test_fused_front_launch_equals_separate_launches(hip, algo, envname, shared, ride, monkeypatch):
+    ("ddpg", "pendulum", True, "0")]
+# SpringPendulum with a projection budget past the workspace kernel's (31 > 30 steps): no rpo_split_critic_pfront, so front=1 is
+# fwd_a | projection | rpo_split_critic_mid / _mid_pol (ride=0) / _mid_ride (ride=1).  Batch 128: 8 row tiles, one per XCD.
+_MID_CASES = [("sac", "pendulum", False, "0"), ("ddpg", "pendulum", False, "1")]
+
+
+@pytest.mark.parametrize("algo,envname,shared,ride,mid", [pytest.param(*c, False, id="%s-%s-%s-%s" % c) for c in _FRONT_CASES] +
+                         [pytest.param(*c, True, id="%s-%s-%s-%s-mid" % c) for c in _MID_CASES])
+def test_fused_front_launch_equals_separate_launches(hip, algo, envname, shared, ride, mid, monkeypatch):
     """CartSafe critic update: fwd_a, fwd_b and bwd_a as ONE launch (rpo_split_critic_front: the later stages wait inside the
     launch for the workgroups of their own row tile; _pol: pol_a of a policy iteration as one more plane; _ride: the actor
     forward of the next vector step in the planes behind) leaves the same bits as the separate launches, eagerly and replayed
@@ -685,6 +698,8 @@ def test_fused_front_launch_equals_separate_launches(hip, algo, envname, shared,
     dev = torch.device("cuda")
     monkeypatch.setenv("RPO_GRAPH_CYCLE", "8")
     extra = dict(shared_param=shared) if algo == "ddpg" else {}
+    if mid:
+        extra.update(batch_size=128, max_steps=31)
     runs = {}
     for front in ("0", "1"):
         monkeypatch.setenv("RPO_SCHEDULE", "ride=%s,front=%s" % (ride, front))   # (rides in the graph windows only)
@@ -701,6 +716,7 @@ def test_fused_front_launch_equals_separate_launches(hip, algo, envname, shared,
         assert float(a.last_losses["critic"]) == float(b.last_losses["critic"]), key
     assert runs["1", True]._front_ok() and runs["1", False]._front_ok() and not runs["0", True]._front_ok()
     assert runs["1", True]._ride_ok(True) == (ride == "1")
+    assert not (mid and runs["1", True]._pfront)
     sync = runs["1", True]._split_state()._held["tile_sync"]
     assert int(sync.abs().sum()) == 0
 
