@@ -561,7 +561,13 @@ int rpo_mlp_supported(int E, int H, int cat);
 
 /* Forward of n rows.  s [n, >=S] / a [n, >=A] are read with row strides (columns of a gathered batch are fine).
  * out [n, n_out]; x0_save [n, Ein] / h1_save [n, H] (pre-activations, for rpo_mlp_backward) may be NULL.
- * out_mode 1 applies BoxConstraint's tanh map to output 0: scale * tanh(o) + base (model/utils.py:40-51). */
+ * out_mode 1 applies BoxConstraint's tanh map to output 0: scale * tanh(o) + base (model/utils.py:40-51).
+ * Non-finite values: relu(x) is x for x > 0 AND for a NaN of either sign, 0 otherwise -- a NaN pre-activation stays NaN.  A NaN
+ * in row r of s / a therefore makes x0[r] (the part that read it), every entry of h1[r] and every output of row r NaN; +-inf does
+ * the same wherever inf * 0 or inf - inf arises (a zero weight is enough).  Rows are independent: no other row changes a bit.
+ * This holds for rpo_mlp_forward in every form (row tile, first layer on either unit, x0 / h1 saved or not, layer by layer),
+ * rpo_mlp_forward_multi and rpo_mlp_forward_split + rpo_mlp_split_head, which agree on such rows as on all others; the failure
+ * flag (RPO_CTRL_NONFINITE) relies on it.  The streaming forms of n >= 12288 rows keep a NaN only when its sign bit is clear. */
 int rpo_mlp_forward(const rpo_mlp* net_host, int n, const float* s, int s_stride, const float* a, int a_stride,
                     float* out, float* x0_save, float* h1_save, int out_mode, float scale, float base, void* stream);
 

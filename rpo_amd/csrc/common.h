@@ -30,6 +30,13 @@ __device__ __forceinline__ float rpo_relu_bits(float x) {
     return __int_as_float(b > 0 ? b : 0);
 }
 
+// relu of the forward kernels (row tile, column split, layer by layer): IEEE 754-2019 maximum(x, 0), which returns the NaN when x
+// is one, whatever its sign -- a NaN pre-activation stays NaN and reaches the row's output (include/rpo_hip.h, rpo_mlp_forward; the
+// failure flag of DESIGN 4.7 rests on it).  fmaxf(x, 0.0f) returns 0 for a NaN.  ONE v_maximum3_f32 on gfx950 where fmaxf is two
+// v_max_f32 (the first quiets a signalling NaN); the same bits as fmaxf for every non-NaN x (maximum(-0.0, +0.0) = +0.0).
+// (!(x <= 0.0f) ? x : 0.0f, a compare and a select, is equivalent and measured 0.4 - 0.7 % slower on the headline.)
+__device__ __forceinline__ float rpo_relu(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
+
 // Compute units of the CURRENT device, cached per device id (the persistent kernels launch one workgroup per CU; ADVICE r05:
 // one cache for the streaming forward, backward and rollout instead of a query per launch / a first-device-only static).
 static inline int rpo_cu_count() {

@@ -129,7 +129,7 @@ __device__ __forceinline__ void gemm_stage(float* a_s, int ldk, int kw, const fl
             for (int u = 0; u < 8; ++u) {
                 const int idx = base + u * kGemmThreads, r = idx / q, k = (idx % q) * 4;
                 float4 w = (m0 + r < M && k + 3 < K) ? v[u] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (relu) { w.x = fmaxf(w.x, 0.0f); w.y = fmaxf(w.y, 0.0f); w.z = fmaxf(w.z, 0.0f); w.w = fmaxf(w.w, 0.0f); }
+                if (relu) { w.x = rpo_relu(w.x); w.y = rpo_relu(w.y); w.z = rpo_relu(w.z); w.w = rpo_relu(w.w); }
                 if (idx < total) *reinterpret_cast<float4*>(&a_s[r * ldk + k]) = w;
             }
         }
@@ -148,7 +148,7 @@ __device__ __forceinline__ void gemm_stage(float* a_s, int ldk, int kw, const fl
         for (int u = 0; u < 8; ++u) {
             const int idx = base + u * kGemmThreads, r = idx / kw, k = idx % kw;
             const float w = (m0 + r < M && k < K) ? v[u] : 0.0f;
-            if (idx < total) a_s[r * ldk + k] = relu ? fmaxf(w, 0.0f) : w;
+            if (idx < total) a_s[r * ldk + k] = relu ? rpo_relu(w) : w;
         }
     }
 }

@@ -208,7 +208,7 @@ __device__ __forceinline__ void tile_compute(const Mlp& net, const TileWeights<E
                     else { dst[0] = c[0]; dst[1] = c[1]; dst[2] = c[2]; dst[3] = c[3]; }
                 }
                 *reinterpret_cast<f32x4*>(&x1[row * LDX + e0]) =
-                    f32x4{fmaxf(c[0], 0.0f), fmaxf(c[1], 0.0f), fmaxf(c[2], 0.0f), fmaxf(c[3], 0.0f)};
+                    f32x4{rpo_relu(c[0]), rpo_relu(c[1]), rpo_relu(c[2]), rpo_relu(c[3])};
             }
         }
     }
@@ -246,7 +246,7 @@ __device__ __forceinline__ void tile_compute(const Mlp& net, const TileWeights<E
 #pragma unroll
         for (int r = 0; r < RPT; ++r) {
             if (x0_save && row0 + r_lo + r < n) x0_save[(size_t)(row0 + r_lo + r) * EIN + e_col] = acc1[r];
-            x1[(r_lo + r) * LDX + e_col] = fmaxf(acc1[r], 0.0f);
+            x1[(r_lo + r) * LDX + e_col] = rpo_relu(acc1[r]);
         }
     }
     __syncthreads();
@@ -299,7 +299,7 @@ __device__ __forceinline__ void tile_compute(const Mlp& net, const TileWeights<E
                 const float h = acc[0][c][i] + w.b0v[c];
                 const int row = row0 + lg * 4 + i;
                 if (h1_save && row < n) h1_save[(size_t)row * H + col] = h;
-                lds.hr[(lg * 4 + i) * LDH + col] = fmaxf(h, 0.0f);
+                lds.hr[(lg * 4 + i) * LDH + col] = rpo_relu(h);
             }
         }
         __syncthreads();
@@ -339,7 +339,7 @@ __device__ __forceinline__ void tile_compute(const Mlp& net, const TileWeights<E
                 const float h = acc[rt][c][i] + w.b0v[c];
                 const int row = row0 + rt * kRows + lg * 4 + i;
                 if (h1_save && row < n) h1_save[(size_t)row * H + col] = h;
-                const float hr = fmaxf(h, 0.0f);
+                const float hr = rpo_relu(h);
                 po[0][i] = fmaf(hr, w.w1av[c], po[0][i]);
                 po[1][i] = fmaf(hr, w.w1bv[c], po[1][i]);
             }

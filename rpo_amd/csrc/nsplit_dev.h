@@ -133,7 +133,7 @@ __device__ __forceinline__ void ns_hidden(const Mlp& net, const NsWeights<EIN>& 
             else { dst[0] = c[0]; dst[1] = c[1]; dst[2] = c[2]; dst[3] = c[3]; }
         }
         *reinterpret_cast<f32x4*>(&lds.x1[li * LDX + e0]) =
-            f32x4{fmaxf(c[0], 0.0f), fmaxf(c[1], 0.0f), fmaxf(c[2], 0.0f), fmaxf(c[3], 0.0f)};
+            f32x4{rpo_relu(c[0]), rpo_relu(c[1]), rpo_relu(c[2]), rpo_relu(c[3])};
     }
     __syncthreads();
     // ---- layer 2 (MFMA): one 16 x 16 output tile per wave, k-ordered chain of EIN / 4 instructions
@@ -154,7 +154,7 @@ __device__ __forceinline__ void ns_hidden(const Mlp& net, const NsWeights<EIN>& 
         const float h = acc[i] + w.b0v;
         const int row = row0 + lg * 4 + i;
         if (h1_save && row < n) h1_save[(size_t)row * H + col] = h;
-        hr[i] = fmaxf(h, 0.0f);
+        hr[i] = rpo_relu(h);
     }
     // ---- head partial of the slab: the row-tile kernel's wave runs fmaf over its two column tiles in order, so wave 0
     //      hands its term to wave 1, which adds its own and reduces over the 16 lanes of a row

@@ -324,3 +324,23 @@ def worst(got, ref, mag):
     """max |got - ref| / (EPS32 * mag) over the elements (the quantity C_REF_* bound and the GPU tests limit)."""
     err = (torch.as_tensor(got).to(torch.float64) - ref).abs()
     return float((err / (EPS32 * mag + TINY)).max())
+
+
+# ============================================================================ the tanh box as the epilogue of rpo_mlp_forward
+C_REF_BOX_FWD = 0.40     # measured 0.398 (tests/test_mlp_f64.py::test_box_forward_yardstick): ap = scale tanh(o) + base from o, three boxes
+
+
+def tanh_box_fwd_mags(o, scale, base):
+    """Magnitude sum of ap = scale tanh(o) + base from a given o (module docstring with xm = |o|): scale ym + |scale y| + |base|;
+    scale / base Python floats, o on any device."""
+    o = o.to(torch.float64)
+    y = torch.tanh(o)
+    ym = (1 - y * y) * o.abs() + y.abs()
+    return abs(scale) * ym + (scale * y).abs() + abs(base)
+
+
+def box_fwd_rows(seed=0):
+    """The o values of the yardstick of the forward map: MEANS, their neighbours, and random rows."""
+    g = torch.Generator().manual_seed(seed)
+    edge = [float(w) for v in MEANS for w in [np.float32(v)] + _neighbours(v)]
+    return torch.cat([torch.tensor(edge, dtype=torch.float64), 3.0 * torch.randn(4096, generator=g, dtype=torch.float64)]).float()

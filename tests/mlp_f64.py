@@ -183,3 +183,233 @@ def td(q, qn1, reward, done, gamma, qn2=None, logp=None, alpha=0.0, qn_err=None)
     loss = float(hub.sum())
     loss_bound = float(row_bound.sum() + bound(hub.abs(), 16).sum())
     return dq, dq_bound, loss, loss_bound, d
+
+
+def _td_rows(q, qn1, reward, done, gamma, qn2=None, logp=None, alpha=0.0):
+    """Per-row float64 TD error d, the bound delta on a float32 d, the Huber term / n and its bound (see ``td``)."""
+    f = lambda t: None if t is None else t.to(torch.float64).reshape(-1)      # noqa: E731
+    q, qn1, reward, done, qn2, logp = f(q), f(qn1), f(reward), f(done), f(qn2), f(logp)
+    n = q.numel()
+    g32 = float(torch.tensor(gamma, dtype=torch.float32))
+    a32 = float(torch.tensor(alpha, dtype=torch.float32))
+    qn = qn1 if qn2 is None else torch.minimum(qn1, qn2)
+    qn_abs = qn.abs()
+    if logp is not None:
+        qn = qn - a32 * logp
+        qn_abs = qn_abs + abs(a32) * logp.abs()
+    d = q - (reward + g32 * (1.0 - done) * qn)
+    delta = bound(q.abs() + reward.abs() + abs(g32) * (1.0 - done).abs() * qn_abs, 8)
+    ad = d.abs()
+    hub = torch.where(ad < 1.0, 0.5 * d * d, ad - 0.5) / n
+    row_bound = (ad.clamp(max=1.0) + delta) * delta / n + bound(hub.abs(), 3)
+    return d, delta, hub, row_bound
+
+
+def td_partials(q, qn1, reward, done, gamma, qn2=None, logp=None, alpha=0.0):
+    """loss_partial of rpo_td tile by tile: (ref [ceil(n / 16)], bound) -- the float64 sum of the Huber terms / n of rows
+    [16 t, 16 t + 16) (the last tile holds n - 16 t rows, each STILL divided by n), the rows' own bounds (``td``) and gamma_16 of
+    the tile's |terms| for the 16-term sum of the kernel."""
+    d, delta, hub, row_bound = _td_rows(q, qn1, reward, done, gamma, qn2, logp, alpha)
+    n = d.numel()
+    pad = (-n) % 16
+    z = torch.zeros(pad, dtype=torch.float64, device=d.device)
+    tiles = lambda t: torch.cat([t, z]).view(-1, 16).sum(1)                   # noqa: E731
+    return tiles(hub), tiles(row_bound) + bound(tiles(hub.abs()), 16)
+
+
+# ------------------------------------------------------------------------------- out_mode 1: the tanh box on output 0
+def box_out(o, scale, base):
+    """out_mode = 1 of rpo_mlp_forward from the kernel's own float32 o: (ref, allowed) with ref = scale tanh(o) + base in
+    float64 and allowed = MARGIN * C_REF_BOX_FWD * eps32 * magnitude sum -- the convention of tests/heads_f64.py for the same
+    map (tanh_box_fwd_mags there: |scale| ((1 - y^2) |o| + |y|) + |scale y| + |base|; C_REF_BOX_FWD the float32-CPU constant)."""
+    import heads_f64
+    o = o.to(torch.float64)
+    s32, b32 = heads_f64.f32(scale), heads_f64.f32(base)
+    ref = s32 * torch.tanh(o) + b32
+    return ref, heads_f64.MARGIN * heads_f64.C_REF_BOX_FWD * heads_f64.EPS32 * heads_f64.tanh_box_fwd_mags(o, s32, b32) + TINY
+
+
+# ------------------------------------------------------------------------------------------------- the += form
+def accumulate(entry, g0):
+    """A parameter gradient ADDED onto a buffer that held g0 (float32): ref g0 + grad, |.| expression |g0| + abs, one more
+    rounding."""
+    ref, absval, L = entry
+    g0 = g0.to(torch.float64).reshape(ref.shape)
+    return ref + g0, absval + g0.abs(), L + 1
+
+
+# ----------------------------------------------------------------------- networks, inputs and the checker of the small-n tests
+# (name, kind, S, A, E, n_out, head_dim): the smallest set that reaches every instantiation and first-layer form of the row-tile,
+# multi-output and layer-by-layer kernels (tests/test_mlp_small_f64_gpu.py; the float32 CPU stand-in of tests/test_mlp_f64.py)
+NETWORKS = [
+    ("add_6_2", "add", 6, 2, 128, 1, 1), ("add_5_2", "add", 5, 2, 128, 1, 1),            # cart / pendulum critics (MFMA layer 1)
+    ("actor_6", "actor", 6, 0, 128, 1, 1), ("actor_1", "actor", 1, 0, 128, 1, 1),        # lower edge of the k slots
+    ("gauss_5", "gauss", 5, 0, 128, 2, 1),                                               # second scalar head
+    ("add_3_1", "add", 3, 1, 128, 1, 1), ("add_6_4", "add", 6, 4, 128, 1, 1),            # edges of the MFMA first layer
+    ("add_7_2", "add", 7, 2, 128, 1, 1), ("add_6_5", "add", 6, 5, 128, 1, 1),            # vector first layer just beyond them
+    ("add_64_48", "add", 64, 48, 128, 1, 1),                                             # the full LDS input strides
+    ("add256_6_2", "add", 6, 2, 256, 1, 1), ("gauss256_5", "gauss", 5, 0, 256, 2, 1),    # Ein 256 (layer by layer; 2 head problems)
+    ("cat_57_43", "cat", 57, 43, 256, 1, 1),                                             # EVOPF critic (Ein 512)
+    ("actor14", "actor", 57, 0, 256, 1, 14), ("gauss14", "gauss", 57, 0, 256, 2, 14),    # EVOPF actors
+    ("wide14", "actor", 6, 0, 128, 1, 14), ("wide2", "actor", 6, 0, 128, 1, 2), ("wide16", "actor", 6, 0, 128, 1, 16),
+]
+NET_BY_NAME = {t[0]: t for t in NETWORKS}
+H = 256
+ZERO_COL = 5            # the planted dead column of the first layer (make_params)
+
+
+def make_params(spec, seed, device=None, zero_col=True):
+    """Float32 parameters of one network of NETWORKS, nn.Linear layout and its default U(-1/sqrt(fan_in), 1/sqrt(fan_in))
+    ranges.  zero_col: row ZERO_COL of Ws (and Wa, unless concatenated) and its biases are exactly 0 -- x0[:, ZERO_COL] is
+    exactly 0 for every input and contributes exactly nothing to h1."""
+    _, kind, S, A, E, n_out, hd = spec
+    g = torch.Generator().manual_seed(seed)
+    u = lambda shape, fan: ((torch.rand(*shape, generator=g) * 2 - 1) / fan ** 0.5)      # noqa: E731
+    ein = 2 * E if kind == "cat" else E
+    p = dict(Ws=u((E, S), S), bs=u((E,), S), W0=u((H, ein), ein), b0=u((H,), ein), W1=u((hd, H), H), b1=u((hd,), H))
+    if A:
+        p.update(Wa=u((E, A), A), ba=u((E,), A))
+    if n_out > 1:
+        p.update(W1b=u((hd, H), H), b1b=u((hd,), H))
+    if zero_col:
+        for k in ("Ws", "bs") + (("Wa", "ba") if A and kind != "cat" else ()):
+            p[k][ZERO_COL] = 0.0
+    return {k: v.to(device) for k, v in p.items()}
+
+
+def mlp64_of(spec, params, device=None):
+    _, kind, S, A, E, n_out, hd = spec
+    return Mlp64(params, S, A, E, H, n_out=n_out, cat=kind == "cat", head_dim=hd, device=device)
+
+
+HUGE, SMALL = 1e30, 1e-38
+
+
+def make_inputs(spec, n, seed, device=None, guard=4, planted=True):
+    """s / a [n, S] / [n, A] as strided column views of ONE wider matrix with `guard` rows of NaN before and after (a padded lane
+    that reads past row n - 1 AND lets it contribute shows as NaN).  planted (n >= 4): row 1 holds +-1e30 and row 2 +-1e-38
+    (float32 denormals) in every input -- a float32 forward stays finite: |x0| <= (S + A) 1e30, |h1| <= 512 (S + A) 1e30 / 16,
+    |out| below 1e36 -- and row 3 exact zeros."""
+    _, kind, S, A, E, n_out, hd = spec
+    g = torch.Generator().manual_seed(seed)
+    wide = torch.randn(n + 2 * guard, S + A + 3, generator=g)
+    wide[:guard] = float("nan")
+    wide[guard + n:] = float("nan")
+    if planted and n >= 4:
+        sign = torch.where(torch.rand(S + A + 3, generator=g) < 0.5, -1.0, 1.0)
+        wide[guard + 1] = HUGE * sign
+        wide[guard + 2] = SMALL * sign
+        wide[guard + 3] = 0.0
+    wide = wide.to(device)
+    body = wide[guard:guard + n]
+    return body[:, 1:1 + S], (body[:, 1 + S:1 + S + A] if A else None), wide
+
+
+def plant_activations(x0, h1, seed):
+    """Edge values written INTO saved pre-activations (the backward reads them): per row >= 2 one entry each of +0, -0, the
+    smallest positive and negative denormal at seeded columns of x0 and of h1; row 0 of x0 all +0 and row 1 of h1 all -0 (n
+    permitting).  The mask is `> 0`: the gradient through +-0 and the negative denormal is exactly 0, through the positive
+    denormal it passes."""
+    g = torch.Generator().manual_seed(seed)
+    den = float(torch.tensor(1, dtype=torch.int32).view(torch.float32))      # 2^-149
+    vals = torch.tensor([0.0, -0.0, den, -den], dtype=torch.float32)
+    for t in (x0, h1):
+        n, w = t.shape
+        cols = torch.rand(n, w, generator=g).topk(4, dim=1).indices.to(t.device)     # four distinct columns per row
+        t.scatter_(1, cols, vals.to(t.device).expand(n, 4).contiguous())
+    x0[0] = 0.0
+    if x0.shape[0] > 1:
+        h1[1] = -0.0
+    return x0, h1
+
+
+def check(what, got, ref, absval, L, worst, allowed=None):
+    """Every element of got within gamma_L absval (or `allowed`) of ref; the worst ratio is recorded under the last word of
+    `what` ("probe" / "+=" prefixed when `what` says so)."""
+    got = got.to(torch.float64).reshape(ref.shape)
+    assert bool(torch.isfinite(got).all()), "%s: non-finite (never written?)" % what
+    if allowed is None:
+        r = ratio(got, ref, absval, L)
+    else:
+        r = float(((got - ref).abs() / allowed).max())
+    key = ("probe " if " probe " in what else "+= " if " += " in what else "") + what.split()[-1]
+    worst[key] = max(worst.get(key, 0.0), r)
+    assert r <= 1.0, "%s: |got - ref| is %.3g x the bound%s" % (what, r, "" if allowed is not None else " gamma_%d |A||B|" % L)
+
+
+def report(tag, worst):
+    print("%s: worst |err| / bound %s" % (tag, ", ".join("%s %.3g" % (k, v) for k, v in sorted(worst.items()))))
+
+
+def check_forward(net, s, a, out, x0, h1, worst, tag):
+    """out / x0 / h1 of one forward, layer by layer from the given (the kernel's own float32) input to each layer."""
+    r, ab, L = net.first_layer(s, a)
+    check(tag + " x0", x0, r, ab, L, worst)
+    r, ab, L = net.hidden(x0)
+    check(tag + " h1", h1, r, ab, L, worst)
+    r, ab, L = net.head(h1)
+    check(tag + " out", out, r, ab, L, worst)
+
+
+def batch_chain(rows):
+    """Additions a parameter-gradient element meets over `rows` rows in ANY of the small-n paths.  Every path gives an element
+    one owner and a fixed order over a partition of the batch: the one-owner pass 4 wave (or 16 / 8 slice) partials of
+    contiguous row ranges added in order, then one add onto the gradient (mlp_bwd_weights_body, mlp_bwd_first_layer_impl: 16
+    phases); the MFMA first-layer role of the 256-wide networks (mlp_bwd_first_layer_mfma) and the dW0 tiles k-steps of 4 rows
+    per wave, ((t0 + t1) + t2) + t3 and the add onto the gradient; the multi-output head role 16 slices of each 256-row pass.
+    The deepest chain of any such order has at most rows - 1 + (partials <= 16) additions; + 1 for the add onto the gradient and
+    + 3 of slack: rows + 20, the one-owner figure of tests/test_large_batch_f64_gpu.py (batch_chain(n, 0)).  The rows launches of
+    the layer-by-layer path (gemm_backward_rows: dh, dx0, da) are per-row chains over H / Ein / E products in k order, or -- with
+    the k range split over four waves -- in another order: the bound gamma_L |A||B| holds for any order, no batch term.
+    rows = 1 (a one-hot probe): every other row adds exact zeros (0 x finite, x + 0), so the row's product meets ONE addition."""
+    return 1 if rows == 1 else rows + 20
+
+
+def check_backward(net, s, a, x0, h1, dout, got, pre, worst, tag, param_grads=True, state_only=False, rows=None, want_da=True):
+    """One backward call against float64 from the x0 / h1 / dout it read.  got: dict(dx0=, da=, <parameter>=gradient buffer
+    after the call); pre: {parameter: what the buffer held before}.  Parameter gradients are judged as pre + gradient (+= form);
+    every parameter a reduced mode must not write is compared BITWISE with `pre`.  rows: the number of rows with a non-zero
+    dout (one-hot probes: 1 -- every other row adds exact zeros); default the batch."""
+    res = net.backward(s, a, x0, h1, dout, param_grads=param_grads, first_layer_state_only=state_only)
+    chain = batch_chain(dout.shape[0] if rows is None else rows)
+    r, ab, L = res["dx0"]
+    check(tag + " dx0", got["dx0"], r, ab, L, worst)
+    if net.A > 0 and want_da:
+        r, ab, L = res["da"]
+        check(tag + " da", got["da"], r, ab, L, worst)
+    written = []
+    for name in FIELDS:
+        if net.p[name] is None:
+            continue
+        if name in res:
+            r, ab, L = accumulate(res[name], pre[name])
+            check("%s %s" % (tag, name), got[name], r, ab, L + chain, worst)
+            written.append(got[name])
+        else:
+            same = torch.equal(got[name].reshape(-1).view(torch.int32), pre[name].reshape(-1).view(torch.int32))
+            assert same, "%s %s: written by a mode that must not touch it" % (tag, name)
+    return written
+
+
+def gradmax_of(written):
+    """max |element| over the gradient tensors a call wrote: what its gradmax slots must hold, exactly."""
+    return max([float(t.abs().max()) for t in written] + [0.0])
+
+
+def plant_td_kink(q, qn1, reward, done, gamma, qn2=None, logp=None):
+    """Rows with |q - y| EXACTLY 1 and within a few float32 ulps either side, written into q / qn1 / reward / done (/ qn2 / logp)
+    in place (n permitting): rows 0 / 1 (of the first five) d = +1 / -1, then 1 + 2 ulp, 1 - 2 ulp, -(1 + 2 ulp).  With reward,
+    qn1, qn2, logp and done all 0 the target is y = 0 exactly whatever gamma and alpha, and d = q.  Returns the planted rows."""
+    up = float(torch.nextafter(torch.nextafter(torch.tensor(1.0), torch.tensor(2.0)), torch.tensor(2.0)))
+    dn = float(torch.nextafter(torch.nextafter(torch.tensor(1.0), torch.tensor(0.0)), torch.tensor(0.0)))
+    rows = []
+    for i, d in enumerate((1.0, -1.0, up, dn, -up)):
+        if i >= q.numel():
+            break
+        qn1[i], done[i], reward[i] = 0.0, 0.0, 0.0
+        for extra in (qn2, logp):
+            if extra is not None:
+                extra[i] = 0.0
+        q[i] = d
+        rows.append(i)
+    return rows

@@ -1,7 +1,10 @@
 """Hand-written f32-MFMA MLP kernels (rpo_mlp_forward / rpo_mlp_backward) against the PyTorch modules they replace.
 
 Tolerance: both sides are float32; the MFMA is an exact fmaf chain, so only summation order differs from rocBLAS /
-torch reductions: forward 1e-5 relative, gradients 2e-5 relative to the largest entry of each gradient tensor.
+torch reductions: forward 1e-5 relative, gradients 2e-5 relative to the largest entry of each gradient tensor.  That is a
+plumbing check against the modules (a wrong SMALL entry of a gradient passes it): what holds these kernels element by element,
+against float64 with a derived bound, at their row-count and value edges, is tests/test_mlp_small_f64_gpu.py (and
+tests/test_large_batch_f64_gpu.py above the large-batch thresholds).
 """
 import numpy as np
 import pytest
