@@ -11,14 +11,12 @@
 //
 // Nothing is carried between rows, no env state, control word or generator is touched.  The per-row chain is act_dev.h's.
 #include "act_dev.h"
+#include "host_glue.h"
 
 namespace {
 
 using namespace rpo_mlp_dev;
-
-Mlp act_to_dev(const rpo_mlp* h) {
-    return Mlp{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H, h->n_out, h->cat, h->head_dim};
-}
+using rpo_host::to_dev;
 
 // PROFILE = 1: the row's projection also writes its entries of the profile planes (act_dev.h: act_project_profile); the
 // PROFILE = 0 instances take no profile argument and are the kernel as it was.  The profile is touched behind the forward only.
@@ -73,7 +71,7 @@ int launch_project_profile(const typename ENV::ActArgs& a, const typename ENV::C
     return 0;
 }
 
-int check_act_actor(const Mlp& actor, int obs_dim, int gauss) {  // (check_eval_actor's conditions; E below)
+int check_act_actor(const Mlp& actor, int obs_dim, int gauss) {  // (host_glue.h's check_actor and every bias; E below)
     if (actor.hd > 1 || actor.S != obs_dim || actor.A != 0 || actor.n_out != (gauss ? 2 : 1) || actor.cat || actor.H != 256 || !actor.Ws ||
         !actor.bs || !actor.W0 || !actor.b0 || !actor.W1 || !actor.b1 || (gauss && (!actor.W1b || !actor.b1b)))
         return RPO_ERR_ARG;
@@ -125,7 +123,7 @@ int fill_act_args(PolicyActArgs<ENV>& args, const rpo_mlp* actor_host, int gauss
     if (!obs || !action) return RPO_ERR_NULL;
     if (reinterpret_cast<uintptr_t>(action) % 8) return RPO_ERR_ARG;                       // 8-byte stores of the action rows
     if (std::is_same<ENV, CartEnv>::value && reinterpret_cast<uintptr_t>(ineq_resid) % 8) return RPO_ERR_ARG;   // ... and of g[0..5]
-    args.actor = act_to_dev(actor_host);
+    args.actor = to_dev(actor_host);
     if (int e = check_act_actor(args.actor, ENV::OBS, gauss)) return e;
     args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.n = n; args.obs = obs; args.obs_stride = obs_stride;
     args.proposal = proposal; args.iters = iters; args.eq = eq_resid; args.ineq = ineq_resid;

@@ -27,6 +27,7 @@
 #include "cartsafe_dev.h"
 #include "eval_dev.h"
 #include "heads_dev.h"
+#include "host_glue.h"
 #include "mlp_tile.h"
 #include "pendulum_dev.h"
 #include "rollout_env.h"
@@ -34,15 +35,13 @@
 namespace {
 
 using namespace rpo_mlp_dev;
+using rpo_host::check_actor;
+using rpo_host::to_dev;
 using rpo_eval_dev::con_width;
 using rpo_eval_dev::nanmax;
 using rpo_eval_dev::rpo_eval_lane_update;
 using rpo_eval_dev::trace_head;
 using rpo_eval_dev::trace_width;
-
-Mlp to_dev(const rpo_mlp* h) {
-    return Mlp{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H, h->n_out, h->cat, h->head_dim};
-}
 
 template <class ENV>
 struct EvalArgs {
@@ -435,13 +434,6 @@ int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, in
     return rec ? launch_eval<ENV, 1, 1>(ca, c, n, stream) : launch_eval<ENV, 0, 1>(ca, c, n, stream);
 }
 
-int check_eval_actor(const Mlp& actor, int obs_dim, int gauss) {
-    if (actor.hd > 1 || actor.S != obs_dim || actor.A != 0 || actor.n_out != (gauss ? 2 : 1) || actor.cat || actor.H != 256 || !actor.Ws ||
-        !actor.W0 || !actor.W1 || (gauss && !actor.W1b))
-        return RPO_ERR_ARG;
-    return 0;
-}
-
 int check_eval_range(int n, int t0, int steps, int max_episode_steps, int max_steps) {
     if (n <= 0 || t0 < 0 || steps <= 0 || max_episode_steps <= 0 || max_steps < 0) return RPO_ERR_ARG;
     if ((long long)t0 + steps > (1ll << 24)) return RPO_ERR_ARG;   // lengths and step indices stay exact in the f32 row
@@ -779,7 +771,7 @@ int evaluate_entry(const EvalCommon& q, const EvalOpts& o) {
         if (int e = check_eval_con(o.con)) return e;
     EvalArgs<ENV> args{};
     args.actor = to_dev(q.actor_host);
-    if (int e = check_eval_actor(args.actor, kObs, q.gauss)) return e;
+    if (int e = check_actor(args.actor, kObs, q.gauss)) return e;
     typename ENV::Consts c;
     if (int e = eval_consts(c, q)) return e;
     args.scale = q.scale; args.base = q.base; args.gauss = q.gauss ? 1 : 0; args.t0 = q.t0; args.steps = q.steps; args.acc = q.acc;

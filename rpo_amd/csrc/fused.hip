@@ -11,10 +11,12 @@
 // One workgroup = 16 rows (lanes / batch samples) and 512 threads; the MLP tile forward is mlp_tile.h.
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "cartsafe_dev.h"
 #include "heads_dev.h"
+#include "host_glue.h"
 #include "mlp_bwd.h"
 #include "mlp_tile.h"
 #include "pendulum_dev.h"
@@ -24,14 +26,11 @@
 namespace {
 
 using namespace rpo_mlp_dev;
+using namespace rpo_host;
 using rpo_cart_dev::ActArgs;
 using rpo_cart_dev::CartConsts;
 using rpo_cart_dev::cart_explore_project;
 using rpo_cart_dev::load_consts;
-
-Mlp to_dev(const rpo_mlp* h) {
-    return Mlp{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H, h->n_out, h->cat, h->head_dim};
-}
 
 // ------------------------------------------------------------------------------------------------------ rollout
 // (RolloutArgs<ENV>: rollout_args.h)
@@ -118,46 +117,8 @@ __global__ __launch_bounds__(kFwdThreads) void rollout_kernel(RolloutArgs<ENV> p
     if (!p.defer_clock) rpo_step_epilogue(p.step.ctrl, t, p.step.stats, p.step.stats_cap);
 }
 
-template <class ENV>
-int launch_rollout(const RolloutArgs<ENV>& args, const typename ENV::Consts& c, int n_envs, void* stream) {
-    // RPO_TUNE_ROLLOUT_WIDE: 0 / 1 force the 16- / 64-lane row tiles, 3 the streaming form (tests), 2 (default) by size:
-    // 16-lane tiles below 64 x 192 lanes, 64-lane tiles up to RPO_ROLLOUT_STREAM_FROM, the streaming form from there
-    {
-        const int sel = rpo_tune(RPO_TUNE_ROLLOUT_WIDE);
-        if (sel == 3 || sel == 4 || (sel == 2 && n_envs >= RPO_ROLLOUT_STREAM_FROM)) {   // (4: 64-lane groups forced, tests)
-            const int e = rpo_rollout_stream_launch(std::is_same<ENV, CartEnv>::value ? 0 : 1, &args, &c, n_envs, stream);
-            if (e >= 0) return e;                                // (-1: the streaming form does not apply to this network / env)
-        }
-    }
-    // 64 lanes per workgroup once that still fills the chip: the 128 KB hidden-layer matrix is streamed once per
-    // workgroup, so wider tiles cut the L2 traffic 4x (rpo_tuning(RPO_TUNE_ROLLOUT_WIDE, 0 / 1) overrides the size rule)
-    const int wide_sel = rpo_tune(RPO_TUNE_ROLLOUT_WIDE);        // 0 / 1: forced (tests), 2: by size
-    const int E = args.actor.E;
-    const bool wide = E == 128 && (wide_sel == 0 || wide_sel == 1 ? wide_sel != 0 : n_envs >= 64 * 192);
-    if (E == 128 && wide) {
-        hipLaunchKernelGGL((rollout_kernel<ENV, 128, 256, 4>), dim3((n_envs + 63) / 64), dim3(kFwdThreads), 0,
-                           (hipStream_t)stream, args, c);
-    } else if (E == 128) {
-        hipLaunchKernelGGL((rollout_kernel<ENV, 128, 256, 1>), dim3((n_envs + 15) / 16), dim3(kFwdThreads), 0,
-                           (hipStream_t)stream, args, c);
-    } else if (E == 256) {
-        hipLaunchKernelGGL((rollout_kernel<ENV, 256, 256, 1>), dim3((n_envs + 15) / 16), dim3(kFwdThreads), 0,
-                           (hipStream_t)stream, args, c);
-    } else {
-        return RPO_ERR_ARG;
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-int check_actor(const Mlp& actor, int obs_dim, int gauss) {
-    if (actor.hd > 1 || actor.S != obs_dim || actor.A != 0 || actor.n_out != (gauss ? 2 : 1) || actor.cat || actor.H != 256 || !actor.Ws ||
-        !actor.W0 || !actor.W1 || (gauss && !actor.W1b))
-        return RPO_ERR_ARG;
-    return 0;
-}
-
 // ----------------------------------------------------------------------------------------------- critic forward
+// (its kernel spells out sac_sample and the role helpers below once more; folding them changes device code on an update path)
 struct CriticFwdArgs {
     Mlp actor_target, critic_target, critic;
     float scale, base;
@@ -804,6 +765,172 @@ __global__ __launch_bounds__(kThreads) void sac_actor_backward_kernel(SacActorBw
 
 }  // namespace
 
+// ===================================================================================================== host side
+// One body per family (rollout, critic forward, actor update); the 12 exported symbols below keep what differs between them.
+// The ORDER of an entry point's checks is part of its behaviour (tests/test_fused_entry_refusals.py pins it).
+namespace {
+
+// ---- the kernels
+// The one-launch rollout of an env: its 64-lane tile (E = 128 only) and its 16-lane tiles
+template <class ENV> using RolloutKernel = void(RolloutArgs<ENV>, typename ENV::Consts);
+template <class ENV> struct RolloutKernels { RolloutKernel<ENV>* wide; EmbedKernels<RolloutKernel<ENV>> tile; };
+
+// Every instantiation the entry points launch, named once.  The compiler emits the kernels in the order of their first use, this
+// list: keep it, the code object's layout follows it.
+const RolloutKernels<CartEnv> kRolloutCart{rollout_kernel<CartEnv, 128, 256, 4>,
+                                           {rollout_kernel<CartEnv, 128, 256, 1>, rollout_kernel<CartEnv, 256, 256, 1>}};
+const RolloutKernels<PendEnv> kRolloutPend{rollout_kernel<PendEnv, 128, 256, 4>,
+                                           {rollout_kernel<PendEnv, 128, 256, 1>, rollout_kernel<PendEnv, 256, 256, 1>}};
+const auto kCartDdpgCritic = embed_kernels(cart_ddpg_critic_forward_kernel<128, 256>, cart_ddpg_critic_forward_kernel<256, 256>);
+const auto kCartSacCritic = embed_kernels(cart_sac_critic_forward_kernel<128, 256>, cart_sac_critic_forward_kernel<256, 256>);
+const auto kPendSacFront = embed_kernels(pend_sac_critic_front_kernel<128, 256>, pend_sac_critic_front_kernel<256, 256>);
+const auto kPendSacBack = embed_kernels(pend_critic_back_kernel<128, 256, 1>, pend_critic_back_kernel<256, 256, 1>);
+const auto kDdpgActorFwd = env_kernels(ddpg_actor_forward_kernel<CartActEnv, 128, 256>, ddpg_actor_forward_kernel<PendActEnv, 128, 256>);
+const auto kDdpgActorBwd = env_kernels(ddpg_actor_backward_kernel<CartActEnv, 128, 256>, ddpg_actor_backward_kernel<PendActEnv, 128, 256>);
+const auto kWeightsSplitK = launch_weights_splitk<128, 256>;     // (mlp_bwd.h: the split-K weights pass and its reduction)
+const auto kActorWeights = actor_weights_kernel<128, 256>;
+const auto kSacActorFwd = env_kernels(sac_actor_forward_kernel<CartActEnv, 128, 256>, sac_actor_forward_kernel<PendActEnv, 128, 256>);
+const auto kSacActorBwd = env_kernels(sac_actor_backward_kernel<CartActEnv, 128, 256>, sac_actor_backward_kernel<PendActEnv, 128, 256>);
+const auto kPendDdpgFront = embed_kernels(pend_ddpg_critic_front_kernel<128, 256>, pend_ddpg_critic_front_kernel<256, 256>);
+const auto kPendDdpgBack = embed_kernels(pend_critic_back_kernel<128, 256, 0>, pend_critic_back_kernel<256, 256, 0>);
+
+int tiles(int n) { return (n + kRows - 1) / kRows; }
+
+// ---- the networks
+// Every call site passes what its entry point has always tested; they do not agree with each other.
+struct NetSlot { const rpo_mlp* host; Mlp* dev; };
+enum ActorTest { kActorTanh = 0, kActorGauss = 1, kActorShape = 2 };   // check_actor's two heads | shape only: no head_dim, no weights
+constexpr int kEmbedAny = 0;                                     // (the launch refuses what is not instantiated, behind the other checks)
+
+// An entry point's actor -> m.  E: 128 (the actor pipelines' only instantiation) or kEmbedAny
+int fill_actor(int obs_dim, const rpo_mlp* host, Mlp& m, ActorTest test, int E) {
+    if (!host) return RPO_ERR_NULL;
+    m = to_dev(host);
+    if (test == kActorShape) {
+        if (m.S != obs_dim || m.A != 0 || m.n_out != 1 || m.cat || m.H != 256) return RPO_ERR_ARG;
+    } else if (int e = check_actor(m, obs_dim, test)) {
+        return e;
+    }
+    return E != kEmbedAny && m.E != E ? RPO_ERR_ARG : 0;
+}
+
+// An entry point's critics: NULL ones first, then the shapes.  E: the width they have to have (the actor's), or NULL where there
+// is no actor: 128 or 256, the first critic's for all.  hd: whether head_dim is tested
+int fill_critics(int obs_dim, std::initializer_list<NetSlot> critics, const int* E, bool hd) {
+    for (const NetSlot& q : critics)
+        if (!q.host) return RPO_ERR_NULL;
+    for (const NetSlot& q : critics) *q.dev = to_dev(q.host);
+    const int want = E ? *E : critics.begin()->dev->E;
+    for (const NetSlot& q : critics)
+        if (int e = check_critic(*q.dev, obs_dim, want, !E, hd)) return e;
+    return 0;
+}
+
+// ---- rollout
+// RPO_TUNE_ROLLOUT_WIDE: 0 / 1 force the 16- / 64-lane row tiles, 3 / 4 the streaming form (16- / 64-lane groups; tests), 2 (default)
+// by size: 16-lane tiles below 64 x 192 lanes, 64-lane tiles up to RPO_ROLLOUT_STREAM_FROM, the streaming form from there.  64
+// lanes per workgroup once that still fills the chip: the 128 KB hidden-layer matrix is streamed once per workgroup, so wider
+// tiles cut the L2 traffic 4x.
+template <class ENV>
+int launch_rollout(const RolloutKernels<ENV>& k, const RolloutArgs<ENV>& args, const typename ENV::Consts& c, int n_envs, void* stream) {
+    const int sel = rpo_tune(RPO_TUNE_ROLLOUT_WIDE);
+    if (sel == 3 || sel == 4 || (sel == 2 && n_envs >= RPO_ROLLOUT_STREAM_FROM)) {
+        const int e = rpo_rollout_stream_launch(std::is_same<ENV, CartEnv>::value ? 0 : 1, &args, &c, n_envs, stream);
+        if (e >= 0) return e;                                    // (-1: the streaming form does not apply to this network / env)
+    }
+    const int E = args.actor.E;
+    if (E == 128 && (sel == 0 || sel == 1 ? sel == 1 : n_envs >= 64 * 192))
+        return launch(k.wide, dim3((n_envs + 63) / 64), kFwdThreads, 0, stream, args, c);
+    return launch_embed(k.tile, E, dim3((n_envs + 15) / 16), kFwdThreads, stream, args, c);
+}
+
+// The env's constants: CartSafe's table, loaded and checked | SpringPendulum has none
+int env_consts(CartConsts& c, const float* consts_host, int partial) { return load_consts(c, consts_host, partial); }
+int env_consts(PendEnv::Consts& c, const float*, int) { c = PendEnv::Consts{0}; return 0; }
+
+// r: the arguments both rollouts take, in the struct the riding rollout of nsplit.hip takes them in (part, lane_begin, lane_end unused)
+template <class ENV>
+int rollout(const RolloutKernels<ENV>& k, const rpo_mlp* actor_host, const rpo_rollout_rider& r, const float* consts_host, int partial,
+            void* stream) {
+    if (!actor_host) return RPO_ERR_NULL;
+    if (r.n_envs <= 0 || r.max_episode_steps <= 0 || r.max_steps < 0) return RPO_ERR_ARG;
+    if (r.noise_mode != RPO_NOISE_NONE && r.noise_mode != RPO_NOISE_PHILOX && r.noise_mode != RPO_NOISE_CLIP_ONLY) return RPO_ERR_ARG;
+    if (!r.state || !r.action || !r.ep_len || !r.ep_ret || !r.ep_count || !r.ctrl) return RPO_ERR_NULL;
+    if ((r.rows && r.cap_steps <= 0) || (r.stats && r.stats_cap <= 0)) return RPO_ERR_ARG;
+    RolloutArgs<ENV> args{};
+    args.actor = to_dev(actor_host);
+    if (int e = check_actor(args.actor, ENV::OBS, r.gauss)) return e;
+    typename ENV::Consts c;
+    if (int e = env_consts(c, consts_host, partial)) return e;
+    rollout_env_args(r, args.act, args.step);
+    args.scale = r.scale; args.base = r.base; args.gauss = r.gauss; args.defer_clock = r.defer_clock ? 1 : 0;
+    return launch_rollout(k, args, c, r.n_envs, stream);
+}
+
+// ---- critic forward
+// The replay sample's fields, for either argument struct (the seed is named differently in the two)
+template <class Args>
+void fill_sample(Args& a, float scale, float base, const float* rows, long long cap_steps, int n_envs, int batch, float* batch_out,
+                 long long* idx_out, const long long* idx_in, unsigned sample_salt, const long long* ctrl) {
+    a.scale = scale; a.base = base; a.rows = rows; a.cap_steps = cap_steps; a.n_envs = n_envs; a.batch = batch;
+    a.batch_out = batch_out; a.idx_out = idx_out; a.idx_in = idx_in; a.salt = (uint32_t)sample_salt; a.ctrl = ctrl;
+}
+
+// ... the policy draw's (the RPOSAC forward and front), and the projection's (the CartSafe forwards)
+void fill_noise(SacCriticFwdArgs& a, const float* eps_in, unsigned long long noise_seed, unsigned noise_id_base, unsigned noise_salt) {
+    a.eps_in = eps_in; a.seed = (uint64_t)noise_seed; a.noise_id_base = (uint32_t)noise_id_base; a.noise_salt = (uint32_t)noise_salt;
+}
+
+template <class Args>
+void fill_projection(Args& a, int max_steps, float corr_lr, float corr_eps, float corr_momentum, float box_lo, float box_hi) {
+    a.max_steps = max_steps; a.corr_lr = corr_lr; a.corr_eps = corr_eps; a.corr_momentum = corr_momentum;
+    a.box_lo = box_lo; a.box_hi = box_hi;
+}
+
+// ---- actor update
+// The env launch of an actor pipeline over the batch's row tiles: CartSafe's constants are loaded (and checked) here
+template <class C, class P, class A>
+int launch_actor(const EnvKernels<C, P>& k, int env, int batch, int roles, int threads, void* stream, const A& a, const float* consts_host,
+                 int partial) {
+    const dim3 grid(tiles(batch), roles);
+    if (env != 0) return launch(k.pend, grid, threads, 0, stream, a, PendActEnv::Consts{0});
+    CartConsts c;
+    if (int e = load_consts(c, consts_host, partial)) return e;
+    return launch(k.cart, grid, threads, 0, stream, a, c);
+}
+
+// The actor's gradient struct of a backward pipeline: the fields its weights pass writes (gauss: the second head's too), and the
+// alignment the split-K scratch is zeroed with (as rpo_mlp_backward)
+int actor_grad(const rpo_mlp_grad* g, int gauss, MlpGrad& ag) {
+    ag = grad_dev(g);
+    if (!ag.Ws || !ag.bs || !ag.W0 || !ag.b0 || !ag.W1 || !ag.b1 || (gauss && (!ag.W1b || !ag.b1b))) return RPO_ERR_NULL;
+    if ((reinterpret_cast<uintptr_t>(g->splitk_scratch) & 15u) != 0) return RPO_ERR_ARG;
+    return 0;
+}
+
+// The BwdArgs of the policy step over the gathered batch (row: floats per row).  A critic only propagates (d/d action, and dx0
+// for a shared embedding): no parameter gradients of its own
+BwdArgs critic_bwd(const Mlp& q, int n, const float* batch, int row, const float* actions, const float* x0, const float* h1,
+                   const float* dq, float* dh, float* dx0, float* da) {
+    return BwdArgs{q, grad_dev(nullptr), n, batch, row, actions, 2, x0, h1, dq, dh, dx0, da, 0, 0, nullptr};
+}
+
+BwdArgs actor_bwd(const Mlp& actor, const MlpGrad& ag, int n, const float* batch, int row, const float* x0, const float* h1,
+                  const float* dout, float* dh, float* dx0, float* gradmax) {
+    return BwdArgs{actor, ag, n, batch, row, nullptr, 0, x0, h1, dout, dh, dx0, nullptr, 1, 0, gradmax};
+}
+
+// The actor's weights pass behind a backward pipeline: split-K from RPO_SPLITK_FROM rows (large batches)
+int actor_weights(const BwdArgs& actor, const rpo_mlp_grad* g, void* stream) {
+    const Mlp& m = actor.net;
+    const int grid_w = (m.H / 16) * (128 / 64) + m.H / 64 + mlp_fl_blocks(m.E * (m.S + 1));
+    const SplitK sk = splitk_plan(actor, g->splitk_scratch, g->splitk_floats);
+    if (sk.Z > 0) return kWeightsSplitK(actor, sk, grid_w, (hipStream_t)stream);
+    return launch(kActorWeights, dim3(grid_w), kThreads, 0, stream, actor);
+}
+
+}  // namespace
+
 extern "C" {
 
 int rpo_cartsafe_rollout(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* state,
@@ -813,24 +940,10 @@ int rpo_cartsafe_rollout(const rpo_mlp* actor_host, int gauss, float scale, floa
                          float corr_momentum, const float* consts_host, int partial, int max_episode_steps,
                          int auto_reset, float viol_thresh, unsigned long long seed, unsigned env_id_base, int defer_clock,
                          void* stream) {
-    if (!actor_host) return RPO_ERR_NULL;
-    if (n_envs <= 0 || max_episode_steps <= 0 || max_steps < 0) return RPO_ERR_ARG;
-    if (noise_mode != RPO_NOISE_NONE && noise_mode != RPO_NOISE_PHILOX && noise_mode != RPO_NOISE_CLIP_ONLY) return RPO_ERR_ARG;
-    if (!state || !action || !ep_len || !ep_ret || !ep_count || !ctrl) return RPO_ERR_NULL;
-    if ((rows && cap_steps <= 0) || (stats && stats_cap <= 0)) return RPO_ERR_ARG;
-    RolloutArgs<CartEnv> args{};
-    args.actor = to_dev(actor_host);
-    if (int e = check_actor(args.actor, 6, gauss)) return e;
-    CartConsts c;
-    if (int e = load_consts(c, consts_host, partial)) return e;
-    args.scale = scale; args.base = base; args.gauss = gauss; args.defer_clock = defer_clock ? 1 : 0;
-    args.act = rpo_cart_dev::ActArgs{n_envs, nullptr, nullptr, action, nullptr, noise_mode, eps_start, eps_end, eps_decay,
-                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, (uint64_t)seed,
-                                     (uint32_t)env_id_base, ctrl, stats, stats_cap};
-    args.step = rpo_cart_dev::StepArgs{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap,
-                                       ctrl, max_episode_steps, auto_reset, viol_thresh, (uint64_t)seed,
-                                       (uint32_t)env_id_base, 0};
-    return launch_rollout<CartEnv>(args, c, n_envs, stream);
+    const rpo_rollout_rider r{n_envs, gauss, scale, base, state, nullptr, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats,
+                              stats_cap, noise_mode, ctrl, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps,
+                              corr_momentum, max_episode_steps, auto_reset, viol_thresh, env_id_base, seed, nullptr, 0, 0, defer_clock};
+    return rollout(kRolloutCart, actor_host, r, consts_host, partial, stream);
 }
 
 int rpo_pendulum_rollout(const rpo_mlp* actor_host, int gauss, float scale, float base, int n_envs, float* internal,
@@ -839,22 +952,10 @@ int rpo_pendulum_rollout(const rpo_mlp* actor_host, int gauss, float scale, floa
                          float eps_start, float eps_end, float eps_decay, float box_lo, float box_hi, int max_steps,
                          float corr_lr, float corr_eps, float corr_momentum, int max_episode_steps, int auto_reset,
                          float viol_thresh, unsigned long long seed, unsigned env_id_base, int defer_clock, void* stream) {
-    if (!actor_host) return RPO_ERR_NULL;
-    if (n_envs <= 0 || max_episode_steps <= 0 || max_steps < 0) return RPO_ERR_ARG;
-    if (noise_mode != RPO_NOISE_NONE && noise_mode != RPO_NOISE_PHILOX && noise_mode != RPO_NOISE_CLIP_ONLY) return RPO_ERR_ARG;
-    if (!internal || !action || !ep_len || !ep_ret || !ep_count || !ctrl) return RPO_ERR_NULL;
-    if ((rows && cap_steps <= 0) || (stats && stats_cap <= 0)) return RPO_ERR_ARG;
-    RolloutArgs<PendEnv> args{};
-    args.actor = to_dev(actor_host);
-    if (int e = check_actor(args.actor, 5, gauss)) return e;
-    args.scale = scale; args.base = base; args.gauss = gauss; args.defer_clock = defer_clock ? 1 : 0;
-    args.act = rpo_pend_dev::ActArgs{n_envs, nullptr, 5, nullptr, nullptr, action, nullptr, noise_mode, eps_start, eps_end,
-                                     eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, (uint64_t)seed,
-                                     (uint32_t)env_id_base, ctrl, stats, stats_cap};
-    args.step = rpo_pend_dev::StepArgs{n_envs, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats,
-                                       stats_cap, ctrl, max_episode_steps, auto_reset, viol_thresh, (uint64_t)seed,
-                                       (uint32_t)env_id_base};
-    return launch_rollout<PendEnv>(args, PendEnv::Consts{0}, n_envs, stream);
+    const rpo_rollout_rider r{n_envs, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats,
+                              stats_cap, noise_mode, ctrl, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps,
+                              corr_momentum, max_episode_steps, auto_reset, viol_thresh, env_id_base, seed, nullptr, 0, 0, defer_clock};
+    return rollout(kRolloutPend, actor_host, r, nullptr, 0, stream);
 }
 
 int rpo_cartsafe_ddpg_critic_forward(const rpo_mlp* actor_target_host, const rpo_mlp* critic_target_host,
@@ -869,29 +970,14 @@ int rpo_cartsafe_ddpg_critic_forward(const rpo_mlp* actor_target_host, const rpo
     if (batch <= 0 || cap_steps <= 0 || n_envs <= 0 || max_steps < 0) return RPO_ERR_ARG;
     if (!rows || !batch_out || !ctrl || !q_out || !qn_out || !x0_save || !h1_save) return RPO_ERR_NULL;
     CriticFwdArgs a{};
-    a.actor_target = to_dev(actor_target_host); a.critic_target = to_dev(critic_target_host); a.critic = to_dev(critic_host);
-    const Mlp& at = a.actor_target;
-    const Mlp& ct = a.critic_target;
-    const Mlp& cr = a.critic;
-    if (at.S != 6 || at.A != 0 || at.n_out != 1 || at.cat || ct.S != 6 || ct.A != 2 || ct.cat || cr.S != 6 || cr.A != 2 || cr.cat ||
-        at.H != 256 || ct.H != 256 || cr.H != 256 || at.E != ct.E || at.E != cr.E || ct.n_out != 1 || cr.n_out != 1)
-        return RPO_ERR_ARG;
+    if (int e = fill_actor(6, actor_target_host, a.actor_target, kActorShape, kEmbedAny)) return e;
+    if (int e = fill_critics(6, {{critic_target_host, &a.critic_target}, {critic_host, &a.critic}}, &a.actor_target.E, false)) return e;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
-    a.scale = scale; a.base = base; a.rows = rows; a.cap_steps = cap_steps; a.n_envs = n_envs; a.batch = batch;
-    a.batch_out = batch_out; a.idx_out = idx_out; a.idx_in = idx_in; a.seed = (uint64_t)seed; a.salt = (uint32_t)sample_salt;
-    a.ctrl = ctrl; a.max_steps = max_steps; a.corr_lr = corr_lr; a.corr_eps = corr_eps; a.corr_momentum = corr_momentum;
-    a.box_lo = box_lo; a.box_hi = box_hi; a.q_out = q_out; a.qn_out = qn_out; a.x0_save = x0_save; a.h1_save = h1_save;
-    const int grid = (batch + kRows - 1) / kRows;                   // x: row tile, y: role (target chain | critic)
-    if (at.E == 128) {
-        hipLaunchKernelGGL((cart_ddpg_critic_forward_kernel<128, 256>), dim3(grid, 2), dim3(kFwdThreads), 0, (hipStream_t)stream, a, c);
-    } else if (at.E == 256) {
-        hipLaunchKernelGGL((cart_ddpg_critic_forward_kernel<256, 256>), dim3(grid, 2), dim3(kFwdThreads), 0, (hipStream_t)stream, a, c);
-    } else {
-        return RPO_ERR_ARG;
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    fill_sample(a, scale, base, rows, cap_steps, n_envs, batch, batch_out, idx_out, idx_in, sample_salt, ctrl);
+    fill_projection(a, max_steps, corr_lr, corr_eps, corr_momentum, box_lo, box_hi);
+    a.seed = (uint64_t)seed; a.q_out = q_out; a.qn_out = qn_out; a.x0_save = x0_save; a.h1_save = h1_save;
+    return launch_embed(kCartDdpgCritic, a.actor_target.E, dim3(tiles(batch), 2), kFwdThreads, stream, a, c);   // y: target | critic
 }
 
 int rpo_cartsafe_sac_critic_forward(const rpo_mlp* actor_host, const rpo_mlp* critic_target1_host,
@@ -911,51 +997,18 @@ int rpo_cartsafe_sac_critic_forward(const rpo_mlp* actor_host, const rpo_mlp* cr
         !x0_save2 || !h1_save2)
         return RPO_ERR_NULL;
     SacCriticFwdArgs a{};
-    a.actor = to_dev(actor_host);
-    a.critic_target1 = to_dev(critic_target1_host); a.critic_target2 = to_dev(critic_target2_host);
-    a.critic1 = to_dev(critic1_host); a.critic2 = to_dev(critic2_host);
-    if (int e = check_actor(a.actor, 6, 1)) return e;
-    const Mlp* qs[4] = {&a.critic_target1, &a.critic_target2, &a.critic1, &a.critic2};
-    for (const Mlp* q : qs)
-        if (q->S != 6 || q->A != 2 || q->cat || q->H != 256 || q->E != a.actor.E || q->n_out != 1 || q->hd > 1) return RPO_ERR_ARG;
+    if (int e = fill_actor(6, actor_host, a.actor, kActorGauss, kEmbedAny)) return e;
+    if (int e = fill_critics(6, {{critic_target1_host, &a.critic_target1}, {critic_target2_host, &a.critic_target2},
+                                 {critic1_host, &a.critic1}, {critic2_host, &a.critic2}}, &a.actor.E, true))
+        return e;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
-    a.scale = scale; a.base = base; a.rows = rows; a.cap_steps = cap_steps; a.n_envs = n_envs; a.batch = batch;
-    a.batch_out = batch_out; a.idx_out = idx_out; a.idx_in = idx_in; a.eps_in = eps_in; a.seed = (uint64_t)noise_seed;
-    a.sample_seed = (uint64_t)sample_seed; a.salt = (uint32_t)sample_salt; a.noise_salt = (uint32_t)noise_salt;
-    a.noise_id_base = (uint32_t)noise_id_base; a.ctrl = ctrl; a.max_steps = max_steps; a.corr_lr = corr_lr;
-    a.corr_eps = corr_eps; a.corr_momentum = corr_momentum; a.box_lo = box_lo; a.box_hi = box_hi;
-    a.q1_out = q1_out; a.q2_out = q2_out; a.qn1_out = qn1_out; a.qn2_out = qn2_out; a.logp_out = logp_out;
-    a.x0_save1 = x0_save1; a.h1_save1 = h1_save1; a.x0_save2 = x0_save2; a.h1_save2 = h1_save2;
-    const int grid = (batch + kRows - 1) / kRows;                   // x: row tile, y: role
-    if (a.actor.E == 128) {
-        hipLaunchKernelGGL((cart_sac_critic_forward_kernel<128, 256>), dim3(grid, 4), dim3(kFwdThreads), 0, (hipStream_t)stream, a, c);
-    } else if (a.actor.E == 256) {
-        hipLaunchKernelGGL((cart_sac_critic_forward_kernel<256, 256>), dim3(grid, 4), dim3(kFwdThreads), 0, (hipStream_t)stream, a, c);
-    } else {
-        return RPO_ERR_ARG;
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-static int fill_sac_args(SacCriticFwdArgs& a, int obs_dim, const rpo_mlp* actor_host, const rpo_mlp* ct1, const rpo_mlp* ct2,
-                         const rpo_mlp* c1, const rpo_mlp* c2, bool need_actor, bool need_critics) {
-    if (need_actor) {
-        if (!actor_host) return RPO_ERR_NULL;
-        a.actor = to_dev(actor_host);
-        if (int e = check_actor(a.actor, obs_dim, 1)) return e;
-    }
-    if (need_critics) {
-        if (!ct1 || !ct2 || !c1 || !c2) return RPO_ERR_NULL;
-        a.critic_target1 = to_dev(ct1); a.critic_target2 = to_dev(ct2); a.critic1 = to_dev(c1); a.critic2 = to_dev(c2);
-        const Mlp* qs[4] = {&a.critic_target1, &a.critic_target2, &a.critic1, &a.critic2};
-        for (const Mlp* q : qs)
-            if (q->S != obs_dim || q->A != 2 || q->cat || q->H != 256 || (q->E != 128 && q->E != 256) || q->E != qs[0]->E ||
-                q->n_out != 1 || q->hd > 1)
-                return RPO_ERR_ARG;
-    }
-    return 0;
+    fill_sample(a, scale, base, rows, cap_steps, n_envs, batch, batch_out, idx_out, idx_in, sample_salt, ctrl);
+    fill_noise(a, eps_in, noise_seed, noise_id_base, noise_salt);
+    fill_projection(a, max_steps, corr_lr, corr_eps, corr_momentum, box_lo, box_hi);
+    a.sample_seed = (uint64_t)sample_seed; a.q1_out = q1_out; a.q2_out = q2_out; a.qn1_out = qn1_out; a.qn2_out = qn2_out;
+    a.logp_out = logp_out; a.x0_save1 = x0_save1; a.h1_save1 = h1_save1; a.x0_save2 = x0_save2; a.h1_save2 = h1_save2;
+    return launch_embed(kCartSacCritic, a.actor.E, dim3(tiles(batch), 4), kFwdThreads, stream, a, c);   // y: role
 }
 
 int rpo_pendulum_sac_critic_front(const rpo_mlp* actor_host, float scale, float base, float box_lo, float box_hi,
@@ -967,22 +1020,11 @@ int rpo_pendulum_sac_critic_front(const rpo_mlp* actor_host, float scale, float 
     if (batch <= 0 || cap_steps <= 0 || n_envs <= 0) return RPO_ERR_ARG;
     if (!rows || !batch_out || !ctrl || !ap_out || !logp_out) return RPO_ERR_NULL;
     SacCriticFwdArgs a{};
-    if (int e = fill_sac_args(a, 5, actor_host, nullptr, nullptr, nullptr, nullptr, true, false)) return e;
-    a.scale = scale; a.base = base; a.box_lo = box_lo; a.box_hi = box_hi; a.rows = rows; a.cap_steps = cap_steps;
-    a.n_envs = n_envs; a.batch = batch; a.batch_out = batch_out; a.idx_out = idx_out; a.idx_in = idx_in; a.eps_in = eps_in;
-    a.sample_seed = (uint64_t)sample_seed; a.salt = (uint32_t)sample_salt; a.seed = (uint64_t)noise_seed;
-    a.noise_id_base = (uint32_t)noise_id_base; a.noise_salt = (uint32_t)noise_salt; a.ctrl = ctrl; a.ap_out = ap_out;
-    a.logp_out = logp_out;
-    const int grid = (batch + kRows - 1) / kRows;
-    if (a.actor.E == 128) {
-        hipLaunchKernelGGL((pend_sac_critic_front_kernel<128, 256>), dim3(grid), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    } else if (a.actor.E == 256) {
-        hipLaunchKernelGGL((pend_sac_critic_front_kernel<256, 256>), dim3(grid), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    } else {
-        return RPO_ERR_ARG;
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = fill_actor(5, actor_host, a.actor, kActorGauss, kEmbedAny)) return e;
+    fill_sample(a, scale, base, rows, cap_steps, n_envs, batch, batch_out, idx_out, idx_in, sample_salt, ctrl);
+    fill_noise(a, eps_in, noise_seed, noise_id_base, noise_salt);
+    a.sample_seed = (uint64_t)sample_seed; a.box_lo = box_lo; a.box_hi = box_hi; a.ap_out = ap_out; a.logp_out = logp_out;
+    return launch_embed(kPendSacFront, a.actor.E, dim3(tiles(batch)), kFwdThreads, stream, a);
 }
 
 int rpo_pendulum_sac_critic_back(const rpo_mlp* critic_target1_host, const rpo_mlp* critic_target2_host,
@@ -994,130 +1036,70 @@ int rpo_pendulum_sac_critic_back(const rpo_mlp* critic_target1_host, const rpo_m
         !h1_save2)
         return RPO_ERR_NULL;
     SacCriticFwdArgs a{};
-    if (int e = fill_sac_args(a, 5, nullptr, critic_target1_host, critic_target2_host, critic1_host, critic2_host, false, true))
+    if (int e = fill_critics(5, {{critic_target1_host, &a.critic_target1}, {critic_target2_host, &a.critic_target2},
+                                 {critic1_host, &a.critic1}, {critic2_host, &a.critic2}}, nullptr, true))
         return e;
     a.batch = batch; a.batch_out = batch_rows; a.next_actions = next_actions;
     a.q1_out = q1_out; a.q2_out = q2_out; a.qn1_out = qn1_out; a.qn2_out = qn2_out;
     a.x0_save1 = x0_save1; a.h1_save1 = h1_save1; a.x0_save2 = x0_save2; a.h1_save2 = h1_save2;
-    const int grid = (batch + kRows - 1) / kRows;                   // x: row tile, y: role
-    if (a.critic1.E == 128) {
-        hipLaunchKernelGGL((pend_critic_back_kernel<128, 256, 1>), dim3(grid, 4), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    } else {
-        hipLaunchKernelGGL((pend_critic_back_kernel<256, 256, 1>), dim3(grid, 4), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_embed(kPendSacBack, a.critic1.E, dim3(tiles(batch), 4), kFwdThreads, stream, a);   // y: role
 }
 
-int rpo_ddpg_actor_forward(int env, const rpo_mlp* actor_host, const rpo_mlp* critic_host, float scale, float base,
-                                    float box_lo, float box_hi, float eps_start, float eps_end, float eps_decay,
-                                    const float* batch, int batch_size, const float* noise_in, unsigned long long seed,
-                                    unsigned noise_id_base, unsigned noise_salt, const long long* ctrl, const float* nu,
-                                    const float* consts_host, int partial, float* ap_det, float* noise_out,
-                                    float* actions, float* q_out, float* dq_out, float* g_act, float* partial_out,
-                                    float* actor_x0, float* actor_h1, float* critic_x0, float* critic_h1, void* stream) {
+int rpo_ddpg_actor_forward(int env, const rpo_mlp* actor_host, const rpo_mlp* critic_host, float scale, float base, float box_lo,
+                           float box_hi, float eps_start, float eps_end, float eps_decay, const float* batch, int batch_size,
+                           const float* noise_in, unsigned long long seed, unsigned noise_id_base, unsigned noise_salt,
+                           const long long* ctrl, const float* nu, const float* consts_host, int partial, float* ap_det,
+                           float* noise_out, float* actions, float* q_out, float* dq_out, float* g_act, float* partial_out,
+                           float* actor_x0, float* actor_h1, float* critic_x0, float* critic_h1, void* stream) {
     if (!actor_host || !critic_host) return RPO_ERR_NULL;
     if (batch_size <= 0) return RPO_ERR_ARG;
     if (!batch || !ctrl || !nu || !ap_det || !noise_out || !actions || !q_out || !dq_out || !g_act || !partial_out ||
         !actor_x0 || !actor_h1 || !critic_x0 || !critic_h1)
         return RPO_ERR_NULL;
     if (env != 0 && env != 1) return RPO_ERR_ARG;
-    const int obs_dim = env == 0 ? 6 : 5;
     ActorFwdArgs a{};
-    a.actor = to_dev(actor_host); a.critic = to_dev(critic_host);
-    if (int e = check_actor(a.actor, obs_dim, 0)) return e;
-    if (a.actor.E != 128 || a.critic.S != obs_dim || a.critic.A != 2 || a.critic.cat || a.critic.H != 256 || a.critic.E != 128 ||
-        a.critic.n_out != 1 || a.critic.hd > 1)
-        return RPO_ERR_ARG;
+    const int obs_dim = env == 0 ? 6 : 5;
+    if (int e = fill_actor(obs_dim, actor_host, a.actor, kActorTanh, 128)) return e;
+    if (int e = fill_critics(obs_dim, {{critic_host, &a.critic}}, &a.actor.E, true)) return e;
     a.scale = scale; a.base = base; a.box_lo = box_lo; a.box_hi = box_hi; a.eps_start = eps_start; a.eps_end = eps_end;
     a.eps_decay = eps_decay; a.batch = batch; a.B = batch_size; a.noise_in = noise_in; a.seed = (uint64_t)seed;
     a.noise_id_base = (uint32_t)noise_id_base; a.noise_salt = (uint32_t)noise_salt; a.ctrl = ctrl; a.nu = nu;
     a.ap_det = ap_det; a.noise_out = noise_out; a.actions = actions; a.q_out = q_out; a.dq_out = dq_out; a.g_act = g_act;
     a.partial = partial_out; a.ax0 = actor_x0; a.ah1 = actor_h1; a.cx0 = critic_x0; a.ch1 = critic_h1;
-    const int grid = (batch_size + kRows - 1) / kRows;
-    if (env == 0) {
-        CartConsts c;
-        if (int e = load_consts(c, consts_host, partial)) return e;
-        hipLaunchKernelGGL((ddpg_actor_forward_kernel<CartActEnv, 128, 256>), dim3(grid), dim3(kFwdThreads), 0,
-                           (hipStream_t)stream, a, c);
-    } else {
-        hipLaunchKernelGGL((ddpg_actor_forward_kernel<PendActEnv, 128, 256>), dim3(grid), dim3(kFwdThreads), 0,
-                           (hipStream_t)stream, a, PendActEnv::Consts{0});
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_actor(kDdpgActorFwd, env, batch_size, 1, kFwdThreads, stream, a, consts_host, partial);
 }
 
-int rpo_ddpg_actor_backward(int env, const rpo_mlp* actor_host, const rpo_mlp_grad* actor_grad_host,
-                                     const rpo_mlp* critic_host, int shared_embedding, const float* batch,
-                                     int batch_size, const float* actions, const float* g_act, const float* ap_det,
-                                     const float* noise, const float* dq, float eps_start, float eps_end,
-                                     float eps_decay, float box_lo, float box_hi, float scale, float base,
-                                     const long long* ctrl, const float* consts_host, int partial,
-                                     const float* actor_x0, const float* actor_h1, const float* critic_x0,
-                                     const float* critic_h1, float* actor_dh, float* actor_dx0, float* critic_dh,
-                                     float* critic_dx0, float* da, float* dout, const float* partial_in, float* lag_out,
-                                     float* nu_grad, float* gradmax, void* stream) {
+int rpo_ddpg_actor_backward(int env, const rpo_mlp* actor_host, const rpo_mlp_grad* actor_grad_host, const rpo_mlp* critic_host,
+                            int shared_embedding, const float* batch, int batch_size, const float* actions, const float* g_act,
+                            const float* ap_det, const float* noise, const float* dq, float eps_start, float eps_end,
+                            float eps_decay, float box_lo, float box_hi, float scale, float base, const long long* ctrl,
+                            const float* consts_host, int partial, const float* actor_x0, const float* actor_h1,
+                            const float* critic_x0, const float* critic_h1, float* actor_dh, float* actor_dx0, float* critic_dh,
+                            float* critic_dx0, float* da, float* dout, const float* partial_in, float* lag_out,
+                            float* nu_grad, float* gradmax, void* stream) {
     if (!actor_host || !actor_grad_host || !critic_host) return RPO_ERR_NULL;
     if (batch_size <= 0) return RPO_ERR_ARG;
     if (!batch || !actions || !g_act || !ap_det || !noise || !dq || !ctrl || !da || !dout || !partial_in || !lag_out || !nu_grad)
         return RPO_ERR_NULL;
     if (env != 0 && env != 1) return RPO_ERR_ARG;
-    const int obs_dim = env == 0 ? 6 : 5, row = env == 0 ? RPO_CART_ROW : RPO_PEND_ROW;
     ActorBwdArgs p{};
-    Mlp actor = to_dev(actor_host), critic = to_dev(critic_host);
-    if (int e = check_actor(actor, obs_dim, 0)) return e;
-    if (actor.E != 128 || critic.S != obs_dim || critic.A != 2 || critic.cat || critic.H != 256 || critic.E != 128 ||
-        critic.n_out != 1)
-        return RPO_ERR_ARG;
+    Mlp actor, critic;
+    MlpGrad ag;
+    const int obs_dim = env == 0 ? 6 : 5;
+    if (int e = fill_actor(obs_dim, actor_host, actor, kActorTanh, 128)) return e;
+    if (int e = fill_critics(obs_dim, {{critic_host, &critic}}, &actor.E, false)) return e;
     if (!actor_x0 || !actor_h1 || !critic_x0 || !critic_h1 || !actor_dh || !actor_dx0 || !critic_dh || !critic_dx0)
         return RPO_ERR_NULL;
-    MlpGrad none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    MlpGrad ag{actor_grad_host->Ws, actor_grad_host->bs, actor_grad_host->Wa, actor_grad_host->ba, actor_grad_host->W0,
-               actor_grad_host->b0, actor_grad_host->W1, actor_grad_host->b1, actor_grad_host->W1b, actor_grad_host->b1b};
-    if (!ag.Ws || !ag.bs || !ag.W0 || !ag.b0 || !ag.W1 || !ag.b1) return RPO_ERR_NULL;
-    if ((reinterpret_cast<uintptr_t>(actor_grad_host->splitk_scratch) & 15u) != 0) return RPO_ERR_ARG;   // (as rpo_mlp_backward)
-    // the critic only propagates (d/d action, and dx0 for a shared embedding): no parameter gradients of its own
-    p.critic = BwdArgs{critic, none, batch_size, batch, row, actions, 2, critic_x0, critic_h1, dq, critic_dh,
-                       critic_dx0, da, 0, 0, nullptr};
-    p.actor = BwdArgs{actor, ag, batch_size, batch, row, nullptr, 0, actor_x0, actor_h1, dout, actor_dh, actor_dx0,
-                      nullptr, 1, 0, gradmax};
+    if (int e = actor_grad(actor_grad_host, 0, ag)) return e;
+    const int B = batch_size, row = env == 0 ? RPO_CART_ROW : RPO_PEND_ROW;
+    p.critic = critic_bwd(critic, B, batch, row, actions, critic_x0, critic_h1, dq, critic_dh, critic_dx0, da);
+    p.actor = actor_bwd(actor, ag, B, batch, row, actor_x0, actor_h1, dout, actor_dh, actor_dx0, gradmax);
     p.g_act = g_act; p.ap_det = ap_det; p.noise = noise; p.eps_start = eps_start; p.eps_end = eps_end;
     p.eps_decay = eps_decay; p.box_lo = box_lo; p.box_hi = box_hi; p.scale = scale; p.base = base; p.ctrl = ctrl;
-    p.dout = dout; p.partial = partial_in; p.n_parts = (batch_size + kRows - 1) / kRows; p.lag_out = lag_out;
+    p.dout = dout; p.partial = partial_in; p.n_parts = tiles(batch_size); p.lag_out = lag_out;
     p.nu_grad = nu_grad; p.shared_embedding = shared_embedding;
-    const int grid = (batch_size + kRows - 1) / kRows;
-    if (env == 0) {
-        CartConsts c;
-        if (int e = load_consts(c, consts_host, partial)) return e;
-        hipLaunchKernelGGL((ddpg_actor_backward_kernel<CartActEnv, 128, 256>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
-                           p, c);
-    } else {
-        hipLaunchKernelGGL((ddpg_actor_backward_kernel<PendActEnv, 128, 256>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
-                           p, PendActEnv::Consts{0});
-    }
-    RPO_LAUNCH_CHECK();
-    const int fl_outputs = actor.E * (actor.S + 1);
-    const int grid_w = (actor.H / 16) * (128 / 64) + actor.H / 64 + mlp_fl_blocks(fl_outputs);
-    {
-        const SplitK sk = splitk_plan(p.actor, actor_grad_host->splitk_scratch, actor_grad_host->splitk_floats);
-        if (sk.Z > 0) return launch_weights_splitk<128, 256>(p.actor, sk, grid_w, (hipStream_t)stream);     // large batches
-    }
-    hipLaunchKernelGGL((actor_weights_kernel<128, 256>), dim3(grid_w), dim3(kThreads), 0, (hipStream_t)stream, p.actor);
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-static int sac_actor_nets(int obs_dim, const rpo_mlp* actor_host, const rpo_mlp* c1, const rpo_mlp* c2, Mlp& actor, Mlp& q1,
-                          Mlp& q2) {
-    if (!actor_host || !c1 || !c2) return RPO_ERR_NULL;
-    actor = to_dev(actor_host); q1 = to_dev(c1); q2 = to_dev(c2);
-    if (int e = check_actor(actor, obs_dim, 1)) return e;
-    if (actor.E != 128) return RPO_ERR_ARG;
-    const Mlp* qs[2] = {&q1, &q2};
-    for (const Mlp* q : qs)
-        if (q->S != obs_dim || q->A != 2 || q->cat || q->H != 256 || q->E != 128 || q->n_out != 1 || q->hd > 1) return RPO_ERR_ARG;
-    return 0;
+    if (int e = launch_actor(kDdpgActorBwd, env, batch_size, 1, kThreads, stream, p, consts_host, partial)) return e;
+    return actor_weights(p.actor, actor_grad_host, stream);
 }
 
 int rpo_sac_actor_forward(int env, const rpo_mlp* actor_host, const rpo_mlp* critic1_host, const rpo_mlp* critic2_host,
@@ -1133,24 +1115,16 @@ int rpo_sac_actor_forward(int env, const rpo_mlp* actor_host, const rpo_mlp* cri
         !actor_x0 || !actor_h1 || !critic1_x0 || !critic1_h1 || !critic2_x0 || !critic2_h1)
         return RPO_ERR_NULL;
     SacActorFwdArgs a{};
-    if (int e = sac_actor_nets(env == 0 ? 6 : 5, actor_host, critic1_host, critic2_host, a.actor, a.critic1, a.critic2)) return e;
+    if (!actor_host || !critic1_host || !critic2_host) return RPO_ERR_NULL;
+    const int obs_dim = env == 0 ? 6 : 5;
+    if (int e = fill_actor(obs_dim, actor_host, a.actor, kActorGauss, 128)) return e;
+    if (int e = fill_critics(obs_dim, {{critic1_host, &a.critic1}, {critic2_host, &a.critic2}}, &a.actor.E, true)) return e;
     a.scale = scale; a.base = base; a.box_lo = box_lo; a.box_hi = box_hi; a.alpha = alpha; a.batch = batch; a.B = batch_size;
     a.noise_in = noise_in; a.seed = (uint64_t)seed; a.noise_id_base = (uint32_t)noise_id_base;
     a.noise_salt = (uint32_t)noise_salt; a.ctrl = ctrl; a.nu = nu; a.raw = raw; a.noise_out = noise_out; a.logp = logp;
     a.actions = actions; a.dq1 = dq1; a.dq2 = dq2; a.g_act = g_act; a.partial = partial_out; a.ax0 = actor_x0;
     a.ah1 = actor_h1; a.c1x0 = critic1_x0; a.c1h1 = critic1_h1; a.c2x0 = critic2_x0; a.c2h1 = critic2_h1;
-    const int grid = (batch_size + kRows - 1) / kRows;
-    if (env == 0) {
-        CartConsts c;
-        if (int e = load_consts(c, consts_host, partial)) return e;
-        hipLaunchKernelGGL((sac_actor_forward_kernel<CartActEnv, 128, 256>), dim3(grid, 2), dim3(kFwdThreads), 0,
-                           (hipStream_t)stream, a, c);
-    } else {
-        hipLaunchKernelGGL((sac_actor_forward_kernel<PendActEnv, 128, 256>), dim3(grid, 2), dim3(kFwdThreads), 0,
-                           (hipStream_t)stream, a, PendActEnv::Consts{0});
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_actor(kSacActorFwd, env, batch_size, 2, kFwdThreads, stream, a, consts_host, partial);   // roles: critic 1 | 2
 }
 
 int rpo_sac_actor_backward(int env, const rpo_mlp* actor_host, const rpo_mlp_grad* actor_grad_host,
@@ -1171,43 +1145,22 @@ int rpo_sac_actor_backward(int env, const rpo_mlp* actor_host, const rpo_mlp_gra
         return RPO_ERR_NULL;
     SacActorBwdArgs p{};
     Mlp actor, q1, q2;
-    const int obs_dim = env == 0 ? 6 : 5, row = env == 0 ? RPO_CART_ROW : RPO_PEND_ROW;
-    if (int e = sac_actor_nets(obs_dim, actor_host, critic1_host, critic2_host, actor, q1, q2)) return e;
-    MlpGrad none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    MlpGrad ag{actor_grad_host->Ws, actor_grad_host->bs, actor_grad_host->Wa, actor_grad_host->ba, actor_grad_host->W0,
-               actor_grad_host->b0, actor_grad_host->W1, actor_grad_host->b1, actor_grad_host->W1b, actor_grad_host->b1b};
-    if (!ag.Ws || !ag.bs || !ag.W0 || !ag.b0 || !ag.W1 || !ag.b1 || !ag.W1b || !ag.b1b) return RPO_ERR_NULL;
-    if ((reinterpret_cast<uintptr_t>(actor_grad_host->splitk_scratch) & 15u) != 0) return RPO_ERR_ARG;   // (as rpo_mlp_backward)
-    p.critic1 = BwdArgs{q1, none, batch_size, batch, row, actions, 2, critic1_x0, critic1_h1, dq1, critic1_dh, critic1_dx0, da1,
-                        0, 0, nullptr};
-    p.critic2 = BwdArgs{q2, none, batch_size, batch, row, actions, 2, critic2_x0, critic2_h1, dq2, critic2_dh, critic2_dx0, da2,
-                        0, 0, nullptr};
-    p.actor = BwdArgs{actor, ag, batch_size, batch, row, nullptr, 0, actor_x0, actor_h1, dout, actor_dh, actor_dx0, nullptr, 1, 0,
-                      gradmax};
+    MlpGrad ag;
+    if (!actor_host || !critic1_host || !critic2_host) return RPO_ERR_NULL;
+    const int obs_dim = env == 0 ? 6 : 5;
+    if (int e = fill_actor(obs_dim, actor_host, actor, kActorGauss, 128)) return e;
+    if (int e = fill_critics(obs_dim, {{critic1_host, &q1}, {critic2_host, &q2}}, &actor.E, true)) return e;
+    if (int e = actor_grad(actor_grad_host, 1, ag)) return e;
+    const int B = batch_size, row = env == 0 ? RPO_CART_ROW : RPO_PEND_ROW;
+    p.critic1 = critic_bwd(q1, B, batch, row, actions, critic1_x0, critic1_h1, dq1, critic1_dh, critic1_dx0, da1);
+    p.critic2 = critic_bwd(q2, B, batch, row, actions, critic2_x0, critic2_h1, dq2, critic2_dh, critic2_dx0, da2);
+    p.actor = actor_bwd(actor, ag, B, batch, row, actor_x0, actor_h1, dout, actor_dh, actor_dx0, gradmax);
     p.logp = logp; p.q_dq1 = dq1; p.q_dq2 = dq2;
     p.g_act = g_act; p.raw = raw; p.noise = noise; p.dlogp = dlogp; p.box_lo = box_lo; p.box_hi = box_hi; p.scale = scale;
-    p.base = base; p.dout = dout; p.partial = partial_in; p.n_parts = (batch_size + kRows - 1) / kRows; p.lag_out = lag_out;
+    p.base = base; p.dout = dout; p.partial = partial_in; p.n_parts = tiles(batch_size); p.lag_out = lag_out;
     p.nu_grad = nu_grad; p.n_ineq = env == 0 ? 6 : 1; p.shared_embedding = shared_embedding;
-    const int grid = (batch_size + kRows - 1) / kRows;
-    if (env == 0) {
-        CartConsts c;
-        if (int e = load_consts(c, consts_host, partial)) return e;
-        hipLaunchKernelGGL((sac_actor_backward_kernel<CartActEnv, 128, 256>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
-                           p, c);
-    } else {
-        hipLaunchKernelGGL((sac_actor_backward_kernel<PendActEnv, 128, 256>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream,
-                           p, PendActEnv::Consts{0});
-    }
-    RPO_LAUNCH_CHECK();
-    const int fl_outputs = actor.E * (actor.S + 1);
-    const int grid_w = (actor.H / 16) * (128 / 64) + actor.H / 64 + mlp_fl_blocks(fl_outputs);
-    {
-        const SplitK sk = splitk_plan(p.actor, actor_grad_host->splitk_scratch, actor_grad_host->splitk_floats);
-        if (sk.Z > 0) return launch_weights_splitk<128, 256>(p.actor, sk, grid_w, (hipStream_t)stream);     // large batches
-    }
-    hipLaunchKernelGGL((actor_weights_kernel<128, 256>), dim3(grid_w), dim3(kThreads), 0, (hipStream_t)stream, p.actor);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = launch_actor(kSacActorBwd, env, batch_size, 1, kThreads, stream, p, consts_host, partial)) return e;
+    return actor_weights(p.actor, actor_grad_host, stream);
 }
 
 int rpo_pendulum_ddpg_critic_front(const rpo_mlp* actor_target_host, float scale, float base, const float* rows,
@@ -1218,21 +1171,10 @@ int rpo_pendulum_ddpg_critic_front(const rpo_mlp* actor_target_host, float scale
     if (batch <= 0 || cap_steps <= 0 || n_envs <= 0) return RPO_ERR_ARG;
     if (!rows || !batch_out || !ctrl || !ap_out) return RPO_ERR_NULL;
     SacCriticFwdArgs a{};
-    a.actor = to_dev(actor_target_host);
-    if (int e = check_actor(a.actor, 5, 0)) return e;
-    a.scale = scale; a.base = base; a.rows = rows; a.cap_steps = cap_steps; a.n_envs = n_envs; a.batch = batch;
-    a.batch_out = batch_out; a.idx_out = idx_out; a.idx_in = idx_in; a.sample_seed = (uint64_t)sample_seed;
-    a.salt = (uint32_t)sample_salt; a.ctrl = ctrl; a.ap_out = ap_out;
-    const int grid = (batch + kRows - 1) / kRows;
-    if (a.actor.E == 128) {
-        hipLaunchKernelGGL((pend_ddpg_critic_front_kernel<128, 256>), dim3(grid), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    } else if (a.actor.E == 256) {
-        hipLaunchKernelGGL((pend_ddpg_critic_front_kernel<256, 256>), dim3(grid), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    } else {
-        return RPO_ERR_ARG;
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = fill_actor(5, actor_target_host, a.actor, kActorTanh, kEmbedAny)) return e;
+    fill_sample(a, scale, base, rows, cap_steps, n_envs, batch, batch_out, idx_out, idx_in, sample_salt, ctrl);
+    a.sample_seed = (uint64_t)sample_seed; a.ap_out = ap_out;
+    return launch_embed(kPendDdpgFront, a.actor.E, dim3(tiles(batch)), kFwdThreads, stream, a);
 }
 
 int rpo_pendulum_ddpg_critic_back(const rpo_mlp* critic_target_host, const rpo_mlp* critic_host, int batch,
@@ -1242,22 +1184,10 @@ int rpo_pendulum_ddpg_critic_back(const rpo_mlp* critic_target_host, const rpo_m
     if (batch <= 0) return RPO_ERR_ARG;
     if (!batch_rows || !next_actions || !q_out || !qn_out || !x0_save || !h1_save) return RPO_ERR_NULL;
     SacCriticFwdArgs a{};
-    a.critic_target1 = to_dev(critic_target_host); a.critic1 = to_dev(critic_host);
-    const Mlp* qs[2] = {&a.critic_target1, &a.critic1};
-    for (const Mlp* q : qs)
-        if (q->S != 5 || q->A != 2 || q->cat || q->H != 256 || (q->E != 128 && q->E != 256) || q->E != qs[0]->E || q->n_out != 1 ||
-            q->hd > 1)
-            return RPO_ERR_ARG;
+    if (int e = fill_critics(5, {{critic_target_host, &a.critic_target1}, {critic_host, &a.critic1}}, nullptr, true)) return e;
     a.batch = batch; a.batch_out = batch_rows; a.next_actions = next_actions; a.q1_out = q_out; a.qn1_out = qn_out;
     a.x0_save1 = x0_save; a.h1_save1 = h1_save;
-    const int grid = (batch + kRows - 1) / kRows;                   // x: row tile, y: role (Q_targ | Q)
-    if (a.critic1.E == 128) {
-        hipLaunchKernelGGL((pend_critic_back_kernel<128, 256, 0>), dim3(grid, 2), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    } else {
-        hipLaunchKernelGGL((pend_critic_back_kernel<256, 256, 0>), dim3(grid, 2), dim3(kFwdThreads), 0, (hipStream_t)stream, a);
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_embed(kPendDdpgBack, a.critic1.E, dim3(tiles(batch), 2), kFwdThreads, stream, a);   // y: Q_targ | Q
 }
 
 }  // extern "C"

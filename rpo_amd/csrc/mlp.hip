@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "heads_dev.h"
+#include "host_glue.h"
 #include "mlp_bwd.h"
 #include "mlp_gemm.h"
 #include "mlp_tile.h"
@@ -26,6 +27,8 @@
 namespace {
 
 using namespace rpo_mlp_dev;
+using rpo_host::grad_dev;
+using rpo_host::to_dev;
 
 // ------------------------------------------------------------------------------------------------- forward
 // out_mode: 0 identity, 1 tanh-box on output 0 (scale * tanh(o) + base; BoxConstraint, model/utils.py:40-51)
@@ -247,9 +250,8 @@ int rpo_mlp_supported(int E, int H, int cat) {
 int rpo_mlp_forward(const rpo_mlp* net_host, int n, const float* s, int s_stride, const float* a, int a_stride,
                     float* out, float* x0_save, float* h1_save, int out_mode, float scale, float base, void* stream) {
     if (!net_host) return RPO_ERR_NULL;
-    Mlp net{net_host->Ws, net_host->bs, net_host->Wa, net_host->ba, net_host->W0, net_host->b0, net_host->W1,
-            net_host->b1, net_host->W1b, net_host->b1b, net_host->S, net_host->A, net_host->E, net_host->H,
-            net_host->n_out, net_host->cat, net_host->head_dim, rpo_tune(RPO_TUNE_L1_MFMA) ? 0 : 1};
+    Mlp net = to_dev(net_host);
+    net.l1_vec = rpo_tune(RPO_TUNE_L1_MFMA) ? 0 : 1;
     if (int e = check_net(net)) return e;
     if (n <= 0 || s_stride < net.S || (net.A > 0 && a_stride < net.A)) return RPO_ERR_ARG;
     if (!s || !out || (net.A > 0 && !a)) return RPO_ERR_NULL;
@@ -302,9 +304,7 @@ static int make_bwd_args(BwdArgs& args, const rpo_mlp* net_host, const rpo_mlp_g
                          float* dh, float* dx0, float* da, int param_grads, int first_layer_state_only, float* gradmax,
                          const rpo_td* td) {
     if (!net_host) return RPO_ERR_NULL;
-    Mlp net{net_host->Ws, net_host->bs, net_host->Wa, net_host->ba, net_host->W0, net_host->b0, net_host->W1,
-            net_host->b1, net_host->W1b, net_host->b1b, net_host->S, net_host->A, net_host->E, net_host->H,
-            net_host->n_out, net_host->cat, net_host->head_dim};
+    const Mlp net = to_dev(net_host);
     if (int e = check_net(net)) return e;
     if (n <= 0 || s_stride < net.S || (net.A > 0 && a_stride < net.A)) return RPO_ERR_ARG;
     TdArgs t{};
@@ -317,11 +317,10 @@ static int make_bwd_args(BwdArgs& args, const rpo_mlp* net_host, const rpo_mlp_g
         dout = td->dq_out;
     }
     if (!s || !x0 || !h1 || !dout || !dh || !dx0 || (net.A > 0 && !a)) return RPO_ERR_NULL;
-    MlpGrad g{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    MlpGrad g = grad_dev(nullptr);
     if (param_grads) {
         if (!grad_host) return RPO_ERR_NULL;
-        g = MlpGrad{grad_host->Ws, grad_host->bs, grad_host->Wa, grad_host->ba, grad_host->W0, grad_host->b0,
-                    grad_host->W1, grad_host->b1, grad_host->W1b, grad_host->b1b};
+        g = grad_dev(grad_host);
         if (!g.Ws || !g.bs) return RPO_ERR_NULL;
         if (!first_layer_state_only && (!g.W0 || !g.b0 || !g.W1 || !g.b1 || (net.A > 0 && (!g.Wa || !g.ba))))
             return RPO_ERR_NULL;
@@ -349,8 +348,8 @@ int rpo_mlp_forward_multi(int count, const rpo_mlp* const* nets, int n, const fl
     for (int k = 0; k < count; ++k) {
         const rpo_mlp* h = nets[k];
         if (!h) return RPO_ERR_NULL;
-        Mlp net{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H,
-                h->n_out, h->cat, h->head_dim, rpo_tune(RPO_TUNE_L1_MFMA) ? 0 : 1};
+        Mlp net = to_dev(h);
+        net.l1_vec = rpo_tune(RPO_TUNE_L1_MFMA) ? 0 : 1;
         if (int e = check_net(net)) return e;
         if (net.hd > 1 || s_stride[k] < net.S || (net.A > 0 && a_stride[k] < net.A)) return RPO_ERR_ARG;
         if (!s[k] || !out[k] || (net.A > 0 && !a[k])) return RPO_ERR_NULL;

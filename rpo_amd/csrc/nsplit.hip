@@ -6,18 +6,17 @@
 
 #include "cartsafe_dev.h"
 #include "heads_dev.h"
+#include "host_glue.h"
 #include "mlp_bwd.h"
 #include "nsplit_dev.h"
 #include "pendulum_dev.h"
+#include "rollout_args.h"
 #include "rollout_env.h"
 
 namespace {
 
 using namespace rpo_mlp_dev;
-
-Mlp to_dev(const rpo_mlp* h) {
-    return Mlp{h->Ws, h->bs, h->Wa, h->ba, h->W0, h->b0, h->W1, h->b1, h->W1b, h->b1b, h->S, h->A, h->E, h->H, h->n_out, h->cat, h->head_dim};
-}
+using namespace rpo_host;
 
 bool split_ok(const Mlp& m) {
     return m.E == 128 && m.H == 256 && !m.cat && m.hd <= 1 && m.S <= 6 && m.A <= 4 && m.n_out >= 1 && m.n_out <= 2 && m.Ws && m.W0 &&
@@ -1818,11 +1817,6 @@ __global__ __launch_bounds__(kThreads) void split_policy_e_kernel(SplitArgs p, i
 
 namespace {
 
-MlpGrad grad_dev(const rpo_mlp_grad* g) {
-    if (!g) return MlpGrad{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return MlpGrad{g->Ws, g->bs, g->Wa, g->ba, g->W0, g->b0, g->W1, g->b1, g->W1b, g->b1b};
-}
-
 // What a stage asks to_args for
 enum : unsigned {
     kNeedPolicy = 1u,                       // the network that proposes the next actions: actor (twin) or actor_target
@@ -1903,11 +1897,7 @@ int to_args(const rpo_split_update* u, unsigned need, SplitArgs& a, CartConsts& 
     return 0;
 }
 
-// ---- the stages' kernels
-// A stage's kernel: its CartSafe and its SpringPendulum instantiation
-template <class C, class P> struct EnvKernels { C* cart; P* pend; };
-template <class C, class P> constexpr EnvKernels<C, P> env_kernels(C* cart, P* pend) { return EnvKernels<C, P>{cart, pend}; }
-
+// ---- the stages' kernels (EnvKernels, launch, launch_env: host_glue.h)
 // Every instantiation the stages launch, named once.  The compiler emits the kernels in the order of their first use, this
 // list: keep it, the code object's layout follows it.
 const auto kFwdA = env_kernels(split_critic_fwd_a_kernel<CartRow>, split_critic_fwd_a_kernel<PendRow>);
@@ -1930,19 +1920,6 @@ const auto kPolicyB = env_kernels(split_policy_b_kernel<CartPol>, split_policy_b
 const auto kPolicyFront = env_kernels(split_policy_front_kernel<CartPol>, split_policy_front_kernel<PendPol>);
 const auto kPolicyD = env_kernels(split_policy_d_kernel<CartPol>, split_policy_d_kernel<PendPol>);
 const auto kPolicyE = env_kernels(split_policy_e_kernel<CartPol>, split_policy_e_kernel<PendPol>);
-
-// Launch and answer like RPO_LAUNCH_CHECK: 0 or the hipError_t
-template <class... P, class... A>
-int launch(void (*kernel)(P...), dim3 grid, int threads, size_t lds, void* stream, const A&... args) {
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, (hipStream_t)stream, args...);
-    return (int)hipGetLastError();
-}
-
-// The env dispatch: the CartSafe (env 0) or the SpringPendulum instantiation of a stage's kernel
-template <class C, class P, class... A>
-int launch_env(const EnvKernels<C, P>& k, int env, dim3 grid, int threads, void* stream, const A&... args) {
-    return env == 0 ? launch(k.cart, grid, threads, 0, stream, args...) : launch(k.pend, grid, threads, 0, stream, args...);
-}
 
 // ---- geometry
 int critics(const SplitArgs& a) { return a.twin ? 2 : 1; }
@@ -2032,24 +2009,6 @@ int ride_checks(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v
     return lanes ? ride_range(r) : 0;
 }
 
-void ride_env(const rpo_rollout_rider* r, RideArgs<CartEnv>& o) {
-    o.act = rpo_cart_dev::ActArgs{r->n_envs, nullptr, nullptr, r->action, nullptr, r->noise_mode, r->eps_start, r->eps_end,
-                                  r->eps_decay, r->box_lo, r->box_hi, r->max_steps, r->corr_lr, r->corr_eps, r->corr_momentum,
-                                  (uint64_t)r->seed, (uint32_t)r->env_id_base, r->ctrl, r->stats, r->stats_cap};
-    o.step = rpo_cart_dev::StepArgs{r->n_envs, r->state, r->action, r->ep_len, r->ep_ret, r->ep_count, r->rows, r->cap_steps,
-                                    r->stats, r->stats_cap, r->ctrl, r->max_episode_steps, r->auto_reset, r->viol_thresh,
-                                    (uint64_t)r->seed, (uint32_t)r->env_id_base, 0};
-}
-
-void ride_env(const rpo_rollout_rider* r, RideArgs<PendEnv>& o) {
-    o.act = rpo_pend_dev::ActArgs{r->n_envs, nullptr, 5, nullptr, nullptr, r->action, nullptr, r->noise_mode, r->eps_start,
-                                  r->eps_end, r->eps_decay, r->box_lo, r->box_hi, r->max_steps, r->corr_lr, r->corr_eps,
-                                  r->corr_momentum, (uint64_t)r->seed, (uint32_t)r->env_id_base, r->ctrl, r->stats, r->stats_cap};
-    o.step = rpo_pend_dev::StepArgs{r->n_envs, r->state, r->obs, r->action, r->ep_len, r->ep_ret, r->ep_count, r->rows,
-                                    r->cap_steps, r->stats, r->stats_cap, r->ctrl, r->max_episode_steps, r->auto_reset,
-                                    r->viol_thresh, (uint64_t)r->seed, (uint32_t)r->env_id_base};
-}
-
 // The rider as a launch argument: becomes the RideArgs of the env the launched kernel was instantiated for
 struct Ride {
     const SplitArgs& a; const rpo_rollout_rider* r;
@@ -2057,7 +2016,7 @@ struct Ride {
         RideArgs<ENV> o{};
         o.actor = a.actor; o.scale = r->scale; o.base = r->base; o.gauss = r->gauss ? 1 : 0; o.n = r->n_envs; o.part = r->part;
         o.lane0 = r->lane_begin; o.lane1 = r->lane_end; o.defer_clock = r->defer_clock ? 1 : 0;
-        ride_env(r, o);
+        rollout_env_args(*r, o.act, o.step);
         return o;
     }
 };

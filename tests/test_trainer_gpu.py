@@ -460,44 +460,106 @@ def test_streaming_rollout_equals_the_row_tile_rollout(hip, algo, envname, sel, 
     _stats_equal(a, b, iters)
 
 
-@pytest.mark.parametrize("n_envs", [100, 12500], ids=["16_lane_tiles", "64_lane_tiles"])
-@pytest.mark.parametrize("algo,envname", CASES)
-def test_rollout_pipeline_equals_single_stage_launches(hip, algo, envname, n_envs, monkeypatch):
+def _assert_same(a, b, names, atol=None):
+    """The named tensors of two runs: equal bit for bit, or within atol[name] where a bound is given.  Prints every figure
+    before it asserts (for a run with -s)."""
+    get = {"parameters": lambda t: t.agent.flat.data, "critic targets": lambda t: t.agent.critic_target_flat,
+           "replay rows": lambda t: t.buffer.rows, "env state": lambda t: t.vec.internal, "obs": lambda t: t.vec.obs,
+           "actions": lambda t: t.vec.action, "ep_len": lambda t: t.vec.ep_len, "ep_count": lambda t: t.vec.ep_count}
+    diff = {n: float((get[n](a).double() - get[n](b).double()).abs().max()) for n in names}
+    print("max |a - b|: " + ", ".join("%s %.9g" % (n, diff[n]) for n in names))
+    for n in names:
+        bound = (atol or {}).get(n, 0.0)
+        assert torch.equal(get[n](a), get[n](b)) if bound == 0.0 else diff[n] <= bound, (n, diff[n], bound)
+
+
+def _no_split_no_actor_pipeline(tr):
+    """embed_dim = 256: neither the column-split update nor the actor pipelines apply, so the row-tile kernels' E = 256
+    instantiations run (rollout_kernel<., 256, 256, 1>, the critic forwards / fronts / backs at <256, 256>)"""
+    return tr._split_state() is None and not tr._actor_pipeline and tr.fused.descs["actor"].E == 256
+
+
+# embed_256: the E = 256 instantiations, which no embed_dim = 128 case launches
+_ROLLOUT_CASES = [pytest.param(a, e, n, 128, id="%s-%s-%s" % (a, e, name)) for name, n in (("16_lane_tiles", 100), ("64_lane_tiles", 12500))
+                  for a, e in CASES] + [pytest.param(a, e, 100, 256, id="%s-%s-embed_256" % (a, e)) for a, e in CASES[:4]]
+# The largest |difference| the parent commit left between the two forms at embed_dim = 256, case by case; the bound is twice
+# that.  No entry: the parent is bitwise there, and so is the assertion.  "stats": the per-step statistics that miss rtol 1e-5
+# (sums of residuals near zero).  The cause of the RPOSAC differences has not been looked for.
+_ROLLOUT_MAX_256 = {
+    ("sac", "cart"): {"env state": 2.86102295e-06, "obs": 2.86102295e-06, "replay rows": 2.86102295e-06, "actions": 1.54972076e-06,
+                      "parameters": 1.45286322e-07, "stats": 5.122274e-07},
+    ("sac", "pendulum"): {"env state": 1.78813934e-07, "obs": 1.78813934e-07, "replay rows": 1.49011612e-06, "actions": 9.53674316e-07,
+                          "parameters": 3.7252903e-08, "stats": 2.3841858e-06}}
+
+
+def _twice(measured):
+    return {n: 2 * v for n, v in measured.items()} if measured else {}
+
+
+@pytest.mark.parametrize("algo,envname,n_envs,embed_dim", _ROLLOUT_CASES)
+def test_rollout_pipeline_equals_single_stage_launches(hip, algo, envname, n_envs, embed_dim, monkeypatch):
     """rpo_<env>_rollout (actor -> head -> complete -> project -> step -> scatter in one launch) reproduces the
     sequence rpo_mlp_forward (+ rpo_philox_normal + rpo_gauss_head) + rpo_<env>_act_project + rpo_<env>_step bit for
-    bit, for both envs and both policy heads; n_envs is ragged against both tile heights."""
+    bit, for both envs and both policy heads; n_envs is ragged against both tile heights.
+
+    embed_256 (rollout_kernel<., 256, 256, 1>), as measured on the parent commit:
+      ddpg-cart, ddpg-pendulum   bitwise, statistics within the bound of the embed_dim = 128 cases: asserted like those
+      sac-cart                   states, observations and replay rows within 2.861e-6, actions 1.550e-6, parameters 1.453e-7;
+                                 statistics miss rtol 1e-5 by up to 5.12e-7 absolute
+      sac-pendulum               states and observations 1.788e-7, replay rows 1.490e-6, actions 9.537e-7, parameters 3.73e-8;
+                                 statistics miss rtol 1e-5 by up to 2.384e-6 absolute
+    The RPOSAC cases are asserted at twice their own figures (a margin for data-dependent rounding order), the episode counters
+    exactly."""
     dev = torch.device("cuda")
     iters = 10
     monkeypatch.setenv("RPO_SCHEDULE", "fused_rollout=0")
-    a = _run(algo, envname, hip, dev, iters, n_envs, use_graph=False)
+    a = _run(algo, envname, hip, dev, iters, n_envs, use_graph=False, embed_dim=embed_dim)
     assert not a._rollout_pipeline
     monkeypatch.setenv("RPO_SCHEDULE", "fused_rollout=1")
-    b = _run(algo, envname, hip, dev, iters, n_envs, use_graph=False)
+    b = _run(algo, envname, hip, dev, iters, n_envs, use_graph=False, embed_dim=embed_dim)
     assert b._rollout_pipeline
-    assert torch.equal(a.vec.internal, b.vec.internal) and torch.equal(a.vec.obs, b.vec.obs)
-    assert torch.equal(a.vec.action, b.vec.action)
-    assert torch.equal(a.buffer.rows, b.buffer.rows)
-    assert torch.equal(a.vec.ep_len, b.vec.ep_len) and torch.equal(a.vec.ep_count, b.vec.ep_count)
-    assert torch.equal(a.agent.flat.data, b.agent.flat.data)
+    if embed_dim == 256:
+        assert b._pipelines and _no_split_no_actor_pipeline(b)
+    atol = _twice(_ROLLOUT_MAX_256.get((algo, envname)) if embed_dim == 256 else None)
+    _assert_same(a, b, ["env state", "obs", "actions", "replay rows", "ep_len", "ep_count", "parameters"], atol)
     np.testing.assert_allclose(hip.reduce_stats(a.vec.stats[:iters]).cpu().numpy(),
-                               hip.reduce_stats(b.vec.stats[:iters]).cpu().numpy(), rtol=1e-5, atol=1e-9)
+                               hip.reduce_stats(b.vec.stats[:iters]).cpu().numpy(), rtol=1e-5, atol=atol.get("stats", 1e-9))
 
 
-@pytest.mark.parametrize("algo,envname", [("ddpg", "cart"), ("sac", "cart"), ("sac", "pendulum"), ("ddpg", "pendulum")])
-def test_critic_forward_pipeline_equals_single_stage_launches(hip, algo, envname, monkeypatch):
+_CRITIC_CASES = [("ddpg", "cart"), ("sac", "cart"), ("sac", "pendulum"), ("ddpg", "pendulum")]
+_CRITIC_MAX_256 = {                                              # (as _ROLLOUT_MAX_256; no case is bitwise on the parent)
+    ("ddpg", "cart"): {"parameters": 5.96046448e-08, "critic targets": 1.49011612e-08, "replay rows": 2.86102295e-06, "env state": 2.86102295e-06},
+    ("sac", "cart"): {"parameters": 3.74391675e-07, "critic targets": 2.98023224e-08, "replay rows": 2.86102295e-06, "env state": 2.86102295e-06},
+    ("sac", "pendulum"): {"parameters": 5.96046448e-08, "critic targets": 2.98023224e-08, "replay rows": 1.43051147e-06, "env state": 1.1920929e-07},
+    ("ddpg", "pendulum"): {"parameters": 5.96046448e-08, "critic targets": 1.49011612e-08, "replay rows": 9.53674316e-07, "env state": 1.1920929e-07}}
+
+
+# embed_256: 64 envs and a batch of 100, ragged against the 16-row tile
+@pytest.mark.parametrize("algo,envname,embed_dim", [pytest.param(a, e, 128, id="%s-%s" % (a, e)) for a, e in _CRITIC_CASES] +
+                         [pytest.param(a, e, 256, id="%s-%s-embed_256" % (a, e)) for a, e in _CRITIC_CASES])
+def test_critic_forward_pipeline_equals_single_stage_launches(hip, algo, envname, embed_dim, monkeypatch):
     """rpo_cartsafe_{ddpg,sac}_critic_forward (sample -> policy -> projection -> target critics -> critics -> TD/Huber in
     one launch; SpringPendulum: front | batch-coupled projection | back) leaves the same bits behind as the launches it replaces: parameters, targets and replay after 16
-    iterations with Philox-drawn batches and noise."""
+    iterations with Philox-drawn batches and noise.
+
+    embed_256 (the critic forwards, fronts and backs at <256, 256>): none of the four cases is bitwise on the parent commit.
+    Measured there (parameters | target critics | replay rows | env states):
+      ddpg-cart       5.96e-8 | 1.49e-8 | 2.861e-6 | 2.861e-6        sac-cart        3.744e-7 | 2.98e-8 | 2.861e-6 | 2.861e-6
+      ddpg-pendulum   5.96e-8 | 1.49e-8 | 9.54e-7 | 1.19e-7          sac-pendulum    5.96e-8 | 2.98e-8 | 1.431e-6 | 1.19e-7
+    Each case is asserted at twice its own figures (a margin for data-dependent rounding order)."""
     dev = torch.device("cuda")
+    run = functools.partial(_run, embed_dim=embed_dim, **({} if embed_dim == 128 else dict(batch_size=100)))
+    n_envs = 256 if embed_dim == 128 else 64
     monkeypatch.setenv("RPO_SCHEDULE", "fused_critic=0")
-    a = _run(algo, envname, hip, dev, 16, 256, use_graph=False)
+    a = run(algo, envname, hip, dev, 16, n_envs, use_graph=False)
     assert not a._pipelines
     monkeypatch.setenv("RPO_SCHEDULE", "fused_critic=1")
-    b = _run(algo, envname, hip, dev, 16, 256, use_graph=False)
+    b = run(algo, envname, hip, dev, 16, n_envs, use_graph=False)
     assert b._pipelines
-    assert torch.equal(a.agent.flat.data, b.agent.flat.data)
-    assert torch.equal(a.agent.critic_target_flat, b.agent.critic_target_flat)
-    assert torch.equal(a.buffer.rows, b.buffer.rows) and torch.equal(a.vec.internal, b.vec.internal)
+    if embed_dim == 256:
+        assert b._rollout_pipeline and _no_split_no_actor_pipeline(b)
+    _assert_same(a, b, ["parameters", "critic targets", "replay rows", "env state"],
+                 _twice(_CRITIC_MAX_256[algo, envname] if embed_dim == 256 else None))
     np.testing.assert_allclose(float(a.last_losses["critic"]), float(b.last_losses["critic"]), rtol=1e-5)
 
 
