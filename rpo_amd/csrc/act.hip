@@ -16,6 +16,7 @@
 namespace {
 
 using namespace rpo_mlp_dev;
+using rpo_host::launch;
 using rpo_host::to_dev;
 
 // PROFILE = 1: the row's projection also writes its entries of the profile planes (act_dev.h: act_project_profile); the
@@ -58,19 +59,6 @@ int check_profile(const float* profile, int K) {                 // [K + 1, n, 4
     return 0;
 }
 
-template <class ENV>
-int launch_project_profile(const typename ENV::ActArgs& a, const typename ENV::Consts& c, const float* obs, int obs_stride,
-                           float* profile, void* stream) {
-    if (a.n <= 0) return RPO_ERR_ARG;
-    if (!a.ap_raw || !a.action) return RPO_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(a.action) % 8) return RPO_ERR_ARG;
-    if (int e = check_profile(profile, a.max_steps)) return e;
-    hipLaunchKernelGGL((project_profile_kernel<ENV>), dim3(rpo_grid_for(a.n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a, c, obs,
-                       obs_stride, ActProfile{profile, a.max_steps});
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
 int check_act_actor(const Mlp& actor, int obs_dim, int gauss) {  // (host_glue.h's check_actor and every bias; E below)
     if (actor.hd > 1 || actor.S != obs_dim || actor.A != 0 || actor.n_out != (gauss ? 2 : 1) || actor.cat || actor.H != 256 || !actor.Ws ||
         !actor.bs || !actor.W0 || !actor.b0 || !actor.W1 || !actor.b1 || (gauss && (!actor.W1b || !actor.b1b)))
@@ -79,9 +67,92 @@ int check_act_actor(const Mlp& actor, int obs_dim, int gauss) {  // (host_glue.h
     return 0;
 }
 
-// form: 0 by size (the rollout's rule: launch_stream in rollout_stream.hip), 1 row tile, 2 streaming G = 1, 3 streaming G = 4
+// A projection without exploration, clock or statistics (RPO_NOISE_NONE), as the entry points here take it: what fill_env makes the
+// env's ActArgs and Consts of.  obs / obs_stride: SpringPendulum's rows; consts_host / partial: CartSafe's table.
+struct Projection {
+    int n;
+    const float* obs;
+    int obs_stride;
+    const float* ap_raw;
+    float* action;
+    int* iters;
+    float box_lo, box_hi;
+    int max_steps;
+    float corr_lr, corr_eps, corr_momentum;
+    const float* consts_host;
+    int partial;
+};
+
+int fill_env(rpo_cart_dev::ActArgs& a, CartEnv::Consts& c, const Projection& q) {
+    if (int e = rpo_cart_dev::load_consts(c, q.consts_host, q.partial)) return e;
+    a = rpo_cart_dev::ActArgs{q.n, q.ap_raw, nullptr, q.action, q.iters, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, q.box_lo, q.box_hi,
+                              q.max_steps, q.corr_lr, q.corr_eps, q.corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    return 0;
+}
+
+int fill_env(rpo_pend_dev::ActArgs& a, PendEnv::Consts& c, const Projection& q) {
+    c = PendEnv::Consts{0};
+    a = rpo_pend_dev::ActArgs{q.n, q.obs, q.obs_stride, q.ap_raw, nullptr, q.action, q.iters, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
+                              q.box_lo, q.box_hi, q.max_steps, q.corr_lr, q.corr_eps, q.corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
+    return 0;
+}
+
+// *_project_profile.  The env's constants are tested first, then the rows
 template <class ENV>
-int launch_act(const PolicyActArgs<ENV>& args, const typename ENV::Consts& c, int env, int form, void* stream) {
+int project_profile(const Projection& q, float* profile, void* stream) {
+    typename ENV::ActArgs a;
+    typename ENV::Consts c;
+    if (int e = fill_env(a, c, q)) return e;
+    if (a.n <= 0) return RPO_ERR_ARG;
+    if (!a.ap_raw || !a.action) return RPO_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(a.action) % 8) return RPO_ERR_ARG;
+    if (int e = check_profile(profile, a.max_steps)) return e;
+    return launch(project_profile_kernel<ENV>, dim3(rpo_grid_for(a.n)), RPO_BLOCK, 0, stream, a, c, q.obs, q.obs_stride,
+                  ActProfile{profile, a.max_steps});
+}
+
+// What *_policy_act and *_policy_act_profile take alike (q: its obs rows are the policy's, its ap_raw and iters unused)
+struct PolicyAct {
+    const rpo_mlp* actor_host;
+    int gauss;
+    float scale, base;
+    const float* obs;
+    int obs_stride;
+    float* proposal;
+    int* iters;
+    float *eq_resid, *ineq_resid;
+    Projection q;
+};
+
+template <class ENV>
+int fill_policy_act(PolicyActArgs<ENV>& args, typename ENV::Consts& c, const PolicyAct& p) {
+    const int n = p.q.n;
+    if (!p.actor_host) return RPO_ERR_NULL;
+    if (n <= 0 || p.obs_stride < ENV::OBS || p.q.max_steps < 0) return RPO_ERR_ARG;
+    if (!p.obs || !p.q.action) return RPO_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(p.q.action) % 8) return RPO_ERR_ARG;                   // 8-byte stores of the action rows
+    if (std::is_same<ENV, CartEnv>::value && reinterpret_cast<uintptr_t>(p.ineq_resid) % 8) return RPO_ERR_ARG;   // ... and of g[0..5]
+    args.actor = to_dev(p.actor_host);
+    if (int e = check_act_actor(args.actor, ENV::OBS, p.gauss)) return e;
+    args.scale = p.scale; args.base = p.base; args.gauss = p.gauss ? 1 : 0; args.n = n; args.obs = p.obs; args.obs_stride = p.obs_stride;
+    args.proposal = p.proposal; args.iters = p.iters; args.eq = p.eq_resid; args.ineq = p.ineq_resid;
+    return fill_env(args.act, c, p.q);
+}
+
+// The row tile of n rows: 64 rows per workgroup once that still fills the chip (launch_eval's tile rule)
+template <class ENV, int PROFILE, class Prof>
+int launch_tile(const PolicyActArgs<ENV>& args, const typename ENV::Consts& c, const Prof& prof, void* stream) {
+    const int n = args.n;
+    if (n >= 64 * 192) return launch(policy_act_kernel<ENV, 4, PROFILE>, dim3((n + 63) / 64), kFwdThreads, 0, stream, args, c, prof);
+    return launch(policy_act_kernel<ENV, 1, PROFILE>, dim3((n + 15) / 16), kFwdThreads, 0, stream, args, c, prof);
+}
+
+// *_policy_act.  form: 0 by size (the rollout's rule: launch_stream in rollout_stream.hip), 1 row tile, 2 streaming G = 1, 3 streaming G = 4
+template <class ENV>
+int policy_act(const PolicyAct& p, int env, int form, void* stream) {
+    PolicyActArgs<ENV> args{};
+    typename ENV::Consts c;
+    if (int e = fill_policy_act(args, c, p)) return e;
     const int n = args.n;
     if (form < 0 || form > 3) return RPO_ERR_ARG;
     if (form == 0 && n >= RPO_ROLLOUT_STREAM_FROM) {
@@ -91,43 +162,17 @@ int launch_act(const PolicyActArgs<ENV>& args, const typename ENV::Consts& c, in
         const int e = rpo_act_stream_launch(env, &args, &c, form == 3, stream);
         return e < 0 ? RPO_ERR_ARG : e;
     }
-    if (n >= 64 * 192) {                                         // launch_eval's tile rule
-        hipLaunchKernelGGL((policy_act_kernel<ENV, 4, 0>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, ActNoProfile{});
-    } else {
-        hipLaunchKernelGGL((policy_act_kernel<ENV, 1, 0>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, ActNoProfile{});
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_tile<ENV, 0>(args, c, ActNoProfile{}, stream);
 }
 
-// the PROFILE = 1 instances: always the row tile (a profile instance of the streaming form does not exist)
+// *_policy_act_profile: always the row tile (a profile instance of the streaming form does not exist)
 template <class ENV>
-int launch_act_profile(const PolicyActArgs<ENV>& args, const typename ENV::Consts& c, float* profile, void* stream) {
-    const int n = args.n;
+int policy_act_profile(const PolicyAct& p, float* profile, void* stream) {
+    PolicyActArgs<ENV> args{};
+    typename ENV::Consts c;
+    if (int e = fill_policy_act(args, c, p)) return e;
     if (int e = check_profile(profile, args.act.max_steps)) return e;
-    const ActProfile q{profile, args.act.max_steps};
-    if (n >= 64 * 192) {
-        hipLaunchKernelGGL((policy_act_kernel<ENV, 4, 1>), dim3((n + 63) / 64), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, q);
-    } else {
-        hipLaunchKernelGGL((policy_act_kernel<ENV, 1, 1>), dim3((n + 15) / 16), dim3(kFwdThreads), 0, (hipStream_t)stream, args, c, q);
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
-}
-
-template <class ENV>
-int fill_act_args(PolicyActArgs<ENV>& args, const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
-                  int obs_stride, float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid, int max_steps) {
-    if (!actor_host) return RPO_ERR_NULL;
-    if (n <= 0 || obs_stride < ENV::OBS || max_steps < 0) return RPO_ERR_ARG;
-    if (!obs || !action) return RPO_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(action) % 8) return RPO_ERR_ARG;                       // 8-byte stores of the action rows
-    if (std::is_same<ENV, CartEnv>::value && reinterpret_cast<uintptr_t>(ineq_resid) % 8) return RPO_ERR_ARG;   // ... and of g[0..5]
-    args.actor = to_dev(actor_host);
-    if (int e = check_act_actor(args.actor, ENV::OBS, gauss)) return e;
-    args.scale = scale; args.base = base; args.gauss = gauss ? 1 : 0; args.n = n; args.obs = obs; args.obs_stride = obs_stride;
-    args.proposal = proposal; args.iters = iters; args.eq = eq_resid; args.ineq = ineq_resid;
-    return 0;
+    return launch_tile<ENV, 1>(args, c, ActProfile{profile, args.act.max_steps}, stream);
 }
 
 }  // namespace
@@ -138,77 +183,50 @@ int rpo_cartsafe_policy_act(const rpo_mlp* actor_host, int gauss, float scale, f
                             float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid, float box_lo,
                             float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                             const float* consts_host, int partial, int form, void* stream) {
-    PolicyActArgs<CartEnv> args{};
-    if (int e = fill_act_args<CartEnv>(args, actor_host, gauss, scale, base, n, obs, obs_stride, action, proposal, iters, eq_resid,
-                                       ineq_resid, max_steps))
-        return e;
-    rpo_cart_dev::CartConsts c;
-    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
-    args.act = rpo_cart_dev::ActArgs{n, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, box_lo, box_hi,
-                                     max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    return launch_act<CartEnv>(args, c, 0, form, stream);
+    return policy_act<CartEnv>({actor_host, gauss, scale, base, obs, obs_stride, proposal, iters, eq_resid, ineq_resid,
+                                {n, nullptr, 0, nullptr, action, nullptr, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
+                                 consts_host, partial}}, 0, form, stream);
 }
 
 int rpo_pendulum_policy_act(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs, int obs_stride,
                             float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid, float box_lo,
                             float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum, int form,
                             void* stream) {
-    PolicyActArgs<PendEnv> args{};
-    if (int e = fill_act_args<PendEnv>(args, actor_host, gauss, scale, base, n, obs, obs_stride, action, proposal, iters, eq_resid,
-                                       ineq_resid, max_steps))
-        return e;
-    args.act = rpo_pend_dev::ActArgs{n, nullptr, 5, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
-                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    const PendEnv::Consts c{0};
-    return launch_act<PendEnv>(args, c, 1, form, stream);
+    return policy_act<PendEnv>({actor_host, gauss, scale, base, obs, obs_stride, proposal, iters, eq_resid, ineq_resid,
+                                {n, nullptr, 5, nullptr, action, nullptr, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
+                                 nullptr, 0}}, 1, form, stream);
 }
 
 int rpo_cartsafe_policy_act_profile(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
                                     int obs_stride, float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid,
                                     float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                                     const float* consts_host, int partial, float* profile, void* stream) {
-    PolicyActArgs<CartEnv> args{};
-    if (int e = fill_act_args<CartEnv>(args, actor_host, gauss, scale, base, n, obs, obs_stride, action, proposal, iters, eq_resid,
-                                       ineq_resid, max_steps))
-        return e;
-    rpo_cart_dev::CartConsts c;
-    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
-    args.act = rpo_cart_dev::ActArgs{n, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, box_lo, box_hi,
-                                     max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    return launch_act_profile<CartEnv>(args, c, profile, stream);
+    return policy_act_profile<CartEnv>({actor_host, gauss, scale, base, obs, obs_stride, proposal, iters, eq_resid, ineq_resid,
+                                        {n, nullptr, 0, nullptr, action, nullptr, box_lo, box_hi, max_steps, corr_lr, corr_eps,
+                                         corr_momentum, consts_host, partial}}, profile, stream);
 }
 
 int rpo_pendulum_policy_act_profile(const rpo_mlp* actor_host, int gauss, float scale, float base, int n, const float* obs,
                                     int obs_stride, float* action, float* proposal, int* iters, float* eq_resid, float* ineq_resid,
                                     float box_lo, float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                                     float* profile, void* stream) {
-    PolicyActArgs<PendEnv> args{};
-    if (int e = fill_act_args<PendEnv>(args, actor_host, gauss, scale, base, n, obs, obs_stride, action, proposal, iters, eq_resid,
-                                       ineq_resid, max_steps))
-        return e;
-    args.act = rpo_pend_dev::ActArgs{n, nullptr, 5, nullptr, nullptr, action, nullptr, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f,
-                                     box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    const PendEnv::Consts c{0};
-    return launch_act_profile<PendEnv>(args, c, profile, stream);
+    return policy_act_profile<PendEnv>({actor_host, gauss, scale, base, obs, obs_stride, proposal, iters, eq_resid, ineq_resid,
+                                        {n, nullptr, 5, nullptr, action, nullptr, box_lo, box_hi, max_steps, corr_lr, corr_eps,
+                                         corr_momentum, nullptr, 0}}, profile, stream);
 }
 
 int rpo_cartsafe_project_profile(int n, const float* ap_raw, float* action, int* iters, int max_steps, float corr_lr, float corr_eps,
                                  float corr_momentum, const float* consts_host, int partial, float* profile, void* stream) {
-    rpo_cart_dev::CartConsts c;
-    if (int e = rpo_cart_dev::load_consts(c, consts_host, partial)) return e;
-    const rpo_cart_dev::ActArgs a{n, ap_raw, nullptr, action, iters, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
-                                  max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    return launch_project_profile<CartEnv>(a, c, nullptr, 0, profile, stream);
+    return project_profile<CartEnv>({n, nullptr, 0, ap_raw, action, iters, 0.0f, 0.0f, max_steps, corr_lr, corr_eps, corr_momentum,
+                                     consts_host, partial}, profile, stream);
 }
 
 int rpo_pendulum_project_profile(int n, const float* obs, int obs_stride, const float* ap_raw, float* action, int* iters,
                                  int max_steps, float corr_lr, float corr_eps, float corr_momentum, float* profile, void* stream) {
-    if (n > 0 && !obs) return RPO_ERR_NULL;
+    if (n > 0 && !obs) return RPO_ERR_NULL;                      // (SpringPendulum's rows: tested in front of n)
     if (obs_stride < 5) return RPO_ERR_ARG;
-    const rpo_pend_dev::ActArgs a{n, obs, obs_stride, ap_raw, nullptr, action, iters, RPO_NOISE_NONE, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f,
-                                  max_steps, corr_lr, corr_eps, corr_momentum, 0ull, 0u, nullptr, nullptr, 0};
-    const PendEnv::Consts c{0};
-    return launch_project_profile<PendEnv>(a, c, obs, obs_stride, profile, stream);
+    return project_profile<PendEnv>({n, obs, obs_stride, ap_raw, action, iters, 0.0f, 0.0f, max_steps, corr_lr, corr_eps, corr_momentum,
+                                     nullptr, 0}, profile, stream);
 }
 
 }  // extern "C"

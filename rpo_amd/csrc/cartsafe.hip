@@ -104,9 +104,7 @@ __global__ __launch_bounds__(RPO_BLOCK) void cartsafe_step_kernel(StepArgs p, Ca
     }
 
     if (p.stats) {
-        const int slot[kStepStats] = {RPO_STAT_REWARD_SUM, RPO_STAT_EPISODES, RPO_STAT_RETURN_SUM, RPO_STAT_LENGTH_SUM,
-                                      RPO_STAT_MAX_INEQ_SUM, RPO_STAT_MAX_EQ_SUM, RPO_STAT_VIOL_COUNT, RPO_STAT_TERMINATED,
-                                      RPO_STAT_MAX_INEQ_MAX, RPO_STAT_MAX_EQ_MAX};
+        const int slot[kStepStats] = RPO_STEP_STAT_SLOTS;
         rpo_stats_flush<kStepStats>(st, 8, slot, rpo_stats_row(p.stats, p.stats_cap, t), red);
     }
     rpo_step_epilogue(p.ctrl, t, p.stats, p.stats_cap);
@@ -201,66 +199,42 @@ __global__ __launch_bounds__(RPO_BLOCK) void cartsafe_lagrangian_kernel(int n, c
         for (int w = 0; w < RPO_BLOCK / RPO_WAVE; ++w) r += red[w * 7 + threadIdx.x];
         r *= scale;
         // (a launch that adds into loss_out / grad_nu is always ONE workgroup -- a fixed order; wider batches leave their
-        //  per-workgroup sums in partials_out: see rpo_cartsafe_lagrangian)
+        //  per-workgroup sums in partials_out: see launch_lagrangian)
         if (partials_out) partials_out[(size_t)blockIdx.x * 8 + threadIdx.x] = r;
         else if (threadIdx.x == 0) { if (loss_out) atomicAdd(loss_out, r); }
         else if (grad_nu) atomicAdd(grad_nu + threadIdx.x - 1, r);
     }
 }
 
-// Sum of G per-workgroup partial vectors [G][8] (K <= 8 used) in a FIXED order: thread t takes workgroups t, t + 256, ..., the 256
-// sums meet in an LDS tree; out_k[0] += total_k for the non-NULL outputs.  One workgroup.
-__global__ __launch_bounds__(RPO_BLOCK) void lagrangian_reduce_kernel(int G, int K, const float* __restrict__ partials,
-                                                                      float* __restrict__ loss_out, float* __restrict__ grad_nu) {
-    __shared__ float red[RPO_BLOCK];
-    for (int k = 0; k < K; ++k) {
-        float acc = 0.0f;
-        for (int b = threadIdx.x; b < G; b += RPO_BLOCK) acc += partials[(size_t)b * 8 + k];
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        for (int off = RPO_BLOCK / 2; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            float* dst = k == 0 ? loss_out : (grad_nu ? grad_nu + k - 1 : nullptr);
-            if (dst) *dst += red[0];
-        }
-        __syncthreads();
-    }
-}
-
 }  // namespace
 
+// (behind the unit's kernels: the reduce kernel of env_glue.h keeps its place in the code object)
+#include "env_glue.h"
+using namespace rpo_env_glue;
+
 // ====================================================================================================== C ABI
+// Every entry point: its scalar and NULL checks, the constant table (read on the host, so behind them), one launch.
 extern "C" {
 
 int rpo_cartsafe_reset(int n_envs, float* state, int* ep_len, float* ep_ret, const unsigned* ep_count,
                        unsigned long long seed, unsigned env_id_base, void* stream) {
     if (n_envs <= 0) return RPO_ERR_ARG;
     if (!state || !ep_len || !ep_ret) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(cartsafe_reset_kernel, dim3(rpo_grid_for(n_envs)), dim3(RPO_BLOCK), 0, (hipStream_t)stream,
-                       n_envs, state, ep_len, ep_ret, ep_count, (uint64_t)seed, (uint32_t)env_id_base);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(cartsafe_reset_kernel, dim3(rpo_grid_for(n_envs)), RPO_BLOCK, 0, stream, n_envs, state, ep_len, ep_ret, ep_count,
+                  (uint64_t)seed, (uint32_t)env_id_base);
 }
 
 int rpo_cartsafe_step(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count,
                       float* rows, long long cap_steps, float* stats, int stats_cap, long long* ctrl,
                       const float* consts_host, int partial, int max_episode_steps, int auto_reset,
                       float viol_thresh, unsigned long long seed, unsigned env_id_base, void* stream) {
-    if (n_envs <= 0 || max_episode_steps <= 0) return RPO_ERR_ARG;
-    if (!state || !action || !ep_len || !ep_ret || !ep_count) return RPO_ERR_NULL;
-    if (rows && cap_steps <= 0) return RPO_ERR_ARG;
-    if (stats && stats_cap <= 0) return RPO_ERR_ARG;
+    if (int e = check_step(n_envs, max_episode_steps, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap)) return e;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
     const int tiles_ok = ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(rows)) & 15u) == 0;
-    StepArgs a{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl,
-               max_episode_steps, auto_reset, viol_thresh, (uint64_t)seed, (uint32_t)env_id_base, tiles_ok};
-    hipLaunchKernelGGL(cartsafe_step_kernel, dim3(rpo_grid_for(n_envs)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a, c);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    const StepArgs a{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl,
+                     max_episode_steps, auto_reset, viol_thresh, (uint64_t)seed, (uint32_t)env_id_base, tiles_ok};
+    return launch(cartsafe_step_kernel, dim3(rpo_grid_for(n_envs)), RPO_BLOCK, 0, stream, a, c);
 }
 
 int rpo_cartsafe_act_project(int n, const float* ap_raw, const float* noise, float* action, int* iters,
@@ -268,17 +242,12 @@ int rpo_cartsafe_act_project(int n, const float* ap_raw, const float* noise, flo
                              float box_hi, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
                              const float* consts_host, int partial, unsigned long long seed, unsigned env_id_base,
                              const long long* ctrl, float* stats, int stats_cap, void* stream) {
-    if (n <= 0 || max_steps < 0 || noise_mode < RPO_NOISE_NONE || noise_mode > RPO_NOISE_CLIP_ONLY) return RPO_ERR_ARG;
-    if (!action || (noise_mode != RPO_NOISE_UNIFORM && !ap_raw)) return RPO_ERR_NULL;
-    if (noise_mode == RPO_NOISE_EXPLICIT && !noise) return RPO_ERR_NULL;
-    if (stats && stats_cap <= 0) return RPO_ERR_ARG;
+    if (int e = check_act_project(n, max_steps, noise_mode, 0, nullptr, 0, ap_raw, noise, action, stats, stats_cap)) return e;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
-    ActArgs a{n, ap_raw, noise, action, iters, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps,
-              corr_lr, corr_eps, corr_momentum, (uint64_t)seed, (uint32_t)env_id_base, ctrl, stats, stats_cap};
-    hipLaunchKernelGGL(cartsafe_act_project_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a, c);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    const ActArgs a{n, ap_raw, noise, action, iters, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps,
+                    corr_lr, corr_eps, corr_momentum, (uint64_t)seed, (uint32_t)env_id_base, ctrl, stats, stats_cap};
+    return launch(cartsafe_act_project_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, a, c);
 }
 
 int rpo_cartsafe_complete_bwd(int n, const float* grad_action, float* grad_ap, const float* consts_host,
@@ -287,10 +256,7 @@ int rpo_cartsafe_complete_bwd(int n, const float* grad_action, float* grad_ap, c
     if (!grad_action || !grad_ap) return RPO_ERR_NULL;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
-    hipLaunchKernelGGL(cartsafe_complete_bwd_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream,
-                       n, grad_action, grad_ap, c);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(cartsafe_complete_bwd_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, n, grad_action, grad_ap, c);
 }
 
 int rpo_cartsafe_resid(int n, const float* action, float* eq_resid, float* ineq_resid, const float* consts_host,
@@ -299,10 +265,7 @@ int rpo_cartsafe_resid(int n, const float* action, float* eq_resid, float* ineq_
     if (!action) return RPO_ERR_NULL;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
-    hipLaunchKernelGGL(cartsafe_resid_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n,
-                       action, eq_resid, ineq_resid, c);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(cartsafe_resid_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, n, action, eq_resid, ineq_resid, c);
 }
 
 int rpo_cartsafe_ineq_partial_grad(int n, const float* action, float* step, const float* consts_host, int partial,
@@ -311,10 +274,7 @@ int rpo_cartsafe_ineq_partial_grad(int n, const float* action, float* step, cons
     if (!action || !step) return RPO_ERR_NULL;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
-    hipLaunchKernelGGL(cartsafe_ipg_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action,
-                       step, c);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(cartsafe_ipg_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, n, action, step, c);
 }
 
 int rpo_cartsafe_lagrangian(int n, const float* action, const float* nu, float scale, float* loss_out,
@@ -323,39 +283,7 @@ int rpo_cartsafe_lagrangian(int n, const float* action, const float* nu, float s
     if (!action || !nu) return RPO_ERR_NULL;
     CartConsts c;
     if (int e = load_consts(c, consts_host, partial)) return e;
-    if (n > RPO_BLOCK && (loss_out || grad_nu)) {
-        // More than one workgroup would add its partial sums with float atomics in arrival order (found in round 4: the 2^20-row
-        // updates were not bitwise reproducible from run to run).  Deterministic form: every workgroup leaves its 7 sums in a
-        // scratch area, ONE workgroup adds them in a fixed order, then the elementwise launch writes grad_action -- whose
-        // first 8 G floats ARE the scratch area (G = workgroups <= n / 256, so 8 G <= n / 32 floats of the 2 n).  Without a
-        // grad_action buffer one workgroup recomputes and sums every row.
-        const int G = rpo_grid_for(n);
-        if (grad_action && (long long)8 * G <= (long long)2 * n) {
-            hipLaunchKernelGGL(cartsafe_lagrangian_kernel, dim3(G), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                               (float*)nullptr, (float*)nullptr, (float*)nullptr, c, grad_action);
-            RPO_LAUNCH_CHECK();
-            hipLaunchKernelGGL(lagrangian_reduce_kernel, dim3(1), dim3(RPO_BLOCK), 0, (hipStream_t)stream, G, 7,
-                               (const float*)grad_action, loss_out, grad_nu);
-            RPO_LAUNCH_CHECK();
-            hipLaunchKernelGGL(cartsafe_lagrangian_kernel, dim3(G), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                               (float*)nullptr, grad_action, (float*)nullptr, c, (float*)nullptr);
-            RPO_LAUNCH_CHECK();
-            return 0;
-        }
-        if (grad_action) {
-            hipLaunchKernelGGL(cartsafe_lagrangian_kernel, dim3(G), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                               (float*)nullptr, grad_action, (float*)nullptr, c, (float*)nullptr);
-            RPO_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(cartsafe_lagrangian_kernel, dim3(1), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                           loss_out, (float*)nullptr, grad_nu, c, (float*)nullptr);
-        RPO_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(cartsafe_lagrangian_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n,
-                       action, nu, scale, loss_out, grad_action, grad_nu, c, (float*)nullptr);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_lagrangian(cartsafe_lagrangian_kernel, 7, n, action, nu, scale, loss_out, grad_action, grad_nu, stream, c);
 }
 
 }  // extern "C"

@@ -300,6 +300,12 @@ __device__ __forceinline__ void rpo_stats_flush(const float (&v)[K], int n_sum, 
     }
 }
 
+// The slots of the ten per-thread statistics of the CartSafe and SpringPendulum step kernels, in the order cart_lane / pend_lane
+// keep them: reward, episodes, return, length, max_ineq, max_eq, viol_count, terminated (sums) | max_ineq, max_eq (maxima)
+#define RPO_STEP_STAT_SLOTS                                                                                                  \
+    {RPO_STAT_REWARD_SUM, RPO_STAT_EPISODES, RPO_STAT_RETURN_SUM, RPO_STAT_LENGTH_SUM, RPO_STAT_MAX_INEQ_SUM,               \
+     RPO_STAT_MAX_EQ_SUM, RPO_STAT_VIOL_COUNT, RPO_STAT_TERMINATED, RPO_STAT_MAX_INEQ_MAX, RPO_STAT_MAX_EQ_MAX}
+
 // The *_step kernels own ctrl[RPO_CTRL_T]: the last workgroup to finish advances it and clears the statistics rows of
 // the next vector step.  Every workgroup read t at its start, before any workgroup can have arrived last.  Arrival is
 // hierarchical -- 16 sub-counters on separate cache lines, then one top counter -- because 2048 returning atomics on

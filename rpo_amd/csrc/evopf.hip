@@ -2,8 +2,10 @@
 // rpo/algo/rpo_ddpg.py:72-77,266-305).  One wavefront per env lane / batch row -- see evopf_dev.h.
 #include "evopf_dev.h"
 #include "heads_dev.h"
+#include "launch.h"
 
 using namespace rpo_evopf_dev;
+using rpo_host::launch;
 
 namespace {
 
@@ -511,6 +513,10 @@ __global__ __launch_bounds__(RPO_BLOCK) void evopf_tanh_box_bwd_kernel(int n, co
     }
 }
 
+// the grid and workgroup of the one-wave-per-lane kernels
+constexpr int kActThreads = RPO_WAVE * kActWaves;
+dim3 lane_grid(int n) { return dim3((n + kActWaves - 1) / kActWaves); }
+
 int check_common(int n, const void* a, const void* b, const float* consts) {
     if (n <= 0) return RPO_ERR_ARG;
     if (!a || !b || !consts) return RPO_ERR_NULL;
@@ -526,10 +532,8 @@ int rpo_evopf_reset(int n_envs, float* state, int* ep_len, float* ep_ret, const 
                     const float* consts_dev, unsigned long long seed, unsigned env_id_base, void* stream) {
     if (int e = check_common(n_envs, state, ep_len, consts_dev)) return e;
     if (!ep_ret) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(evopf_reset_kernel, dim3((n_envs + kActWaves - 1) / kActWaves), dim3(RPO_WAVE * kActWaves), 0, (hipStream_t)stream, n_envs, state, ep_len,
-                       ep_ret, ep_count, consts_dev, (uint64_t)seed, (uint32_t)env_id_base);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_reset_kernel, lane_grid(n_envs), kActThreads, 0, stream, n_envs, state, ep_len, ep_ret, ep_count, consts_dev,
+                  (uint64_t)seed, (uint32_t)env_id_base);
 }
 
 int rpo_evopf_step(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count,
@@ -541,9 +545,7 @@ int rpo_evopf_step(int n_envs, float* state, const float* action, int* ep_len, f
     if (max_episode_steps <= 0 || (rows && cap_steps <= 0) || (stats && stats_cap <= 0)) return RPO_ERR_ARG;
     StepArgs p{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl, max_episode_steps,
                auto_reset, viol_thresh, consts_dev, (uint64_t)seed, (uint32_t)env_id_base};
-    hipLaunchKernelGGL(evopf_step_kernel, dim3((n_envs + kActWaves - 1) / kActWaves), dim3(RPO_WAVE * kActWaves), 0, (hipStream_t)stream, p);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_step_kernel, lane_grid(n_envs), kActThreads, 0, stream, p);
 }
 
 int rpo_evopf_act_project(int n, const float* state, int state_stride, const float* ap_raw, const float* noise, float* action, int* iters,
@@ -566,9 +568,7 @@ int rpo_evopf_act_project(int n, const float* state, int state_stride, const flo
         const int per = p.place == 1 ? 2 : 6;
         blocks = (blocks + per - 1) / per * 8;
     }
-    hipLaunchKernelGGL(evopf_act_project_kernel, dim3(blocks), dim3(RPO_WAVE * kActWaves), 0, (hipStream_t)stream, p);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_act_project_kernel, dim3(blocks), kActThreads, 0, stream, p);
 }
 
 int rpo_evopf_tanh_box_bwd(int n, const float* state, int state_stride, const float* raw, const float* noise,
@@ -577,11 +577,8 @@ int rpo_evopf_tanh_box_bwd(int n, const float* state, int state_stride, const fl
     if (int e = check_common(n, state, raw, consts_dev)) return e;
     if (!dap || !dout) return RPO_ERR_NULL;
     if (state_stride < RPO_EVOPF_STATE) return RPO_ERR_ARG;
-    hipLaunchKernelGGL(evopf_tanh_box_bwd_kernel, dim3(rpo_grid_for((long long)n * NP)), dim3(RPO_BLOCK), 0,
-                       (hipStream_t)stream, n, state, state_stride, raw, noise, eps_start, eps_end, eps_decay, ctrl, dap,
-                       dout, consts_dev);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_tanh_box_bwd_kernel, dim3(rpo_grid_for((long long)n * NP)), RPO_BLOCK, 0, stream, n, state, state_stride, raw,
+                  noise, eps_start, eps_end, eps_decay, ctrl, dap, dout, consts_dev);
 }
 
 int rpo_evopf_gauss_head(int n, const float* state, int state_stride, const float* raw, const float* eps, int deterministic,
@@ -589,10 +586,8 @@ int rpo_evopf_gauss_head(int n, const float* state, int state_stride, const floa
     if (int e = check_common(n, state, raw, consts_dev)) return e;
     if (!eps || !ap_out) return RPO_ERR_NULL;
     if (state_stride < RPO_EVOPF_STATE) return RPO_ERR_ARG;
-    hipLaunchKernelGGL(evopf_gauss_head_kernel, dim3(rpo_grid_for((long long)n * 16)), dim3(RPO_BLOCK), 0, (hipStream_t)stream,
-                       n, state, state_stride, raw, eps, deterministic, ap_out, logp_out, consts_dev);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_gauss_head_kernel, dim3(rpo_grid_for((long long)n * 16)), RPO_BLOCK, 0, stream, n, state, state_stride, raw,
+                  eps, deterministic, ap_out, logp_out, consts_dev);
 }
 
 int rpo_evopf_gauss_head_bwd(int n, const float* state, int state_stride, const float* raw, const float* eps,
@@ -600,59 +595,45 @@ int rpo_evopf_gauss_head_bwd(int n, const float* state, int state_stride, const 
     if (int e = check_common(n, state, raw, consts_dev)) return e;
     if (!eps || !dap || !draw) return RPO_ERR_NULL;
     if (state_stride < RPO_EVOPF_STATE) return RPO_ERR_ARG;
-    hipLaunchKernelGGL(evopf_gauss_head_bwd_kernel, dim3(rpo_grid_for((long long)n * NP)), dim3(RPO_BLOCK), 0,
-                       (hipStream_t)stream, n, state, state_stride, raw, eps, dap, dlogp, draw, consts_dev);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_gauss_head_bwd_kernel, dim3(rpo_grid_for((long long)n * NP)), RPO_BLOCK, 0, stream, n, state, state_stride,
+                  raw, eps, dap, dlogp, draw, consts_dev);
 }
 
 int rpo_evopf_complete_bwd(int n, const float* action, const float* grad_action, const float* grad_action_b, const float* grad_action2,
                            float* grad_ap, const float* consts_dev, void* stream) {
     if (int e = check_common(n, action, grad_action, consts_dev)) return e;
     if (!grad_ap) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(evopf_complete_bwd_kernel, dim3((n + kActWaves - 1) / kActWaves), dim3(RPO_WAVE * kActWaves), 0, (hipStream_t)stream, n, action, grad_action,
-                       grad_action_b, grad_action2, grad_ap, consts_dev);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_complete_bwd_kernel, lane_grid(n), kActThreads, 0, stream, n, action, grad_action, grad_action_b, grad_action2,
+                  grad_ap, consts_dev);
 }
 
 int rpo_evopf_resid(int n, const float* state, int state_stride, const float* action, float* eq_out, float* ineq_out,
                     const float* consts_dev, void* stream) {
     if (int e = check_common(n, state, action, consts_dev)) return e;
-    hipLaunchKernelGGL(evopf_resid_kernel, dim3((n + kActWaves - 1) / kActWaves), dim3(RPO_WAVE * kActWaves), 0, (hipStream_t)stream, n, state, state_stride, action, eq_out,
-                       ineq_out, consts_dev);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_resid_kernel, lane_grid(n), kActThreads, 0, stream, n, state, state_stride, action, eq_out, ineq_out,
+                  consts_dev);
 }
 
 int rpo_evopf_ineq_partial_grad(int n, const float* state, int state_stride, const float* action, float* step_out, const float* consts_dev,
                                 void* stream) {
     if (int e = check_common(n, state, action, consts_dev)) return e;
     if (!step_out) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(evopf_ipg_kernel, dim3((n + kActWaves - 1) / kActWaves), dim3(RPO_WAVE * kActWaves), 0, (hipStream_t)stream, n, state, state_stride, action, step_out,
-                       consts_dev);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_ipg_kernel, lane_grid(n), kActThreads, 0, stream, n, state, state_stride, action, step_out, consts_dev);
 }
 
 int rpo_evopf_eq_vjp(int n, const float* action, const float* grad_eq, float* grad_action, int autograd_sign,
                      const float* consts_dev, void* stream) {
     if (int e = check_common(n, action, grad_eq, consts_dev)) return e;
     if (!grad_action) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(evopf_eq_vjp_kernel, dim3(n), dim3(RPO_WAVE), 0, (hipStream_t)stream, n, action, grad_eq, grad_action,
-                       autograd_sign, consts_dev);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_eq_vjp_kernel, dim3(n), RPO_WAVE, 0, stream, n, action, grad_eq, grad_action, autograd_sign, consts_dev);
 }
 
 int rpo_evopf_lagrangian(int n, const float* state, int state_stride, const float* action, const float* nu, float scale, float* loss_out,
                          float* grad_action, float* grad_nu, const float* consts_dev, int overwrite, void* stream) {
     if (int e = check_common(n, state, action, consts_dev)) return e;
     if (!nu) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(evopf_lagrangian_kernel, dim3(1), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, state, state_stride,
-                       action, nu, scale, loss_out, grad_action, grad_nu, consts_dev, overwrite);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(evopf_lagrangian_kernel, dim3(1), RPO_BLOCK, 0, stream, n, state, state_stride, action, nu, scale, loss_out,
+                  grad_action, grad_nu, consts_dev, overwrite);
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // Host-side glue of the C-ABI entry points, shared by the translation units that take networks (fused.hip, nsplit.hip,
 // evaluate.hip, act.hip, mlp.hip): the host structs -> the kernels' argument structs, the shape checks of the 128 / 256 -> 256
-// networks with scalar heads, and the launch plumbing.  Host code only: nothing here reaches a code object.
+// networks with scalar heads, and the launch plumbing (the launch itself: launch.h).  Host code only: nothing here reaches a code
+// object.
 #pragma once
+#include "launch.h"
 #include "mlp_tile.h"
 
 namespace rpo_host {
@@ -32,13 +34,6 @@ inline int check_critic(const Mlp& q, int obs_dim, int E, bool tiled, bool hd) {
     if (q.S != obs_dim || q.A != 2 || q.cat || q.H != 256 || q.n_out != 1 || (hd && q.hd > 1)) return RPO_ERR_ARG;
     if (q.E != E || (tiled && E != 128 && E != 256)) return RPO_ERR_ARG;
     return 0;
-}
-
-// Launch and answer like RPO_LAUNCH_CHECK: 0 or the hipError_t
-template <class... P, class... A>
-int launch(void (*kernel)(P...), dim3 grid, int threads, size_t lds, void* stream, const A&... args) {
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, (hipStream_t)stream, args...);
-    return (int)hipGetLastError();
 }
 
 // A stage's kernel: its CartSafe and its SpringPendulum instantiation

@@ -50,9 +50,7 @@ __global__ __launch_bounds__(RPO_BLOCK) void pendulum_step_kernel(StepArgs p) {
     }
 
     if (p.stats) {
-        const int slot[kStepStats] = {RPO_STAT_REWARD_SUM, RPO_STAT_EPISODES, RPO_STAT_RETURN_SUM, RPO_STAT_LENGTH_SUM,
-                                      RPO_STAT_MAX_INEQ_SUM, RPO_STAT_MAX_EQ_SUM, RPO_STAT_VIOL_COUNT, RPO_STAT_TERMINATED,
-                                      RPO_STAT_MAX_INEQ_MAX, RPO_STAT_MAX_EQ_MAX};
+        const int slot[kStepStats] = RPO_STEP_STAT_SLOTS;
         rpo_stats_flush<kStepStats>(st, 8, slot, rpo_stats_row(p.stats, p.stats_cap, t), red);
     }
     rpo_step_epilogue(p.ctrl, t, p.stats, p.stats_cap);
@@ -171,7 +169,7 @@ __global__ __launch_bounds__(RPO_BLOCK) void pendulum_lagrangian_kernel(int n, c
         for (int w = 0; w < RPO_BLOCK / RPO_WAVE; ++w) s += red[w];
         s *= scale;
         // (a launch that adds into loss_out / grad_nu is always ONE workgroup; wider batches leave per-workgroup sums in
-        //  partials_out: see rpo_cartsafe_lagrangian)
+        //  partials_out: see launch_lagrangian)
         if (partials_out) { partials_out[(size_t)blockIdx.x * 8] = nu0 * s; partials_out[(size_t)blockIdx.x * 8 + 1] = s; }
         else {
             if (loss_out) atomicAdd(loss_out, nu0 * s);
@@ -180,28 +178,11 @@ __global__ __launch_bounds__(RPO_BLOCK) void pendulum_lagrangian_kernel(int n, c
     }
 }
 
-// (== lagrangian_reduce_kernel of cartsafe.hip: G partial vectors [G][8] summed in a fixed order by one workgroup)
-__global__ __launch_bounds__(RPO_BLOCK) void pend_lagrangian_reduce_kernel(int G, int K, const float* __restrict__ partials,
-                                                                           float* __restrict__ loss_out, float* __restrict__ grad_nu) {
-    __shared__ float red[RPO_BLOCK];
-    for (int k = 0; k < K; ++k) {
-        float acc = 0.0f;
-        for (int b = threadIdx.x; b < G; b += RPO_BLOCK) acc += partials[(size_t)b * 8 + k];
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        for (int off = RPO_BLOCK / 2; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            float* dst = k == 0 ? loss_out : (grad_nu ? grad_nu + k - 1 : nullptr);
-            if (dst) *dst += red[0];
-        }
-        __syncthreads();
-    }
-}
-
 }  // namespace
+
+// (behind the unit's kernels: the reduce kernel of env_glue.h keeps its place in the code object)
+#include "env_glue.h"
+using namespace rpo_env_glue;
 
 extern "C" {
 
@@ -209,25 +190,18 @@ int rpo_pendulum_reset(int n_envs, float* internal, float* obs, int* ep_len, flo
                        unsigned long long seed, unsigned env_id_base, void* stream) {
     if (n_envs <= 0) return RPO_ERR_ARG;
     if (!internal || !ep_len || !ep_ret) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(pendulum_reset_kernel, dim3(rpo_grid_for(n_envs)), dim3(RPO_BLOCK), 0, (hipStream_t)stream,
-                       n_envs, internal, obs, ep_len, ep_ret, ep_count, (uint64_t)seed, (uint32_t)env_id_base);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(pendulum_reset_kernel, dim3(rpo_grid_for(n_envs)), RPO_BLOCK, 0, stream, n_envs, internal, obs, ep_len, ep_ret,
+                  ep_count, (uint64_t)seed, (uint32_t)env_id_base);
 }
 
 int rpo_pendulum_step(int n_envs, float* internal, float* obs, const float* action, int* ep_len, float* ep_ret,
                       unsigned* ep_count, float* rows, long long cap_steps, float* stats, int stats_cap,
                       long long* ctrl, int max_episode_steps, int auto_reset, float viol_thresh,
                       unsigned long long seed, unsigned env_id_base, void* stream) {
-    if (n_envs <= 0 || max_episode_steps <= 0) return RPO_ERR_ARG;
-    if (!internal || !action || !ep_len || !ep_ret || !ep_count) return RPO_ERR_NULL;
-    if (rows && cap_steps <= 0) return RPO_ERR_ARG;
-    if (stats && stats_cap <= 0) return RPO_ERR_ARG;
-    StepArgs a{n_envs, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl,
-               max_episode_steps, auto_reset, viol_thresh, (uint64_t)seed, (uint32_t)env_id_base};
-    hipLaunchKernelGGL(pendulum_step_kernel, dim3(rpo_grid_for(n_envs)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = check_step(n_envs, max_episode_steps, internal, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap)) return e;
+    const StepArgs a{n_envs, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl,
+                     max_episode_steps, auto_reset, viol_thresh, (uint64_t)seed, (uint32_t)env_id_base};
+    return launch(pendulum_step_kernel, dim3(rpo_grid_for(n_envs)), RPO_BLOCK, 0, stream, a);
 }
 
 int rpo_pendulum_act_project(int n, const float* obs, int obs_stride, const float* ap_raw, const float* noise,
@@ -235,18 +209,12 @@ int rpo_pendulum_act_project(int n, const float* obs, int obs_stride, const floa
                              float eps_decay, float box_lo, float box_hi, int max_steps, float corr_lr,
                              float corr_eps, float corr_momentum, unsigned long long seed, unsigned env_id_base,
                              const long long* ctrl, float* stats, int stats_cap, void* stream) {
-    if (n <= 0 || max_steps < 0 || obs_stride < RPO_PEND_OBS_DIM || noise_mode < RPO_NOISE_NONE ||
-        noise_mode > RPO_NOISE_CLIP_ONLY)
-        return RPO_ERR_ARG;
-    if (!obs || !action || (noise_mode != RPO_NOISE_UNIFORM && !ap_raw)) return RPO_ERR_NULL;
-    if (noise_mode == RPO_NOISE_EXPLICIT && !noise) return RPO_ERR_NULL;
-    if (stats && stats_cap <= 0) return RPO_ERR_ARG;
-    ActArgs a{n, obs, obs_stride, ap_raw, noise, action, iters, noise_mode, eps_start, eps_end, eps_decay, box_lo,
-              box_hi, max_steps, corr_lr, corr_eps, corr_momentum, (uint64_t)seed, (uint32_t)env_id_base, ctrl, stats,
-              stats_cap};
-    hipLaunchKernelGGL(pendulum_act_project_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, a);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (int e = check_act_project(n, max_steps, noise_mode, RPO_PEND_OBS_DIM, obs, obs_stride, ap_raw, noise, action, stats, stats_cap))
+        return e;
+    const ActArgs a{n, obs, obs_stride, ap_raw, noise, action, iters, noise_mode, eps_start, eps_end, eps_decay, box_lo,
+                    box_hi, max_steps, corr_lr, corr_eps, corr_momentum, (uint64_t)seed, (uint32_t)env_id_base, ctrl, stats,
+                    stats_cap};
+    return launch(pendulum_act_project_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, a);
 }
 
 int rpo_pendulum_project_batchref(int n, const float* obs, int obs_stride, const float* ap, float* action,
@@ -254,81 +222,40 @@ int rpo_pendulum_project_batchref(int n, const float* obs, int obs_stride, const
                                   void* stream) {
     if (n <= 0 || n > 1024 || max_steps < 0 || obs_stride < RPO_PEND_OBS_DIM) return RPO_ERR_ARG;
     if (!obs || !ap || !action) return RPO_ERR_NULL;
-    const size_t lds = ((size_t)n + 4) * sizeof(float);
-    if (n <= 256) {                                                // four samples x 16 values per thread (project_batchref_wide)
-        hipLaunchKernelGGL(pendulum_project_batchref_wide_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, obs,
-                           obs_stride, ap, action, iters_out, max_steps, corr_lr, corr_eps, corr_momentum);
-    } else {
-        const int threads = (n + RPO_WAVE - 1) / RPO_WAVE * RPO_WAVE;
-        hipLaunchKernelGGL(pendulum_project_batchref_kernel<1>, dim3(1), dim3(threads), lds, (hipStream_t)stream, n, obs,
-                           obs_stride, ap, action, iters_out, max_steps, corr_lr, corr_eps, corr_momentum);
-    }
-    RPO_LAUNCH_CHECK();
-    return 0;
+    if (n <= 256)                                                  // four samples x 16 values per thread (project_batchref_wide)
+        return launch(pendulum_project_batchref_wide_kernel, dim3(1), 1024, 0, stream, n, obs, obs_stride, ap, action, iters_out,
+                      max_steps, corr_lr, corr_eps, corr_momentum);
+    return launch(pendulum_project_batchref_kernel<1>, dim3(1), (n + RPO_WAVE - 1) / RPO_WAVE * RPO_WAVE, ((size_t)n + 4) * sizeof(float),
+                  stream, n, obs, obs_stride, ap, action, iters_out, max_steps, corr_lr, corr_eps, corr_momentum);
 }
 
+// (the three below read obs rows; resid only for the equality)
 int rpo_pendulum_complete_bwd(int n, const float* obs, int obs_stride, const float* grad_action, float* grad_ap,
                               void* stream) {
     if (n <= 0 || obs_stride < RPO_PEND_OBS_DIM) return RPO_ERR_ARG;
     if (!obs || !grad_action || !grad_ap) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(pendulum_complete_bwd_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n,
-                       obs, obs_stride, grad_action, grad_ap);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(pendulum_complete_bwd_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, n, obs, obs_stride, grad_action, grad_ap);
 }
 
 int rpo_pendulum_resid(int n, const float* obs, int obs_stride, const float* action, float* eq_resid,
                        float* ineq_resid, void* stream) {
     if (n <= 0 || obs_stride < RPO_PEND_OBS_DIM) return RPO_ERR_ARG;
     if (!action || (eq_resid && !obs)) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(pendulum_resid_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, obs,
-                       obs_stride, action, eq_resid, ineq_resid);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(pendulum_resid_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, n, obs, obs_stride, action, eq_resid, ineq_resid);
 }
 
 int rpo_pendulum_ineq_partial_grad(int n, const float* obs, int obs_stride, const float* action, float* step,
                                    void* stream) {
     if (n <= 0 || obs_stride < RPO_PEND_OBS_DIM) return RPO_ERR_ARG;
     if (!obs || !action || !step) return RPO_ERR_NULL;
-    hipLaunchKernelGGL(pendulum_ipg_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, obs,
-                       obs_stride, action, step);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch(pendulum_ipg_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, n, obs, obs_stride, action, step);
 }
 
 int rpo_pendulum_lagrangian(int n, const float* action, const float* nu, float scale, float* loss_out,
                             float* grad_action, float* grad_nu, void* stream) {
     if (n <= 0) return RPO_ERR_ARG;
     if (!action || !nu) return RPO_ERR_NULL;
-    if (n > RPO_BLOCK && (loss_out || grad_nu)) {               // (deterministic sums: see rpo_cartsafe_lagrangian)
-        const int G = rpo_grid_for(n);
-        if (grad_action && (long long)8 * G <= (long long)2 * n) {
-            hipLaunchKernelGGL(pendulum_lagrangian_kernel, dim3(G), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                               (float*)nullptr, (float*)nullptr, (float*)nullptr, grad_action);
-            RPO_LAUNCH_CHECK();
-            hipLaunchKernelGGL(pend_lagrangian_reduce_kernel, dim3(1), dim3(RPO_BLOCK), 0, (hipStream_t)stream, G, 2,
-                               (const float*)grad_action, loss_out, grad_nu);
-            RPO_LAUNCH_CHECK();
-            hipLaunchKernelGGL(pendulum_lagrangian_kernel, dim3(G), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                               (float*)nullptr, grad_action, (float*)nullptr, (float*)nullptr);
-            RPO_LAUNCH_CHECK();
-            return 0;
-        }
-        if (grad_action) {
-            hipLaunchKernelGGL(pendulum_lagrangian_kernel, dim3(G), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                               (float*)nullptr, grad_action, (float*)nullptr, (float*)nullptr);
-            RPO_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(pendulum_lagrangian_kernel, dim3(1), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n, action, nu, scale,
-                           loss_out, (float*)nullptr, grad_nu, (float*)nullptr);
-        RPO_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(pendulum_lagrangian_kernel, dim3(rpo_grid_for(n)), dim3(RPO_BLOCK), 0, (hipStream_t)stream, n,
-                       action, nu, scale, loss_out, grad_action, grad_nu, (float*)nullptr);
-    RPO_LAUNCH_CHECK();
-    return 0;
+    return launch_lagrangian(pendulum_lagrangian_kernel, 2, n, action, nu, scale, loss_out, grad_action, grad_nu, stream);
 }
 
 }  // extern "C"

@@ -439,24 +439,121 @@ def _act_profile(profile, n, steps):
 
 # =================================================================================================== env kernel sets
 
-class _FusedEvaluate(object):
-    """The ``evaluate*`` methods of the env kernel classes that have the fused evaluation kernel (rpo_<env>_evaluate*, rpo_amd/
-    csrc/evaluate.hip).  The class says what its entry points differ in: ``_eval_env`` (the <env> of the symbols),
-    ``_eval_state(internal, obs)`` (the state pointers behind n_envs) and ``_eval_consts()`` (the arguments in front of
-    max_episode_steps)."""
+class _EnvKernels(object):
+    """What the three env kernel classes share: the methods whose entry points rpo_<env>_* differ only in what the class declares.
 
+    ``_env``        the <env> of its symbols;
+    ``_state_obs``  whether the env's state is (internal, obs) -- two pointers behind n_envs -- or internal alone;
+    ``_obs_rows``   whether its constraint functions read the observation: an (obs, row stride) view then goes behind n;
+    ``_consts(like)``  the constants of a launch (a host table and ``partial``, nothing, or a table on ``like``'s device).
+
+    A method whose entry point places these elsewhere or takes more is an override in the class (EvopfKernels has five)."""
+
+    _state_obs = _obs_rows = False
+
+    def _consts(self, like):
+        return ()
+
+    def _state(self, internal, obs, need_obs=False):
+        return (_p(internal), _p(obs, allow_none=not need_obs)) if self._state_obs else (_p(internal),)
+
+    def _rows(self, obs):
+        return _row_view(obs, self.obs_dim) if self._obs_rows else ()
+
+    def _call(self, what, *args):
+        name = "rpo_%s_%s" % (self._env, what)
+        check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+    def reset(self, internal, obs, ep_len, ep_ret, ep_count, seed, env_id_base):
+        # (CartSafe: the observation IS the internal state, `obs` aliases `internal`)
+        self._call("reset", internal.shape[0], *self._state(internal, obs), _p(ep_len, torch.int32), _p(ep_ret),
+                   _p(ep_count, torch.int32), seed, env_id_base)
+
+    def step(self, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, ctrl, max_episode_steps,
+             auto_reset, viol_thresh, seed, env_id_base):
+        self._call("step", internal.shape[0], *self._state(internal, obs), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
+                   _p(ep_count, torch.int32), _ring(rows, self.ring_floats), cap_steps, _p(stats, allow_none=True),
+                   0 if stats is None else stats.shape[0], _p(ctrl, torch.int64, allow_none=True), *self._consts(internal),
+                   max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base)
+
+    def act_project(self, obs, ap_raw, noise, action, iters, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi,
+                    max_steps, corr_lr, corr_eps, corr_momentum, seed=0, env_id_base=0, ctrl=None, stats=None):
+        self._call("act_project", action.shape[0], *self._rows(obs), _p(ap_raw, allow_none=True), _p(noise, allow_none=True),
+                   _p(action), _p(iters, torch.int32, allow_none=True), noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi,
+                   max_steps, corr_lr, corr_eps, corr_momentum, *self._consts(action), seed, env_id_base,
+                   _p(ctrl, torch.int64, allow_none=True), _p(stats, allow_none=True), 0 if stats is None else stats.shape[0])
+
+    def complete_bwd(self, obs, grad_action, grad_ap, action=None):
+        self._call("complete_bwd", grad_action.shape[0], *self._rows(obs), _p(grad_action), _p(grad_ap), *self._consts(grad_action))
+
+    def resid(self, obs, action, eq_out, ineq_out):
+        self._call("resid", action.shape[0], *self._rows(obs), _p(action), _p(eq_out, allow_none=True), _p(ineq_out, allow_none=True),
+                   *self._consts(action))
+
+    def ineq_partial_grad(self, obs, action, step_out):
+        self._call("ineq_partial_grad", action.shape[0], *self._rows(obs), _p(action), _p(step_out), *self._consts(action))
+
+    def lagrangian(self, action, nu, scale, loss_out, grad_action, grad_nu, obs=None):
+        self._call("lagrangian", action.shape[0], _p(action), _p(nu), scale, _p(loss_out), _p(grad_action, allow_none=True),
+                   _p(grad_nu, allow_none=True), *self._consts(action))
+
+
+class _FusedEnvKernels(_EnvKernels):
+    """The envs that have the fused kernels with the actor inside (CartSafe, SpringPendulum): the rollout (rpo_<env>_rollout,
+    csrc/fused.hip), the projected actions for given observations (rpo_<env>_policy_act*, rpo_<env>_project_profile, csrc/act.hip)
+    and the fused evaluation (rpo_<env>_evaluate*, csrc/evaluate.hip)."""
+
+    def rollout(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps,
+                stats, ctrl, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps,
+                corr_momentum, max_episode_steps, auto_reset, viol_thresh, seed, env_id_base, defer_clock=False):
+        net = actor_desc.net_struct()
+        self._call("rollout", ctypes.byref(net), int(gauss), scale, base, internal.shape[0], *self._state(internal, obs), _p(action),
+                   _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _ring(rows, self.ring_floats), cap_steps,
+                   _p(stats, allow_none=True), 0 if stats is None else stats.shape[0], _p(ctrl, torch.int64), noise_mode,
+                   eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
+                   *self._consts(internal), max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, int(defer_clock))
+
+    def _policy_act_args(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
+                         max_steps, corr_lr, corr_eps, corr_momentum):
+        """The arguments both policy_act entry points start with (the byref keeps the actor's struct alive over the call)."""
+        net = actor_desc.net_struct()
+        op, ostride = _row_view(obs, self.obs_dim)
+        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
+        return (ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
+                _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
+                box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, *self._consts(action))
+
+    def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
+                   max_steps, corr_lr, corr_eps, corr_momentum, form=0):
+        """obs [n, obs_dim] (row view) -> action [n, 2] and, where not None, proposal [n], iters int32 [n], eq_resid [n, 1],
+        ineq_resid [n, ineq_num], in one launch (rpo_<env>_policy_act); form: 0 by size, 1 row tile, 2 / 3 streaming (G = 1 / 4)."""
+        self._call("policy_act", *self._policy_act_args(actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid,
+                                                         ineq_resid, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum),
+                   int(form))
+
+    def policy_act_profile(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo,
+                           box_hi, max_steps, corr_lr, corr_eps, corr_momentum, profile):
+        """``policy_act`` (row tile) that also writes profile [max_steps + 1, n, 4]: plane b = (a0, a1, eq_resid, max ineq_resid)
+        of the budget b (rpo_<env>_policy_act_profile)."""
+        self._call("policy_act_profile", *self._policy_act_args(actor_desc, gauss, scale, base, obs, action, proposal, iters,
+                                                                 eq_resid, ineq_resid, box_lo, box_hi, max_steps, corr_lr, corr_eps,
+                                                                 corr_momentum), _act_profile(profile, obs.shape[0], max_steps))
+
+    def project_profile(self, obs, ap_raw, action, iters, max_steps, corr_lr, corr_eps, corr_momentum, profile):
+        """``act_project(NOISE_NONE)`` that also writes profile [max_steps + 1, n, 4] (rpo_<env>_project_profile)."""
+        n = action.shape[0]
+        self._call("project_profile", n, *self._rows(obs), _p(ap_raw), _p(action), _p(iters, torch.int32, allow_none=True),
+                   int(max_steps), corr_lr, corr_eps, corr_momentum, *self._consts(action), _act_profile(profile, n, max_steps))
+
+    # ---- the fused evaluation: the entry points start alike (_eval_args) and differ in their tails
     def _eval_args(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps,
                    box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh):
         """The arguments every entry point starts with (the byref keeps the actor's struct alive over the call)."""
         n = internal.shape[0]
-        return (ctypes.byref(actor_desc.net_struct()), int(gauss), scale, base, n, *self._eval_state(internal, obs), _p(action),
+        return (ctypes.byref(actor_desc.net_struct()), int(gauss), scale, base, n, *self._state(internal, obs, True), _p(action),
                 _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True),
                 _eval_acc(acc, n), int(t0), int(steps), box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
-                *self._eval_consts(), max_episode_steps, viol_thresh)
-
-    def _eval_launch(self, variant, *args):
-        name = "rpo_%s_%s" % (self._eval_env, variant)
-        check(getattr(_lib.load(), name)(*args, _stream()), name)
+                *self._consts(internal), max_episode_steps, viol_thresh)
 
     def _eval_trace(self, trace, n):
         if trace is None:
@@ -480,13 +577,13 @@ class _FusedEvaluate(object):
         if noise is not None:
             tr = self._eval_trace(trace, n)
             sigma, tail = _eval_noise(noise, self.obs_dim)       # (sigma: kept alive over the call that copies it)
-            self._eval_launch("evaluate_noisy", *args, *tr, self._eval_con(con, n), *tail)
+            self._call("evaluate_noisy", *args, *tr, self._eval_con(con, n), *tail)
         elif con is not None:
-            self._eval_launch("evaluate_constraints", *args, *self._eval_trace(trace, n), self._eval_con(con, n))
+            self._call("evaluate_constraints", *args, *self._eval_trace(trace, n), self._eval_con(con, n))
         elif trace is None:
-            self._eval_launch("evaluate", *args)
+            self._call("evaluate", *args)
         else:
-            self._eval_launch("evaluate_record", *args, *self._eval_trace(trace, n))
+            self._call("evaluate_record", *args, *self._eval_trace(trace, n))
 
     def evaluate_budgets(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                          steps, box_lo, box_hi, lane_steps, lane_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
@@ -497,7 +594,7 @@ class _FusedEvaluate(object):
         tail = _eval_lanes(lane_steps, lane_lr, n)
         args = self._eval_args(actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                                steps, box_lo, box_hi, 0, 0.0, corr_eps, corr_momentum, max_episode_steps, viol_thresh)
-        self._eval_launch("evaluate_budgets", *args, None, 0, 0, self._eval_con(con, n), *tail)
+        self._call("evaluate_budgets", *args, None, 0, 0, self._eval_con(con, n), *tail)
 
     def evaluate_policies(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                           steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh, bank,
@@ -509,7 +606,7 @@ class _FusedEvaluate(object):
         tail = _eval_policies(actor_desc, bank, n, group_lanes, episodes)
         args = self._eval_args(actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                                steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh)
-        self._eval_launch("evaluate_policies", *args, self._eval_con(con, n), *tail)
+        self._call("evaluate_policies", *args, self._eval_con(con, n), *tail)
 
     def evaluate_noise_sweep(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                              steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh,
@@ -521,10 +618,10 @@ class _FusedEvaluate(object):
         tail = _eval_noise_sweep(sigma_table, seed, n, group_lanes, episodes)
         args = self._eval_args(actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, ctrl, acc, t0,
                                steps, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, max_episode_steps, viol_thresh)
-        self._eval_launch("evaluate_noise_sweep", *args, self._eval_con(con, n), *tail)
+        self._call("evaluate_noise_sweep", *args, self._eval_con(con, n), *tail)
 
 
-class CartSafeKernels(_FusedEvaluate):
+class CartSafeKernels(_FusedEnvKernels):
     """HIP kernels of CartSafe-v0.  ``consts`` is the float32[35] table of include/rpo_hip.h (RPO_CART_CONSTS_LEN)."""
 
     name = "CartSafe-v0"
@@ -534,6 +631,7 @@ class CartSafeKernels(_FusedEvaluate):
     # column ranges of a transition row
     cols = dict(state=(0, 6), action=(6, 8), next_state=(8, 14), reward=(14, 15), done=(15, 16), eq_viol=(16, 17),
                 ineq_viol=(17, 23))
+    _env = "cartsafe"                          # the state is the observation; the constraints are constants: no obs rows
 
     def __init__(self, consts, partial):
         self.consts = np.ascontiguousarray(consts, dtype=np.float32)     # host table, copied into each launch
@@ -545,83 +643,10 @@ class CartSafeKernels(_FusedEvaluate):
     def _cptr(self):
         return _host_ptr(self.consts)
 
-    _eval_env = "cartsafe"
-
-    def _eval_state(self, internal, obs):
-        return (_p(internal),)
-
-    def _eval_consts(self):
+    def _consts(self, like):
         return self._cptr, self.partial
 
-    def reset(self, internal, obs, ep_len, ep_ret, ep_count, seed, env_id_base):
-        # the observation IS the internal state for this env: `obs` aliases `internal`
-        check(_lib.load().rpo_cartsafe_reset(internal.shape[0], _p(internal), _p(ep_len, torch.int32), _p(ep_ret),
-                                             _p(ep_count, torch.int32), seed, env_id_base, _stream()),
-              "rpo_cartsafe_reset")
-
-    def step(self, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, ctrl, max_episode_steps,
-             auto_reset, viol_thresh, seed, env_id_base):
-        check(_lib.load().rpo_cartsafe_step(
-            internal.shape[0], _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
-            _p(ep_count, torch.int32), _ring(rows, self.ring_floats), cap_steps, _p(stats, allow_none=True),
-            0 if stats is None else stats.shape[0], _p(ctrl, torch.int64, allow_none=True), self._cptr, self.partial,
-            max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, _stream()), "rpo_cartsafe_step")
-
-    def act_project(self, obs, ap_raw, noise, action, iters, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi,
-                    max_steps, corr_lr, corr_eps, corr_momentum, seed=0, env_id_base=0, ctrl=None, stats=None):
-        check(_lib.load().rpo_cartsafe_act_project(
-            action.shape[0], _p(ap_raw, allow_none=True), _p(noise, allow_none=True), _p(action),
-            _p(iters, torch.int32, allow_none=True), noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi,
-            max_steps, corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, seed, env_id_base,
-            _p(ctrl, torch.int64, allow_none=True), _p(stats, allow_none=True),
-            0 if stats is None else stats.shape[0], _stream()), "rpo_cartsafe_act_project")
-
     # ---- fused pipelines (rpo_amd/csrc/fused.hip) ----------------------------------------------------------------
-    def rollout(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps,
-                stats, ctrl, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps,
-                corr_momentum, max_episode_steps, auto_reset, viol_thresh, seed, env_id_base, defer_clock=False):
-        net = actor_desc.net_struct()
-        check(_lib.load().rpo_cartsafe_rollout(
-            ctypes.byref(net), int(gauss), scale, base, internal.shape[0], _p(internal), _p(action),
-            _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _ring(rows, self.ring_floats), cap_steps,
-            _p(stats, allow_none=True), 0 if stats is None else stats.shape[0], _p(ctrl, torch.int64), noise_mode,
-            eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum, self._cptr,
-            self.partial, max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, int(defer_clock), _stream()),
-            "rpo_cartsafe_rollout")
-
-    def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
-                   max_steps, corr_lr, corr_eps, corr_momentum, form=0):
-        """obs [n, 6] (row view) -> action [n, 2] and, where not None, proposal [n], iters int32 [n], eq_resid [n, 1],
-        ineq_resid [n, 6], in one launch (rpo_cartsafe_policy_act); form: 0 by size, 1 row tile, 2 / 3 streaming (G = 1 / 4)."""
-        net = actor_desc.net_struct()
-        op, ostride = _row_view(obs, self.obs_dim)
-        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
-        check(_lib.load().rpo_cartsafe_policy_act(
-            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
-            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
-            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, self._cptr, self.partial, int(form), _stream()),
-            "rpo_cartsafe_policy_act")
-
-    def policy_act_profile(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo,
-                           box_hi, max_steps, corr_lr, corr_eps, corr_momentum, profile):
-        """``policy_act`` (row tile) that also writes profile [max_steps + 1, n, 4]: plane b = (a0, a1, eq_resid, max ineq_resid)
-        of the budget b (rpo_cartsafe_policy_act_profile)."""
-        net = actor_desc.net_struct()
-        op, ostride = _row_view(obs, self.obs_dim)
-        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
-        check(_lib.load().rpo_cartsafe_policy_act_profile(
-            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
-            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
-            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, self._cptr, self.partial,
-            _act_profile(profile, obs.shape[0], max_steps), _stream()), "rpo_cartsafe_policy_act_profile")
-
-    def project_profile(self, obs, ap_raw, action, iters, max_steps, corr_lr, corr_eps, corr_momentum, profile):
-        """``act_project(NOISE_NONE)`` that also writes profile [max_steps + 1, n, 4] (rpo_cartsafe_project_profile)."""
-        n = action.shape[0]
-        check(_lib.load().rpo_cartsafe_project_profile(
-            n, _p(ap_raw), _p(action), _p(iters, torch.int32, allow_none=True), int(max_steps), corr_lr, corr_eps, corr_momentum,
-            self._cptr, self.partial, _act_profile(profile, n, max_steps), _stream()), "rpo_cartsafe_project_profile")
-
     def ddpg_critic_forward(self, actor_target, critic_target, critic, scale, base, rows, cap_steps, n_envs, batch_out,
                             idx_out, idx_in, seed, salt, ctrl, max_steps, corr_lr, corr_eps, corr_momentum, box_lo, box_hi,
                             q_out, qn_out, x0_save, h1_save):
@@ -646,26 +671,8 @@ class CartSafeKernels(_FusedEvaluate):
             _p(q1_out), _p(q2_out), _p(qn1_out), _p(qn2_out), _p(logp_out), _p(x0_save1), _p(h1_save1),
             _p(x0_save2), _p(h1_save2), _stream()), "rpo_cartsafe_sac_critic_forward")
 
-    def complete_bwd(self, obs, grad_action, grad_ap, action=None):
-        check(_lib.load().rpo_cartsafe_complete_bwd(grad_action.shape[0], _p(grad_action), _p(grad_ap), self._cptr,
-                                                    self.partial, _stream()), "rpo_cartsafe_complete_bwd")
 
-    def resid(self, obs, action, eq_out, ineq_out):
-        check(_lib.load().rpo_cartsafe_resid(action.shape[0], _p(action), _p(eq_out, allow_none=True),
-                                             _p(ineq_out, allow_none=True), self._cptr, self.partial, _stream()),
-              "rpo_cartsafe_resid")
-
-    def ineq_partial_grad(self, obs, action, step_out):
-        check(_lib.load().rpo_cartsafe_ineq_partial_grad(action.shape[0], _p(action), _p(step_out), self._cptr,
-                                                         self.partial, _stream()), "rpo_cartsafe_ineq_partial_grad")
-
-    def lagrangian(self, action, nu, scale, loss_out, grad_action, grad_nu, obs=None):
-        check(_lib.load().rpo_cartsafe_lagrangian(action.shape[0], _p(action), _p(nu), scale, _p(loss_out),
-                                                  _p(grad_action, allow_none=True), _p(grad_nu, allow_none=True),
-                                                  self._cptr, self.partial, _stream()), "rpo_cartsafe_lagrangian")
-
-
-class EvopfKernels(object):
+class EvopfKernels(_EnvKernels):
     """HIP kernels of EVOPF-v0 (one wavefront per lane).  ``consts`` = float32[RPO_EVOPF_CONSTS_LEN] built by
     rpo_amd/env/electrical_grid/case14.py; it is uploaded once per device."""
 
@@ -679,6 +686,7 @@ class EvopfKernels(object):
     newton_tol, newton_max_iters = 1e-5, 50          # PFFunction(env, tol=1e-5, bsz=256, max_iters=50), evopf.py:786
     episode_steps = 24                               # the loaders run out of data after one day (demand.py:71)
     partial = 0
+    _env, _obs_rows = "evopf", True            # (resid and ineq_partial_grad are the base's; the others place the table elsewhere)
     CASE14_ADJ = (19, 31, 14, 350, 59, 7216, 456, 192, 9032, 1792, 1568, 6176, 14368, 12544)   # == kAdjMask, evopf_dev.h
 
     def __init__(self, consts):
@@ -701,6 +709,9 @@ class EvopfKernels(object):
         if key not in self._dev:
             self._dev[key] = torch.from_numpy(self.consts).to(like.device)
         return _p(self._dev[key])
+
+    def _consts(self, like):
+        return (self._c(like),)
 
     def reset(self, internal, obs, ep_len, ep_ret, ep_count, seed, env_id_base):
         check(_lib.load().rpo_evopf_reset(internal.shape[0], _p(internal), _p(ep_len, torch.int32), _p(ep_ret),
@@ -752,16 +763,6 @@ class EvopfKernels(object):
                                                  _p(grad_action2, allow_none=True), _p(grad_ap), self._c(action), _stream()),
               "rpo_evopf_complete_bwd")
 
-    def resid(self, obs, action, eq_out, ineq_out):
-        sp, ss = _row_view(obs, self.obs_dim)
-        check(_lib.load().rpo_evopf_resid(action.shape[0], sp, ss, _p(action), _p(eq_out, allow_none=True),
-                                          _p(ineq_out, allow_none=True), self._c(action), _stream()), "rpo_evopf_resid")
-
-    def ineq_partial_grad(self, obs, action, step_out):
-        sp, ss = _row_view(obs, self.obs_dim)
-        check(_lib.load().rpo_evopf_ineq_partial_grad(action.shape[0], sp, ss, _p(action), _p(step_out),
-                                                      self._c(action), _stream()), "rpo_evopf_ineq_partial_grad")
-
     def eq_vjp(self, action, grad_eq, grad_action, autograd_sign=True):
         check(_lib.load().rpo_evopf_eq_vjp(action.shape[0], _p(action), _p(grad_eq), _p(grad_action), int(autograd_sign),
                                            self._c(action), _stream()), "rpo_evopf_eq_vjp")
@@ -776,7 +777,7 @@ class EvopfKernels(object):
     fused_adds = True      # complete_bwd(grad_action2=...) and lagrangian(overwrite=...) exist: no torch launches between them
 
 
-class PendulumKernels(_FusedEvaluate):
+class PendulumKernels(_FusedEnvKernels):
     """HIP kernels of SpringPendulum-v0."""
 
     name = "SpringPendulum-v0"
@@ -786,81 +787,7 @@ class PendulumKernels(_FusedEvaluate):
     cols = dict(state=(0, 5), action=(5, 7), next_state=(7, 12), reward=(12, 13), done=(13, 14), eq_viol=(14, 15),
                 ineq_viol=(15, 16))
     partial = 0
-    _eval_env = "pendulum"
-
-    def _eval_state(self, internal, obs):
-        return _p(internal), _p(obs)
-
-    def _eval_consts(self):
-        return ()
-
-    def reset(self, internal, obs, ep_len, ep_ret, ep_count, seed, env_id_base):
-        check(_lib.load().rpo_pendulum_reset(internal.shape[0], _p(internal), _p(obs, allow_none=True),
-                                             _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), seed,
-                                             env_id_base, _stream()), "rpo_pendulum_reset")
-
-    def step(self, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, ctrl, max_episode_steps,
-             auto_reset, viol_thresh, seed, env_id_base):
-        check(_lib.load().rpo_pendulum_step(
-            internal.shape[0], _p(internal), _p(obs, allow_none=True), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
-            _p(ep_count, torch.int32), _ring(rows, self.ring_floats), cap_steps, _p(stats, allow_none=True),
-            0 if stats is None else stats.shape[0], _p(ctrl, torch.int64, allow_none=True), max_episode_steps,
-            int(auto_reset), viol_thresh, seed, env_id_base, _stream()), "rpo_pendulum_step")
-
-    def act_project(self, obs, ap_raw, noise, action, iters, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi,
-                    max_steps, corr_lr, corr_eps, corr_momentum, seed=0, env_id_base=0, ctrl=None, stats=None):
-        op, ostride = _row_view(obs, 5)
-        check(_lib.load().rpo_pendulum_act_project(
-            action.shape[0], op, ostride, _p(ap_raw, allow_none=True), _p(noise, allow_none=True), _p(action),
-            _p(iters, torch.int32, allow_none=True), noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi,
-            max_steps, corr_lr, corr_eps, corr_momentum, seed, env_id_base, _p(ctrl, torch.int64, allow_none=True),
-            _p(stats, allow_none=True), 0 if stats is None else stats.shape[0], _stream()),
-            "rpo_pendulum_act_project")
-
-    def rollout(self, actor_desc, gauss, scale, base, internal, obs, action, ep_len, ep_ret, ep_count, rows, cap_steps,
-                stats, ctrl, noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps,
-                corr_momentum, max_episode_steps, auto_reset, viol_thresh, seed, env_id_base, defer_clock=False):
-        net = actor_desc.net_struct()
-        check(_lib.load().rpo_pendulum_rollout(
-            ctypes.byref(net), int(gauss), scale, base, internal.shape[0], _p(internal), _p(obs, allow_none=True),
-            _p(action), _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), _ring(rows, self.ring_floats),
-            cap_steps, _p(stats, allow_none=True), 0 if stats is None else stats.shape[0], _p(ctrl, torch.int64),
-            noise_mode, eps_start, eps_end, eps_decay, box_lo, box_hi, max_steps, corr_lr, corr_eps, corr_momentum,
-            max_episode_steps, int(auto_reset), viol_thresh, seed, env_id_base, int(defer_clock), _stream()),
-            "rpo_pendulum_rollout")
-
-    def policy_act(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo, box_hi,
-                   max_steps, corr_lr, corr_eps, corr_momentum, form=0):
-        """obs [n, 5] (row view) -> action [n, 2] and, where not None, proposal [n], iters int32 [n], eq_resid [n, 1],
-        ineq_resid [n, 1], in one launch (rpo_pendulum_policy_act); form: 0 by size, 1 row tile, 2 / 3 streaming (G = 1 / 4)."""
-        net = actor_desc.net_struct()
-        op, ostride = _row_view(obs, self.obs_dim)
-        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
-        check(_lib.load().rpo_pendulum_policy_act(
-            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
-            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
-            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, int(form), _stream()), "rpo_pendulum_policy_act")
-
-    def policy_act_profile(self, actor_desc, gauss, scale, base, obs, action, proposal, iters, eq_resid, ineq_resid, box_lo,
-                           box_hi, max_steps, corr_lr, corr_eps, corr_momentum, profile):
-        """``policy_act`` (row tile) that also writes profile [max_steps + 1, n, 4]: plane b = (a0, a1, eq_resid, ineq_resid) of
-        the budget b (rpo_pendulum_policy_act_profile)."""
-        net = actor_desc.net_struct()
-        op, ostride = _row_view(obs, self.obs_dim)
-        _act_outputs(self, obs.shape[0], action, proposal, iters, eq_resid, ineq_resid)
-        check(_lib.load().rpo_pendulum_policy_act_profile(
-            ctypes.byref(net), int(gauss), scale, base, obs.shape[0], op, ostride, _p(action), _p(proposal, allow_none=True),
-            _p(iters, torch.int32, allow_none=True), _p(eq_resid, allow_none=True), _p(ineq_resid, allow_none=True), box_lo,
-            box_hi, int(max_steps), corr_lr, corr_eps, corr_momentum, _act_profile(profile, obs.shape[0], max_steps), _stream()),
-            "rpo_pendulum_policy_act_profile")
-
-    def project_profile(self, obs, ap_raw, action, iters, max_steps, corr_lr, corr_eps, corr_momentum, profile):
-        """``act_project(NOISE_NONE)`` that also writes profile [max_steps + 1, n, 4] (rpo_pendulum_project_profile)."""
-        n = action.shape[0]
-        op, ostride = _row_view(obs, 5)
-        check(_lib.load().rpo_pendulum_project_profile(
-            n, op, ostride, _p(ap_raw), _p(action), _p(iters, torch.int32, allow_none=True), int(max_steps), corr_lr, corr_eps,
-            corr_momentum, _act_profile(profile, n, max_steps), _stream()), "rpo_pendulum_project_profile")
+    _env, _state_obs, _obs_rows = "pendulum", True, True      # no constants: the equality is a function of the observation
 
     def ddpg_critic_front(self, actor_target, scale, base, rows, cap_steps, n_envs, batch_out, idx_out, idx_in, sample_seed,
                           sample_salt, ctrl, ap_out):
@@ -907,26 +834,6 @@ class PendulumKernels(_FusedEvaluate):
                                                            _p(iters_out, torch.int32, allow_none=True), max_steps, corr_lr,
                                                            corr_eps, corr_momentum, _p(ws, torch.int64), store_mode, _stream()),
               "rpo_pendulum_project_batchref_ws")
-
-    def complete_bwd(self, obs, grad_action, grad_ap, action=None):
-        op, ostride = _row_view(obs, 5)
-        check(_lib.load().rpo_pendulum_complete_bwd(grad_action.shape[0], op, ostride, _p(grad_action), _p(grad_ap),
-                                                    _stream()), "rpo_pendulum_complete_bwd")
-
-    def resid(self, obs, action, eq_out, ineq_out):
-        op, ostride = _row_view(obs, 5)
-        check(_lib.load().rpo_pendulum_resid(action.shape[0], op, ostride, _p(action), _p(eq_out, allow_none=True),
-                                             _p(ineq_out, allow_none=True), _stream()), "rpo_pendulum_resid")
-
-    def ineq_partial_grad(self, obs, action, step_out):
-        op, ostride = _row_view(obs, 5)
-        check(_lib.load().rpo_pendulum_ineq_partial_grad(action.shape[0], op, ostride, _p(action), _p(step_out),
-                                                         _stream()), "rpo_pendulum_ineq_partial_grad")
-
-    def lagrangian(self, action, nu, scale, loss_out, grad_action, grad_nu, obs=None):
-        check(_lib.load().rpo_pendulum_lagrangian(action.shape[0], _p(action), _p(nu), scale, _p(loss_out),
-                                                  _p(grad_action, allow_none=True), _p(grad_nu, allow_none=True),
-                                                  _stream()), "rpo_pendulum_lagrangian")
 
 
 # =================================================================================================== MLP kernels

@@ -110,13 +110,14 @@ def test_checkpoint_roundtrip(tmp_path):
     assert torch.equal(b.agent.actor_target_flat, a.agent.actor_target_flat)
 
 
-def test_harvest_bookkeeping_matches_per_row_loop(capsys):
+def test_harvest_bookkeeping_matches_per_row_loop(capsys, monkeypatch):
     """Trainer._harvest turns statistics rows into Logger rows with whole-array operations; compare with the per-row
     bookkeeping of the reference loop (rpo_ddpg.py:120-137: every step's max violations are logged with the return of
     the episode that step belongs to, once it has finished) over several harvests, a logger that fills up, and rows
     left pending across harvests."""
     from rpo_amd import ops as hip_ops
     S = hip_ops.STAT
+    monkeypatch.setenv("RPO_VERBOSE", "1")                     # (GPU tests of the same session switch the printing off)
     torch.manual_seed(0)
     tr = build_trainer("ddpg", "cart", ob, torch.device("cpu"), num_envs=1)
     rng = np.random.default_rng(3)
