@@ -13,7 +13,7 @@ import torch
 from .. import ops as hip_ops
 from .agent import PDDDPG_PA, PDSAC_PA
 from .model import BoxConstraint
-from .trainer import _SALT_ACTOR, _SALT_CRITIC, RPOTrainerBase, _TDHuberFn
+from .trainer import _SALT_ACTOR, _SALT_CRITIC, RPOTrainerBase, _TDHuberFn, hyperparameters
 
 
 class _LagrangianBase(RPOTrainerBase):
@@ -108,11 +108,8 @@ class DDPG_LA(_LagrangianBase):
             lr_actor=lr_actor, lr_critic=lr_critic, lr_dual=lr_dual, reg=reg, eps=eps, tau=tau, gamma=gamma,
             capacity=capacity, init_lamb=init_lamb, init_nju=init_nju, device=device, backend=backend,
             clip_thres=clip_thres, full_action=True)
-        hp = dict(max_steps=max_steps, corr_lr=corr_lr, eval_lr=corr_lr, corr_eps=corr_eps, corr_momentum=corr_momentum,
-                  corr_mode=corr_mode, grad_eps=grad_eps, clip_thres=clip_thres, eval_steps=eval_steps,
-                  batch_size=batch_size, policy_fre=policy_fre, eval_fre=eval_fre, warmup=warmup, max_epochs=max_epochs,
-                  fixed=fixed, partial=False, eps=eps, eps_start=eps, eps_epoch=1,      # constant exploration scale
-                  eval_episodes=eval_episodes, keep_best=keep_best)
+        # (eps_start == eps: constant exploration scale)
+        hp = hyperparameters(dict(locals(), eval_lr=corr_lr, partial=False, eps_start=eps, eps_epoch=1))
         self._setup_la(env, work_dir, name, logger, agent, hp, device, num_envs, seed, backend, shape)
 
     def _noisy(self, ap, state, noise):
@@ -136,9 +133,8 @@ class DDPG_LA(_LagrangianBase):
     def actor_loss(self, state):
         """ddpg_lag.py:252-266."""
         ag = self.agent
-        self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * self._noise_b.numel(), _SALT_ACTOR,
-                                   hip_ops.STREAM_POLICY, self.vec.ctrl)
-        actions = self._noisy(ag.actor(state), state, self._noise_b)
+        noise = self._draw_batch(_SALT_ACTOR)
+        actions = self._noisy(ag.actor(state), state, noise)
         return (-ag.critic(state, actions)).mean() + self._penalty(state, actions)
 
     def _critic_step(self, actor_step):
@@ -170,19 +166,15 @@ class SAC_LA(_LagrangianBase):
             tau=tau, gamma=gamma, capacity=capacity, init_lamb=init_lamb, init_nju=init_nju, device=device,
             backend=backend, clip_thres=clip_thres, full_action=True)
         self.automatic_entropy_tuning = automatic_entropy_tuning
-        hp = dict(max_steps=max_steps, corr_lr=corr_lr, eval_lr=corr_lr, corr_eps=corr_eps, corr_momentum=corr_momentum,
-                  corr_mode=corr_mode, grad_eps=grad_eps, clip_thres=clip_thres, eval_steps=eval_steps,
-                  batch_size=batch_size, policy_fre=policy_fre, eval_fre=eval_fre, warmup=warmup, max_epochs=max_epochs,
-                  fixed=fixed, partial=False, eps=eps, eps_start=eps, eps_epoch=1, eval_episodes=eval_episodes, keep_best=keep_best)
+        hp = hyperparameters(dict(locals(), eval_lr=corr_lr, partial=False, eps_start=eps, eps_epoch=1))
         self._setup_la(env, work_dir, name, logger, agent, hp, device, num_envs, seed, backend, shape)
 
     def _sample_action(self, state, noise, log_pi=False):
         return self.agent.take_action(state, log_pi=log_pi, eps=noise)                        # agent/sac.py take_action
 
     def _explore(self, obs):
-        self.backend.philox_normal(self._noise_n, self.seed, self.vec.env_id_base * self._noise_n.shape[1], 0,
-                                   hip_ops.STREAM_POLICY, self.vec.ctrl)
-        return self._sample_action(obs, self._noise_n)
+        return self._sample_action(obs, self._draw(self._noise_n, self.vec.env_id_base * self._noise_n.shape[1], 0,
+                                                   rollout=True))
 
     def _deterministic(self, obs):
         return self.agent.take_action(obs, deterministic=True)
@@ -191,9 +183,7 @@ class SAC_LA(_LagrangianBase):
         """sac_lag.py:300-311."""
         ag = self.agent
         with torch.no_grad():
-            self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * self._noise_b.numel(), _SALT_CRITIC,
-                                       hip_ops.STREAM_POLICY, self.vec.ctrl)
-            next_actions, logp = self._sample_action(next_state, self._noise_b, log_pi=True)
+            next_actions, logp = self._sample_action(next_state, self._draw_batch(_SALT_CRITIC), log_pi=True)
             nq1, nq2 = ag.critic_target(next_state, next_actions)
         q1, q2 = ag.critic(state, action)
         return _TDHuberFn.apply(self.backend, ag.gamma, float(ag.alpha), reward, done, nq1, nq2, logp, q1, q2)
@@ -201,9 +191,7 @@ class SAC_LA(_LagrangianBase):
     def actor_loss(self, state):
         """sac_lag.py:280-297 -> (loss, log_pi)."""
         ag = self.agent
-        self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * self._noise_b.numel(), _SALT_ACTOR,
-                                   hip_ops.STREAM_POLICY, self.vec.ctrl)
-        actions, logp = self._sample_action(state, self._noise_b, log_pi=True)
+        actions, logp = self._sample_action(state, self._draw_batch(_SALT_ACTOR), log_pi=True)
         q1, q2 = ag.critic(state, actions)
         return (ag.alpha * logp - torch.min(q1, q2)).mean() + self._penalty(state, actions), logp
 

@@ -6,46 +6,8 @@ from .. import ops as hip_ops
 from .agent import PDDDPG_PA
 from .model import BoxConstraint
 from .agent.flat import FusedAdam
-from .trainer import _SALT_ACTOR, RPOTrainerBase, _LagrangianFn, _TDHuberFn
-
-
-class _LazySum(object):
-    """Per-workgroup loss partials, summed only when somebody looks (keeps a reduction kernel out of the iteration)."""
-
-    def __init__(self, parts):
-        self.parts = parts
-
-    def __float__(self):
-        return float(self.parts.sum())
-
-    def detach(self):
-        return self.parts.sum()
-
-
-class _LazyDiff(object):
-    """mean Lagrangian term - mean Q from the two words the actor-backward pipeline leaves on the device."""
-
-    def __init__(self, pair):
-        self.pair = pair
-
-    def __float__(self):
-        return float(self.pair[0] - self.pair[1])
-
-    def detach(self):
-        return self.pair[0] - self.pair[1]
-
-
-class _LazyMeanDiff(object):
-    """mean Lagrangian term (one device word) - mean Q (a [B, 1] buffer): no reduction launch inside the iteration."""
-
-    def __init__(self, lag, q):
-        self.lag, self.q = lag, q
-
-    def __float__(self):
-        return float(self.detach())
-
-    def detach(self):
-        return self.lag[0] - self.q.mean()
+from .lazy import LazyLoss, LazySum
+from .trainer import _SALT_ACTOR, RPOTrainerBase, _LagrangianFn, _TDHuberFn, hyperparameters
 
 
 class RPODDPG(RPOTrainerBase):
@@ -69,13 +31,8 @@ class RPODDPG(RPOTrainerBase):
             capacity=capacity, init_lamb=init_lamb, init_nju=init_nju, partial=partial,
             partial_idx=base.partial_actions if partial_idx is None else partial_idx, device=device, backend=backend,
             clip_thres=clip_thres)
-        hp = dict(max_steps=max_steps, corr_lr=corr_lr, eval_lr=eval_lr, corr_eps=corr_eps, corr_momentum=corr_momentum,
-                  corr_mode=corr_mode, grad_eps=grad_eps, clip_thres=clip_thres, eval_steps=eval_steps,
-                  batch_size=batch_size, policy_fre=policy_fre, eval_fre=eval_fre, warmup=warmup, max_epochs=max_epochs,
-                  fixed=fixed, partial=partial, eps=eps, eps_start=eps_start, eps_epoch=eps_epoch,
-                  eval_episodes=eval_episodes, keep_best=keep_best)
-        self._setup(env, work_dir, name, logger, agent, hp, device, num_envs, seed, backend, use_graph, updates_per_step,
-                    schedule=schedule)
+        self._setup(env, work_dir, name, logger, agent, hyperparameters(locals()), device, num_envs, seed, backend, use_graph,
+                    updates_per_step, schedule=schedule)
 
     # ---- rollout policy (rpo_ddpg.py:98-106, agent/ddpg_pa.py:101-112) ----------------------------------------
     def _actor_out(self, name, obs, save=False, tag=None):
@@ -103,21 +60,14 @@ class RPODDPG(RPOTrainerBase):
     # ---- fused pipelines (one launch per stage group; CartSafe kernels provide them) -----------------------------
     @property
     def _pipelines(self):
-        k = self.kernels
-        return (self.fused is not None and (hasattr(k, "ddpg_critic_forward") or hasattr(k, "ddpg_critic_front"))
-                and "actor_target" in self.fused.descs and "critic" in self.fused.descs
-                and self.schedule["fused_critic"] and not self._large_batch)
+        return self._critic_pipeline_ok("ddpg_critic", "actor_target", "critic")
 
-    def _sample(self):
-        if self._pipelines:
-            # the critic-forward pipeline draws and gathers the batch itself (into self._batch)
-            c = self.buffer.split(self._batch)
-            return c["state"], c["action"], c["next_state"], c["reward"], c["done"], c["ineq_viol"], c["eq_viol"]
-        return super()._sample()
+    @property
+    def _actor_pipeline(self):
+        return self._actor_pipeline_ok("ddpg_actor_forward", "critic")
 
     def _critic_update_pipeline(self, cols):
-        f, ag, B, buf = self.fused, self.agent, self.batch_size, self.buffer
-        state, action = cols[0], cols[1]
+        f, B, buf = self.fused, self.batch_size, self.buffer
         d = f.descs["critic"]
         scale, base = self._box_affine
         parts = f.buf("loss_parts", (B + 15) // 16)
@@ -149,32 +99,17 @@ class RPODDPG(RPOTrainerBase):
         gm = self._critic_gradmax()
         f.backward("critic", cols[0], cols[1], None, gradmax=gm, td=td)
         self._gradmax_ready = gm is not None
-        self.last_losses["critic"] = _LazySum(parts)
+        self.last_losses["critic"] = LazySum(parts)
 
-    # ---- the update through the hand-written MLP kernels (same arithmetic as critic_loss / actor_loss below) ------
-    def _critic_update(self, cols):
-        if self.fused is None:
-            return super()._critic_update(cols)
-        if self._pipelines:
-            su = self._split_state()
-            if su is not None:
-                return self._critic_update_split(su)
-            return self._critic_update_pipeline(cols)
-        f, ag, B = self.fused, self.agent, self.batch_size
-        state, action, next_state, reward, done = cols[:5]
+    # ---- the update through the generic MLP launches (same arithmetic as critic_loss / actor_loss below) ---------
+    def _critic_update_generic(self, cols):
+        f, B = self.fused, self.batch_size
+        state, action, next_state = cols[:3]
         next_actions = self._project_batch(next_state, self._actor_out("actor_target", next_state))
         qn, q = f.forward_multi([("critic_target", next_state, next_actions, f.buf("qn", B, 1), False),
                                  ("critic", state, action, f.buf("q", B, 1), True)])
         # TD target / Huber loss: the prologue of the backward pass (rpo_td)
         self._critic_backward_td(cols, q, qn, f.buf("loss_parts", (B + 15) // 16))
-
-    @property
-    def _actor_pipeline(self):
-        d = self.fused.descs if self.fused is not None else {}
-        return (hasattr(self.backend, "ddpg_actor_forward") and "actor" in d and "critic" in d and d["actor"].E == 128
-                and d["critic"].E == 128 and not d["critic"].cat and self._box_affine is not None
-                and self.kernels.partial_dim == 1 and self.kernels.action_dim == 2
-                and self.schedule["fused_actor"] and not self._large_batch)
 
     def _actor_update_pipeline(self, cols):
         """The policy step in two launches + the actor's weights pass (fused.hip)."""
@@ -185,47 +120,34 @@ class RPODDPG(RPOTrainerBase):
         parts = b("actor.parts", (B + 15) // 16, 8)
         ap_det, noise, actions = b("act.ap_det", B), b("act.noise", B), b("act_pi", B, k.action_dim)
         q, dq, g_act = b("q_pi", B, 1), b("dq_pi", B, 1), b("g_act", B, k.action_dim)
-        noise_in = None
-        if self._idx_inject is not None:                       # tests replay the reference's draw
-            self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * B * k.partial_dim, _SALT_ACTOR, hip_ops.STREAM_POLICY,
-                                       self._uctrl)
-            noise_in = self._noise_b.view(-1)
+        # (tests replay the reference's draw)
+        noise_in = self._draw_batch(_SALT_ACTOR).view(-1) if self._idx_inject is not None else None
         self.backend.ddpg_actor_forward(k, da_, dc, scale, base, self._box_lo, self._box_hi, self.eps_start, self.eps, self.decay_value,
                              self._batch, noise_in, self.seed, self.dist.rank * B, _SALT_ACTOR, self._uctrl,
                              ag.nju.weight.view(-1), ap_det, noise, actions, q, dq, g_act, parts, b("actor.x0", B, da_.ein),
                              b("actor.h1", B, da_.H), b("critic.x0", B, dc.ein), b("critic.h1", B, dc.H))
         self._zero_grads()
         shared = ag.flat.sizes[1] > 0
-        opt = ag.actor_optim
-        fuse_max = self._self_cleaning and not self.dist.on and opt.clip_thres and opt.clip_thres != float("inf")
+        gm = self._fused_gradmax(ag.actor_optim)
         lag = b("actor.lag", 2)
         self.backend.ddpg_actor_backward(k, da_, dc, shared, self._batch, actions, g_act, ap_det, noise, dq, self.eps_start, self.eps,
                               self.decay_value, self._box_lo, self._box_hi, scale, base, self._uctrl,
                               b("actor.x0", B, da_.ein), b("actor.h1", B, da_.H), b("critic.x0", B, dc.ein),
                               b("critic.h1", B, dc.H), b("actor.dh", B, da_.H), b("actor.dx0", B, da_.ein),
                               b("critic.dh", B, dc.H), b("critic.dx0", B, dc.ein), b("da", B, k.action_dim), b("do", B),
-                              parts, lag, ag.nju.weight.grad.view(-1), opt.gradmax if fuse_max else None)
-        self._actor_gradmax_ready = bool(fuse_max)
-        loss = _LazyDiff(lag)
-        self.last_losses["actor"] = loss
+                              parts, lag, ag.nju.weight.grad.view(-1), gm)
+        self._actor_gradmax_ready = gm is not None
+        return self._pipeline_actor_out(lag, parts, None)
+
+    def _pipeline_actor_out(self, lag, parts, logp):
+        """What `_actor_update` returns from the words the policy pipelines (row-tile or column-split) leave on the device:
+        mean Lagrangian term - mean Q."""
+        loss = self.last_losses["actor"] = LazyLoss(lambda lag: lag[0] - lag[1], lag)
         return loss
 
-    def _actor_update(self, cols):
-        if self.fused is None:
-            return super()._actor_update(cols)
-        if self._actor_pipeline:
-            su = self._split_state()
-            if su is not None:
-                lag, _, _ = self._actor_update_split(su)
-                loss = _LazyDiff(lag)
-                self.last_losses["actor"] = loss
-                return loss
-            return self._actor_update_pipeline(cols)
+    def _actor_update_generic(self, cols, pre):
         f, ag, B, k = self.fused, self.agent, self.batch_size, self.kernels
         state = cols[0]
-        pre, self._actor_pre = getattr(self, "_actor_pre", None), None
-        if pre is None:
-            pre = self._actor_prefix(cols)
         ap_det, noise, actions, lag, g_act, fa = pre
         # (its own buffer: the lazily reduced actor loss below keeps a reference to it, and the next critic-only update writes
         #  Q(s, a_replay) into "q" -- ADVICE r03)
@@ -249,12 +171,11 @@ class RPODDPG(RPOTrainerBase):
                                       self._box_lo, self._box_hi, scale, base, do.view(-1))
         # (no shared embedding: every gradient of the actor's slice is written by this backward -- it leaves the inf-norm for
         #  clip_grad_norm_, no rpo_absmax launch)
-        opt = ag.actor_optim
-        fuse_max = self._self_cleaning and not self.dist.on and opt.clip_thres and opt.clip_thres != float("inf") and not shared
-        f.backward("actor", state, None, do, gradmax=opt.gradmax if fuse_max else None)
-        self._actor_gradmax_ready = bool(fuse_max)
-        loss = _LazyMeanDiff(lag, q)                          # lag[0] - mean(Q), reduced only when somebody looks
-        self.last_losses["actor"] = loss
+        gm = self._fused_gradmax(ag.actor_optim, alone=not shared)
+        f.backward("actor", state, None, do, gradmax=gm)
+        self._actor_gradmax_ready = gm is not None
+        # mean Lagrangian term (one device word) - mean Q (a [B, 1] buffer), reduced only when somebody looks
+        loss = self.last_losses["actor"] = LazyLoss(lambda lag, q: lag[0] - q.mean(), lag, q)
         return loss
 
     def _actor_prefix(self, cols):
@@ -263,22 +184,11 @@ class RPODDPG(RPOTrainerBase):
         the critic update writes, so the graph windows of EVOPF-v0 run it on the second captured branch BESIDE the critic
         update of a policy iteration (trainer._overlapped_window; round 5: ~50 us off a 364 us chain) -- same launches, same
         arguments, same bits as inside `_actor_update`."""
-        f, ag, B, k = self.fused, self.agent, self.batch_size, self.kernels
         state = cols[0]
         ap_det = self._actor_out("actor", state, save=True, tag="pi")
-        self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * B * k.partial_dim, _SALT_ACTOR, hip_ops.STREAM_POLICY,
-                                   self._uctrl)
-        noise = self._noise_b.view(-1)
+        noise = self._draw_batch(_SALT_ACTOR).view(-1)
         actions = self._complete_only(state, ap_det, noise)
-        lag, g_act = f.buf("loss_lag", 1), f.buf("g_act", B, k.action_dim)
-        # (EVOPF kernels write the loss term and add the Lagrangian's d/d action themselves: no torch launch in the step)
-        fa = bool(getattr(k, "fused_adds", False))
-        if not fa:
-            lag.zero_()
-        self._zero_grads()                 # parameters AND multipliers (they live in the same flat buffer)
-        k.lagrangian(actions, ag.nju.weight.view(-1), 1.0 / B, lag, g_act, ag.nju.weight.grad.view(-1), obs=state,
-                     **(dict(overwrite=True) if fa else {}))
-        return ap_det, noise, actions, lag, g_act, fa
+        return (ap_det, noise, actions) + self._lagrangian_term(state, actions)
 
     def _const_dq(self, B):
         key = ("dq_pi_const", B)
@@ -302,9 +212,8 @@ class RPODDPG(RPOTrainerBase):
         take_action comes from the Philox stream instead of torch's global generator."""
         ag = self.agent
         ap = ag.actor(state)
-        self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * self.batch_size * self.kernels.partial_dim, _SALT_ACTOR,
-                                   hip_ops.STREAM_POLICY, self._uctrl)
-        ap = ag.actor.box_constraint.clip(ap + self._eps_now() * self._noise_b, state)
+        noise = self._draw_batch(_SALT_ACTOR)
+        ap = ag.actor.box_constraint.clip(ap + self._eps_now() * noise, state)
         actions = self.base_env.complete_partial(state, ap)
         loss = (-ag.critic(state, actions)).mean()
         return loss + _LagrangianFn.apply(self.kernels, actions, ag.nju.weight, state)
@@ -316,10 +225,9 @@ class RPODDPG(RPOTrainerBase):
     def _critic_step(self, actor_step):
         ag = self.agent
         fuse = actor_step and ag.flat.sizes[1] == 0
-        prepared, self._critic_prepared = getattr(self, "_critic_prepared", False), False
         ag.critic_optim.step(target=ag.critic_target_flat if fuse else None, tau=ag.tau,
-                             gradmax_ready=self._gradmax_ready, clock=self._clock(not actor_step), prepared=prepared)
-        self._gradmax_ready = False
+                             gradmax_ready=self._take("_gradmax_ready"), clock=self._clock(not actor_step),
+                             prepared=self._take("_critic_prepared"))
 
     def _actor_step(self, actor_out):
         # actor Adam (+ Polyak of the actor target) | multiplier DualAdam | Polyak of the critic target: one launch.
@@ -329,12 +237,10 @@ class RPODDPG(RPOTrainerBase):
         c = fl.actor_range[0]                                  # [critic-only | shared | actor-only], padded offsets
         sh = fl.critic_range[1] - c if fl.sizes[1] > 0 else 0
         segs = [ag.actor_optim.segment(target=ag.actor_target_flat, tau=ag.tau,
-                                       gradmax_ready=getattr(self, "_actor_gradmax_ready", False),
+                                       gradmax_ready=self._take("_actor_gradmax_ready"),
                                        target2=ag.critic_target_flat[c:c + sh] if sh > 0 else None, n2=sh)]
-        self._actor_gradmax_ready = False
         if not self.fixed:
             segs.append(ag.nju_optim.segment())                    # lambda is never stepped (rpo_ddpg.py:202)
         if sh > 0 and c > 0:
             segs.append(dict(polyak_only=True, param=fl.param((0, c)), target=ag.critic_target_flat[:c], tau=ag.tau))
-        prepared, self._actor_prepared = getattr(self, "_actor_prepared", False), False
-        FusedAdam.step_many(self.backend, segs, clock=self._clock(True), prepared=prepared)
+        FusedAdam.step_many(self.backend, segs, clock=self._clock(True), prepared=self._take("_actor_prepared"))

@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from .. import ops as hip_ops
 from .agent.fused import FusedNets
+from .lazy import LazySum
 from .model import BoxConstraint
 
 
@@ -290,11 +291,30 @@ def parse_schedule(overrides=None):
     return out
 
 
+_HP_NAMES = ("max_steps", "corr_lr", "eval_lr", "corr_eps", "corr_momentum", "corr_mode", "grad_eps", "clip_thres", "eval_steps",
+             "batch_size", "policy_fre", "eval_fre", "warmup", "max_epochs", "fixed", "partial", "eps", "eps_start", "eps_epoch",
+             "eval_episodes", "keep_best")
+
+
+def hyperparameters(args):
+    """The trainer attributes `_setup` takes from a constructor's arguments (``args``: its ``locals()``)."""
+    return {k: args[k] for k in _HP_NAMES}
+
+
 # ------------------------------------------------------------------------------------------------ trainer core
 class RPOTrainerBase(object):
-    """Everything except agent construction and the two losses."""
+    """Everything except agent construction, the two losses and the leaves of the update that differ between the algorithms."""
 
     sac = False
+
+    #: Host state an iteration's Python changes besides launching (hand-over flags between the update's stages and the
+    #: optimiser steps, what a segment leaves for the next one), with the value it has between iterations.  `_setup` applies
+    #: the table; `_GraphCache` snapshots and restores these names around an aborted capture (`_host_state`).
+    _HOST_STATE_DEFAULTS = dict(
+        _actor_pre=None, _clock_pending=False, _iter_actor_step=None, _critic_prepared=False, _gradmax_stale=False,
+        _actor_prepared=False, _actor_gradmax_stale=False, _pol_a_done=False, _gradmax_ready=False, _actor_gradmax_ready=False,
+        _bump_updates_now=False, _updates_out=None, _last_cols=None, _last_actor_out=None)
+    _HOST_STATE = tuple(_HOST_STATE_DEFAULTS)
 
     def _setup(self, env, work_dir, name, logger, agent, hp, device, num_envs=None, seed=None, backend=None,
                use_graph=None, updates_per_step=None, fused=None, schedule=None):
@@ -355,7 +375,6 @@ class RPOTrainerBase(object):
             use_graph = cycle > 0 and device.type == "cuda"
         self._graphs = _GraphCache(use_graph, owner=self)
         self._tail = None           # data-parallel runs: deferred last segment of the previous iteration
-        self._last_cols = self._last_actor_out = None
         self._cycle = max(cycle, 1) // max(1, self.policy_fre) * max(1, self.policy_fre)
         # projection of training batches: the reference's literal batched semantics (default) or row-wise
         # (RPO_ROWWISE_PROJECTION=1); rollouts are always per lane == the reference's B = 1 calls
@@ -393,7 +412,6 @@ class RPOTrainerBase(object):
         # averaged in place between backward and step, then consumed the same way).  The torch/autograd path keeps its
         # explicit zeroing.
         self._self_cleaning = self.fused is not None
-        self._gradmax_ready = False
         for opt in (agent.critic_optim, agent.actor_optim, agent.nju_optim):
             opt.zero_grad_after = self._self_cleaning
         # fused multi-output actor: raw outputs, the env's projection kernel applies the state-dependent tanh box
@@ -404,14 +422,15 @@ class RPOTrainerBase(object):
         # split path it is an alias of the rollout's ctrl and nothing changes.
         self._uctrl, self._uclock_ok, self._ovl_stream = self.vec.ctrl, True, None
         self._ride, self._rider_cache, self._ride_cut = None, None, 0
-        self._clock_pending, self._iter_actor_step, self._critic_prepared, self._gradmax_stale = False, None, False, False
-        self._actor_prepared, self._actor_gradmax_stale = False, False
-        self._bump_updates_now, self._updates_out, self._pol_a_done = False, None, False
+        self.__dict__.update(self._HOST_STATE_DEFAULTS)
         self._bump = self.updates_per_step == 1
         if self.fused is not None and device.type == "cuda" and getattr(self.backend, "ADAM_CLOCK", False):
             self._uctrl, self._uclock_ok = torch.zeros_like(self.vec.ctrl), False
         self.buffer.sample_ctrl = self._uctrl
-        self._split_state()
+        self._noise_pi = None       # RPOSAC: the policy step's own draw buffer, made by its first `_actor_prefix`
+        self._flag_poll = dict(event=None, calls=0, host={}, pending=[])
+        self._split_cache, self._front_cache, self._pfront = False, False, False   # (False: not probed yet)
+        self._split_state()         # probed here, outside any graph capture
         self._t = 0                 # loop iterations (== vector steps) done
         self._harvested = 0         # vector steps whose statistics were already pulled off the device
         self._pending = []          # per-step rows waiting for the return of the episodes they belong to
@@ -465,6 +484,27 @@ class RPOTrainerBase(object):
     #: RPOSAC samples the squashed Gaussian inside the rollout pipeline; RPODDPG adds exploration noise to the actor
     _gauss_policy = False
 
+    #: The fused pipelines of the critic update / the policy step (one launch per stage group, fused.hip) and, on top of
+    #: them, the column-split stages (`_split_state`): the subclasses say when their kernels provide them.
+    _pipelines = False
+    _actor_pipeline = False
+
+    def _critic_pipeline_ok(self, stem, *nets):
+        """`_pipelines` of a subclass whose env kernels carry ``<stem>_forward`` or ``<stem>_front`` and whose networks ``nets``
+        run through the fused MLP kernels."""
+        k = self.kernels
+        return bool(self.fused is not None and (hasattr(k, stem + "_forward") or hasattr(k, stem + "_front"))
+                    and all(n in self.fused.descs for n in nets) and self.schedule["fused_critic"] and not self._large_batch)
+
+    def _actor_pipeline_ok(self, entry, critic):
+        """`_actor_pipeline` of a subclass whose policy step starts with the backend's ``entry``: 128-wide embeddings, an
+        additive critic (``critic``: its first one), a constant box, one basic action of two."""
+        d = self.fused.descs if self.fused is not None else {}
+        return bool(hasattr(self.backend, entry) and "actor" in d and critic in d and d["actor"].E == 128
+                    and d[critic].E == 128 and not d[critic].cat and self._box_affine is not None
+                    and self.kernels.partial_dim == 1 and self.kernels.action_dim == 2
+                    and self.schedule["fused_actor"] and not self._large_batch)
+
     @property
     def _large_batch(self):
         """One LARGE batch per update (batch_size >= RPO_SPLITK_FROM, e.g. 256 * num_envs: as many sampled transitions per
@@ -483,7 +523,7 @@ class RPOTrainerBase(object):
         """A rollout that is followed by the column-split critic update may leave its step counter to that update's first
         launch (rpo_*_rollout(defer_clock=1), rpo_split_update.rollout_ctrl): saves the arrival counting behind the
         rollout's last workgroup."""
-        return bool(getattr(self, "_pipelines", False) and self._split_state() is not None)
+        return bool(self._pipelines and self._split_state() is not None)
 
     def _rollout(self, warm, defer_clock=False):
         """``defer_clock``: the caller runs the column-split critic update next, whose first launch advances the step
@@ -513,9 +553,29 @@ class RPOTrainerBase(object):
 
     # ------------------------------------------------------------------------------------------ update
     def _sample(self):
-        self.buffer.sample_rows(self.batch_size, out=self._batch)
+        if not self._pipelines:            # (else: the critic-forward pipeline draws and gathers the batch itself)
+            self.buffer.sample_rows(self.batch_size, out=self._batch)
         c = self.buffer.split(self._batch)
         return c["state"], c["action"], c["next_state"], c["reward"], c["done"], c["ineq_viol"], c["eq_viol"]
+
+    def _draw(self, buf, id_base, salt, rollout=False):
+        """N(0,1) draws keyed by the step counter: the rollout's (ctrl[T]) or the update's clock (`_uctrl`)."""
+        self.backend.philox_normal(buf, self.seed, id_base, salt, hip_ops.STREAM_POLICY,
+                                   self.vec.ctrl if rollout else self._uctrl)
+        return buf
+
+    def _draw_batch(self, salt, buf=None):
+        """The update's draw for the sampled batch, into `_noise_b` unless ``buf``: rank r owns the Philox indices
+        [r * numel, (r + 1) * numel)."""
+        buf = self._noise_b if buf is None else buf
+        return self._draw(buf, self.dist.rank * buf.numel(), salt)
+
+    def _take(self, name):
+        """The value of the hand-over flag ``name`` (a name of `_HOST_STATE_DEFAULTS`), which goes back to its default: whoever
+        consumes a flag leaves it down for the next iteration."""
+        value = getattr(self, name)
+        setattr(self, name, self._HOST_STATE_DEFAULTS[name])
+        return value
 
     def _eps_now(self):
         """Exploration scale inside the update (take_action in actor_loss, rpo_ddpg.py:309).  Constant in every script
@@ -529,10 +589,15 @@ class RPOTrainerBase(object):
         """Where the critic's backward kernels may leave the inf-norm of its gradient slice (clip_grad_norm_,
         rpo_ddpg.py:180): only when that slice was zero before (self-cleaning steps) and is not averaged over ranks
         afterwards.  `_critic_step` then skips the rpo_absmax launch."""
-        opt = self.agent.critic_optim
-        ok = self._self_cleaning and not self.dist.on and opt.clip_thres and opt.clip_thres != float("inf")
         self._gradmax_ready = False
-        return opt.gradmax if ok else None
+        return self._fused_gradmax(self.agent.critic_optim)
+
+    def _fused_gradmax(self, opt, alone=True):
+        """``opt.gradmax`` when the backward kernels may leave the inf-norm of `opt`'s gradient slice there: the slice was
+        zero before (self-cleaning steps), is not averaged over ranks afterwards, is clipped at all, and (``alone``) every
+        gradient in it is written by that backward.  None: the optimiser's step launches rpo_absmax."""
+        fuse = alone and self._self_cleaning and not self.dist.on and opt.clip_thres and opt.clip_thres != float("inf")
+        return opt.gradmax if fuse else None
 
     def _zero_grads(self):
         """Before a backward of the fused path: nothing to do when the optimiser steps leave zeroed slices behind
@@ -542,22 +607,56 @@ class RPOTrainerBase(object):
         elif self.fixed:
             self.agent.nju.weight.grad.zero_()
 
+    # The two halves of an update pick their path here, once for both algorithms: no fused nets -> the torch modules + autograd
+    # (`critic_loss` / `actor_loss`); fused pipelines -> the column-split stages when `_split_state()` has them, else the
+    # row-tile pipelines of fused.hip; otherwise the generic MLP launches.  The subclasses provide the leaves.
     def _critic_update(self, cols):
-        state, action, next_state, reward, done, ineq_viol, eq_viol = cols
-        loss = self.critic_loss(state, action, next_state, done, reward, ineq_viol, eq_viol)
-        self.agent.flat.grad.zero_()
-        loss.backward()
-        self.last_losses["critic"] = loss.detach()
+        if self.fused is None:
+            state, action, next_state, reward, done, ineq_viol, eq_viol = cols
+            loss = self.critic_loss(state, action, next_state, done, reward, ineq_viol, eq_viol)
+            self.agent.flat.grad.zero_()
+            loss.backward()
+            self.last_losses["critic"] = loss.detach()
+        elif self._pipelines:
+            su = self._split_state()
+            if su is not None:
+                self._critic_update_split(su)
+            else:
+                self._critic_update_pipeline(cols)
+        else:
+            self._critic_update_generic(cols)
 
     def _actor_update(self, cols):
-        out = self.actor_loss(cols[0])
-        loss = out[0] if isinstance(out, tuple) else out
-        self.agent.flat.grad.zero_()       # parameters and multipliers share the flat gradient buffer
-        loss.backward()
-        self.last_losses["actor"] = loss.detach()
-        # detached: the result outlives the iteration on the trainer (segments / graph replays), and must not keep the
-        # autograd graph alive across iterations
-        return tuple(x.detach() for x in out) if isinstance(out, tuple) else loss.detach()
+        if self.fused is None:
+            out = self.actor_loss(cols[0])
+            loss = out[0] if isinstance(out, tuple) else out
+            self.agent.flat.grad.zero_()       # parameters and multipliers share the flat gradient buffer
+            loss.backward()
+            self.last_losses["actor"] = loss.detach()
+            # detached: the result outlives the iteration on the trainer (segments / graph replays), and must not keep the
+            # autograd graph alive across iterations
+            return tuple(x.detach() for x in out) if isinstance(out, tuple) else loss.detach()
+        if self._actor_pipeline:
+            su = self._split_state()
+            if su is not None:
+                return self._pipeline_actor_out(*self._actor_update_split(su))
+            return self._actor_update_pipeline(cols)
+        pre = self._take("_actor_pre")     # (the overlapped windows ran the actor-only prefix beside the critic update)
+        return self._actor_update_generic(cols, self._actor_prefix(cols) if pre is None else pre)
+
+    def _lagrangian_term(self, state, actions):
+        """Tail of the subclasses' `_actor_prefix`: mean_b nu . relu(g(a_b)) of the completed actions into "loss_lag", its
+        d/d action into "g_act" and its d/d nu into the multipliers' gradient -> (lag, g_act, fa).  ``fa``: the EVOPF kernels
+        write the loss term and add the Lagrangian's d/d action themselves (no torch launch in the step)."""
+        f, ag, B, k = self.fused, self.agent, self.batch_size, self.kernels
+        lag, g_act = f.buf("loss_lag", 1), f.buf("g_act", B, k.action_dim)
+        fa = bool(getattr(k, "fused_adds", False))
+        if not fa:
+            lag.zero_()
+        self._zero_grads()                 # parameters AND multipliers (they live in the same flat buffer)
+        k.lagrangian(actions, ag.nju.weight.view(-1), 1.0 / B, lag, g_act, ag.nju.weight.grad.view(-1), obs=state,
+                     **(dict(overwrite=True) if fa else {}))
+        return lag, g_act, fa
 
     def _segments(self, warm, do_train, actor_step, rollout=True):
         """The iteration as a list of (device work, gradient buffers to all-reduce afterwards).  ``rollout=False``: the
@@ -660,8 +759,23 @@ class RPOTrainerBase(object):
     def _updates_inkernel(self):
         """Several updates per vector step: ctrl[RPO_CTRL_UPDATES] is advanced by the update's own last stage (column-split
         critic AND policy stages) instead of a torch launch between two updates."""
-        return bool(self.updates_per_step > 1 and getattr(self, "_pipelines", False) and getattr(self, "_actor_pipeline", False)
-                    and self._split_state() is not None)
+        return bool(self.updates_per_step > 1 and self._pipelines and self._actor_pipeline and self._split_state() is not None)
+
+    def _critic_half(self, cols, actor_step):
+        """Critic update on the sampled columns | all-reduce of its gradient range | optimiser step.  ``actor_step``: whether
+        `_policy_half` follows (the hand-overs of `_set_hand_overs` depend on it)."""
+        self._iter_actor_step = actor_step
+        self._critic_update(cols)
+        fl = self.agent.flat
+        self.dist.mean_([fl.gradient(fl.critic_range)])
+        self._critic_step(actor_step)
+
+    def _policy_half(self, cols):
+        """Policy step on the same columns | all-reduce of the policy bucket (actor slice + multipliers) | optimiser step."""
+        self._last_actor_out = self._actor_update(cols)
+        fl = self.agent.flat
+        self.dist.mean_([fl.gradient(fl.policy_bucket)])
+        self._actor_step(self._last_actor_out)
 
     def _extra_body(self, actor_step):
         if self._updates_inkernel:
@@ -669,15 +783,9 @@ class RPOTrainerBase(object):
         else:
             self._uctrl[hip_ops.CONST["RPO_CTRL_UPDATES"]] += 1
         cols = self._sample()
-        self._iter_actor_step = actor_step
-        self._critic_update(cols)
-        fl = self.agent.flat
-        self.dist.mean_([fl.gradient(fl.critic_range)])
-        self._critic_step(actor_step)
+        self._critic_half(cols, actor_step)
         if actor_step:
-            out = self._actor_update(cols)
-            self.dist.mean_([fl.gradient(fl.policy_bucket)])
-            self._actor_step(out)
+            self._policy_half(cols)
 
     def _extra_updates(self):
         """The 2nd .. updates_per_step-th update of the current vector step: same kernels as the first one, with
@@ -712,22 +820,17 @@ class RPOTrainerBase(object):
 
     def _train_body(self, t):
         cols = self._sample()
-        actor_step = self._iter_actor_step = t % self.policy_fre == 0
-        self._critic_update(cols)
-        fl = self.agent.flat
-        self.dist.mean_([fl.gradient(fl.critic_range)])
-        self._critic_step(actor_step)
+        actor_step = t % self.policy_fre == 0
+        self._critic_half(cols, actor_step)
         if actor_step:
-            out = self._actor_update(cols)
-            self.dist.mean_([fl.gradient(fl.policy_bucket)])
-            self._actor_step(out)
+            self._policy_half(cols)
 
     # ------------------------------------------------------------------------------------------ column-split update
     def _split_state(self):
         """The column-split update stages (rpo_split_*, rpo_amd/csrc/nsplit.hip) when this configuration supports them:
         CartSafe / SpringPendulum kernels, every network 128 -> 256 with scalar heads, the reference's batched projection
         semantics on SpringPendulum, batch <= 1024.  Schedule ``split=0`` keeps the row-tile pipelines."""
-        if getattr(self, "_split_cache", False) is not False:
+        if self._split_cache is not False:
             return self._split_cache
         self._split_cache = None
         f, k, be = self.fused, self.kernels, self.backend
@@ -797,12 +900,10 @@ class RPOTrainerBase(object):
 
     def _actor_update_split(self, su):
         """Policy step through the column-split stages: pol_a .. pol_e (rpo_amd/csrc/nsplit.hip)."""
-        B, ag, k = self.batch_size, self.agent, self.kernels
+        B, ag = self.batch_size, self.agent
         noise_in = None
         if self._idx_inject is not None:                          # tests replay the reference's draw
-            self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * B * k.partial_dim, _SALT_ACTOR,
-                                       hip_ops.STREAM_POLICY, self._uctrl)
-            noise_in = self._noise_b.view(-1)
+            noise_in = self._draw_batch(_SALT_ACTOR).view(-1)
         crit_logp, pi_logp = self._split_logp
         su.set(noise_salt=_SALT_ACTOR, eps_in=noise_in, logp=pi_logp)
         early, self._pol_a_done = self._pol_a_done, False
@@ -815,15 +916,15 @@ class RPOTrainerBase(object):
             su.run("policy_b")
             su.run("policy_c")
         self._zero_grads()
-        opt = ag.actor_optim
-        fuse_max = self._self_cleaning and not self.dist.on and opt.clip_thres and opt.clip_thres != float("inf")
-        su.set(gradmax=opt.gradmax if fuse_max else None)
+        gm = self._fused_gradmax(ag.actor_optim)
+        fuse_max = gm is not None
+        su.set(gradmax=gm)
         if not front:
             su.run("policy_d")
         # "prepared" optimiser launch behind the policy step (as for the critic's, `_critic_update_split`): pol_e advances the
         # step counters of the slices `_actor_step` will step and the update clock; the next fwd_a zeroes the actor's gradmax
         # (only when the critic update runs through the split stages too: its fwd_a is what zeroes the gradmax afterwards)
-        prep = bool(fuse_max) and bool(getattr(self, "_pipelines", False))
+        prep = bool(fuse_max) and bool(self._pipelines)
         optims = [o for o in self._policy_optims() if o is not None] if prep else []
         su.set_prep2([(o.step_dev, o.betas[0], o.betas[1]) for o in optims])
         su.set(clock_out=self._clock(True) if prep else None, updates_out=self._updates_out)
@@ -876,10 +977,7 @@ class RPOTrainerBase(object):
         idx_in = self._idx_inject() if inject else None
         eps_in = None
         if inject and self.sac:
-            B = self.batch_size
-            self.backend.philox_normal(self._noise_b, self.seed, self.dist.rank * B * self.kernels.partial_dim, _SALT_CRITIC,
-                                       hip_ops.STREAM_POLICY, self._uctrl)
-            eps_in = self._noise_b.view(-1)
+            eps_in = self._draw_batch(_SALT_CRITIC).view(-1)
         buf = self.buffer
         su.set(idx_in=idx_in, eps_in=eps_in, rows=buf.rows, cap_steps=buf.capacity, n_envs=buf.n_envs)   # (tests swap the ring)
         actor_step, self._iter_actor_step = self._iter_actor_step, None
@@ -890,7 +988,7 @@ class RPOTrainerBase(object):
             ride.set(lane_begin=0, lane_end=cut)
         # CartSafe: fwd_a, fwd_b and bwd_a are one launch (the later stages' workgroups wait inside it for the
         # workgroups of their own row tile, rpo_split_critic_front) -- same values, two launch boundaries less
-        early = bool(actor_step) and ride is None and self.agent.flat.sizes[1] == 0 and getattr(self, "_actor_pipeline", False)
+        early = bool(actor_step) and ride is None and self.agent.flat.sizes[1] == 0 and self._actor_pipeline
         if su.st.env == 0 and self._front_ok():
             self._pol_a_done = early
             if ride is not None:
@@ -920,20 +1018,17 @@ class RPOTrainerBase(object):
         su.run("critic_fwd_b_pol" if early else "critic_fwd_b", rider=ride)   # (+ actor forward of lanes [cut, n))
         self._critic_update_split_back(su, ride)
 
-    _HOST_STATE = ("_actor_pre", "_clock_pending", "_iter_actor_step", "_critic_prepared", "_gradmax_stale", "_actor_prepared",
-                   "_actor_gradmax_stale", "_pol_a_done", "_gradmax_ready", "_actor_gradmax_ready", "_bump_updates_now",
-                   "_updates_out", "_last_cols", "_last_actor_out")
-
     def _host_state(self):
-        """What an iteration's Python changes on the HOST besides launching (hand-over flags, the argument struct of the
-        column-split stages, the host mirror of the step counter): `_GraphCache` restores it when a capture is aborted."""
+        """What an iteration's Python changes on the HOST besides launching (the names of `_HOST_STATE_DEFAULTS`, the argument
+        struct of the column-split stages, the host mirror of the step counter): `_GraphCache` restores it when a capture is
+        aborted."""
         import ctypes
-        st = {k: getattr(self, k) for k in self._HOST_STATE if hasattr(self, k)}
+        st = {k: getattr(self, k) for k in self._HOST_STATE}
         st["steps_host"] = self.vec.steps_host
-        su = getattr(self, "_split_cache", None)
+        su = self._split_cache
         if su:
             st["su"] = (ctypes.string_at(ctypes.addressof(su.st), ctypes.sizeof(su.st)), dict(su._held))
-        rc = getattr(self, "_rider_cache", None)
+        rc = self._rider_cache
         if rc is not None and hasattr(rc, "st"):
             st["rider"] = ctypes.string_at(ctypes.addressof(rc.st), ctypes.sizeof(rc.st))
         return st
@@ -953,10 +1048,10 @@ class RPOTrainerBase(object):
 
     def _handover_flags(self):
         """Device words the in-launch hand-overs raise when a wait was given up: (tile_sync's last word, proj_ws's)."""
-        su = getattr(self, "_split_cache", None)
+        su = self._split_cache
         sync = su._held.get("tile_sync") if su else None
         ws = su._held.get("proj_ws") if su else None
-        return (sync[-32:-31] if sync is not None and getattr(self, "_front_cache", False) else None,
+        return (sync[-32:-31] if sync is not None and self._front_cache else None,
                 ws[hip_ops.PROJ_WS_GAVE_UP:hip_ops.PROJ_WS_GAVE_UP + 1] if ws is not None else None)
 
     def _device_flags(self):
@@ -1005,9 +1100,7 @@ class RPOTrainerBase(object):
         instead of at the next statistics harvest."""
         if self.device.type != "cuda":
             return self._raise_flags({k: int(x[0]) for k, x in self._device_flags()})
-        st = getattr(self, "_flag_poll", None)
-        if st is None:
-            st = self._flag_poll = dict(event=None, calls=0, host={}, pending=[])
+        st = self._flag_poll
         if st["event"] is not None:
             if not st["event"].query():
                 return                                            # the previous copy is still in flight: look again later
@@ -1044,8 +1137,7 @@ class RPOTrainerBase(object):
             self._clock_pending = bool(self._defer_ok)
             self.vec.steps_host += 1
         self._gradmax_ready = gm is not None
-        from .rpo_ddpg import _LazySum
-        self.last_losses["critic"] = _LazySum(self._split_loss if self.sac else self._split_loss[0])
+        self.last_losses["critic"] = LazySum(self._split_loss if self.sac else self._split_loss[0])
 
     # ------------------------------------------------------------------------------------------ fused-MLP helpers
     def _project_batch(self, state, ap_flat):
@@ -1233,7 +1325,7 @@ class RPOTrainerBase(object):
         on its own clock.  Results are identical to the serial order.  Schedule ``ride=0`` keeps the serial windows."""
         if not (do_train and self._uctrl is not self.vec.ctrl and self.agent.flat.sizes[1] == 0 and self._bump):
             return False
-        if not (getattr(self, "_pipelines", False) and self._split_state() is not None and self._rollout_pipeline):
+        if not (self._pipelines and self._split_state() is not None and self._rollout_pipeline):
             return False
         return bool(self.schedule["ride"])
 
@@ -1262,25 +1354,20 @@ class RPOTrainerBase(object):
         i -- its actor forward in the launches of fwd_a and fwd_b (a lane range each), its explore / project / step / scatter
         in bwd_b's, behind fwd_a, which gathers the batch out of the ring first -- unless iteration i ends with a policy step,
         whose new actor the next rollout has to wait for."""
-        F, fl = self.policy_fre, self.agent.flat
+        F = self.policy_fre
         self._rollout(False, defer_clock=True)
         for i in range(L):
             actor_step = (t + i + 1) % F == 0
             more = i + 1 < L
             ride = more and not actor_step
             self._ride = self._rider() if ride else None
-            self._iter_actor_step = actor_step
-            try:
+            try:                                                # (only the critic update's launches read `_ride`)
                 cols = self._last_cols = self._sample()
-                self._critic_update(cols)
+                self._critic_half(cols, actor_step)
             finally:
                 self._ride = None
-            self.dist.mean_([fl.gradient(fl.critic_range)])
-            self._critic_step(actor_step)
             if actor_step:
-                self._last_actor_out = self._actor_update(cols)
-                self.dist.mean_([fl.gradient(fl.policy_bucket)])
-                self._actor_step(self._last_actor_out)
+                self._policy_half(cols)
             if more and not ride:
                 self._rollout(False, defer_clock=True)
 
@@ -1294,7 +1381,7 @@ class RPOTrainerBase(object):
         on a trainer keeps the serial order: the A/B test.)"""
         if not (do_train and self._uctrl is not self.vec.ctrl and self.agent.flat.sizes[1] == 0 and self._bump):
             return False
-        if getattr(self, "_pipelines", False):                            # short launches: the branch costs more than it hides
+        if self._pipelines:                                               # short launches: the branch costs more than it hides
             return False
         return bool(self.schedule["branch"] and getattr(self, "_overlap_enabled", True))
 
@@ -1303,7 +1390,7 @@ class RPOTrainerBase(object):
         pipelines, whose front is one launch), multipliers stepped (`fixed` runs would zero nu's gradient inside the prefix,
         concurrently with the critic update, for nothing: serial there).  `_policy_prefix_enabled = False` on a
         trainer keeps the serial order (A/B: tests/test_evopf_gpu.py)."""
-        return bool(self.fused is not None and hasattr(self, "_actor_prefix") and not getattr(self, "_actor_pipeline", False)
+        return bool(self.fused is not None and hasattr(self, "_actor_prefix") and not self._actor_pipeline
                     and self.agent.flat.sizes[1] == 0 and not self.fixed and getattr(self, "_policy_prefix_enabled", True))
 
     def _overlapped_window(self, t, L):
@@ -1316,7 +1403,7 @@ class RPOTrainerBase(object):
         second queue (9.5 us).  So the fork is an EVENT recorded behind the sampling launch, the update's launches -- the
         critical chain -- are captured first, and the second branch is captured behind them waiting for that event (it has the
         slack); the join then costs 5 us instead of 8.5.  Same dependencies, same bits."""
-        F, fl = self.policy_fre, self.agent.flat
+        F = self.policy_fre
         main = torch.cuda.current_stream()
         if self._ovl_stream is None:
             self._ovl_stream = torch.cuda.Stream()
@@ -1326,8 +1413,6 @@ class RPOTrainerBase(object):
             actor_step = (t + i + 1) % F == 0
             more = i + 1 < L
             overlap = more and not actor_step
-
-            self._iter_actor_step = actor_step
             cols = self._last_cols = self._sample()
             # policy iteration: what the policy step computes from the actor alone (pi(s), noise, Complete, Lagrangian) runs on
             # the second branch beside the critic update (`_actor_prefix`; no shared embedding here: `_overlap_ok`)
@@ -1335,9 +1420,7 @@ class RPOTrainerBase(object):
             if overlap or prefix:
                 forked = torch.cuda.Event()
                 forked.record(main)                                         # (_sample() launched the gather)
-            self._critic_update(cols)
-            self.dist.mean_([fl.gradient(fl.critic_range)])
-            self._critic_step(actor_step)
+            self._critic_half(cols, actor_step)
             if overlap or prefix:                                           # the second branch, captured behind the critical chain
                 side.wait_event(forked)
                 with torch.cuda.stream(side):
@@ -1348,9 +1431,7 @@ class RPOTrainerBase(object):
             if actor_step:
                 if prefix:
                     main.wait_stream(side)
-                self._last_actor_out = self._actor_update(cols)
-                self.dist.mean_([fl.gradient(fl.policy_bucket)])
-                self._actor_step(self._last_actor_out)
+                self._policy_half(cols)
             if overlap:
                 main.wait_stream(side)
             elif more:
