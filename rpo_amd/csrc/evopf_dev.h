@@ -692,7 +692,18 @@ __device__ __forceinline__ bool grg_iteration_v2(Ws& w, const RowLane& L, bool f
     if (!first) {
         float m = fabsf(resid);                                // (0 outside the row lanes)
         if (tid < NY) m = fmaxf(m, fmaxf(up, dn));
-        if (!(rpo_wave_max_nonneg(fmaxf(m, 0.0f)) > corr_eps)) return false;
+        // torch.max propagates a NaN and NaN > corr_eps is false (rpo_ddpg.py:271-272), fmaxf drops it: a residual with a NaN
+        // takes its whole term out of the test (wave-uniform, rare; the angles carry no bound, so a NaN there is not one of ineq_dist)
+        const bool bounded = tid < VA0 || (tid >= PE0 && tid < NY);
+        const bool my_eq = resid != resid, my_ineq = bounded && (up != up || dn != dn);
+        m = fmaxf(m, 0.0f);
+        if (__builtin_amdgcn_ballot_w64(my_eq || my_ineq) != 0ull) {   // the term that holds a NaN counts as 0 (corr_eps >= 0)
+            const bool nan_eq = __builtin_amdgcn_ballot_w64(my_eq) != 0ull, nan_ineq = __builtin_amdgcn_ballot_w64(my_ineq) != 0ull;
+            const float e = nan_eq ? 0.0f : fmaxf(fabsf(resid), 0.0f);
+            const float i = (nan_ineq || !bounded) ? 0.0f : fmaxf(fmaxf(up, dn), 0.0f);
+            m = fmaxf(e, i);
+        }
+        if (!(rpo_wave_max_nonneg(m) > corr_eps)) return false;
     }
     const float g = tid < NY ? ((up > 0.0f ? 1.0f : 0.0f) - (dn > 0.0f ? 1.0f : 0.0f)) : 0.0f;
     w.vec[L.colpos] = g;                                       // (lanes >= NY park a zero in slot NY: never read)

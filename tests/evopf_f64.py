@@ -1,0 +1,1542 @@
+"""Float64 restatement of the EVOPF-v0 kernels (csrc/evopf_dev.h, the non-head kernels of csrc/evopf.hip), the float32 emulation of
+them, and the checkers that turn "close to float64" into a number.  Not collected; used by test_evopf_f64.py (CPU) and
+test_evopf_f64_gpu.py.  Same construction as envs_f64.py, whose tracked-value classes (V / B64 / F32) are reused.
+
+Every formula is written ONCE against an arithmetic ``A`` (evopf.py:520-546 eq_resid, :548-563 ineq_resid, :614-661 eq_jac with
+the -I battery columns of hazard E1, :663-707 ineq_jac, :110-116 battery bounds, :74-102,145-149 Battery.step, :350-353,509-518
+reward, demand.py:35-65 / price.py:29-55 on Philox words) and runs as
+
+    B64E  float64 with the running error bound m of envs_f64.py (units of eps32): the yardstick;
+    B64I  the same plus the device intrinsics' extra ulps (below): m(B64I) - m(B64E) is the explicit intrinsic term;
+    F32E  numpy float32, one rounding per operation, in the kernels' order: the emulation, from which C_REF is measured and on
+          which the mutations of test_evopf_f64.py are shown to fail.
+
+Only the kernels' float32 inputs enter: the RPO_EVOPF_C_* constants table (rpo_amd/env/electrical_grid/case14.py) is one of them;
+the compiled-in constants (0.1, 0.8, 0.9, 0.2, 0.5, 5, 2 pi, 1 - 0.9) are the reference's float64 values in B64 and their float32
+roundings in F32.  oracle/evopf.py is the source of the case tables, index sets and Philox keys, and is called for nothing else.
+
+Tolerance of an element = MARGIN (4) * C_REF[group] * eps32 * m  +  eps32 * (intrinsic term).  The intrinsic term counts, per
+logf / acosf / tanf that enters an output, ULP_* ulps of its result, propagated like any other error (so tan(acos(pf)) near pf -> 1
+carries 4 ulps of acos(pf) times sec^2): the bounds OpenCL's full profile sets for single precision, which the ROCm device library
+is built to meet (log 3, acos 4, tan 5); sinf / cosf keep the two roundings of envs_f64.py; sqrtf and the divisions are correctly
+rounded.  Quantities that pass through a linear solve get the componentwise bound |inv J| ((|J| + m_J) |x| + |b| + m_b) evaluated in
+float64 at the kernel's own input (Oettli-Prager / Skeel: the first-order error of ANY backward-stable elimination in ANY order,
+with m_J / m_b the running bounds of the float32 Jacobian entries and right-hand side), never a norm of the tensor.
+
+Discontinuities: a bound mask a - hi > 0 whose float64 margin lies within its own tolerance of 0 is AMBIGUOUS: the row is judged
+under both outcomes (up to MAX_ENUM per row, a row with more is left out and counted); at most AMBIG_CAP (2 %) of the rows of one
+comparison may be ambiguous or left out.
+
+Iterative paths are held ONE iteration at a time from the kernel's own previous iterate: ``check_newton`` (newton_max_iters = 1 .. M),
+``check_grg`` (max_steps = 0 .. K, momentum 0), ``check_momentum`` (whole trajectories within the sum of the K single-step tolerances).
+Stop decisions are exact, except a lane whose float64 stop quantity lies within its own bound of the threshold (both accepted, under the
+same cap).  Two thresholds of the scripts lie INSIDE those bounds and so cannot be pinned at their shipped values: the running bound of
+a power balance is ~470 eps32 = 4e-5 > corr_eps = 1e-5 (every feasible lane would be ambiguous), and ||delta|| at a converged Newton
+point is bounded by ~1e-4 > newton_tol = 1e-5; the tests use corr_eps = 1e-4 and newton_tol = 1e-3, where the decisions are decidable.
+
+C_REF below is measured by test_evopf_f64.py::test_yardstick on the inputs of the GPU file (same generators, same seeds), never
+from a device; the emulation's share of ambiguous rows on them is asserted there too (largest: 1.6 %, the rows built to be ambiguous).
+"""
+import os
+import re
+
+import numpy as np
+
+import envs_f64 as ef
+from envs_f64 import AMBIG_CAP, EPS32, MARGIN, V  # noqa: F401  (AMBIG_CAP: used by the test files)
+from oracle import evopf as oe
+from oracle import philox
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+G = oe.GRID
+NB, NG, NE, NY, NS, NEQ, NINEQ, NP = 14, 5, 5, 43, 57, 28, 58, 14
+PG0, QG0, VM0, VA0, PE0 = 0, 5, 10, 24, 38
+T = oe.T
+SPV = [int(b) for b in G.spv]
+GEN_OF_BUS = {b: g for g, b in enumerate(SPV)}
+LOAD_SLOT = {int(b): j for j, b in enumerate(G.load_idx)}
+MAX_ENUM = 3
+ULP_LOG, ULP_ACOS, ULP_TAN = 3.0, 4.0, 5.0
+
+C_REF = {
+    "resid_eq": 0.18,      # measured 0.178: eq_resid (28 balances)
+    "resid_ineq": 0.50,    # measured 0.500: the signed ineq_resid (58 bounds); also the band of an ambiguous mask
+    "eq_vjp": 0.11,        # measured 0.100: grad_eq^T eq_jac, both battery signs
+    "lag_grad": 0.44,      # measured 0.432: scale * (nu_up 1[up] - nu_lo 1[lo]) per row and component
+    "lag_sum": 0.45,       # measured 0.446: grad_nu (58 sums over the rows in the four waves' order) and the loss
+    "step_viol": 0.50,     # measured 0.498: eq_viol and relu(ineq) of the transition row
+    "step_reward": 0.15,   # measured 0.144
+    "step_soc": 0.47,      # measured 0.464: soc + eta(clip(pe))
+    "episode": 0.36,       # measured 0.353: pd, qd and the price window from Philox words (plus the explicit intrinsic ulps)
+    "act": 0.48,           # measured 0.478: the proposal z of every noise mode, raw and boxed
+    "ipg": 0.05,           # measured 0.048: the reduced gradient, static order and partial pivoting, hand-over rows included
+    "cbwd": 0.50,          # measured 0.493: complete_bwd, one to three gradient terms
+    "newton": 0.065,       # measured 0.064: one Newton update of the 22 unknowns, both elimination orders
+    "grg": 0.48,           # measured 0.478: one GRG step a - lr * grad
+}
+
+
+def tol_c(group):
+    return MARGIN * C_REF[group]
+
+
+# ===================================================================================================== tables from the sources
+def _defines():
+    text = open(os.path.join(ROOT, "include", "rpo_hip.h")).read()
+    return {k: int(v) for k, v in re.findall(r"#define (RPO_EVOPF_\w+) (\d+)\b", text)}
+
+
+DEF = _defines()
+OFF = {k[len("RPO_EVOPF_C_"):]: v for k, v in DEF.items() if k.startswith("RPO_EVOPF_C_")}
+
+
+def consts_table(static=True):
+    """The float32[RPO_EVOPF_CONSTS_LEN] table the host uploads (EvopfKernels.__init__ sets the flag word)."""
+    from rpo_amd.env.electrical_grid import case14
+    t = case14.kernel_constants(DEF, DEF["RPO_EVOPF_CONSTS_LEN"])
+    t[OFF["FLAGS"]] = 1.0 if static else 0.0
+    return t
+
+
+def header_table(name):
+    """A compiled-in index table of csrc/evopf_dev.h, read from its text (kRowOrder, kOtherVars, kPartialVars, kKeep, ...)."""
+    text = open(os.path.join(ROOT, "rpo_amd", "csrc", "evopf_dev.h")).read()
+    m = re.search(r"constexpr (?:int|unsigned) %s\[[^\]]*\] = \{([^}]*)\}" % name, text)
+    return [int(v) for v in m.group(1).replace("\n", " ").split(",")]
+
+
+# ===================================================================================================== arithmetics
+class B64E(ef.B64):
+    """B64 with the functions of the episode data; ``ulps`` of the device intrinsics are 0 here (numpy's two roundings only)."""
+    ulp_log = ulp_acos = ulp_tan = 0.0
+
+    @classmethod
+    def log(cls, x):
+        with np.errstate(all="ignore"):
+            r = np.log(x.v)
+            return V(r, x.m / np.abs(x.v) + (2.0 + cls.ulp_log) * np.abs(r))
+
+    @classmethod
+    def acos(cls, x):
+        with np.errstate(all="ignore"):
+            r = np.arccos(x.v)
+            d = 1.0 / np.sqrt(np.maximum(1.0 - x.v * x.v, 0.0))
+            return V(r, np.where(x.m > 0, d * x.m, 0.0) + (2.0 + cls.ulp_acos) * np.abs(r))
+
+    @classmethod
+    def tan(cls, x):
+        with np.errstate(all="ignore"):
+            r = np.tan(x.v)
+            return V(r, (1.0 + r * r) * x.m + (2.0 + cls.ulp_tan) * np.abs(r))
+
+    @staticmethod
+    def sqrt(x):
+        with np.errstate(all="ignore"):
+            r = np.sqrt(x.v)
+            return V(r, np.where(x.m > 0, x.m / (2.0 * r), 0.0) + np.abs(r))
+
+
+class B64I(B64E):
+    ulp_log, ulp_acos, ulp_tan = ULP_LOG, ULP_ACOS, ULP_TAN
+
+
+class F32E(ef.F32):
+    log = staticmethod(np.log)
+    acos = staticmethod(np.arccos)
+    tan = staticmethod(np.tan)
+    sqrt = staticmethod(np.sqrt)
+
+
+def cols(A, x):
+    """[n, d] float32 input -> list of d columns of ``A``."""
+    x = np.asarray(x, np.float32)
+    return [A.inp(x[:, j]) for j in range(x.shape[1])]
+
+
+def val(A, xs):
+    """list of d values [n] -> float64 / float32 [n, d]."""
+    n = max(np.size(A.val(x)) for x in xs)
+    return np.stack([np.broadcast_to(A.val(x), (n,)) for x in xs], axis=1)
+
+
+def mag(A, xs):
+    n = max(np.size(A.val(x)) for x in xs)
+    return np.stack([np.broadcast_to(A.mag(x), (n,)) for x in xs], axis=1)
+
+
+class Tab(object):
+    """The constants table as inputs of ``A`` (exact float32 values, m = 0)."""
+
+    def __init__(self, A, consts):
+        t = np.asarray(consts, np.float32)
+        assert t.shape == (DEF["RPO_EVOPF_CONSTS_LEN"],)
+        seg = lambda name, n: [A.inp(np.float32(v)) for v in t[OFF[name]:OFF[name] + n]]          # noqa: E731
+        yr, yi = (t[OFF[k]:OFF[k] + NB * NB].reshape(NB, NB) for k in ("YR", "YI"))
+        self.adj = (yr != 0) | (yi != 0)
+        self.yr = [[A.inp(np.float32(yr[i, k])) for k in range(NB)] for i in range(NB)]
+        self.yi = [[A.inp(np.float32(yi[i, k])) for k in range(NB)] for i in range(NB)]
+        self.pmax, self.pmin, self.qmax, self.qmin = (seg(k, NG) for k in ("PMAX", "PMIN", "QMAX", "QMIN"))
+        self.vmax, self.vmin = seg("VMAX", NB), seg("VMIN", NB)
+        self.quad, self.lin, self.const = seg("QUAD", NG), seg("LIN", NG), seg("CONST", 1)[0]
+        self.ps, self.share, self.qsign, self.price = seg("PS", T), seg("SHARE", NB), seg("QSIGN", NB), seg("PRICE", T)
+        self.raw = t
+
+
+# ===================================================================================================== constraints
+def flows(A, c, a):
+    """cos / sin / rectangular voltages and the admittance products (evopf.py:523-528,623-630), sums in bus order."""
+    cs = [A.cos(a[VA0 + i]) for i in range(NB)]
+    sn = [A.sin(a[VA0 + i]) for i in range(NB)]
+    vr = [a[VM0 + i] * cs[i] for i in range(NB)]
+    vi = [a[VM0 + i] * sn[i] for i in range(NB)]
+    t1, t2 = [], []
+    for k in range(NB):
+        s1 = s2 = None
+        for i in range(NB):
+            if not c.adj[i][k]:
+                continue                                             # (an exact zero term)
+            x1 = vr[i] * c.yr[i][k] - vi[i] * c.yi[i][k]
+            x2 = vr[i] * c.yi[i][k] + vi[i] * c.yr[i][k]
+            s1, s2 = (x1, x2) if s1 is None else (s1 + x1, s2 + x2)
+        t1.append(s1)
+        t2.append(s2)
+    return dict(cs=cs, sn=sn, vr=vr, vi=vi, t1=t1, t2=t2)
+
+
+def eq_resid(A, c, s, a, f, mut=()):
+    """evopf.py:520-546 -> 28 values (real then reactive power balance)."""
+    out = []
+    for i in range(NB):
+        g = GEN_OF_BUS.get(i)
+        flow = f["vr"][i] * f["t1"][i] + f["vi"][i] * f["t2"][i]
+        if g is None:
+            out.append(-s[i] - flow)
+        else:
+            inj = a[PG0 + g] if "no_pe_in_balance" in mut else a[PG0 + g] + a[PE0 + g]
+            out.append((inj - s[i]) - flow)
+    for i in range(NB):
+        g = GEN_OF_BUS.get(i)
+        flow = -f["vr"][i] * f["t2"][i] + f["vi"][i] * f["t1"][i]
+        out.append((-s[NB + i] - flow) if g is None else ((a[QG0 + g] - s[NB + i]) - flow))
+    return out
+
+
+def battery_bounds(A, soc, mut=()):
+    """Battery.update_bound / ineq_resid (evopf.py:110-116,135-141)."""
+    if "bounds_no_eta" in mut:
+        return A.minimum(A.k(oe.B_PMAX), A.k(oe.B_HIGH) - soc), A.maximum(A.k(oe.B_PMIN), A.k(oe.B_LOW) - soc)
+    p_max = A.minimum(A.k(oe.B_PMAX), A.k(oe.B_HIGH) - soc) / A.k(oe.ETA_IN)
+    p_min = A.k(oe.ETA_OUT) * A.maximum(A.k(oe.B_PMIN), A.k(oe.B_LOW) - soc)
+    return p_max, p_min
+
+
+def bounds(A, c, s, mut=()):
+    """(hi, lo) of the 43 action components (None: the angles are free): ineq_resid (evopf.py:548-563) per component."""
+    hi, lo = [None] * NY, [None] * NY
+    for g in range(NG):
+        hi[PG0 + g], lo[PG0 + g] = c.pmax[g], c.pmin[g]
+        hi[QG0 + g], lo[QG0 + g] = c.qmax[g], c.qmin[g]
+        hi[PE0 + g], lo[PE0 + g] = battery_bounds(A, s[2 * NB + g], mut)
+    for i in range(NB):
+        hi[VM0 + i], lo[VM0 + i] = c.vmax[i], c.vmin[i]
+    return hi, lo
+
+
+def ineq_rows():
+    """(component, is_upper) of the 58 rows of ineq_resid."""
+    out = []
+    for start, size in ((PG0, NG), (QG0, NG), (VM0, NB), (PE0, NE)):
+        out += [(start + j, True) for j in range(size)] + [(start + j, False) for j in range(size)]
+    return out
+
+
+INEQ_ROWS = ineq_rows()
+
+
+def ineq_resid(A, c, s, a, mut=()):
+    hi, lo = bounds(A, c, s, mut)
+    return [(a[v] - hi[v]) if up else (lo[v] - a[v]) for v, up in INEQ_ROWS]
+
+
+def jac_entry(A, c, f, row, var, mut=()):
+    """One entry of eq_jac (evopf.py:614-661) in the reference's orientation; None where it is structurally zero."""
+    real = row < NB
+    i = row if real else row - NB
+    if var < VM0:
+        g = var if var < QG0 else var - QG0
+        return A.k(1.0) if (real == (var < QG0) and SPV[g] == i) else None
+    if var >= PE0:
+        return A.k(-1.0) if (real and SPV[var - PE0] == i) else None
+    dvm = var < VA0
+    k = var - VM0 if dvm else var - VA0
+    if not c.adj[i][k]:
+        return None
+    yr, yi = c.yr[i][k], c.yi[i][k]
+    p, q = (f["cs"][k], f["sn"][k]) if dvm else (-f["vi"][k], f["vr"][k])
+    pi_, qi_ = (f["cs"][i], f["sn"][i]) if dvm else (-f["vi"][i], f["vr"][i])
+    vr, vi, t1, t2 = f["vr"][i], f["vi"][i], f["t1"][i], f["t2"][i]
+    A_, B_ = yr * p - yi * q, yi * p + yr * q
+    if real:
+        e = -(vr * A_) - vi * B_ if i != k else -(pi_ * t1) - vr * A_ - (qi_ * t2) - vi * B_
+        if "jac_sign_block" in mut and not dvm:
+            e = -e
+    else:
+        e = vr * B_ - vi * A_ if i != k else (pi_ * t2) + vr * B_ - (qi_ * t1) - vi * A_
+    return e
+
+
+def eq_jac(A, c, a, mut=()):
+    """[28][43] entries (None: structural zero) and the flows they came from."""
+    f = flows(A, c, a)
+    return [[jac_entry(A, c, f, r, v, mut) for v in range(NY)] for r in range(NEQ)], f
+
+
+def eq_vjp(A, c, a, ge, autograd_sign, mut=()):
+    """out[v] = sum_r grad_eq[r] d eq[r] / d a[v] (rpo_evopf_eq_vjp); the battery columns flip under ``autograd_sign``."""
+    jac, _ = eq_jac(A, c, a, mut)
+    out = []
+    flip = bool(autograd_sign) != ("vjp_sign_swapped" in mut)
+    for v in range(NY):
+        acc = None
+        for r in range(NEQ):
+            if jac[r][v] is None:
+                continue
+            term = ge[r] * jac[r][v]
+            acc = term if acc is None else acc + term
+        out.append(-acc if (flip and v >= PE0) else acc)
+    return out
+
+
+# ===================================================================================================== Lagrangian
+def seq_sum(A, terms):
+    """Sum of a list of values in order, from the first."""
+    acc = None
+    for t in terms:
+        acc = t if acc is None else acc + t
+    return acc
+
+
+def wave_sum(A, lanes):
+    """rpo_wave_sum: the xor butterfly 32, 16, 8, 4, 2, 1 over 64 lanes (list of 64 values, None = 0); lane 0's result."""
+    v = list(lanes) + [None] * (64 - len(lanes))
+    off = 32
+    while off:
+        v = [(v[l] if v[l ^ off] is None else v[l ^ off] if v[l] is None else v[l] + v[l ^ off]) for l in range(64)]
+        off >>= 1
+    return v[0]
+
+
+def lagrangian(A, c, s, a, nu, scale, loss_in, gnu_in, overwrite, mask=None, mut=()):
+    """mean_b sum_j nu_j relu(g_j) with its gradients (rpo_evopf_lagrangian; dual.py:63-65, rpo_ddpg.py:312-319).  s, a: column
+    lists over ALL rows.  Returns dict(grad [n,43] values, dist (58 per-row relu'd), loss, grad_nu[58], margins)."""
+    n = np.size(A.val(a[0]))
+    resid = ineq_resid(A, c, s, a)
+    zero = A.k(0.0)
+    dist = [A.maximum(r, zero) for r in resid]
+    nu_c = [A.inp(np.float32(v)) for v in np.asarray(nu, np.float32)]
+    sc = A.inp(np.float32(scale))
+    on = [((A.val(r) >= 0) if "ge_mask" in mut else (A.val(r) > 0)) if mask is None else mask[:, j] for j, r in enumerate(resid)]
+    row_of = {vu: j for j, vu in enumerate(INEQ_ROWS)}
+    grad = []
+    for v in range(NY):
+        if (v, True) not in row_of:
+            grad.append(A.inp(np.zeros(n, np.float32)))
+            continue
+        ju, jl = row_of[(v, True)], row_of[(v, False)]
+        g = A.where(on[ju], nu_c[ju], zero) - A.where(on[jl], nu_c[jl], zero)
+        grad.append(sc * g)
+    # sums: wave q takes rows q, q + 4, ... in order; the four partial sums are added in wave order, from 0
+    sums = []
+    for j in range(NINEQ):
+        parts = []
+        for q in range(4):
+            d = dist[j]
+            dq = V(np.broadcast_to(d.v, (n,))[q::4], np.broadcast_to(d.m, (n,))[q::4]) if isinstance(d, V) else np.broadcast_to(d, (n,))[q::4]
+            parts.append(_cumsum_last(A, dq))
+        sums.append(seq_sum(A, [p for p in parts if p is not None]))
+    gnu = [A.inp(np.float32(gnu_in[j])) + sc * sums[j] for j in range(NINEQ)]
+    lanes = []
+    for v in range(NY):
+        if (v, True) not in row_of:
+            lanes.append(None)
+        else:
+            ju, jl = row_of[(v, True)], row_of[(v, False)]
+            lanes.append(nu_c[ju] * sums[ju] + nu_c[jl] * sums[jl])
+    total = wave_sum(A, lanes)
+    base = zero if (overwrite and "never_overwrite" not in mut) else A.inp(np.float32(loss_in))
+    loss = base + sc * total
+    return dict(grad=grad, dist=dist, loss=loss, grad_nu=gnu, margins=resid)
+
+
+def _cumsum_last(A, x):
+    """Sequential sum over a 1-d run of values (None for an empty run)."""
+    if isinstance(x, V):
+        if x.v.size == 0:
+            return None
+        cs = np.cumsum(x.v)
+        return V(cs[-1], x.m.sum() + np.abs(cs[1:]).sum())
+    x = np.asarray(x, np.float32)
+    if x.size == 0:
+        return None
+    return np.cumsum(x, dtype=np.float32)[-1]
+
+
+# ===================================================================================================== episode data and the step
+def normal(A, wa, wb):
+    """rpo_normal: Box-Muller from two words, u1 in (0, 1]."""
+    u1 = A.inp((((np.asarray(wa, np.uint32) >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24).astype(np.float32))
+    u2 = A.inp(philox.u01(wb))
+    return A.sqrt(A.k(-2.0) * A.log(u1)) * A.cos(A.k(6.283185307179586) * u2)
+
+
+def episode_obs(A, c, seed, env_ids, episode, t, mut=()):
+    """The loaders' hour-t data (demand.py:35-65, price.py:29-55) re-keyed on Philox(seed; env, episode): 57 columns, the battery
+    slots None.  ``t`` [n] int; all zero when t >= 24."""
+    env_ids, episode, t = (np.asarray(x) for x in (env_ids, episode, t))
+    n = env_ids.shape[0]
+    t = np.broadcast_to(t, (n,)).astype(np.int64)
+    over = t >= T
+    tt = np.minimum(t, T - 1)
+    if "t24_not_zeroed" in mut:
+        over = np.zeros(n, bool)
+    words = np.concatenate([philox.draw(seed, env_ids, episode, oe.STREAM_DEMAND, t * 8 + cc) for cc in range(7)], axis=1)
+    zero = A.inp(np.zeros(n, np.float32))
+    u1 = (((words[:, :11] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24).astype(np.float32)
+    e = [-A.log(A.inp(u1[:, j])) for j in range(11)]
+    esum = seq_sum(A, e)
+    pf_w = A.k(oe.MAX_PF) - A.k(oe.MIN_PF)
+    out = [None] * NS
+    ps = _pick(A, c.ps, tt)
+    for i in range(NB):
+        ratio = c.share[i]
+        if i in LOAD_SLOT:
+            ratio = ratio + A.k(oe.RHO) * (e[LOAD_SLOT[i]] / esum)
+        pd = ratio * ps
+        pf = A.inp(philox.u01(words[:, 11 + i])) * pf_w + A.k(oe.MIN_PF)
+        qd = pd * A.tan(A.acos(pf)) * c.qsign[i]
+        out[i] = A.where(over, zero, pd)
+        out[NB + i] = A.where(over, zero, qd)
+    mw = philox.draw(seed, env_ids, episode, oe.STREAM_PRICE, T // 2)
+    magn = A.k(oe.REG_BIAS) * normal(A, mw[:, 0], mw[:, 1]) + A.k(1.0)
+    for j in range(oe.NAHEAD):
+        h = t + j + (1 if "price_shift" in mut else 0)
+        live = ~over & (h < T) if "price_past_midnight" not in mut else ~over
+        hh = np.minimum(h, T - 1)
+        w = philox.draw(seed, env_ids, episode, oe.STREAM_PRICE, hh >> 1)
+        odd = (hh & 1) == 1
+        z = normal(A, np.where(odd, w[:, 2], w[:, 0]), np.where(odd, w[:, 3], w[:, 1]))
+        v = magn * _pick(A, c.price, hh) * (A.k(1.0) + z)
+        out[2 * NB + NE + j] = A.where(live, v, zero)
+    return out
+
+
+def _pick(A, table, idx):
+    """table[idx[row]] per row for a list of scalar table entries."""
+    vals = np.array([float(A.val(x)) for x in table])
+    return A.inp(vals[idx].astype(np.float32))
+
+
+def step(A, c, s, a, mut=()):
+    """EVOPFEnv.step (evopf.py:348-366) + Battery.step (:74-102) on column lists: dict(eq, ineq (relu'd), reward, soc)."""
+    f = flows(A, c, a)
+    eq = eq_resid(A, c, s, a, f, mut)
+    zero = A.k(0.0)
+    ineq = ineq_resid(A, c, s, a, mut)
+    if "no_relu_viol" not in mut:
+        ineq = [A.maximum(r, zero) for r in ineq]
+    price = s[2 * NB + NE]
+    parts = []
+    for g in range(NG):
+        pg = a[PG0 + g]
+        parts.append(-(c.quad[g] * pg * pg + c.lin[g] * pg) - A.k(oe.WE) * (a[PE0 + g] * price))
+    reward = wave_sum(A, parts)
+    if "reward_no_const" not in mut:
+        reward = reward - c.const
+    soc = []
+    for g in range(NE):
+        p_max, p_min = battery_bounds(A, s[2 * NB + g])
+        pe = a[PE0 + g]
+        if "clip_after_eff" in mut:
+            x = A.where(A.val(pe) >= 0, pe * A.k(oe.ETA_IN), pe / A.k(oe.ETA_OUT))
+            x = A.minimum(A.maximum(x, p_min), p_max)
+        else:
+            x = A.minimum(A.maximum(pe, p_min), p_max)
+            pos = A.val(x) >= 0
+            if "eff_swapped" in mut:
+                pos = ~pos
+            x = A.where(pos, x * A.k(oe.ETA_IN), x / A.k(oe.ETA_OUT))
+        soc.append(s[2 * NB + g] + x)
+    return dict(eq=eq, ineq=ineq, reward=reward, soc=soc)
+
+
+# ===================================================================================================== judging
+def judge(group, got, ref_vals, ref_mag, intr=None, what=""):
+    """max over elements of |got - ref| / tolerance; asserts nothing.  Elements whose tolerance is not finite are counted in the
+    second return value (share of the elements that could not be judged)."""
+    got = np.asarray(got, np.float64)
+    ref_vals, ref_mag = np.asarray(ref_vals, np.float64), np.asarray(ref_mag, np.float64)
+    tol = tol_c(group) * EPS32 * ref_mag + (0.0 if intr is None else EPS32 * np.asarray(intr, np.float64))
+    with np.errstate(all="ignore"):
+        err = np.abs(got - ref_vals)
+        unj = ~np.isfinite(tol) | ~np.isfinite(ref_vals)
+        r = np.where(err == 0, 0.0, err / np.maximum(tol, ef.TINY))
+        r = np.where(unj, 0.0, r)
+        r = np.where(np.isnan(r), np.inf, r)                           # a NaN from the kernel where float64 is finite
+    return (float(r.max()) if r.size else 0.0), (float(unj.mean()) if unj.size else 0.0)
+
+
+def ratios(group, got, ref_vals, ref_mag, intr=None):
+    """|got - ref| / tolerance per element (inf where the tolerance is not finite or the kernel's value is a NaN)."""
+    got = np.asarray(got, np.float64)
+    ref_vals, ref_mag = np.asarray(ref_vals, np.float64), np.asarray(ref_mag, np.float64)
+    tol = tol_c(group) * EPS32 * ref_mag + (0.0 if intr is None else EPS32 * np.asarray(intr, np.float64))
+    with np.errstate(all="ignore"):
+        err = np.abs(got - ref_vals)
+        r = np.where(err == 0, 0.0, err / np.maximum(tol, ef.TINY))
+        return np.where(np.isfinite(r), r, np.inf)
+
+
+def ratios(group, got, ref_vals, ref_mag, intr=None):
+    """|got - ref| / tolerance per element (inf where the tolerance is not finite or the kernel's value is a NaN)."""
+    got = np.asarray(got, np.float64)
+    ref_vals, ref_mag = np.asarray(ref_vals, np.float64), np.asarray(ref_mag, np.float64)
+    tol = tol_c(group) * EPS32 * ref_mag + (0.0 if intr is None else EPS32 * np.asarray(intr, np.float64))
+    with np.errstate(all="ignore"):
+        err = np.abs(got - ref_vals)
+        r = np.where(err == 0, 0.0, err / np.maximum(tol, ef.TINY))
+        return np.where(np.isfinite(r), r, np.inf)
+
+
+def both(fn, *args, **kw):
+    """(values, magnitude, intrinsic term) of a formula: B64E for the value and the arithmetic bound, B64I - B64E for the ulps."""
+    a, b = fn(B64E, *args, **kw), fn(B64I, *args, **kw)
+    return a, b
+
+
+# ===================================================================================================== linear solves: float64 side
+ROW_ORDER, OTHER, PARTV = header_table("kRowOrder"), header_table("kOtherVars"), header_table("kPartialVars")
+KEEP, NEWTV, PVPOS, PARTA = header_table("kKeep"), header_table("kNewtonVars"), header_table("kPvPos"), header_table("kPartialActions")
+COLS = OTHER + PARTV
+NO, NPV, NN = 28, 15, 22
+assert sorted(OTHER) == sorted(int(v) for v in G.other_vars) and sorted(PARTV) == sorted(int(v) for v in G.partial_vars)
+assert sorted(KEEP) == sorted(int(v) for v in G.keep_constr) and sorted(NEWTV) == sorted(int(v) for v in G.newton_vars)
+assert KEEP == ROW_ORDER[6:] and NEWTV == OTHER[6:] and PARTA == [int(v) for v in G.partial_actions]
+
+
+def dense_jac(consts, a, mut=()):
+    """float64 eq_jac [n, 28, 43] at the float32 action and the running bound of its float32 entries (units of eps32)."""
+    c = Tab(B64E, consts)
+    jac, f = eq_jac(B64E, c, cols(B64E, a), mut)
+    n = np.asarray(a).shape[0]
+    jv, jm = np.zeros((n, NEQ, NY)), np.zeros((n, NEQ, NY))
+    for r in range(NEQ):
+        for v in range(NY):
+            if jac[r][v] is not None:
+                jv[:, r, v], jm[:, r, v] = jac[r][v].v, jac[r][v].m
+    return jv, jm
+
+
+def mask_margins(consts, s, a):
+    """Per component: (a - hi, lo - a) as B64E values -> up [n,43], dn [n,43] (values, tolerances); free components -1."""
+    c = Tab(B64E, consts)
+    S, Ac = cols(B64E, s), cols(B64E, a)
+    hi, lo = bounds(B64E, c, S)
+    n = np.asarray(a).shape[0]
+    up, dn, tu, td = -np.ones((n, NY)), -np.ones((n, NY)), np.zeros((n, NY)), np.zeros((n, NY))
+    for v in range(NY):
+        if hi[v] is None:
+            continue
+        u, d = Ac[v] - hi[v], lo[v] - Ac[v]
+        up[:, v], dn[:, v] = u.v, d.v
+        tu[:, v], td[:, v] = MARGIN * 0.5 * EPS32 * u.m, MARGIN * 0.5 * EPS32 * d.m
+    return up, dn, tu, td
+
+
+def mask_choices(up, dn, tu, td):
+    """Per row the list of direct gradients g [43] (+1 per violated upper, -1 per violated lower bound) to accept: one, or every
+    combination of the ambiguous masks (|margin| <= its tolerance; exact margins have tolerance 0 and are never ambiguous); None
+    for a row with more than MAX_ENUM of them."""
+    out = []
+    for r in range(up.shape[0]):
+        base = (up[r] > 0).astype(np.float64) - (dn[r] > 0).astype(np.float64)
+        amb = [(v, 1.0) for v in range(NY) if tu[r, v] > 0 and abs(up[r, v]) <= tu[r, v]] + \
+              [(v, -1.0) for v in range(NY) if td[r, v] > 0 and abs(dn[r, v]) <= td[r, v]]
+        if len(amb) > MAX_ENUM:
+            out.append(None)
+            continue
+        gs = []
+        for bits_ in range(1 << len(amb)):
+            g = base.copy()
+            for k, (v, sgn) in enumerate(amb):
+                on = (up[r, v] > 0) if sgn > 0 else (dn[r, v] > 0)
+                if (bits_ >> k) & 1:
+                    g[v] += -sgn if on else sgn
+            gs.append(g)
+        out.append(gs)
+    return out
+
+
+def reduced_grad_ref(jv, jm, g):
+    """ineq_partial_grad (evopf.py:596-612) of one row in float64 with the componentwise bound: (full [43], bound [43])."""
+    jo, jp, mo, mp = jv[:, OTHER], jv[:, PARTV], jm[:, OTHER], jm[:, PARTV]
+    go, gp = g[OTHER], g[PARTV]
+    inv = np.linalg.inv(jo)
+    ainv = np.abs(inv)
+    y = inv.T @ go
+    fp = gp - jp.T @ y
+    x = -(inv @ (jp @ fp))
+    by = ainv.T @ ((np.abs(jo) + mo).T @ np.abs(y) + np.abs(go))
+    bfp = np.abs(jp).T @ by + (np.abs(jp) + mp).T @ np.abs(y) + np.abs(gp) + np.abs(fp)
+    bx = ainv @ ((np.abs(jo) + mo) @ np.abs(x) + (np.abs(jp) + mp) @ np.abs(fp) + np.abs(jp) @ bfp) + np.abs(x)
+    full, bound = np.zeros(NY), np.zeros(NY)
+    full[PARTV], bound[PARTV] = fp, bfp
+    full[OTHER], bound[OTHER] = x, bx
+    return full, bound
+
+
+def check_ipg(consts, s, a, got, group="ipg", mut=()):
+    """Every element of rpo_evopf_ineq_partial_grad's output against float64; returns (worst ratio, share of ambiguous or
+    left-out rows)."""
+    jv, jm = dense_jac(consts, a, mut)
+    choices = mask_choices(*mask_margins(consts, s, a))
+    worst, odd = 0.0, 0
+    for r in range(got.shape[0]):
+        if choices[r] is None or not np.isfinite(jv[r]).all():
+            odd += 1
+            continue
+        odd += len(choices[r]) > 1
+        best = np.inf
+        for g in choices[r]:
+            with np.errstate(all="ignore"):
+                full, bound = reduced_grad_ref(jv[r], jm[r], g)
+            ratio, _ = judge(group, got[r], full, bound)
+            best = min(best, ratio)
+        worst = max(worst, best)
+    return worst, odd / float(got.shape[0])
+
+
+def complete_bwd_ref(jv, jm, dl, dlm):
+    """PFFunction.backward (evopf.py:857-910) of one row with the Jacobian at the given action: dl [43] float64 (sum of the
+    gradient terms, dlm its running bound) -> (dz [14], bound [14])."""
+    aj, last_eq, last_var = np.abs(jv) + jm, [0] + [NB + b for b in SPV], [PG0] + list(range(QG0, QG0 + NG))
+    vec, vm_ = dl.copy(), dlm.copy()
+    for v in range(VM0, PE0):
+        acc = jv[last_eq, v] @ dl[last_var]
+        am = aj[last_eq, v] @ np.abs(dl[last_var]) + np.abs(jv[last_eq, v]) @ dlm[last_var] + np.abs(jv[last_eq, v] * dl[last_var]).sum()
+        vec[v] = dl[v] - acc
+        vm_[v] = dlm[v] + am + abs(vec[v])
+    jn = jv[KEEP][:, NEWTV]
+    jnm = jm[KEEP][:, NEWTV]
+    inv = np.linalg.inv(jn.T)
+    rhs, rm = vec[NEWTV], vm_[NEWTV]
+    d = inv @ rhs
+    bd = np.abs(inv) @ ((np.abs(jn) + jnm).T @ np.abs(d) + np.abs(rhs) + rm)
+    dz, bz = np.zeros(NP), np.zeros(NP)
+    for j in range(NP):
+        if j < 4:
+            dz[j] = -d[PVPOS[j]] + dl[PG0 + 1 + j]
+            bz[j] = bd[PVPOS[j]] + dlm[PG0 + 1 + j] + abs(dz[j])
+        elif j < 9:
+            var = VM0 + SPV[j - 4]
+            col, colm = jv[KEEP, var], jm[KEEP, var]
+            dz[j] = -(col @ d) + vec[var]
+            bz[j] = np.abs(col) @ bd + (np.abs(col) + colm) @ np.abs(d) + np.abs(col * d).sum() + vm_[var] + abs(dz[j])
+        elif j == 9:
+            dz[j] = dl[PG0] + dl[PE0]
+            bz[j] = dlm[PG0] + dlm[PE0] + abs(dz[j])
+        else:
+            dz[j] = d[PVPOS[j - 10]] + dl[PE0 + j - 9]
+            bz[j] = bd[PVPOS[j - 10]] + dlm[PE0 + j - 9] + abs(dz[j])
+    return dz, bz
+
+
+def check_cbwd(consts, a, g1, gb, g2, got, group="cbwd", mut=()):
+    """rpo_evopf_complete_bwd: dL/dy = (g1 [+ gb]) [+ g2] added in float32 in that order, then the backward; every element."""
+    jv, jm = dense_jac(consts, a, mut)
+    dl = [B64E.inp(np.asarray(g1, np.float32)[:, v]) for v in range(NY)]
+    for extra in (gb, g2):
+        if extra is not None:
+            dl = [dl[v] + B64E.inp(np.asarray(extra, np.float32)[:, v]) for v in range(NY)]
+    dv, dm = val(B64E, dl), mag(B64E, dl)
+    worst = 0.0
+    for r in range(got.shape[0]):
+        with np.errstate(all="ignore"):
+            dz, bz = complete_bwd_ref(jv[r], jm[r], dv[r], dm[r])
+        worst = max(worst, judge(group, got[r], dz, bz)[0])
+    return worst
+
+
+# ===================================================================================================== linear solves: float32 emulation
+F = np.float32
+
+
+def fma(a, b, c):
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def jac_struct(adj, eq, var):
+    real = eq < NB
+    i = eq if real else eq - NB
+    if var < QG0:
+        return real and SPV[var] == i
+    if var < VM0:
+        return (not real) and SPV[var - QG0] == i
+    if var >= PE0:
+        return real and SPV[var - PE0] == i
+    return bool(adj[i][(var - VM0) % NB])
+
+
+def symbolic_gj(pat, k0):
+    """symbolic_gj of evopf_dev.h: live[k][c] = column c (> k) of pivot row k can be non-zero when pivot k is taken."""
+    p = np.array(pat, bool)
+    n, nc = p.shape
+    live = np.zeros((n, nc), bool)
+    for k in range(k0, n):
+        live[k, k + 1:] = p[k, k + 1:]
+        for r in range(n):
+            if r != k and p[r, k]:
+                p[r, k + 1:] |= p[k, k + 1:]
+    return live
+
+
+def live_tables(consts):
+    t = np.asarray(consts, np.float32)
+    adj = (t[OFF["YR"]:OFF["YR"] + 196].reshape(NB, NB) != 0) | (t[OFF["YI"]:OFF["YI"] + 196].reshape(NB, NB) != 0)
+    grg = symbolic_gj([[jac_struct(adj, ROW_ORDER[r], COLS[cc]) for cc in range(NY)] for r in range(NEQ)], 0)
+    newt = symbolic_gj([[cc == NN or jac_struct(adj, KEEP[r], NEWTV[cc]) for cc in range(NN + 1)] for r in range(NN)], 0)
+    newt_t = symbolic_gj([[cc == NN or jac_struct(adj, KEEP[cc], NEWTV[r]) for cc in range(NN + 1)] for r in range(NN)], 0)
+    return dict(grg=grg, newton=newt, newton_t=newt_t)
+
+
+def emu_volt(consts, a):
+    """own_volt + the admittance products of every bus in float32 (sincosf, unfused sums in bus order)."""
+    t = np.asarray(consts, np.float32)
+    yr, yi = (t[OFF[k]:OFF[k] + 196].reshape(NB, NB) for k in ("YR", "YI"))
+    a = np.asarray(a, np.float32)
+    vm, va = a[:, VM0:VA0], a[:, VA0:PE0]
+    cs, sn = np.cos(va), np.sin(va)
+    vr, vi = vm * cs, vm * sn
+    t1, t2 = np.zeros_like(vr), np.zeros_like(vr)
+    for k in range(NB):
+        t1 = t1 + (vr[:, k:k + 1] * yr[k][None] - vi[:, k:k + 1] * yi[k][None])
+        t2 = t2 + (vr[:, k:k + 1] * yi[k][None] + vi[:, k:k + 1] * yr[k][None])
+    return dict(cs=cs, sn=sn, vr=vr, vi=vi, t1=t1, t2=t2, yr=yr, yi=yi)
+
+
+def emu_jac_v2(f, eqs, vars_, mut=()):
+    """jacobian_row of evopf_dev.h: rows ``eqs`` x columns ``vars_`` in float32 with its association (alpha / beta per bus, two
+    fmas per entry) -> [n, len(eqs), len(vars_)]."""
+    n = f["vr"].shape[0]
+    out = np.zeros((n, len(eqs), len(vars_)), np.float32)
+    big = F(3.0e38)
+    for ri, eq in enumerate(eqs):
+        real = eq < NB
+        i = eq if real else eq - NB
+        vr, vi, cs, sn, t1, t2 = (f[k][:, i] for k in ("vr", "vi", "cs", "sn", "t1", "t2"))
+        ca, cb = (-vr, -vi) if real else (-vi, vr)
+        with np.errstate(all="ignore"):
+            dg_vm = -(cs * t1 + sn * t2) if real else (cs * t2 - sn * t1)
+            dg_va = -(-vi * t1 + vr * t2) if real else (-vi * t2 - vr * t1)
+            dg_vm, dg_va = np.fmin(np.fmax(dg_vm, -big), big), np.fmin(np.fmax(dg_va, -big), big)
+            alpha = ca[:, None] * f["yr"][i][None] + cb[:, None] * f["yi"][i][None]
+            beta = cb[:, None] * f["yr"][i][None] - ca[:, None] * f["yi"][i][None]
+            for ci, var in enumerate(vars_):
+                if var < QG0:
+                    e = F(1.0) if (real and SPV[var] == i) else F(0.0)
+                elif var < VM0:
+                    e = F(1.0) if ((not real) and SPV[var - QG0] == i) else F(0.0)
+                elif var >= PE0:
+                    e = F(-1.0) if (real and SPV[var - PE0] == i) else F(0.0)
+                    if "battery_autograd_sign" in mut:
+                        e = -e
+                else:
+                    dvm = var < VA0
+                    k = var - VM0 if dvm else var - VA0
+                    p, q = (f["cs"][:, k], f["sn"][:, k]) if dvm else (-f["vi"][:, k], f["vr"][:, k])
+                    e = fma(p, alpha[:, k], q * beta[:, k])
+                    if i == k:
+                        e = fma(F(1.0), dg_vm if dvm else dg_va, e)
+                    if "jac_sign_block" in mut and real and not dvm:
+                        e = -e
+                out[:, ri, ci] = e
+    return out
+
+
+def emu_gj_static(m, kb, ke, kunit, live, rcp=True):
+    """gj_static / gauss_jordan_static on [n, R, NC] (rows beyond the pivots ride along); returns the pivots [n, R] (1 where none)."""
+    n, rows, nc = m.shape
+    piv = np.ones((n, rows), np.float32)
+    with np.errstate(all="ignore"):
+        for k in range(kb, ke):
+            if k < kunit:
+                fct = -m[:, :, k].copy()
+            else:
+                pk = m[:, k, k].copy()
+                fct = (-m[:, :, k] * (F(1.0) / pk)[:, None]).astype(np.float32)
+                piv[:, k] = pk
+            fct[:, k] = 0
+            cs_ = np.nonzero(live[k])[0]
+            cs_ = cs_[cs_ > k]
+            if cs_.size:
+                m[:, :, cs_] = fma(fct[:, :, None], m[:, k, cs_][:, None, :], m[:, :, cs_])
+    return piv
+
+
+def emu_pivots_ok(piv, k0, ke):
+    a = np.abs(piv[:, k0:ke])
+    with np.errstate(all="ignore"):
+        amax = np.fmax.reduce(a, axis=1)
+        return ((a > (amax * F(0.015625))[:, None]) & (a < F(3.0e38))).all(axis=1)
+
+
+def emu_gj_dynamic(m, kb, ke):
+    """gj_dynamic / gauss_jordan_rows: partial pivoting among rows [kb, ke) by the key (|value| bits & ~31) | row, rows not
+    swapped.  Returns (pivots [n, R], mycol [n, R])."""
+    n, rows, nc = m.shape
+    piv = np.ones((n, rows), np.float32)
+    mycol = np.tile(np.arange(rows), (n, 1))
+    used = np.zeros((n, rows), bool)
+    used[:, :kb] = True
+    used[:, ke:] = True
+    ar = np.arange(n)
+    with np.errstate(all="ignore"):
+        for k in range(kb, ke):
+            key = (np.abs(m[:, :, k]).view(np.uint32) & np.uint32(0xFFFFFFE0)) | np.arange(rows, dtype=np.uint32)[None]
+            key = np.where(used, np.uint32(0), key)
+            p = (key.max(axis=1) & np.uint32(31)).astype(np.int64)
+            pk = m[ar, p, k].copy()
+            fct = (-m[:, :, k] * (F(1.0) / pk)[:, None]).astype(np.float32)
+            fct[ar, p] = 0
+            used[ar, p] = True
+            mycol[ar, p] = k
+            piv[ar, p] = pk
+            if k + 1 < nc:
+                m[:, :, k + 1:] = fma(fct[:, :, None], m[ar, p, k + 1:][:, None, :], m[:, :, k + 1:])
+    return piv, mycol
+
+
+def emu_ipg(consts, s, a, mut=(), force_dynamic=None):
+    """grg_iteration_v2(apply = false) in float32 -> (grad [n, 43], used_static [n])."""
+    t = np.asarray(consts, np.float32)
+    s, a = np.asarray(s, np.float32), np.asarray(a, np.float32)
+    n = a.shape[0]
+    c = Tab(F32E, consts)
+    hi, lo = bounds(F32E, c, cols(F32E, s))
+    g = np.zeros((n, NY), np.float32)
+    for v in range(NY):
+        if hi[v] is not None:
+            up, dn = a[:, v] - hi[v], lo[v] - a[:, v]
+            if "ge_mask" in mut:
+                g[:, v] = (up >= 0).astype(np.float32) - (dn >= 0).astype(np.float32)
+            else:
+                g[:, v] = (up > 0).astype(np.float32) - (dn > 0).astype(np.float32)
+    f = emu_volt(consts, a)
+    live = live_tables(consts)["grg"].copy()
+    if "dead_fill_in" in mut:
+        k, cc = [(k, cc) for k in range(6, NEQ) for cc in range(NO, NY) if live[k, cc] and not jac_struct(c.adj, ROW_ORDER[k], COLS[cc])][0]
+        live[k, cc] = False
+    force = (t[OFF["FLAGS"]] != 1.0) if force_dynamic is None else force_dynamic
+
+    def system():
+        m = np.zeros((n, NEQ + 1, NY), np.float32)
+        m[:, :NEQ] = emu_jac_v2(f, ROW_ORDER, COLS, mut)
+        m[:, NEQ] = g[:, COLS]
+        return m
+    grad = np.zeros((n, NY), np.float32)
+    ok = np.zeros(n, bool)
+    with np.errstate(all="ignore"):
+        if not force:
+            m = system()
+            piv = emu_gj_static(m, 0, NEQ, 6, live)
+            ok = np.ones(n, bool) if "no_pivot_test" in mut else emu_pivots_ok(piv, 6, NEQ)
+            fp = m[:, NEQ, NO:]
+            acc = np.zeros((n, NEQ), np.float32)
+            for p in range(NPV):
+                acc = fma(m[:, :NEQ, NO + p], fp[:, p:p + 1], acc)
+            ds = acc / piv[:, :NEQ]
+            if "pivot_twice" in mut:
+                ds = ds / piv[:, :NEQ]
+            grad[:, PARTV] = fp
+            grad[:, OTHER] = -ds
+        if not ok.all():
+            bad = np.nonzero(~ok)[0]
+            m = system()[bad]
+            emu_gj_static(m, 0, 6, 6, live)
+            piv, mycol = emu_gj_dynamic(m, 6, NEQ)
+            fp = m[:, NEQ, NO:]
+            acc = np.zeros((len(bad), NEQ), np.float32)
+            for p in range(NPV):
+                acc = fma(m[:, :NEQ, NO + p], fp[:, p:p + 1], acc)
+            ds = acc / piv[:, :NEQ]
+            gb = np.zeros((len(bad), NY), np.float32)
+            gb[:, PARTV] = fp
+            other = np.asarray(OTHER)
+            for j in range(len(bad)):
+                gb[j, other[mycol[j, :NEQ]]] = -ds[j]
+            grad[bad] = gb
+    return grad, ok
+
+
+def emu_jac_v1(consts, a, mut=()):
+    """jac_entry of evopf_dev.h (the v1 association, shared with the float64 side's formula) -> float32 [n, 28, 43]."""
+    c = Tab(F32E, consts)
+    jac, _ = eq_jac(F32E, c, cols(F32E, a), mut)
+    n = np.asarray(a).shape[0]
+    out = np.zeros((n, NEQ, NY), np.float32)
+    for r in range(NEQ):
+        for v in range(NY):
+            if jac[r][v] is not None:
+                out[:, r, v] = jac[r][v]
+    return out
+
+
+def emu_cbwd(consts, a, g1, gb=None, g2=None, mut=(), force_dynamic=None):
+    """evopf_complete_bwd_kernel in float32 -> grad_ap [n, 14]."""
+    t = np.asarray(consts, np.float32)
+    a = np.asarray(a, np.float32)
+    n = a.shape[0]
+    dl = np.asarray(g1, np.float32).copy()
+    if gb is not None:
+        dl = dl + np.asarray(gb, np.float32)
+    if g2 is not None:
+        dl = dl + np.asarray(g2, np.float32)
+    jac = emu_jac_v1(consts, a, mut)
+    last_eq, last_var = [0] + [NB + b for b in SPV], [PG0] + list(range(QG0, QG0 + NG))
+    vec = np.zeros((n, 2 * NB), np.float32)
+    for tid in range(2 * NB):
+        acc = jac[:, last_eq[0], VM0 + tid] * dl[:, last_var[0]]
+        for j in range(1, 6):
+            acc = acc + jac[:, last_eq[j], VM0 + tid] * dl[:, last_var[j]]
+        vec[:, tid] = dl[:, VM0 + tid] - acc
+    force = (t[OFF["FLAGS"]] != 1.0) if force_dynamic is None else force_dynamic
+
+    def system():
+        m = np.zeros((n, NN, NN + 1), np.float32)
+        for r in range(NN):
+            for cc in range(NN):
+                m[:, r, cc] = jac[:, KEEP[cc], NEWTV[r]]
+            m[:, r, NN] = vec[:, NEWTV[r] - VM0]
+        return m
+    dint = np.zeros((n, NN), np.float32)
+    ok = np.zeros(n, bool)
+    with np.errstate(all="ignore"):
+        if not force:
+            m = system()
+            piv = emu_gj_static(m, 0, NN, 0, live_tables(consts)["newton_t"])
+            ok = emu_pivots_ok(piv, 0, NN)
+            dint = m[:, :, NN] / piv
+        if not ok.all():
+            bad = np.nonzero(~ok)[0]
+            m = system()[bad]
+            piv, mycol = emu_gj_dynamic(m, 0, NN)
+            d = m[:, :, NN] / piv
+            for j, r in enumerate(bad):
+                dint[r, mycol[j]] = d[j]
+        if "dint_not_permuted" in mut:
+            dint = dint[:, ::-1]
+        out = np.zeros((n, NP), np.float32)
+        for j in range(NP):
+            if j < 4:
+                out[:, j] = -dint[:, PVPOS[j]] + dl[:, PG0 + 1 + j]
+            elif j < 9:
+                var = VM0 + SPV[j - 4]
+                acc = np.zeros(n, np.float32)
+                for r in range(NN):
+                    acc = acc + jac[:, KEEP[r], var] * dint[:, r]
+                out[:, j] = -acc + vec[:, var - VM0]
+            elif j == 9:
+                out[:, j] = dl[:, PG0] + dl[:, PE0]
+            else:
+                out[:, j] = dint[:, PVPOS[j - 10]] + dl[:, PE0 + j - 9]
+    return out
+
+
+# ===================================================================================================== inputs
+def nxt(x, up):
+    return np.nextafter(np.float32(x), np.float32(np.inf if up else -np.inf))
+
+
+FIXED_EDGES = [(v, side, off) for v in list(range(PG0, VA0)) for side in (True, False) for off in (-1, 0, 1)]   # 24 x 2 x 3 = 144
+
+
+def make_rows(n, seed, spread=0.02, edges=True, consts=None):
+    """(state [n, 57], action [n, 43]) float32: hours 0..23 of Philox episodes, states of charge over [0.1, 0.8], actions = the
+    oracle's completed basic actions + ``spread`` * N(0, 1) (so bounds are violated on both sides and the balance is not zero), and
+    with ``edges``: every row has one pg / qg / |v| component exactly on, one ulp inside or one ulp outside one of its two bounds
+    (all 144 combinations from 144 rows on, offset by the seed); every 16th row a state of charge on 0.1 / 0.8 or a float32
+    neighbour (the shrunk charge-rate box collapses) with pe = +-0, a denormal, or on the clip, or soc + x landing on a limit; and
+    rows 7, 57, 107, ... (under 2 %) a pe exactly on / beside its COMPUTED bound, where the float64 mask is ambiguous."""
+    consts = consts_table() if consts is None else consts
+    rng = np.random.RandomState(seed)
+    ids = np.arange(n) + 11 * seed
+    hours = rng.randint(0, T, n)
+    soc = rng.uniform(oe.B_LOW, oe.B_HIGH, (n, NE))
+    s = np.concatenate([oe.episode_demand(seed, ids, 1 + seed % 3, hours), soc, oe.episode_price(seed, ids, 1 + seed % 3, hours)],
+                       axis=1).astype(np.float32)
+    lo, hi = oe.partial_box(s.astype(np.float64))
+    ap = lo + rng.uniform(0.05, 0.95, lo.shape) * (hi - lo)
+    ap[:, :4] = rng.uniform(0.0, 0.6, (n, 4))
+    ap[:, 4:9] = rng.uniform(1.0, 1.06, (n, 5))
+    a = (oe.complete_partial(s.astype(np.float64), ap) + spread * rng.randn(n, NY)).astype(np.float32)
+    if not edges:
+        return s, a
+    t = np.asarray(consts, np.float32)
+    c = Tab(F32E, consts)
+    hi_f, lo_f = bounds(F32E, c, cols(F32E, s))
+    for r in range(n):
+        v, side, off = FIXED_EDGES[(r + 37 * seed) % len(FIXED_EDGES)]
+        b = np.float32(np.broadcast_to((hi_f if side else lo_f)[v], (n,))[r])
+        a[r, v] = b if off == 0 else nxt(b, off > 0)
+        if r % 16 == 3:
+            j, kind = (r // 16) % NE, (r // 16) % 8
+            s[r, 2 * NB + j] = [np.float32(0.1), np.float32(0.8), nxt(0.1, True), nxt(0.8, False), nxt(0.1, False), nxt(0.8, True),
+                                np.float32(0.45), np.float32(0.7)][kind]
+            a[r, PE0 + j] = [np.float32(0.0), np.float32(-0.0), np.float32(1e-40), np.float32(-1e-40), np.float32(0.3), np.float32(-0.3),
+                             np.float32((0.8 - 0.45) / 0.9), np.float32(-0.1)][kind]
+    hi_f, lo_f = bounds(F32E, c, cols(F32E, s))
+    for r in range(7, n, 50):
+        j, kind = (r // 50) % NE, (r // 50) % 6
+        b = np.float32(np.broadcast_to((hi_f if kind < 3 else lo_f)[PE0 + j], (n,))[r])
+        a[r, PE0 + j] = [b, nxt(b, True), nxt(b, False)][kind % 3]
+    return s, a
+
+
+# ===================================================================================================== checkers (closed forms)
+def check_resid(consts, s, a, eq_got=None, ineq_got=None):
+    """rpo_evopf_resid: every element of eq [n, 28] and of the signed ineq [n, 58]; returns {group: worst ratio}."""
+    c = Tab(B64E, consts)
+    S, Ac = cols(B64E, s), cols(B64E, a)
+    out = {}
+    if eq_got is not None:
+        eq = eq_resid(B64E, c, S, Ac, flows(B64E, c, Ac))
+        out["resid_eq"] = judge("resid_eq", eq_got, val(B64E, eq), mag(B64E, eq))[0]
+    if ineq_got is not None:
+        iq = ineq_resid(B64E, c, S, Ac)
+        out["resid_ineq"] = judge("resid_ineq", ineq_got, val(B64E, iq), mag(B64E, iq))[0]
+    return out
+
+
+def emu_resid(consts, s, a, mut=()):
+    c = Tab(F32E, consts)
+    S, Ac = cols(F32E, s), cols(F32E, a)
+    return val(F32E, eq_resid(F32E, c, S, Ac, flows(F32E, c, Ac), mut)), val(F32E, ineq_resid(F32E, c, S, Ac, mut))
+
+
+def check_vjp(consts, a, ge, got, autograd_sign):
+    c = Tab(B64E, consts)
+    out = eq_vjp(B64E, c, cols(B64E, a), cols(B64E, ge), autograd_sign)
+    return {"eq_vjp": judge("eq_vjp", got, val(B64E, out), mag(B64E, out))[0]}
+
+
+def emu_vjp(consts, a, ge, autograd_sign, mut=()):
+    c = Tab(F32E, consts)
+    return val(F32E, eq_vjp(F32E, c, cols(F32E, a), cols(F32E, ge), autograd_sign, mut))
+
+
+def emu_lagrangian(consts, s, a, nu, scale, loss_in, gnu_in, overwrite, mut=()):
+    """-> (loss, grad_action [n, 43], grad_nu [58]) in float32."""
+    c = Tab(F32E, consts)
+    r = lagrangian(F32E, c, cols(F32E, s), cols(F32E, a), nu, scale, loss_in, gnu_in, overwrite, mut=mut)
+    return np.float32(r["loss"]), val(F32E, r["grad"]), np.array([np.float32(x) for x in r["grad_nu"]], np.float32)
+
+
+def check_lagrangian(consts, s, a, nu, scale, loss_in, gnu_in, overwrite, loss_got=None, grad_got=None, gnu_got=None):
+    """rpo_evopf_lagrangian: every element of grad_action (ambiguous masks: either value), grad_nu and the loss.
+    Returns ({group: worst ratio}, share of rows with an ambiguous mask)."""
+    c = Tab(B64E, consts)
+    S, Ac = cols(B64E, s), cols(B64E, a)
+    r = lagrangian(B64E, c, S, Ac, nu, scale, loss_in, gnu_in, overwrite)
+    out = {}
+    mv, mm = val(B64E, r["margins"]), mag(B64E, r["margins"])
+    amb = (mm > 0) & (np.abs(mv) <= tol_c("resid_ineq") * EPS32 * mm)
+    if grad_got is not None:
+        best = ratios("lag_grad", grad_got, val(B64E, r["grad"]), mag(B64E, r["grad"]))
+        if amb.any():
+            up = np.array([u for _, u in INEQ_ROWS])
+            for flip in (amb & up[None], amb & ~up[None], amb):
+                alt = lagrangian(B64E, c, S, Ac, nu, scale, loss_in, gnu_in, overwrite, mask=(mv > 0) ^ flip)
+                best = np.minimum(best, ratios("lag_grad", grad_got, val(B64E, alt["grad"]), mag(B64E, alt["grad"])))
+        out["lag_grad"] = float(best.max())
+    worst = 0.0
+    if gnu_got is not None:
+        worst = max(worst, judge("lag_sum", gnu_got, np.array([float(x.v) for x in r["grad_nu"]]), np.array([float(x.m) for x in r["grad_nu"]]))[0])
+    if loss_got is not None:
+        worst = max(worst, judge("lag_sum", [loss_got], [float(r["loss"].v)], [float(r["loss"].m)])[0])
+    if gnu_got is not None or loss_got is not None:
+        out["lag_sum"] = worst
+    return out, float(amb.any(axis=1).mean())
+
+
+def emu_step(consts, s, a, mut=()):
+    """-> dict(eq [n,28], ineq [n,58], reward [n], soc [n,5]) in float32."""
+    c = Tab(F32E, consts)
+    r = step(F32E, c, cols(F32E, s), cols(F32E, a), mut)
+    return dict(eq=val(F32E, r["eq"]), ineq=val(F32E, r["ineq"]), reward=np.asarray(r["reward"], np.float32), soc=val(F32E, r["soc"]))
+
+
+def check_step(consts, s, a, got):
+    """The float fields of a transition row: got = dict(eq, ineq, reward, soc) -> {group: worst ratio}."""
+    c = Tab(B64E, consts)
+    r = step(B64E, c, cols(B64E, s), cols(B64E, a))
+    viol = r["eq"] + r["ineq"]
+    return {"step_viol": judge("step_viol", np.concatenate([got["eq"], got["ineq"]], axis=1), val(B64E, viol), mag(B64E, viol))[0],
+            "step_reward": judge("step_reward", got["reward"], r["reward"].v, B64E.mag(r["reward"]))[0],
+            "step_soc": judge("step_soc", got["soc"], val(B64E, r["soc"]), mag(B64E, r["soc"]))[0]}
+
+
+DATA_COLS = list(range(2 * NB)) + list(range(2 * NB + NE, NS))
+
+
+def emu_episode(consts, seed, env_ids, episode, t, mut=()):
+    """-> the 52 data columns (pd, qd, price window) of the hour-t observation in float32 [n, 52]."""
+    out = episode_obs(F32E, Tab(F32E, consts), seed, env_ids, episode, t, mut)
+    return val(F32E, [out[j] for j in DATA_COLS])
+
+
+def check_episode(consts, seed, env_ids, episode, t, got):
+    """The data columns of an observation (got [n, 52], DATA_COLS order) against float64; returns ({group: ratio}, share unjudged)."""
+    a = episode_obs(B64E, Tab(B64E, consts), seed, env_ids, episode, t)
+    b = episode_obs(B64I, Tab(B64I, consts), seed, env_ids, episode, t)
+    xa, xb = [a[j] for j in DATA_COLS], [b[j] for j in DATA_COLS]
+    ratio, unj = judge("episode", got, val(B64E, xa), mag(B64E, xa), mag(B64I, xb) - mag(B64E, xa))
+    return {"episode": ratio}, unj
+
+
+def extreme_episodes(seed, n_envs=4096, episodes=(0, 1, 2)):
+    """(env id, episode, hour) triples whose Philox words give the largest / smallest power factor word and the smallest / largest
+    exponential word among n_envs x episodes x 24 hours (tan(acos(pf)) next to pf = 1 and 0.9, -log of the extremes)."""
+    ids = np.arange(n_envs)
+    best = {}
+    for ep in episodes:
+        for t in range(T):
+            words = np.concatenate([philox.draw(seed, ids, ep, oe.STREAM_DEMAND, t * 8 + cc) for cc in range(7)], axis=1) >> np.uint32(8)
+            for name, blk, fn in (("pf_max", words[:, 11:25], np.argmax), ("pf_min", words[:, 11:25], np.argmin),
+                                  ("exp_min", words[:, :11], np.argmin), ("exp_max", words[:, :11], np.argmax)):
+                k = fn(blk.max(axis=1) if "max" in name else blk.min(axis=1))
+                v = int(blk[k].max() if "max" in name else blk[k].min())
+                if name not in best or (v > best[name][0] if "max" in name else v < best[name][0]):
+                    best[name] = (v, int(k), ep, t)
+    return {k: v[1:] for k, v in best.items()}
+
+
+# ===================================================================================================== the shared cases
+LANES = [1, 3, 4, 5, 63, 64, 65, 257]              # four env lanes share a workgroup
+LAG_ROWS = [1, 255, 256, 257, 513]                 # the Lagrangian's four waves take rows q, q + 4, ...: full and ragged chunks of 256
+
+
+def mask_rows(n, seed, spread=0.02, consts=None):
+    """``make_rows`` for the comparisons in which a mask decides (Lagrangian gradient, reduced gradient): the rows whose float64
+    mask is ambiguous by construction (pe on its computed bound, the collapsed box) are rows 7, 71, 135, ... only -- under 2 %."""
+    s, a = make_rows(n, seed, spread, edges=True, consts=consts)
+    s2, a2 = make_rows(n, seed, spread, edges=False, consts=consts)
+    keep = np.ones(n, bool)
+    keep[7::64] = False
+    cfix = Tab(F32E, consts_table() if consts is None else consts)
+    hi_f, lo_f = bounds(F32E, cfix, cols(F32E, s2))
+    for r in np.nonzero(keep)[0]:                      # the fixed-bound edge of the row stays, its battery edges go
+        v, side, off = FIXED_EDGES[(r + 37 * seed) % len(FIXED_EDGES)]
+        b = np.float32(np.broadcast_to((hi_f if side else lo_f)[v], (n,))[r])
+        a2[r, v] = b if off == 0 else nxt(b, off > 0)
+        s[r], a[r] = s2[r], a2[r]
+    return s, a
+
+
+def pivot_ratio(consts, a):
+    """min |pivot| / max |pivot| of the static order's 22 pivots on [J_other | J_partial] in float32 (what pivots_ok tests)."""
+    f = emu_volt(consts, a)
+    m = emu_jac_v2(f, ROW_ORDER, COLS)
+    with np.errstate(all="ignore"):
+        piv = np.abs(emu_gj_static(m, 0, NEQ, 6, live_tables(consts)["grg"])[:, 6:NEQ])
+        return piv.min(axis=1) / piv.max(axis=1)
+
+
+def handover_rows(consts, n_pairs, seed):
+    """(state, action) rows in pairs: the same perturbation direction of voltages and angles scaled so that the static order's
+    pivot ratio lies just above (even rows) and just below (odd rows) 2^-6: both sides of the hand-over to partial pivoting."""
+    s0, a0 = make_rows(4 * n_pairs, seed, spread=0.0, edges=False, consts=consts)
+    rng = np.random.RandomState(seed + 1)
+    d = np.zeros_like(a0)
+    d[:, VM0:VA0] = 0.25 * rng.randn(len(a0), NB)
+    d[:, VA0:PE0] = 0.8 * rng.randn(len(a0), NB)
+    lo, hi = np.zeros(len(a0)), np.full(len(a0), 4.0)
+    thr = 2.0 ** -6
+    ok = pivot_ratio(consts, (a0 + hi[:, None] * d).astype(np.float32)) < thr
+    for _ in range(30):
+        mid = 0.5 * (lo + hi)
+        below = pivot_ratio(consts, (a0 + mid[:, None] * d).astype(np.float32)) < thr
+        hi, lo = np.where(below, mid, hi), np.where(below, lo, mid)
+    rows_s, rows_a = [], []
+    for r in np.nonzero(ok)[0]:
+        above, under = (a0[r] + lo[r] * 0.999 * d[r]).astype(np.float32), (a0[r] + hi[r] * 1.001 * d[r]).astype(np.float32)
+        pr = pivot_ratio(consts, np.stack([above, under]))
+        if pr[0] > thr and pr[1] < thr and pr[0] < 2 * thr and pr[1] > 0.5 * thr:
+            rows_s += [s0[r], s0[r]]
+            rows_a += [above, under]
+        if len(rows_a) == 2 * n_pairs:
+            break
+    return np.array(rows_s, np.float32), np.array(rows_a, np.float32)
+
+
+# ===================================================================================================== exploration (the proposal z)
+ULP_TANH = 5.0
+NOISE_NONE, NOISE_EXPLICIT, NOISE_PHILOX, NOISE_UNIFORM, NOISE_CLIP_ONLY = 0, 1, 2, 3, 4
+STREAM_ACT = philox.STREAM_ACT
+
+
+def _tanh(A, x):
+    if A is F32E:
+        return np.tanh(x)
+    r = np.tanh(x.v)
+    return V(r, (1.0 - r * r) * x.m + (2.0 + (ULP_TANH if A is B64I else 0.0)) * np.abs(r))
+
+
+def eps_at(eps_start, eps_end, eps_decay, t):
+    """fmaxf(eps_end, eps_start - eps_decay * (float) t) in float32."""
+    return np.fmax(np.float32(eps_end), np.float32(eps_start) - np.float32(eps_decay) * np.float32(t))
+
+
+def proposal(A, c, s, ap, noise, mode, raw, eps_t, seed, env_ids, t):
+    """The basic action the projection starts from (ddpg_pa.py:101-112, model/utils.py:40-62,75-101 with the state-dependent box of
+    evopf.py:769-783): 14 columns.  s: state columns; ap / noise: [n, 14] float32 or None."""
+    n = np.size(A.val(s[0]))
+    out = []
+    eps = A.inp(np.float32(eps_t))
+    for j in range(NP):
+        if j < 4:
+            lo, hi = c.pmin[1 + j], c.pmax[1 + j]
+        elif j < 9:
+            lo, hi = c.vmin[SPV[j - 4]], c.vmax[SPV[j - 4]]
+        else:
+            hi, lo = battery_bounds(A, s[2 * NB + j - 9])
+        scale = (hi - lo) * A.k(0.5)
+        clamp = lambda x: A.where(np.isnan(A.val(x)), x, A.minimum(A.maximum(x, lo), hi))          # noqa: E731
+        if mode == NOISE_UNIFORM:
+            w = philox.draw(seed, env_ids, t, STREAM_ACT, j >> 2)[:, j & 3]
+            out.append(scale * (A.k(2.0) * A.inp(philox.u01(w)) - A.k(1.0)) + (lo + scale))
+            continue
+        z = A.inp(np.asarray(ap, np.float32)[:, j])
+        if raw:
+            z = scale * _tanh(A, z) + (lo + scale)
+        if mode == NOISE_EXPLICIT:
+            z = clamp(z + eps * A.inp(np.asarray(noise, np.float32)[:, j]))
+        elif mode == NOISE_PHILOX:
+            w = philox.draw(seed, env_ids, t, STREAM_ACT, j >> 1)
+            nz = normal(A, w[:, 2], w[:, 3]) if (j & 1) else normal(A, w[:, 0], w[:, 1])
+            z = clamp(z + eps * nz)
+        elif mode == NOISE_CLIP_ONLY:
+            z = clamp(z)
+        out.append(z + A.inp(np.zeros(n, np.float32)) if np.ndim(A.val(z)) == 0 else z)
+    return out
+
+
+def emu_proposal(consts, s, ap, noise, mode, raw, eps_t, seed, env_ids, t):
+    return val(F32E, proposal(F32E, Tab(F32E, consts), cols(F32E, s), ap, noise, mode, raw, eps_t, seed, env_ids, t))
+
+
+def check_proposal(consts, s, ap, noise, mode, raw, eps_t, seed, env_ids, t, got):
+    """got [n, 14] = the basic components of an act_project output -> {"act": worst ratio}."""
+    a = proposal(B64E, Tab(B64E, consts), cols(B64E, s), ap, noise, mode, raw, eps_t, seed, env_ids, t)
+    b = proposal(B64I, Tab(B64I, consts), cols(B64I, s), ap, noise, mode, raw, eps_t, seed, env_ids, t)
+    return {"act": judge("act", got, val(B64E, a), mag(B64E, a), mag(B64I, b) - mag(B64E, a))[0]}
+
+
+# ===================================================================================================== Newton (complete_partial)
+def flat_start(consts, z):
+    """The iterate Newton starts from (evopf.py:796-807): z [n, 14] placed, load-bus guesses, qg = slack pg = 0."""
+    t = np.asarray(consts, np.float32)
+    a = np.zeros((np.asarray(z).shape[0], NY), np.float32)
+    a[:, VM0:VA0] = t[OFF["VM_INIT"]:OFF["VM_INIT"] + NB]
+    a[:, VA0:PE0] = t[OFF["VA_INIT"]:OFF["VA_INIT"] + NB]
+    a[:, PARTA] = np.asarray(z, np.float32)
+    return a
+
+
+def newton_point(out):
+    """An act_project(max_steps = 0) output as the Newton iterate it ended on: qg and the slack pg back at zero."""
+    a = np.asarray(out, np.float32).copy()
+    a[:, OTHER[:6]] = 0.0
+    return a
+
+
+def newton_step_ref(consts, s, a):
+    """One float64 Newton update from the float32 iterate a (evopf.py:819-834): (next values of the 22 Newton unknowns [n, 22] in
+    kNewtonVars order, their bounds, ||delta||_2, its bound)."""
+    c = Tab(B64E, consts)
+    S, Ac = cols(B64E, s), cols(B64E, a)
+    jv, jm = dense_jac(consts, a)
+    eq = eq_resid(B64E, c, S, Ac, flows(B64E, c, Ac))
+    gv, gm = val(B64E, eq)[:, KEEP], mag(B64E, eq)[:, KEEP]
+    n = gv.shape[0]
+    nxt_, bnd, nrm, nb_ = np.zeros((n, NN)), np.zeros((n, NN)), np.zeros(n), np.zeros(n)
+    for r in range(n):
+        with np.errstate(all="ignore"):
+            jn, jnm = jv[r][KEEP][:, NEWTV], jm[r][KEEP][:, NEWTV]
+            if not (np.isfinite(jn).all() and np.isfinite(gv[r]).all()):
+                nxt_[r], bnd[r], nrm[r], nb_[r] = np.nan, np.inf, np.nan, np.inf
+                continue
+            inv = np.linalg.inv(jn)
+            d = inv @ gv[r]
+            bd = np.abs(inv) @ ((np.abs(jn) + jnm) @ np.abs(d) + np.abs(gv[r]) + gm[r])
+            cur = np.asarray(a, np.float64)[r, NEWTV]
+            nxt_[r] = cur - d
+            bnd[r] = bd + np.abs(nxt_[r])
+            nrm[r] = np.sqrt((d * d).sum())
+            nb_[r] = (np.abs(d) * bd).sum() / max(nrm[r], ef.TINY) + 8.0 * nrm[r]       # 22 squares, the tree sum, the root
+    return nxt_, bnd, nrm, nb_
+
+
+def check_newton(consts, s, outs, tol, group="newton"):
+    """outs[m - 1] = act_project(max_steps = 0, newton_max_iters = m) for m = 1 .. M, same inputs.  Iterate m + 1 must be one
+    float64 Newton step from iterate m unless the float64 stop test ||delta|| < tol ended the loop before (then: the same bits); a
+    lane whose ||delta|| lies within its bound of tol is ambiguous (both accepted).  The tail (qg, slack pg = -resid at the final
+    point) and the untouched basic components are checked on every output.
+    Returns ({group: ratio, "resid_eq": ratio of the tails}, share of ambiguous lanes)."""
+    n = outs[0].shape[0]
+    z = outs[0][:, PARTA]
+    prev = flat_start(consts, z)
+    stopped, amb = np.zeros(n, bool), np.zeros(n, bool)
+    worst, tail = 0.0, 0.0
+    cB = Tab(B64E, consts)
+    for m, out in enumerate(outs, start=1):
+        assert (bits(out[:, PARTA]) == bits(z)).all() and (bits(out[:, VA0]) == bits(prev[:, VA0])).all(), "basic components moved"
+        nv, nbd, nrm, nrb = newton_step_ref(consts, s, prev)
+        r_step = ratios(group, out[:, NEWTV], nv, nbd).max(axis=1)
+        same = (bits(out[:, NEWTV]) == bits(prev[:, NEWTV])).all(axis=1)
+        r = np.where(stopped & ~amb, np.where(same, 0.0, np.inf), np.where(amb & same, 0.0, r_step))
+        worst = max(worst, float(r.max()))
+        # the tail of this output at its own final point
+        pt = newton_point(out)
+        Ac = cols(B64E, pt)
+        eq = eq_resid(B64E, cB, cols(B64E, s), Ac, flows(B64E, cB, Ac))
+        rows_ = [0] + [NB + b for b in SPV]
+        tv, tm = -val(B64E, eq)[:, rows_], mag(B64E, eq)[:, rows_]
+        tail = max(tail, judge("resid_eq", out[:, OTHER[:6]], tv, tm)[0])
+        # the float64 stop decision of THIS update (from the kernel's previous iterate), for the next output
+        with np.errstate(all="ignore"):
+            near = np.abs(nrm - tol) <= tol_c(group) * EPS32 * nrb
+            amb = amb | (~stopped & near)
+            stopped = stopped | (~amb & (nrm < tol))
+        prev = pt                                                        # (a stopped lane's output is its previous one)
+    return {group: worst, "resid_eq": tail}, float(amb.mean())
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def emu_newton(consts, s, z, tol, max_iters, mut=(), force_dynamic=None):
+    """complete_partial_v2 in float32 -> (action [n, 43], iterations [n])."""
+    t = np.asarray(consts, np.float32)
+    s = np.asarray(s, np.float32)
+    a = flat_start(consts, z)
+    n = a.shape[0]
+    live = live_tables(consts)["newton"]
+    force = (t[OFF["FLAGS"]] != 1.0) if force_dynamic is None else force_dynamic
+    c = Tab(F32E, consts)
+    S = cols(F32E, s)
+    active = np.ones(n, bool)
+    iters = np.zeros(n, np.int32)
+    newt = np.asarray(NEWTV)
+    last = None
+    with np.errstate(all="ignore"):
+        for _ in range(max_iters):
+            if not active.any():
+                break
+            Ac = cols(F32E, a)
+            resid = val(F32E, eq_resid(F32E, c, S, Ac, flows(F32E, c, Ac)))[:, KEEP]
+            f = emu_volt(consts, a)
+            jn = emu_jac_v2(f, KEEP, NEWTV, mut)
+
+            def system():
+                m = np.zeros((n, NN, NN + 1), np.float32)
+                m[:, :, :NN], m[:, :, NN] = jn, resid
+                return m
+            delta = np.zeros((n, NN), np.float32)
+            ok = np.zeros(n, bool)
+            if not force:
+                m = system()
+                piv = emu_gj_static(m, 0, NN, 0, live)
+                ok = np.ones(n, bool) if "no_pivot_test" in mut else emu_pivots_ok(piv, 0, NN)
+                delta = m[:, :, NN] / piv
+            if not ok.all():
+                bad = np.nonzero(~ok)[0]
+                m = system()[bad]
+                piv, mycol = emu_gj_dynamic(m, 0, NN)
+                d = m[:, :, NN] / piv
+                for j, r in enumerate(bad):
+                    delta[r, mycol[j]] = d[j]
+            last = a.copy()
+            a[np.ix_(active, newt)] = (a[:, newt] - delta)[active]
+            iters += active
+            nrm = np.abs(delta).max(axis=1) if "stop_inf_norm" in mut else np.sqrt((delta * delta).sum(axis=1, dtype=np.float32))
+            active = active & ~(nrm < np.float32(tol))
+        pt = last if ("tail_before_update" in mut and last is not None) else a
+        Ac = cols(F32E, pt)
+        eq = val(F32E, eq_resid(F32E, c, S, Ac, flows(F32E, c, Ac)))
+        a[:, OTHER[:6]] = -eq[:, [0] + [NB + b for b in SPV]]
+    return a, iters
+
+
+# ===================================================================================================== GRG (grad_steps)
+def check_grg(consts, s, outs, iters, lr, corr_eps, group="grg"):
+    """outs[k] = act_project(max_steps = k) for k = 0 .. K on the same inputs (momentum 0), iters[k] its iteration counts.  Output
+    k + 1 must be output k minus lr * the float64 reduced gradient at output k, unless the float64 stop test (k >= 1; torch.max
+    propagates a NaN and NaN > corr_eps is false: ``stop_decision``) ended the loop: then the same bits, and iters says so.
+    A stop quantity within its bound of corr_eps and masks within their bound of 0 are ambiguous: both outcomes are accepted.
+    Returns ({group: ratio}, share of lanes with an ambiguous stop or mask)."""
+    n = outs[0].shape[0]
+    RUN, AMB = -1, -2
+    status = np.full(n, RUN)                                  # or the k at which the float64 test stopped the lane
+    amb_mask = np.zeros(n, bool)
+    worst = 0.0 if (np.asarray(iters[0]) == 0).all() else np.inf
+    for k in range(len(outs) - 1):
+        cur, nx = outs[k], outs[k + 1]
+        if k >= 1:
+            stop_now, near = stop_decision(consts, s, cur, corr_eps)
+            run = status == RUN
+            status = np.where(run & near, AMB, np.where(run & stop_now, k, status))
+        same = (bits(nx) == bits(cur)).all(axis=1)
+        need = np.nonzero((status == RUN) | ((status == AMB) & ~same))[0]
+        for r in np.nonzero(status >= 0)[0]:
+            if not (same[r] and iters[k + 1][r] == status[r]):
+                worst = np.inf
+        for r in np.nonzero((status == AMB) & same)[0]:
+            if iters[k + 1][r] != iters[k][r]:
+                worst = np.inf
+        if not len(need):
+            continue
+        jv, jm = dense_jac(consts, cur[need])
+        choices = mask_choices(*mask_margins(consts, s[need], cur[need]))
+        for q, r in enumerate(need):
+            if iters[k + 1][r] != k + 1:
+                worst = np.inf
+            if choices[q] is None or not np.isfinite(jv[q]).all() or not np.isfinite(cur[r]).all():
+                amb_mask[r] = True                            # (left out: counted)
+                continue
+            amb_mask[r] |= len(choices[q]) > 1
+            best = np.inf
+            for g in choices[q]:
+                with np.errstate(all="ignore"):
+                    full, bound = reduced_grad_ref(jv[q], jm[q], g)
+                st = lr * full
+                want = cur[r].astype(np.float64) - st
+                best = min(best, judge(group, nx[r], want, lr * bound + np.abs(st) + np.abs(want))[0])
+            worst = max(worst, best)
+    return {group: float(worst)}, float(((status == AMB) | amb_mask).mean())
+
+
+def stop_decision(consts, s, a, corr_eps):
+    """The loop condition of rpo_ddpg.py:271-272 for k >= 1, per row in float64: continue iff max |eq_resid| > corr_eps or
+    max ineq_dist > corr_eps, where torch.max returns NaN when its tensor holds one and NaN > corr_eps is false.  Returns
+    (stop [n], near [n]): near = a deciding quantity within its error bound of corr_eps."""
+    c = Tab(B64E, consts)
+    S, Ac = cols(B64E, s), cols(B64E, a)
+    eq = eq_resid(B64E, c, S, Ac, flows(B64E, c, Ac))
+    iq = ineq_resid(B64E, c, S, Ac)
+    with np.errstate(all="ignore"):
+        ev, em = np.abs(val(B64E, eq)), mag(B64E, eq)
+        iv, im = np.maximum(val(B64E, iq), 0.0), mag(B64E, iq)
+        iv = np.where(np.isnan(val(B64E, iq)), np.nan, iv)
+        cont, near = np.zeros(len(ev), bool), np.zeros(len(ev), bool)
+        for v, m, cgrp in ((ev, em, "resid_eq"), (iv, im, "resid_ineq")):
+            has_nan = np.isnan(v).any(axis=1)
+            tol = tol_c(cgrp) * EPS32 * m
+            cont |= ~has_nan & (v > corr_eps).any(axis=1)
+            near |= ~has_nan & (np.abs(v - corr_eps) <= tol).any(axis=1) & ~(v > corr_eps + tol).any(axis=1)
+        near &= ~(cont & ~near)                                # (another quantity clearly above corr_eps decides)
+    return ~cont, near
+
+
+def emu_grg(consts, s, a0, max_steps, lr, corr_eps, momentum=0.0, mut=(), force_dynamic=None):
+    """grad_steps_v2 in float32 -> (outs [max_steps + 1, n, 43] = the action after min(k, iters) steps, iters [n])."""
+    s = np.asarray(s, np.float32)
+    a = np.asarray(a0, np.float32).copy()
+    n = a.shape[0]
+    old = np.zeros_like(a)
+    live = np.ones(n, bool)
+    iters = np.zeros(n, np.int32)
+    outs = [a.copy()]
+    lr, mom, eps = np.float32(lr), np.float32(momentum), np.float32(corr_eps)
+    with np.errstate(all="ignore"):
+        for k in range(max_steps):
+            if k >= 1 or "no_k0" in mut:
+                eq, iq = emu_resid(consts, s, a)
+                if "nan_dropped" in mut:
+                    go = np.fmax(np.fmax.reduce(np.abs(eq), axis=1), np.fmax(np.fmax.reduce(iq, axis=1), np.float32(0))) > eps
+                else:
+                    go = (np.abs(eq).max(axis=1) > eps) | (np.maximum(iq, np.float32(0)).max(axis=1) > eps)    # (np.max propagates NaN)
+                live = live & go
+            g, _ = emu_ipg(consts, s, a, mut, force_dynamic)
+            st = lr * g + mom * old
+            if "lr_other_only" in mut:
+                st[:, PARTV] = g[:, PARTV] + mom * old[:, PARTV]
+            a = np.where(live[:, None], a - st, a)
+            old = np.where(live[:, None], st, old)
+            iters += live
+            outs.append(a.copy())
+    return np.array(outs), iters
+
+
+def check_momentum(consts, s, start, got, got_iters, K, lr, corr_eps, momentum, group="grg"):
+    """Momentum trajectories as wholes (as check_batch_momentum of envs_f64.py): the action after K steps with momentum against
+    the float64 trajectory from the same start, within the SUM of the K single-step tolerances along that trajectory; lanes in
+    which a float64 stop test or mask is ambiguous anywhere on the way are left out and counted.
+    Returns ({group + "_mom": ratio in units of the summed tolerances}, share of lanes left out)."""
+    n = start.shape[0]
+    a = np.asarray(start, np.float64).copy()
+    old, tol_sum = np.zeros_like(a), np.zeros_like(a)
+    live, out_ = np.ones(n, bool), np.zeros(n, bool)
+    steps = np.zeros(n, np.int64)
+    for k in range(K):
+        a32 = a.astype(np.float32)                             # (the formulas take float32 inputs: the bound below covers it)
+        if k >= 1:
+            stop_now, near = stop_decision(consts, s, a32, corr_eps)
+            out_ |= live & near
+            live &= ~stop_now
+        jv, jm = dense_jac(consts, a32)
+        choices = mask_choices(*mask_margins(consts, s, a32))
+        for r in np.nonzero(live & ~out_)[0]:
+            if choices[r] is None or len(choices[r]) > 1:
+                out_[r] = True
+                continue
+            with np.errstate(all="ignore"):
+                full, bound = reduced_grad_ref(jv[r], jm[r], choices[r][0])
+            st = lr * full + momentum * old[r]
+            a[r] = a[r] - st
+            old[r] = st
+            tol_sum[r] += lr * bound + np.abs(lr * full) + np.abs(st) + 2.0 * np.abs(a[r])
+            steps[r] += 1
+    keep = ~out_
+    ok_iters = (np.asarray(got_iters)[keep] == steps[keep]).all()
+    ratio = judge(group, got[keep], a[keep], tol_sum[keep])[0] if keep.any() else 0.0
+    return {group + "_mom": ratio if ok_iters else np.inf}, float(out_.mean())
+
+
+def basic_rows(n, seed, consts=None):
+    """(state [n, 57], basic action [n, 14]) float32 for the projection: basic actions inside their box (5 % .. 95 %), and on the
+    edge rows: pg / |v| on box corners (rows 1, 9, 17, ...; those bounds are table entries, the masks exact), demands scaled to 0
+    and to 2x the curve (rows 5, 21, ... / 13, 29, ...), and pe on the corners of its COMPUTED box (rows 7, 71, ...: under 2 %,
+    the float64 mask is ambiguous there by construction)."""
+    s, _ = make_rows(n, seed, edges=False, consts=consts)
+    rng = np.random.RandomState(seed + 100)
+    for r in range(n):
+        if r % 16 == 5:
+            s[r, :2 * NB] = 0.0
+        elif r % 16 == 13:
+            s[r, :2 * NB] *= np.float32(2.0)
+    lo, hi = oe.partial_box(s.astype(np.float64))
+    ap = (lo + rng.uniform(0.05, 0.95, lo.shape) * (hi - lo)).astype(np.float32)
+    ap[:, :4] = rng.uniform(0.0, 0.6, (n, 4))
+    ap[:, 4:9] = rng.uniform(1.0, 1.06, (n, 5))
+    c = Tab(F32E, consts_table() if consts is None else consts)
+    S = cols(F32E, s)
+    for r in range(1, n, 8):
+        corner = (r // 8) % 4
+        ap[r, :4] = [np.float32(c.pmin[1 + j]) if corner & 1 else np.float32(c.pmax[1 + j]) for j in range(4)]
+        ap[r, 4:9] = [np.float32(c.vmin[SPV[j]]) if corner & 2 else np.float32(c.vmax[SPV[j]]) for j in range(5)]
+    for r in range(7, n, 64):
+        for j in range(NE):
+            p_max, p_min = battery_bounds(F32E, S[2 * NB + j])
+            ap[r, 9 + j] = (p_max if (r // 64 + j) % 2 else p_min)[r]
+    return s, ap
