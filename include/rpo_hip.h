@@ -152,6 +152,13 @@ extern "C" {
 #define RPO_EVAL_NONFINITE 2     /* a live step produced a non-finite reward or violation */
 #define RPO_EVAL_LEN_SHIFT 2     /* steps taken (the step that ended the episode included) */
 #define RPO_EVAL_LANE_STEPS 4194304  /* lane-steps per evaluate launch the host aims at: steps = clamp(this / n, 1, horizon) */
+/* The same for rpo_evopf_evaluate, where a lane-step is a power-flow solve and not a row of a tile.  The kernel's geometry (one
+ * wave per lane, one wave per SIMD) runs 4 waves x 256 CUs = 1024 lanes at once, so L lane-steps take about L / 1024 lane-step
+ * times.  A lane-step is Newton + the GRG iterations of the evaluation budget: ~48 us at 10 iterations, ~3.4 us
+ * per further iteration, so ~190 us at the scripts' eval_steps = 50 -- measured 195 us with the actor.
+ * 12 rounds of the chip = 12 * 1024 = 12288 lane-steps ~ 2.3 ms per launch at that budget (0.6 ms at 10 iterations): a
+ * 24-step day in one launch up to 512 lanes, two launches at 1024, one step per launch from 12288 lanes on. */
+#define RPO_EVOPF_EVAL_LANE_STEPS 12288
 
 /* Per-step record of a policy evaluation (rpo_<env>_evaluate_record, rpo_eval_record): float[T, R, W], step-major -- row
  * (s, i) is env step s of episode i < R, so the lanes of a workgroup write neighbouring rows.  With O / P / A the widths of
@@ -880,6 +887,29 @@ int rpo_evopf_eq_vjp(int n, const float* action, const float* grad_eq, float* gr
 int rpo_evopf_lagrangian(int n, const float* state, int state_stride, const float* action, const float* nu, float scale, float* loss_out,
                          float* grad_action, float* grad_nu, const float* consts_dev, int overwrite, void* stream);
 /* (overwrite != 0: loss_out is written instead of accumulated -- one launch instead of a fill + this one; grad_nu accumulates) */
+
+/* Policy evaluation on EVOPF-v0 (RPOTrainerBase.evaluate under schedule fused_eval_evopf=1; csrc/evopf_eval.hip): env steps
+ * [t0, t0 + steps) of n_envs independent episodes in one launch that loops over the steps inside each workgroup (4 waves = 4
+ * episodes): the 57 -> 256 -> 256 -> 14 actor layer by layer on the workgroup's four observation rows, with the ordered MFMA
+ * chains and the summation order of rpo_mlp_forward's layer-by-layer launches -> tanh box (gauss = 0: one head) | mean head
+ * (gauss = 1: two heads) in the state-dependent box -> complete_partial -> grad_steps (max_steps iterations, no noise) -> env
+ * step + violations + TimeLimit (no auto-reset, no replay row, no statistics row) -> acc [n_envs, RPO_EVAL_LEN] (t0 == 0
+ * writes a row from scratch) and, with con != NULL, the per-constraint report con [n_envs, 144] (layout RPO_CON_*; 16-byte
+ * aligned).  A lane whose episode has ended is not stepped again; a workgroup whose lanes have all ended returns.  The host
+ * enqueues the launches back to back, t0 = 0, steps, 2 * steps, ...; the split changes no bit.
+ * == per step: rpo_mlp_forward (n <= 16384, RPO_TUNE_MLP_GEMM and RPO_TUNE_GEMM_KSPLIT at their defaults)
+ *    [+ rpo_evopf_gauss_head(deterministic)] + rpo_evopf_act_project(RPO_NOISE_NONE, ap_is_raw = !gauss, iters) +
+ *    rpo_evopf_step(auto_reset 0, cap_steps 1) [+ rpo_eval_constraints] + rpo_eval_accumulate, bit for bit.
+ * Refused before any HIP call: a NULL actor_host (RPO_ERR_NULL); n_envs <= 0, steps <= 0, t0 < 0, max_episode_steps <= 0,
+ * max_steps < 0, newton_max_iters <= 0 (RPO_ERR_ARG); a NULL state, action, ep_len, ep_ret, ep_count, acc or consts_dev
+ * (RPO_ERR_NULL); a con that is not 16-byte aligned (RPO_ERR_ARG); an actor that is not S = 57, E = H = 256 with 14 outputs per
+ * head, one head (gauss = 0) or two (RPO_ERR_ARG).  ctrl (may be NULL) receives ctrl[RPO_CTRL_NONFINITE] like rpo_evopf_step;
+ * ctrl[RPO_CTRL_T] is neither read nor advanced. */
+int rpo_evopf_evaluate(const rpo_mlp* actor_host, int gauss, int n_envs, float* state, float* action, int* ep_len, float* ep_ret,
+                       unsigned* ep_count, long long* ctrl, float* acc, int t0, int steps, int max_steps, float corr_lr,
+                       float corr_eps, float corr_momentum, float newton_tol, int newton_max_iters, const float* consts_dev,
+                       int max_episode_steps, float viol_thresh, unsigned long long seed, unsigned env_id_base, float* con,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused pipelines of one RPO iteration (rpo_amd/csrc/fused.hip): the row-local stages chained

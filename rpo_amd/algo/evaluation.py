@@ -7,7 +7,10 @@ episodes and returns per-episode arrays (``EvalResult``).  Two paths, chosen fro
 * **fused** -- RPODDPG / RPOSAC on CartSafe-v0 and SpringPendulum-v0 with the fused MLP kernels: ``rpo_<env>_evaluate``
   (csrc/evaluate.hip) runs actor -> head -> Complete -> GRG -> env step -> per-episode accumulators for up to ``steps`` env
   steps per launch, ``ceil(horizon / steps)`` launches back to back, no host synchronisation in between.
-* **stepwise** -- everything else (EVOPF-v0, the Lagrangian baselines, ``fused_mlp=0``, the CPU oracle backend, and
+* **fused, EVOPF-v0** -- opt-in by schedule ``fused_eval_evopf=1`` (default 0): ``rpo_evopf_evaluate`` (csrc/evopf_eval.hip) does
+  the same for RPODDPG / RPOSAC with the fused 256-wide actor, four episodes per workgroup (``fused_evopf_ok``); ``record=``,
+  ``obs_noise=``, curve mode / ``keep_best``, single-launch sweeps and ``act()`` stay stepwise there.
+* **stepwise** -- everything else (EVOPF-v0 by default, the Lagrangian baselines, ``fused_mlp=0``, the CPU oracle backend, and
   schedule ``fused_eval=0``): ``_eval_action`` + ``step(auto_reset=False)`` + ``rpo_eval_accumulate`` per env step, or the
   same update in torch ops on a backend without that kernel.
 
@@ -367,6 +370,29 @@ def fused_ok(tr):
                 and tr._box_affine is not None and f.descs["actor"].E == 128 and tr.device.type == "cuda")
 
 
+#: episodes up to which FusedNets.forward runs a wide network layer by layer (csrc/mlp_gemm.h: gemm_path_ok)
+_GEMM_PATH_ROWS = 16384
+
+
+def fused_evopf_ok(tr, episodes, record=0, sigma=None):
+    """The fused EVOPF-v0 evaluation kernel (``rpo_evopf_evaluate``) applies to this ``evaluate()`` call: schedule
+    ``fused_eval_evopf`` (default 0) and ``fused_eval``, RPODDPG / RPOSAC with the fused 256-wide actor on an env with a
+    state-dependent box whose backend has ``evopf_evaluate`` for it, no record, no observation noise -- and the stepwise path's actor
+    forward being the layer-by-layer launches whose summation order the kernel reproduces: at most 16384 episodes and the
+    tunings ``mlp_gemm`` / ``gemm_ksplit`` at their defaults.  ``CurveRunner`` keeps ``fused_ok``: curve mode stays stepwise."""
+    f = tr.fused
+    if not (tr.schedule.get("fused_eval_evopf", 0) and tr.schedule.get("fused_eval", 1)) or tr.device.type != "cuda":
+        return False
+    if f is None or "actor" not in f.descs or hasattr(tr, "_deterministic"):
+        return False
+    if not hasattr(tr.backend, "evopf_evaluate") or getattr(tr.kernels, "name", None) != "EVOPF-v0":
+        return False
+    d = f.descs["actor"]
+    if tr._box_affine is not None or d.E != 256 or d.H != 256 or episodes > _GEMM_PATH_ROWS or record or sigma is not None:
+        return False
+    return hip_ops.tuning.get("mlp_gemm") == 1 and hip_ops.tuning.get("gemm_ksplit") == 1
+
+
 def check_episodes(episodes, what="evaluate: episodes"):
     try:
         ok = not isinstance(episodes, bool) and int(episodes) == episodes and episodes >= 1
@@ -512,6 +538,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     H = check_horizon(tr, horizon)
     k = tr.kernels
     fused = fused_ok(tr)
+    fused_evopf = not fused and fused_evopf_ok(tr, n, R, sigma)
     dims = (k.obs_dim, k.partial_dim if fused else tr._eval_proposal_dim(), k.action_dim)
     if R:
         nbytes = 4 * H * R * hip_ops.trace_layout(*dims)[1]
@@ -528,7 +555,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     # the per-constraint report: step 0 writes every row from scratch, nothing to clear
     con = torch.empty(n, hip_ops.con_width(k.ineq_num, k.eq_num), device=tr.device) if want_con else None
     noise = {} if sigma is None else dict(noise=(sigma, seed))   # keyed by the evaluation's seed, like the reset stream
-    path, run = ("fused", _run_fused) if fused else ("stepwise", _run_stepwise)
+    path, run = ("fused", _run_fused) if fused else ("fused", _run_fused_evopf) if fused_evopf else ("stepwise", _run_stepwise)
     with torch.no_grad():
         run(tr, v, acc, H, trace=trace, budget=budget, con=con, **noise)
     res = EvalResult(acc.cpu().numpy(), path, H, seed, obs_noise=sigma)
@@ -577,6 +604,20 @@ def _run_fused(tr, v, acc, H, desc=None, trace=None, budget=(None, None), con=No
                                     v.action, v.ep_len, v.ep_ret, v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), tr._box_lo,
                                     tr._box_hi, eval_steps, eval_lr, tr.corr_eps, tr.corr_momentum, v.max_episode_steps,
                                     v.viol_thresh, *tail, **kw)
+
+
+def _run_fused_evopf(tr, v, acc, H, trace=None, budget=(None, None), con=None, noise=None):
+    """_run_fused on EVOPF-v0 (``fused_evopf_ok``: neither trace nor noise): ceil(H / steps) launches of rpo_evopf_evaluate back to
+    back, EVOPF_EVAL_LANE_STEPS lane-steps per launch -- a lane-step is a power-flow solve there, not a row of a tile.  The box
+    depends on the state, so there is no (scale, base): the kernel applies it like rpo_evopf_act_project / rpo_evopf_gauss_head."""
+    assert trace is None and noise is None
+    eval_steps = tr.eval_steps if budget[0] is None else budget[0]
+    eval_lr = tr.eval_lr if budget[1] is None else budget[1]
+    steps = max(1, min(H, hip_ops.EVOPF_EVAL_LANE_STEPS // v.n))
+    for t0 in range(0, H, steps):
+        tr.backend.evopf_evaluate(tr.kernels, tr.fused.descs["actor"], tr._gauss_policy, v.internal, v.action, v.ep_len, v.ep_ret,
+                                  v.ep_count, v.ctrl, acc, t0, min(steps, H - t0), eval_steps, eval_lr, tr.corr_eps,
+                                  tr.corr_momentum, v.max_episode_steps, v.viol_thresh, v.seed, v.env_id_base, con=con)
 
 
 def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, noise=None):

@@ -267,13 +267,16 @@ def _env_int(name, default):
 #:                  actor-only prefix of the policy step beside the critic update (0: serial windows)
 #:   fused_eval     evaluate(): actor -> head -> Complete -> GRG -> env step -> per-episode statistics as a few launches that
 #:                  loop over the env steps (0: the stepwise path, one _eval_action + step + rpo_eval_accumulate per step)
+#:   fused_eval_evopf  (default 0) evaluate() on EVOPF-v0: the same loop as one launch of rpo_evopf_evaluate per few env steps, four
+#:                  episodes per workgroup (needs fused_eval; 0: the stepwise path).  The same bits; measured 6-14 % faster up to
+#:                  1024 episodes and 1.5 x slower at 16384, so it is off
 #:   fused_act      act(): actor -> head -> Complete -> GRG -> residuals as ONE launch (0: the stepwise path, the trainer's
 #:                  deterministic proposal + rpo_*_act_project + rpo_*_resid)
 #:   eval_overlap   curve mode (`eval_episodes=N`), fused path: an evaluation point runs on its own stream, on a snapshot of the
 #:                  actor, beside the update that follows it (0: in order on the training stream)
 #:   force_dist     (default 0) data-parallel code path over a one-rank process group
 SCHEDULE_DEFAULTS = dict(fused_mlp=1, fused_rollout=1, fused_critic=1, fused_actor=1, split=1, ride=1, front=1, branch=1,
-                         fused_eval=1, fused_act=1, eval_overlap=1, force_dist=0)
+                         fused_eval=1, fused_eval_evopf=0, fused_act=1, eval_overlap=1, force_dist=0)
 
 
 def parse_schedule(overrides=None):

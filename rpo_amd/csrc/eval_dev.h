@@ -10,6 +10,16 @@ __device__ __forceinline__ float nanmax(float a, float b) {
     return a != a ? a : (b != b ? b : (b > a ? b : a));
 }
 
+// the step's max inequality violation / max |equality residual| of a transition row, columns in order (the stepwise path's
+// kernels read the row rpo_<env>_step wrote; the fused EVOPF evaluation the row its lane keeps in LDS)
+__device__ __forceinline__ void row_violations(const float* r, int ineq_col, int ineq_num, int eq_col, int eq_num, float& ineq,
+                                               float& eq) {
+    ineq = r[ineq_col];
+    eq = fabsf(r[eq_col]);
+    for (int j = 1; j < ineq_num; ++j) ineq = nanmax(ineq, r[ineq_col + j]);
+    for (int j = 1; j < eq_num; ++j) eq = nanmax(eq, fabsf(r[eq_col + j]));
+}
+
 // One env step of one lane into its accumulator row acc[RPO_EVAL_LEN] (include/rpo_hip.h: RPO_EVAL_*), with the arithmetic
 // of RPOTrainerBase.eval() in its order: `step` is the 0-based step index of the evaluation (every lane starts at 0; step 0
 // initialises the row), `ineq` / `eq` the step's max inequality violation / max |equality residual|.  A lane that is no

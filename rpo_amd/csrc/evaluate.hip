@@ -36,9 +36,12 @@ namespace {
 
 using namespace rpo_mlp_dev;
 using rpo_host::check_actor;
+using rpo_host::check_eval_con;
+using rpo_host::check_eval_range;
 using rpo_host::to_dev;
 using rpo_eval_dev::con_width;
 using rpo_eval_dev::nanmax;
+using rpo_eval_dev::row_violations;
 using rpo_eval_dev::rpo_eval_lane_update;
 using rpo_eval_dev::trace_head;
 using rpo_eval_dev::trace_width;
@@ -434,12 +437,6 @@ int launch_eval_any(const EvalArgs<ENV>& args, const typename ENV::Consts& c, in
     return rec ? launch_eval<ENV, 1, 1>(ca, c, n, stream) : launch_eval<ENV, 0, 1>(ca, c, n, stream);
 }
 
-int check_eval_range(int n, int t0, int steps, int max_episode_steps, int max_steps) {
-    if (n <= 0 || t0 < 0 || steps <= 0 || max_episode_steps <= 0 || max_steps < 0) return RPO_ERR_ARG;
-    if ((long long)t0 + steps > (1ll << 24)) return RPO_ERR_ARG;   // lengths and step indices stay exact in the f32 row
-    return 0;
-}
-
 // The trace arguments of the *_evaluate_record entry points: 1 <= R <= n rows per step, steps [t0, t0 + steps) inside the
 // buffer's T steps, 16-byte aligned for the float4 stores.
 int check_eval_trace(const float* trace, int n, int trace_rows, int trace_steps, int t0, int steps) {
@@ -447,12 +444,6 @@ int check_eval_trace(const float* trace, int n, int trace_rows, int trace_steps,
     if (trace_rows <= 0 || trace_rows > n || trace_steps <= 0 || (long long)t0 + steps > trace_steps) return RPO_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(trace) % 16) return RPO_ERR_ARG;
     return 0;
-}
-
-// The report of the *_evaluate_constraints entry points: 16-byte aligned for the float4 accesses.
-int check_eval_con(const float* con) {
-    if (!con) return RPO_ERR_NULL;
-    return reinterpret_cast<uintptr_t>(con) % 16 ? RPO_ERR_ARG : 0;
 }
 
 // ------------------------------------------------------------------------------------------- stepwise accumulation
@@ -465,15 +456,6 @@ struct AccArgs {
     float viol_thresh;
     float* acc;
 };
-
-// the step's max inequality violation / max |equality residual| of a transition row, columns in order
-__device__ __forceinline__ void row_violations(const float* r, int ineq_col, int ineq_num, int eq_col, int eq_num, float& ineq,
-                                               float& eq) {
-    ineq = r[ineq_col];
-    eq = fabsf(r[eq_col]);
-    for (int j = 1; j < ineq_num; ++j) ineq = nanmax(ineq, r[ineq_col + j]);
-    for (int j = 1; j < eq_num; ++j) eq = nanmax(eq, fabsf(r[eq_col + j]));
-}
 
 __global__ __launch_bounds__(RPO_BLOCK) void eval_accumulate_kernel(AccArgs p) {
     for (int i = blockIdx.x * RPO_BLOCK + threadIdx.x; i < p.n; i += gridDim.x * RPO_BLOCK) {

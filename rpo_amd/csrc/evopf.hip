@@ -9,10 +9,6 @@ using rpo_host::launch;
 
 namespace {
 
-__device__ __forceinline__ void load_row(float* dst, const float* __restrict__ src, int n) {
-    for (int i = lane_id(); i < n; i += RPO_WAVE) dst[i] = src[i];
-}
-
 // Env lanes per workgroup of the one-wave-per-lane kernels: four waves = one on each SIMD of a CU.  As 64-thread workgroups the
 // dispatcher packed several waves onto one SIMD while others stayed empty -- and two issue-bound waves on a SIMD run at 3/4 of
 // the speed each: the 1024-lane projection took 171 us inside the training windows and 123 us in this form.
@@ -38,107 +34,7 @@ __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_reset_kernel(int n
 }
 
 // -------------------------------------------------------------------------------------------------------- step
-struct StepArgs {
-    int n;
-    float* state;
-    const float* action;
-    int* ep_len;
-    float* ep_ret;
-    unsigned* ep_count;
-    float* rows;
-    long long cap_steps;
-    float* stats;
-    int stats_cap;
-    long long* ctrl;
-    int max_episode_steps;
-    int auto_reset;
-    float viol_thresh;
-    const float* consts;
-    uint64_t seed;
-    uint32_t env_id_base;
-};
-
-// EVOPFEnv.step (evopf.py:348-366) + Battery.step (:74-102) + the bookkeeping of the run loop (rpo_ddpg.py:120-145):
-// violations of the pre-step observation, reward, next hour of the episode data, replay scatter, statistics, auto-reset.
-__device__ __forceinline__ void evopf_step_lane(const StepArgs& p, Ws& w, float* row, int i, long long t) {
-    RPO_FP_STRICT
-    const int tid = lane_id();
-    load_consts(w, p.consts);
-    load_row(w.s, p.state + (size_t)i * NS, NS);
-    load_row(w.a, p.action + (size_t)i * NY, NY);
-    sync();
-    flows(w);
-    eq_resid(w);
-    ineq_resid(w);
-    const uint32_t env_id = p.env_id_base + (uint32_t)i;
-    const int len = p.ep_len[i] + 1;                                   // == the loaders' counter (demand.py:69-73)
-    const unsigned ep = p.ep_count[i];
-    const bool data_done = len >= T;
-    const bool done = data_done || len >= p.max_episode_steps;
-
-    // reward = wg * (-obj_fn) + we * (-sum(pe * price)) (evopf.py:350-353,509-518; Battery.step :99-100)
-    float part = 0.0f;
-    if (tid < NG) {
-        const float pg = w.a[PG0 + tid];
-        part = -kWg * (w.c[RPO_EVOPF_C_QUAD + tid] * pg * pg + w.c[RPO_EVOPF_C_LIN + tid] * pg) -
-               kWe * (w.a[PE0 + tid] * w.s[2 * NB + NE]);
-    }
-    const float reward = rpo_wave_sum(part) - kWg * w.c[RPO_EVOPF_C_CONST];
-    const float max_eq = rpo_wave_max(tid < NEQ ? fabsf(w.eq[tid]) : 0.0f);
-    const float max_ineq = rpo_wave_max(tid < NINEQ ? fmaxf(w.ineq[tid], 0.0f) : 0.0f);
-
-    // transition row: state | action | next_state | reward | done | eq_viol | ineq_viol (ReplayBuffer.add, buffer.py:22-29)
-    for (int k = tid; k < NS; k += RPO_WAVE) row[k] = w.s[k];
-    if (tid < NY) row[NS + tid] = w.a[tid];
-    float* nxt = row + NS + NY;
-    episode_obs(w, nxt, p.seed, env_id, ep, len);
-    if (tid < NE) {                                                    // Battery.step :86-97
-        const float soc = w.s[2 * NB + tid];
-        float p_max, p_min;
-        battery_bounds(soc, p_max, p_min);
-        float x = fminf(fmaxf(w.a[PE0 + tid], p_min), p_max);
-        x = x >= 0.0f ? x * kEtaIn : x / kEtaOut;                       // process_action :145-149
-        nxt[2 * NB + tid] = soc + x;
-    }
-    if (tid == 0) { row[2 * NS + NY] = reward; row[2 * NS + NY + 1] = done ? 1.0f : 0.0f; }
-    if (tid < NEQ) row[2 * NS + NY + 2 + tid] = w.eq[tid];
-    if (tid < NINEQ) row[2 * NS + NY + 2 + NEQ + tid] = fmaxf(w.ineq[tid], 0.0f);
-    if (tid < RPO_EVOPF_ROW - (2 * NS + NY + 2 + NEQ + NINEQ)) row[2 * NS + NY + 2 + NEQ + NINEQ + tid] = 0.0f;
-    sync();
-    {   // failure detection (RPO_CTRL_NONFINITE): the reference has no assertion in EVOPFEnv.step (evopf.py:348-366) and would go
-        // on with NaNs; here a non-finite entry anywhere in the transition row (action, next state, reward, violations) stops the run
-        bool bad = false;
-        for (int k = tid; k < 2 * NS + NY + 2 + NEQ + NINEQ; k += RPO_WAVE) bad |= !__builtin_isfinite(row[k]);
-        if (__ballot(bad) != 0ull) rpo_flag_nonfinite(p.ctrl, tid == 0);
-    }
-    if (p.rows) {
-        const long long ring = (t % p.cap_steps) * (long long)p.n + i;
-        float4* dst = reinterpret_cast<float4*>(p.rows + (size_t)ring * RPO_EVOPF_ROW);
-        if (tid < RPO_EVOPF_ROW / 4) dst[tid] = reinterpret_cast<const float4*>(row)[tid];
-    }
-    // the lane continues from the next observation, or from a fresh episode (env.reset() after a done, rpo_ddpg.py:142)
-    const float ret = p.ep_ret[i] + reward;
-    if (done && p.auto_reset) {
-        episode_obs(w, w.s, p.seed, env_id, ep + 1u, 0);
-        if (tid < NE) w.s[2 * NB + tid] = kBInit;
-        sync();
-        for (int k = tid; k < NS; k += RPO_WAVE) p.state[(size_t)i * NS + k] = w.s[k];
-        if (tid == 0) { p.ep_count[i] = ep + 1u; p.ep_len[i] = 0; p.ep_ret[i] = 0.0f; }
-    } else {
-        for (int k = tid; k < NS; k += RPO_WAVE) p.state[(size_t)i * NS + k] = nxt[k];
-        if (tid == 0) { p.ep_len[i] = len; p.ep_ret[i] = ret; }
-    }
-    if (p.stats) {                                             // (uniform values: one request per lane, rpo_stats_commit)
-        const float dn = done ? 1.0f : 0.0f;
-        const float vals[10] = {reward, max_ineq, max_eq, fmaxf(max_ineq, max_eq) > p.viol_thresh ? 1.0f : 0.0f, max_ineq, max_eq,
-                                dn, dn * ret, dn * (float)len, (done && data_done) ? 1.0f : 0.0f};
-        const int slot[10] = {RPO_STAT_REWARD_SUM, RPO_STAT_MAX_INEQ_SUM, RPO_STAT_MAX_EQ_SUM, RPO_STAT_VIOL_COUNT,
-                              RPO_STAT_MAX_INEQ_MAX, RPO_STAT_MAX_EQ_MAX, RPO_STAT_EPISODES, RPO_STAT_RETURN_SUM,
-                              RPO_STAT_LENGTH_SUM, RPO_STAT_TERMINATED};
-        rpo_stats_commit(vals, 3u << 4, slot, rpo_stats_row(p.stats, p.stats_cap, t));
-    }
-}
-
+// (StepArgs and evopf_step_lane: evopf_dev.h -- the fused evaluation steps its lanes with them too)
 __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_step_kernel(StepArgs p) {
     __shared__ Ws wss[kActWaves];
     __shared__ __align__(16) float rows_s[kActWaves][RPO_EVOPF_ROW];
@@ -202,10 +98,7 @@ __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_act_project_kernel
         float lo, hi;
         partial_box(w, tid, lo, hi);
         z = (p.noise_mode == RPO_NOISE_UNIFORM) ? 0.0f : p.ap_raw[(size_t)i * NP + tid];
-        if (p.ap_is_raw && p.noise_mode != RPO_NOISE_UNIFORM) {         // BoxConstraint.__call__ (model/utils.py:40-51,75-88)
-            const float scale = (hi - lo) * 0.5f;
-            z = scale * tanhf(z) + (lo + scale);
-        }
+        if (p.ap_is_raw && p.noise_mode != RPO_NOISE_UNIFORM) z = tanh_box_raw(z, lo, hi);
         if (p.noise_mode == RPO_NOISE_EXPLICIT) {
             z = rpo_clamp(z + eps_t * p.noise[(size_t)i * NP + tid], lo, hi);
         } else if (p.noise_mode == RPO_NOISE_PHILOX) {

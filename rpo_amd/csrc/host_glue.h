@@ -36,6 +36,19 @@ inline int check_critic(const Mlp& q, int obs_dim, int E, bool tiled, bool hd) {
     return 0;
 }
 
+// The step range of every *_evaluate* entry point (evaluate.hip, evopf_eval.hip)
+inline int check_eval_range(int n, int t0, int steps, int max_episode_steps, int max_steps) {
+    if (n <= 0 || t0 < 0 || steps <= 0 || max_episode_steps <= 0 || max_steps < 0) return RPO_ERR_ARG;
+    if ((long long)t0 + steps > (1ll << 24)) return RPO_ERR_ARG;   // lengths and step indices stay exact in the f32 row
+    return 0;
+}
+
+// The per-constraint report of the evaluation entry points that take one: 16-byte aligned for the float4 accesses.
+inline int check_eval_con(const float* con) {
+    if (!con) return RPO_ERR_NULL;
+    return reinterpret_cast<uintptr_t>(con) % 16 ? RPO_ERR_ARG : 0;
+}
+
 // A stage's kernel: its CartSafe and its SpringPendulum instantiation
 template <class C, class P> struct EnvKernels { C* cart; P* pend; };
 template <class C, class P> constexpr EnvKernels<C, P> env_kernels(C* cart, P* pend) { return EnvKernels<C, P>{cart, pend}; }

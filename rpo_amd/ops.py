@@ -233,6 +233,7 @@ def polyak(param, target, tau):
 
 EVAL_LEN = CONST["RPO_EVAL_LEN"]
 EVAL_LANE_STEPS = CONST["RPO_EVAL_LANE_STEPS"]
+EVOPF_EVAL_LANE_STEPS = CONST["RPO_EVOPF_EVAL_LANE_STEPS"]
 
 
 def _eval_acc(acc, n):
@@ -775,6 +776,21 @@ class EvopfKernels(_EnvKernels):
                                                _p(grad_nu, allow_none=True), self._c(action), int(bool(overwrite)), _stream()),
               "rpo_evopf_lagrangian")
     fused_adds = True      # complete_bwd(grad_action2=...) and lagrangian(overwrite=...) exist: no torch launches between them
+
+
+def evopf_evaluate(kernels, actor_desc, gauss, internal, action, ep_len, ep_ret, ep_count, ctrl, acc, t0, steps, max_steps, corr_lr,
+                   corr_eps, corr_momentum, max_episode_steps, viol_thresh, seed, env_id_base, con=None):
+    """Env steps [t0, t0 + steps) of a policy evaluation on EVOPF-v0 in one launch (rpo_evopf_evaluate); ``kernels``: the
+    trainer's EvopfKernels (constant table, Newton parameters); acc [n, EVAL_LEN]; con [n, con_width]: the per-constraint
+    report.  A function of the backend beside eval_accumulate, not a method: the env kernel classes keep their public methods."""
+    n = internal.shape[0]
+    net = actor_desc.net_struct()
+    check(_lib.load().rpo_evopf_evaluate(
+        ctypes.byref(net), int(gauss), n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret),
+        _p(ep_count, torch.int32), _p(ctrl, torch.int64, allow_none=True), _eval_acc(acc, n), int(t0), int(steps),
+        int(max_steps), corr_lr, corr_eps, corr_momentum, kernels.newton_tol, kernels.newton_max_iters, kernels._c(internal),
+        max_episode_steps, viol_thresh, seed, env_id_base,
+        None if con is None else _con(con, n, con_width(kernels.ineq_num, kernels.eq_num)), _stream()), "rpo_evopf_evaluate")
 
 
 class PendulumKernels(_FusedEnvKernels):

@@ -45,6 +45,11 @@ EVOPF-v0: a thousandth of them) against the 8 evaluate(obs_noise=) calls it is d
 0.05), in ONE build, by the same method.  Fused cart-RPODDPG and pendulum-RPOSAC at --sizes episodes, stepwise EVOPF-RPODDPG at
 10 (where evaluate_noise() runs those 8 calls itself: the ratio there measures only its bookkeeping).  Reported per size: the
 three legs, the ratios sweep / eight calls and sweep / one call, and the padded lanes of the launch.
+--evopf-fused: evaluate() on EVOPF-v0 under schedule fused_eval_evopf=1 (rpo_evopf_evaluate) against the stepwise path of the
+same build, whose kernels are the ones from before that switch existed: EVOPF-RPODDPG and EVOPF-RPOSAC after 32 training steps,
+at 10, 1024 and 16384 episodes (--sizes), the two legs alternating, medians and min-max spreads of the whole call's wall time,
+the time per env step of a lane (the call over its horizon) and whether fused is faster by more than both legs' spreads; the
+two legs must return the same bits.  --out profiles/eval_evopf_fused_bench.json.
 Every call ends with a host read of the results (evaluate()'s .cpu(), eval()'s), so wall times include the device work.
 Run each GPU step under its own time limit (timeout -k 10 ...).
 """
@@ -283,6 +288,40 @@ def noise_sweep_bench(a, sizes):
     return line
 
 
+def evopf_fused_bench(a, sizes):
+    line = dict(tool="bench_eval --evopf-fused", device=torch.cuda.get_device_name(0), reps=a.reps,
+                lane_steps_per_launch=ops.EVOPF_EVAL_LANE_STEPS, configs={})
+
+    def leg(tr, on, n):
+        tr.schedule["fused_eval_evopf"] = on
+        try:
+            return tr.evaluate(n, seed=5)
+        finally:
+            tr.schedule["fused_eval_evopf"] = 0
+    for workload in ("evopf_ddpg", "evopf_sac"):
+        tr = trainer(workload)
+        row = {}
+        for n in sizes:
+            legs = {"fused": lambda: leg(tr, 1, n), "stepwise": lambda: leg(tr, 0, n)}
+            res = alternating(legs, a.reps)
+            f, s = legs["fused"](), legs["stepwise"]()
+            assert f.path == "fused" and s.path == "stepwise"
+            assert all(getattr(f, k).tobytes() == getattr(s, k).tobytes() for k in f.FIELDS), (workload, n)   # the same bits
+            steps = int(f.length.sum())
+            for k in res:
+                res[k]["s_per_env_step_of_a_lane"] = res[k]["median_s"] / f.horizon      # the call over its 24 serial steps
+            spread = max(res["fused"]["max_s"] - res["fused"]["min_s"], res["stepwise"]["max_s"] - res["stepwise"]["min_s"])
+            res.update(ratio_fused_to_stepwise=res["fused"]["median_s"] / res["stepwise"]["median_s"],
+                       faster_beyond_spreads=bool(res["stepwise"]["median_s"] - res["fused"]["median_s"] > spread),
+                       horizon=f.horizon, env_steps=steps, launches=-(-f.horizon // max(1, min(f.horizon, ops.EVOPF_EVAL_LANE_STEPS // n))))
+            row[str(n)] = res
+            del f, s
+        line["configs"][workload] = row
+        del tr
+        torch.cuda.empty_cache()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -294,9 +333,17 @@ def main():
     ap.add_argument("--budgets", action="store_true")
     ap.add_argument("--policies", action="store_true")
     ap.add_argument("--noise-sweep", action="store_true")
+    ap.add_argument("--evopf-fused", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sizes = [int(x) for x in a.sizes.split(",") if x]
+    if a.evopf_fused:
+        s = json.dumps(evopf_fused_bench(a, [10, 1024, 16384] if a.sizes == ap.get_default("sizes") else sizes))
+        print(s)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(s + "\n")
+        return
     if a.record or a.constraints or a.obs_noise or a.budgets or a.policies or a.noise_sweep:
         small = [10, 1024, 65536] if a.sizes == ap.get_default("sizes") else sizes
         bench = noise_sweep_bench if a.noise_sweep else policies_bench if a.policies else budgets_bench if a.budgets else noise_bench if a.obs_noise else (constraints_bench if a.constraints else record_bench)
