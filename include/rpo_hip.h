@@ -845,6 +845,22 @@ int rpo_evopf_act_project(int n, const float* state, int state_stride, const flo
                           const float* consts_dev, unsigned long long seed, unsigned env_id_base, const long long* ctrl,
                           float* stats, int stats_cap, void* stream);
 
+/* The projection profile of RPOTrainerBase.act(profile=True) on EVOPF-v0 (schedule profile_evopf=1): rpo_evopf_act_project under
+ * RPO_NOISE_NONE (its arguments without the noise, the generator, ctrl and stats; ap_raw [n,14] is required) that also writes
+ * every budget 0..K of the projection, K = max_steps >= 0, in ONE launch.  profile [K + 1, n, 4], 16-byte aligned: plane b, row
+ * i = (a[0], a[1], eq*, ineq*) of the row's iterate after min(b, iters[i]) GRG iterations, one non-temporal 16-byte store per row
+ * and plane, with the residuals of rpo_evopf_resid (its bits): ineq* = the largest of the 58 inequality residuals (a NaN among
+ * them is returned, as torch.max does); eq* = the equality residual of largest magnitude with its sign, the lowest index among
+ * equal magnitudes, the first NaN if there is one.  Every plane of every row is written (a row whose stop test has fired
+ * repeats its final entry): the buffer needs no zeroing.  action [n,43] and iters [n] (may be NULL) are those of the budget K.
+ * == for b = 0..K: rpo_evopf_act_project(RPO_NOISE_NONE, max_steps = b) + rpo_evopf_resid, bit for bit.
+ * Refused before any HIP call: n <= 0, max_steps < 0, newton_max_iters <= 0, state_stride < RPO_EVOPF_STATE (RPO_ERR_ARG); a NULL
+ * state, ap_raw, action, consts_dev or profile (RPO_ERR_NULL); a profile that is not 16-byte aligned, or of more than
+ * RPO_TRACE_MAX_BYTES = 16 (K + 1) n bytes (RPO_ERR_ARG). */
+int rpo_evopf_project_profile(int n, const float* state, int state_stride, const float* ap_raw, int ap_is_raw,
+                              float* action, int* iters, int max_steps, float corr_lr, float corr_eps, float corr_momentum,
+                              float newton_tol, int newton_max_iters, const float* consts_dev, float* profile, void* stream);
+
 /* Backward of the actor's output map for EVOPF: ap = clip(scale(s) * tanh(raw) + base(s) + eps_t * noise, lo(s), hi(s))
  * (model/policy.py:24-33 with the state-dependent box, then ddpg_pa.py:108-110); dout [n,14] = dap * d ap / d raw.
  * noise NULL: no noise and no clip. */

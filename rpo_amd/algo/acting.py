@@ -16,8 +16,10 @@ chosen like ``evaluate()``'s:
 every budget b = 0..K (K = the call's ``eval_steps``) what ``act(obs, eval_steps=b)`` would return, written down by ONE run at
 the budget K -- the loop is deterministic and every row has its own stop test, so a run at K passes through every smaller
 budget's result.  Three paths: **fused** (``rpo_<env>_policy_act_profile``, the row tile), **stepwise** (the proposal launches +
-``rpo_<env>_project_profile`` + the residual kernel) and **sweep** (EVOPF-v0, the oracle backend: K + 1 stepwise ``act()`` calls
-assembled with torch ops; correct by construction and slow).
+``rpo_<env>_project_profile`` + the residual kernel; on EVOPF-v0 opt-in by schedule ``profile_evopf=1``, default 0:
+``rpo_evopf_project_profile``, whose planes hold the first two action components and the equality residual of largest magnitude
+with its sign) and **sweep** (EVOPF-v0 by default, the oracle backend: K + 1 stepwise ``act()`` calls assembled with torch ops;
+correct by construction and slow).
 
 All paths compute the same bits (``tests/test_act_gpu.py``, ``tests/test_act_profile_gpu.py``).  Rows are ALWAYS projected
 independently with a per-row stop test -- the B = 1 semantics of the rollout and of ``eval()``; SpringPendulum's batch-coupled reference projection is never
@@ -25,6 +27,8 @@ used here, whatever ``batch_reference`` is: ``act(obs)[i]`` is ``act(obs[i:i+1])
 and writes its result buffers, nothing else: no env lane, control word, replay row, Philox counter or graph is touched, nothing
 is drawn from a generator, and nothing waits for the device.  Data-parallel runs: the calling rank acts alone, no collective.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -88,7 +92,9 @@ class ProjectionProfile(object):
     """The projection at every budget 0..K of one ``act(obs, profile=True)`` call.
 
     ``data``: float32 [K + 1, n, 4] on the trainer's device; plane b, row i = (a0, a1, eq_resid, max_j ineq_resid_j) of what
-    ``act(obs, eval_steps=b)`` returns for that row (signed residuals; EVOPF-v0: the first two action components).  ``iters``:
+    ``act(obs, eval_steps=b)`` returns for that row (signed residuals; EVOPF-v0, swept or -- schedule ``profile_evopf=1`` -- from
+    the one launch of ``rpo_evopf_project_profile``: the first two action components, and ``eq_resid`` is the row's equality
+    residual of largest magnitude with its sign, the lowest index among equal magnitudes).  ``iters``:
     int32 [n], the GRG iterations at the budget K.  Plane 0 is Complete alone and plane 1 is always one step further (the
     loop's first iteration is unconditional), even for a row that was already feasible.  The helpers are plain torch ops on
     ``data``; none of them is on ``act()``'s path."""
@@ -166,6 +172,21 @@ def fused_ok(tr):
                 and _projects(tr) and tr._box_affine is not None and f.descs["actor"].E == 128 and tr.device.type == "cuda")
 
 
+def profile_kernel(tr):
+    """The stand-alone profile launch (``rpo_<env>_project_profile``) of a device trainer as a callable with the signature of
+    ``project_profile``, or None where the call sweeps: the kernels' own method (CartSafe-v0, SpringPendulum-v0); on EVOPF-v0 the
+    backend's ``evopf_project_profile``, and only under the schedule key ``profile_evopf`` (default 0)."""
+    k = tr.kernels
+    if tr.device.type != "cuda":
+        return None
+    if hasattr(k, "project_profile"):
+        return k.project_profile
+    if (tr.schedule.get("profile_evopf", 0) and getattr(k, "name", None) == "EVOPF-v0"
+            and hasattr(tr.backend, "evopf_project_profile")):
+        return functools.partial(tr.backend.evopf_project_profile, k)
+    return None
+
+
 def _check(tr, obs, eval_steps, eval_lr, residuals, out, form, profile=False):
     k = tr.kernels
     obs = torch.as_tensor(obs, dtype=torch.float32, device=tr.device)
@@ -223,17 +244,19 @@ def _act_profile(tr, obs, steps, lr, residuals, out):
     n, k = obs.shape[0], tr.kernels
     r = out if out is not None else ActResult.empty(tr, n, residuals)
     data = out.profile.data if out is not None else torch.empty(steps + 1, n, 4, device=tr.device)
+    project_profile = profile_kernel(tr)
     with torch.no_grad():
         if fused_ok(tr) and hasattr(k, "policy_act_profile"):
             scale, base = tr._box_affine
             k.policy_act_profile(tr.fused.descs["actor"], tr._gauss_policy, scale, base, obs, r.action, r.proposal, r.iters,
                                  r.eq_resid, r.ineq_resid, tr._box_lo, tr._box_hi, steps, lr, tr.corr_eps, tr.corr_momentum, data)
             r.path, r.form = "fused", "tile"
-        elif hasattr(k, "project_profile") and tr.device.type == "cuda":
+        elif project_profile is not None:
             obs = obs.contiguous()
             ap = tr._eval_partial(obs)
             r.proposal.copy_(ap.reshape(r.proposal.shape))
-            k.project_profile(obs, ap, r.action, r.iters, steps, lr, tr.corr_eps, tr.corr_momentum, data)
+            # (_act_kw: RPODDPG's ap_is_raw on EVOPF-v0 with the fused MLPs; empty wherever project_profile takes no such keyword)
+            project_profile(obs, ap, r.action, r.iters, steps, lr, tr.corr_eps, tr.corr_momentum, data, **tr._act_kw)
             if residuals:
                 k.resid(obs, r.action, r.eq_resid, r.ineq_resid)
             r.path, r.form = "stepwise", None

@@ -272,11 +272,13 @@ def _env_int(name, default):
 #:                  1024 episodes and 1.5 x slower at 16384, so it is off
 #:   fused_act      act(): actor -> head -> Complete -> GRG -> residuals as ONE launch (0: the stepwise path, the trainer's
 #:                  deterministic proposal + rpo_*_act_project + rpo_*_resid)
+#:   profile_evopf  (default 0) act(profile=True) on EVOPF-v0: every budget 0..K from ONE launch of rpo_evopf_project_profile behind
+#:                  the proposal launches (0: the sweep, K + 1 stepwise act() calls).  The same bits; opt-in like fused_eval_evopf
 #:   eval_overlap   curve mode (`eval_episodes=N`), fused path: an evaluation point runs on its own stream, on a snapshot of the
 #:                  actor, beside the update that follows it (0: in order on the training stream)
 #:   force_dist     (default 0) data-parallel code path over a one-rank process group
 SCHEDULE_DEFAULTS = dict(fused_mlp=1, fused_rollout=1, fused_critic=1, fused_actor=1, split=1, ride=1, front=1, branch=1,
-                         fused_eval=1, fused_eval_evopf=0, fused_act=1, eval_overlap=1, force_dist=0)
+                         fused_eval=1, fused_eval_evopf=0, fused_act=1, profile_evopf=0, eval_overlap=1, force_dist=0)
 
 
 def parse_schedule(overrides=None):
@@ -1723,7 +1725,7 @@ class RPOTrainerBase(object):
         ``profile=True``: the result also carries ``profile``, a ``ProjectionProfile`` whose ``data`` [K + 1, n, 4] (K = the
         call's ``eval_steps``) holds for every budget b = 0..K the row's (a0, a1, eq_resid, max ineq_resid) -- what
         ``act(obs, eval_steps=b)`` returns -- written by one launch; ``path`` is "fused", "stepwise" or "sweep" (EVOPF-v0:
-        K + 1 stepwise calls).  ``out=`` then needs a result whose profile has the same shape.  ValueError: a trainer without
+        K + 1 stepwise calls, unless schedule ``profile_evopf=1`` selects its one-launch stepwise form).  ``out=`` then needs a result whose profile has the same shape.  ValueError: a trainer without
         a projection, ``form != 0``, a profile above RPO_TRACE_MAX_BYTES.  See rpo_amd/algo/acting.py."""
         from .acting import act
         return act(self, obs, eval_steps=eval_steps, eval_lr=eval_lr, residuals=residuals, out=out, form=form, profile=profile)

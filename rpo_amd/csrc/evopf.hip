@@ -124,6 +124,52 @@ __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_act_project_kernel
     }
 }
 
+// ------------------------------------------------------------------------------------- complete + project + profile
+struct ProfileArgs {
+    int n;
+    const float* state;
+    int state_stride;
+    const float* ap_raw;
+    int ap_is_raw;
+    float* action;
+    int* iters;
+    int max_steps;
+    float corr_lr, corr_eps, corr_momentum;
+    float newton_tol;
+    int newton_iters;
+    const float* consts;
+    float* profile;               // [max_steps + 1, n, 4], 16-byte aligned
+};
+
+// evopf_act_project_kernel under RPO_NOISE_NONE (no clamp, no generator, no clock, no statistics, no placement, no raised
+// priority) that also writes the row's projection profile: plane b, row i of profile = (a[0], a[1], eq*, ineq*) of the iterate
+// after min(b, iters[i]) GRG iterations (evopf_dev.h: profile_entry, grad_steps_profile_v2).  The same geometry: one lane per
+// wave, a workspace each, and the waves never meet at a workgroup barrier.  The residual pass between two iterations may
+// clobber w.cs, w.sn, w.vr, w.vi, w.t1, w.t2, w.eq and w.ineq: the v2 solver and GRG iteration read none of them (they keep
+// w.a, w.old, w.c, w.s and the RowLane; w.vec and w.fp are rewritten before use, with static pivots and in the fallback).
+__global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_project_profile_kernel(ProfileArgs p) {
+    __shared__ Ws wss[kActWaves];
+    Ws& w = wss[threadIdx.x / RPO_WAVE];
+    const int i = blockIdx.x * kActWaves + threadIdx.x / RPO_WAVE, tid = lane_id();
+    if (i >= p.n) return;                                        // (waves never meet at a workgroup barrier)
+    load_consts(w, p.consts);
+    load_row(w.s, p.state + (size_t)i * p.state_stride, NS);
+    sync();
+    float z = 0.0f;
+    if (tid < NP) {
+        float lo, hi;
+        partial_box(w, tid, lo, hi);
+        z = p.ap_raw[(size_t)i * NP + tid];
+        if (p.ap_is_raw) z = tanh_box_raw(z, lo, hi);
+    }
+    const RowLane L = make_row_lane(w);
+    complete_partial_v2(w, L, z, p.newton_tol, p.newton_iters);
+    const int k = grad_steps_profile_v2(w, L, p.max_steps, p.corr_lr, p.corr_eps, p.corr_momentum, p.profile + (size_t)i * 4,
+                                        (size_t)p.n * 4);
+    if (tid < NY) p.action[(size_t)i * NY + tid] = w.a[tid];
+    if (tid == 0 && p.iters) p.iters[i] = k;
+}
+
 // PFFunction.backward (evopf.py:857-910) with the Jacobians re-evaluated at the completed action (the reference keeps
 // those of the last Newton point, one update of size < tol earlier).  grad_ap [n,14] = dL/dz.
 __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_complete_bwd_kernel(int n, const float* __restrict__ action,
@@ -462,6 +508,18 @@ int rpo_evopf_act_project(int n, const float* state, int state_stride, const flo
         blocks = (blocks + per - 1) / per * 8;
     }
     return launch(evopf_act_project_kernel, dim3(blocks), kActThreads, 0, stream, p);
+}
+
+int rpo_evopf_project_profile(int n, const float* state, int state_stride, const float* ap_raw, int ap_is_raw, float* action, int* iters,
+                              int max_steps, float corr_lr, float corr_eps, float corr_momentum, float newton_tol, int newton_max_iters,
+                              const float* consts_dev, float* profile, void* stream) {
+    if (n <= 0 || max_steps < 0 || newton_max_iters <= 0 || state_stride < RPO_EVOPF_STATE) return RPO_ERR_ARG;
+    if (!state || !ap_raw || !action || !consts_dev || !profile) return RPO_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(profile) % 16) return RPO_ERR_ARG;                       // (written with 16-byte stores)
+    if (16ll * ((long long)max_steps + 1) * (long long)n > (long long)RPO_TRACE_MAX_BYTES) return RPO_ERR_ARG;
+    ProfileArgs p{n, state, state_stride, ap_raw, ap_is_raw, action, iters, max_steps, corr_lr, corr_eps, corr_momentum, newton_tol,
+                  newton_max_iters, consts_dev, profile};
+    return launch(evopf_project_profile_kernel, lane_grid(n), kActThreads, 0, stream, p);
 }
 
 int rpo_evopf_tanh_box_bwd(int n, const float* state, int state_stride, const float* raw, const float* noise,

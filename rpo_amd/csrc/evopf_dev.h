@@ -787,6 +787,84 @@ __device__ __forceinline__ int grad_steps_v2(Ws& w, const RowLane& L, int max_st
     return k;
 }
 
+// ------------------------------------------------------------------------------------------------ projection profiles
+// trainer.act(profile=True) on EVOPF-v0 (evopf_project_profile_kernel): the plane entry of the iterate in w.a is
+// (a[0], a[1], eq*, ineq*), with the residuals of evopf_resid_kernel -- the same three calls, so rpo_evopf_resid's bits:
+//   ineq* = the maximum of the 58 inequality residuals; a NaN among them is returned (the first one), as torch.max does;
+//   eq*   = the equality residual of largest magnitude WITH ITS SIGN; among entries of equal magnitude the lowest index
+//           wins; if any entry is a NaN, the first NaN wins (acting.py: _signed_absmax).
+// The pass writes w.cs, w.sn, w.vr, w.vi, w.t1, w.t2, w.eq and w.ineq and nothing else.  grg_iteration_v2 recomputes its
+// voltages and admittance products from w.a into registers on every call (own_volt, row_residual) and keeps only w.a, w.old,
+// w.c, w.s and the RowLane across iterations (w.vec and w.fp are written before they are read, in the static order and in the
+// partial-pivoting fallback alike), so a pass between two iterations changes nothing the loop reads.
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+// max over the wave of unsigned keys (lanes that take no part pass 0), the same in every lane: DPP inside the 16-lane rows
+// (row_shl fills with zeros), v_readlane across them -- rpo_wave_max_nonneg's steps on integers
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+    unsigned o;
+    o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x108, 0xf, 0xf, true); v = v > o ? v : o;   // row_shl:8
+    o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xf, 0xf, true); v = v > o ? v : o;   // row_shl:4
+    o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true); v = v > o ? v : o;    // quad_perm:[2,3,0,1]
+    o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true); v = v > o ? v : o;    // quad_perm:[1,0,3,2]
+    const unsigned m0 = (unsigned)__builtin_amdgcn_readlane((int)v, 0), m1 = (unsigned)__builtin_amdgcn_readlane((int)v, 16);
+    const unsigned m2 = (unsigned)__builtin_amdgcn_readlane((int)v, 32), m3 = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
+    const unsigned a = m0 > m1 ? m0 : m1, b = m2 > m3 ? m2 : m3;
+    return a > b ? a : b;
+}
+
+__device__ __forceinline__ f32x4_t profile_entry(Ws& w) {
+    const int tid = lane_id();
+    flows(w);
+    eq_resid(w);
+    ineq_resid(w);
+    const float e = tid < NEQ ? w.eq[tid] : 0.0f, g = tid < NINEQ ? w.ineq[tid] : 0.0f;
+    const float a0 = w.a[0], a1 = w.a[1];
+    // eq*: the lowest lane that holds the largest magnitude (exact: magnitudes are compared, not rounded), or the first NaN
+    const unsigned long long e_nan = __builtin_amdgcn_ballot_w64(e != e);
+    const float mag = (e != e) ? 0.0f : fabsf(e);
+    const float top = rpo_wave_max_nonneg(mag);                  // (lanes >= NEQ hold 0)
+    const unsigned long long e_at = e_nan ? e_nan : __builtin_amdgcn_ballot_w64(tid < NEQ && mag == top);
+    const float eq_star = lane_bcast(e, __builtin_ctzll(e_at));  // (never empty: the lane that holds `top` is in it)
+    // ineq*: the maximum through the order-preserving map of IEEE bit patterns onto unsigned integers (every real key is > 0, the
+    // key of the lanes that take no part); a NaN is returned as it is
+    const unsigned long long g_nan = __builtin_amdgcn_ballot_w64(g != g);
+    const unsigned bits = __float_as_uint(g);
+    const unsigned key = (tid < NINEQ && g == g) ? ((bits & 0x80000000u) ? ~bits : (bits | 0x80000000u)) : 0u;
+    const unsigned kmax = wave_umax(key);
+    float ineq_star = __uint_as_float((kmax & 0x80000000u) ? (kmax & 0x7fffffffu) : ~kmax);
+    if (g_nan) ineq_star = lane_bcast(g, __builtin_ctzll(g_nan));
+    return f32x4_t{a0, a1, eq_star, ineq_star};
+}
+
+// grad_steps_v2 with the profile: the same calls in the same order -- w.old zeroed, then grg_iteration_v2 while the row is
+// live -- and the entry of the iterate written after Complete (plane 0) and after each of the max_steps iterations (plane
+// k + 1), ONE non-temporal 16-byte store by lane 0 each, `plane_stride` floats apart.  A row whose stop test has fired steps no
+// more and stores its final entry again for every remaining plane (kept in registers: no further residual pass), so every
+// plane of the row is written.  Returns the iteration count, as grad_steps_v2 does.
+__device__ __forceinline__ int grad_steps_profile_v2(Ws& w, const RowLane& L, int max_steps, float lr, float corr_eps, float momentum,
+                                                     float* __restrict__ plane, size_t plane_stride) {
+    const int tid = lane_id();
+    if (tid < NY) w.old[tid] = 0.0f;
+    sync();
+    f32x4_t entry = profile_entry(w);
+    if (tid == 0) __builtin_nontemporal_store(entry, reinterpret_cast<f32x4_t*>(plane));
+    int k = 0;
+    bool live = true;
+    for (int b = 0; b < max_steps; ++b) {
+        if (live) {
+            live = grg_iteration_v2(w, L, b == 0, corr_eps, lr, momentum, true, nullptr);
+            if (live) {
+                ++k;
+                entry = profile_entry(w);
+            }
+        }
+        plane += plane_stride;
+        if (tid == 0) __builtin_nontemporal_store(entry, reinterpret_cast<f32x4_t*>(plane));
+    }
+    return k;
+}
+
 // Episode data of the loaders (data/demand.py:35-65, data/price.py:29-55) re-keyed on Philox(seed, env, episode):
 // hour-t observation (pd[14], qd[14]) into out[0..28) and the price window [t, t+24) into out[33..57) -- all zero when
 // t >= 24 (the loaders' `done`, demand.py:71 / price.py:51).

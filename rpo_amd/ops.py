@@ -793,6 +793,20 @@ def evopf_evaluate(kernels, actor_desc, gauss, internal, action, ep_len, ep_ret,
         None if con is None else _con(con, n, con_width(kernels.ineq_num, kernels.eq_num)), _stream()), "rpo_evopf_evaluate")
 
 
+def evopf_project_profile(kernels, obs, ap_raw, action, iters, max_steps, corr_lr, corr_eps, corr_momentum, profile, ap_is_raw=False):
+    """``kernels.act_project(NOISE_NONE)`` on EVOPF-v0 that also writes profile [max_steps + 1, n, 4]: plane b = (a[0], a[1], the
+    equality residual of largest magnitude with its sign, max ineq_resid) of the budget b (rpo_evopf_project_profile).  The
+    signature of ``_FusedEnvKernels.project_profile`` behind ``kernels`` (the trainer's EvopfKernels: constant table, Newton
+    parameters), plus ``act_project``'s ``ap_is_raw``.  A function of the backend like ``evopf_evaluate``, not a method: the env
+    kernel classes keep their public methods."""
+    n = action.shape[0]
+    sp, ss = _row_view(obs, kernels.obs_dim)
+    check(_lib.load().rpo_evopf_project_profile(
+        n, sp, ss, _p(ap_raw), int(ap_is_raw), _p(action), _p(iters, torch.int32, allow_none=True), int(max_steps), corr_lr,
+        corr_eps, corr_momentum, kernels.newton_tol, kernels.newton_max_iters, kernels._c(action),
+        _act_profile(profile, n, max_steps), _stream()), "rpo_evopf_project_profile")
+
+
 class PendulumKernels(_FusedEnvKernels):
     """HIP kernels of SpringPendulum-v0."""
 
