@@ -927,6 +927,22 @@ int rpo_evopf_evaluate(const rpo_mlp* actor_host, int gauss, int n_envs, float* 
                        int max_episode_steps, float viol_thresh, unsigned long long seed, unsigned env_id_base, float* con,
                        void* stream);
 
+/* Single-step AC optimal power flow on EVOPF-v0 (EVOPFEnv.opf / opt_solve, EvalTrajectory.opf_gap; csrc/evopf_opf.hip): for
+ * each of n states the cheapest (pg, qg, vm, va) that meets eq_resid = 0 and the bounds on pg, qg, vm, for the demand in the
+ * first 28 floats of the row of obs (obs_stride >= 28 floats between rows: [n,57] observations, [n,28] demands or a column
+ * slice of something wider) and the battery power pe [n,5] (NULL: zeros), which is data of the problem and not a variable.  What
+ * the reference asks of pypower (evopf.py:729-759), as a MIPS-style primal-dual interior point method from the flat start, one
+ * wavefront per state, float32; the reduced KKT system of order 55 is eliminated in registers, one row per lane.
+ * action_out [n,43]: the full action vector (va at the slack bus = slack_va, pe as given), so eq_resid / ineq_resid / obj_fn
+ * apply to it; info_out [n,4] = (cost, the largest of the three stop quantities at exit, iterations, converged 0 / 1).  The stop
+ * test: max(|g|_inf, max h), |L_x|_inf and z^T mu all below tol; a row that does not meet it leaves after max_iters iterations
+ * with converged = 0 (max_iters = 0: the flat start).  A row's output does not depend on the other rows of the launch.  Reads obs,
+ * pe and consts_dev, writes the two outputs, nothing else.
+ * Refused before any HIP call, sizes before pointers: n <= 0, max_iters < 0, tol <= 0 (or NaN), obs_stride < 28 (RPO_ERR_ARG); a
+ * NULL obs, action_out, info_out or consts_dev (RPO_ERR_NULL). */
+int rpo_evopf_opf(int n, const float* obs, int obs_stride, const float* pe, float* action_out, float* info_out, float tol,
+                  int max_iters, const float* consts_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused pipelines of one RPO iteration (rpo_amd/csrc/fused.hip): the row-local stages chained
  * inside one workgroup of 16 rows, because at 4096 lanes / batch 256 every launch is dominated by dispatch + cold-start

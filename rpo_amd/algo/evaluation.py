@@ -190,8 +190,90 @@ class EvalTrajectory(object):
         with np.load(path) as z:
             return cls(float(z["viol_thresh"]), **{name: z[name] for name in cls.ARRAYS})
 
+    def opf_gap(self, env, tol=1e-4, max_iters=40):
+        """The optimality gap of every recorded step of an EVOPF-v0 evaluation (``opf_gap`` below) -> ``OpfGap``."""
+        return opf_gap(self, env, tol=tol, max_iters=max_iters)
+
     def __repr__(self):
         return "EvalTrajectory(episodes=%d, horizon=%d, steps=%d)" % (self.episodes, self.horizon, int(self.valid.sum()))
+
+
+class OpfGap(object):
+    """Optimality gaps of a recorded EVOPF-v0 evaluation (``EvalTrajectory.opf_gap``): float64 / bool numpy arrays indexed
+    [episode, step].
+
+    ``cost_policy``: ``obj_fn`` of the recorded action (NaN only where the step is not valid); ``cost_opt``: the cost of the
+    single-step AC-OPF at that step's observation with the recorded action's battery power pe -- the battery schedule is the
+    policy's on both sides, so the reward difference is the cost difference; ``gap`` = (cost_policy - cost_opt) / cost_opt;
+    ``converged``: the solver met its stop test (False on non-valid steps).  ``cost_opt`` and ``gap`` are NaN where the solver did
+    not converge (infeasible single-step problems exist) or the step is not valid.  ``violation``: the step's max(ineq, eq) of the
+    policy's action as recorded.  A NEGATIVE gap is possible and is not clipped: the optimum is taken over feasible dispatches,
+    and a policy action that violates a constraint can be cheaper than any of them -- ``feasible_only(viol_thresh)`` masks
+    those steps."""
+
+    ARRAYS = ("cost_policy", "cost_opt", "gap", "converged", "valid", "violation")
+
+    def __init__(self, tol, max_iters, **arrays):
+        for name in self.ARRAYS:
+            setattr(self, name, np.asarray(arrays[name]))
+        self.tol, self.max_iters = float(tol), int(max_iters)
+
+    def mean(self):
+        """Mean gap over the steps that have one (NaN if none has)."""
+        return float(np.nanmean(self.gap)) if np.isfinite(self.gap).any() else float("nan")
+
+    def quantile(self, q):
+        return float(np.nanquantile(self.gap, q)) if np.isfinite(self.gap).any() else float("nan")
+
+    def converged_rate(self):
+        """Share of the valid steps whose OPF converged."""
+        return float(self.converged[self.valid].mean()) if self.valid.any() else float("nan")
+
+    def feasible_only(self, viol_thresh):
+        """A copy whose ``gap`` is NaN also where the policy's own action violates a constraint by more than ``viol_thresh``."""
+        keep = self.violation <= float(viol_thresh)
+        arrays = {name: getattr(self, name).copy() for name in self.ARRAYS}
+        arrays["gap"] = np.where(keep, self.gap, np.nan)
+        return OpfGap(self.tol, self.max_iters, **arrays)
+
+    def save(self, path):
+        with open(path, "wb") as f:
+            np.savez(f, tol=np.float64(self.tol), max_iters=np.int64(self.max_iters), **{name: getattr(self, name) for name in self.ARRAYS})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(float(z["tol"]), int(z["max_iters"]), **{name: z[name] for name in cls.ARRAYS})
+
+    def __repr__(self):
+        return "OpfGap(steps=%d, converged=%.3f, mean gap=%.4g)" % (int(self.valid.sum()), self.converged_rate(), self.mean())
+
+
+def opf_gap(trajectory, env, tol=1e-4, max_iters=40):
+    """For every valid step of ``trajectory`` (``trainer.evaluate(..., record=...)`` on EVOPF-v0): ``env.opf`` at the step's
+    recorded observation with the recorded action's pe, in one launch over all steps, against ``env.obj_fn`` of the recorded
+    action -> ``OpfGap``.  ``env``: an EVOPFEnv on a GPU device (NotImplementedError otherwise, with the reason).  With
+    ``evaluate(obs_noise=)`` the recorded observation is the noisy one the policy saw."""
+    if not hasattr(env, "opf"):
+        raise TypeError("opf_gap: env must be an EVOPFEnv, got %s" % type(env).__name__)
+    obs, action, valid = np.asarray(trajectory.obs), np.asarray(trajectory.action), np.asarray(trajectory.valid, dtype=bool)
+    if obs.ndim != 3 or obs.shape[2] != env.state_dim or action.shape[2] != env.action_dim:
+        raise ValueError("opf_gap: the trajectory is not one of EVOPF-v0 (obs %s, action %s)" % (obs.shape, action.shape))
+    shape = valid.shape
+    cost_policy, cost_opt = np.full(shape, np.nan), np.full(shape, np.nan)
+    converged = np.zeros(shape, dtype=bool)
+    if valid.any():
+        o = np.ascontiguousarray(obs[valid], dtype=np.float32)
+        a = np.ascontiguousarray(action[valid], dtype=np.float32)
+        res = env.opf(o, pe=a[:, -env.ne:], tol=tol, max_iters=max_iters).numpy()
+        cost_policy[valid] = env.obj_fn(a).detach().cpu().numpy().astype(np.float64)
+        converged[valid] = res["converged"]
+        cost_opt[valid] = np.where(res["converged"], res["cost"].astype(np.float64), np.nan)
+    with np.errstate(all="ignore"):
+        gap = (cost_policy - cost_opt) / cost_opt
+    violation = np.where(valid, np.maximum(np.asarray(trajectory.ineq, dtype=np.float64), np.asarray(trajectory.eq, dtype=np.float64)), np.nan)
+    return OpfGap(tol, max_iters, cost_policy=cost_policy, cost_opt=cost_opt, gap=gap, converged=converged, valid=valid,
+                  violation=violation)
 
 
 class ConstraintReport(object):

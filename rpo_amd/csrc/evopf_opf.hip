@@ -1,0 +1,262 @@
+// Single-step AC optimal power flow of EVOPF-v0 on the device (EVOPFEnv.opf / opt_solve, EvalTrajectory.opf_gap): the cheapest
+// dispatch (pg, qg, vm, va) that meets the 28 power-balance equations and the 48 bounds on pg, qg, vm for a given demand and a
+// given battery power pe -- the problem the reference hands to pypower's interior-point solver once per state on the CPU
+// (evopf.py:729-759).  ONE WAVEFRONT PER STATE, four states per workgroup, float32 throughout (geometry and workspace of evopf.hip).
+//
+// Method: primal-dual interior point in the form of MATPOWER's MIPS (Wang, Murillo-Sanchez, Zimmerman, Thomas 2007; MATPOWER
+// manual app. A) with slacks z on the bounds, multipliers mu, lambda and the barrier parameter gamma; the update formulas stand
+// at their lines below.  The flat start (middle of every box, angles 0, z = max(-h, 1), mu = gamma / z, lambda = 0, gamma = 1),
+// sigma = 0.1, xi = 0.99995 and the stop test (max(|g|_inf, max h), |L_x|_inf and z^T mu all below tol, unscaled) are those of
+// tests/evopf_opf_f64.py, the float64 yardstick, which solves the full 65 x 65 system with LAPACK.
+//
+// The KKT system here: the ten generator variables enter g through a selection matrix and have a diagonal block D in M (2 c2 +
+// Sigma for pg, Sigma for qg), so they are eliminated by hand -- [[H_vv, J_v^T], [J_v, -S D^-1 S^T]] of order 27 + 28 = 55, ONE
+// ROW PER LANE: lanes 0..13 the vm rows, 14..26 the va rows of buses 1..13, 27..54 the equations.  A lane evaluates its own row
+// (Hessian row from the textbook second derivatives of the polar power-flow equations; the Jacobian entries are evopf_dev.h's
+// jac_entry, read by row in the equation lanes and by column in the variable lanes), keeps it in 56 registers and the wave
+// eliminates it by Gauss-Jordan with a dynamic pivot per column (the matrix is symmetric indefinite and its (2, 2) block has
+// zeros on the diagonal at the load buses), as gj_dynamic does for 28 rows: rows are not swapped, every lane remembers the
+// unknown its row ended up solving.  The lane that owns a bounded variable (vm lanes; the equation lane of a generator bus owns
+// that generator's pg or qg) keeps its two slacks and two multipliers in registers; x lives in w.a, lambda in w.dir, the
+// solution passes through w.vec.  Nothing else is shared, and nothing outside the workspace is written but the two outputs.
+//
+// eq_resid is injection minus flow: with F = lambda_p^T P + lambda_q^T Q = sum_ik V_i V_k c_ik, the Hessian of lambda^T g is -F''.
+//   th = va_i - va_k,  G_ik = Yr[k][i], B_ik = Yi[k][i] (flows() multiplies the voltage ROW vector into Ybus)
+//   a = G cos th + B sin th,  b = G sin th - B cos th           (P_i = V_i sum_k V_k a_ik,  Q_i = V_i sum_k V_k b_ik)
+//   c = lp_i a + lq_i b,      d = dc / dth = -lp_i b + lq_i a    (dd / dth = -c);   cs = c + c^T,  dd = d - d^T
+//   F_VmVn = cs_mn;   F_thm,thn = V_m V_n cs_mn - [m == n] V_m sum_k cs_mk V_k;   F_thm,Vn = [m == n] sum_k dd_mk V_k + V_m dd_mn
+// A state that does not converge leaves at max_iters: every loop has a compile-time or max_iters bound, overflowing quotients
+// only produce infinities and NaNs (a NaN in a stop quantity means "not converged").
+#include "evopf_dev.h"
+#include "launch.h"
+
+using namespace rpo_evopf_dev;
+using rpo_host::launch;
+
+namespace {
+
+constexpr int kOpfWaves = 4;                 // states per workgroup, one wave each
+constexpr int NV = 2 * NB - 1;               // voltage unknowns: vm[14], va at the 13 non-slack buses (bus 0 is the slack)
+constexpr int NK = NV + NEQ;                 // order of the reduced KKT system
+constexpr int NBOUND = 2 * (2 * NG + NB);    // 48 inequalities
+constexpr float kSigma = 0.1f, kXi = 0.99995f, kZ0 = 1.0f, kGamma0 = 1.0f;
+static_assert(NK <= RPO_WAVE, "one row of the reduced KKT system per lane");
+
+struct OpfArgs {
+    int n;
+    const float* obs;
+    int obs_stride;
+    const float* pe;          // [n, 5] or NULL (zeros)
+    float* action;            // [n, 43]
+    float* info;              // [n, 4]: cost, largest stop quantity at exit, iterations, converged
+    float tol;
+    int max_iters;
+    const float* consts;
+};
+
+// Gauss-Jordan on the NK x (NK + 1) system held one row per lane, the pivot of column k = the largest |entry| among the rows
+// that own no pivot yet (lowest lane among equals; if every candidate is a NaN, the lowest candidate lane).  Rows are neither
+// swapped nor normalised: on return the lane's row solves unknown `mycol` and row[NK] / (return value) is its value.
+__device__ __forceinline__ float gj_wave(float (&row)[NK + 1], int& mycol) {
+    const int lane = lane_id();
+    bool used = lane >= NK;
+    mycol = lane;
+    float mypiv = 1.0f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const float mag = used ? 0.0f : fabsf(row[k]);
+        const float top = rpo_wave_max_nonneg(mag);
+        unsigned long long cand = __builtin_amdgcn_ballot_w64(!used && mag == top);
+        if (cand == 0ull) cand = __builtin_amdgcn_ballot_w64(!used);     // (NK - k rows are free: never empty)
+        const int p = (int)__builtin_ctzll(cand);
+        const float piv = lane_bcast(row[k], p);
+        const bool is_p = lane == p;
+        const float f = is_p ? 0.0f : -row[k] * (1.0f / piv);
+        if (is_p) { used = true; mycol = k; mypiv = piv; }
+#pragma unroll
+        for (int c = k + 1; c < NK + 1; ++c) row[c] = fmaf(f, lane_bcast(row[c], p), row[c]);
+    }
+    return mypiv;
+}
+
+__global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs p) {
+    __shared__ Ws wss[kOpfWaves];
+    Ws& w = wss[threadIdx.x / RPO_WAVE];
+    const int i = blockIdx.x * kOpfWaves + threadIdx.x / RPO_WAVE, tid = lane_id();
+    if (i >= p.n) return;                                       // (whole waves: only wave-level hand-overs below)
+    load_consts(w, p.consts);
+    load_row(w.s, p.obs + (size_t)i * p.obs_stride, 2 * NB);    // pd, qd: all the problem reads of the observation
+    if (tid <= NY) w.a[tid] = 0.0f;
+    if (tid < NEQ) w.dir[tid] = 0.0f;                           // lambda
+    sync();
+
+    // ---- what the lane owns
+    const bool is_var = tid < NV, is_vm = tid < NB, is_eq = tid >= NV && tid < NK;
+    const int vbus = is_vm ? tid : (is_var ? tid - (NB - 1) : 0);          // bus of the lane's voltage unknown
+    const int myvar = is_vm ? VM0 + vbus : VA0 + vbus;
+    const int e = is_eq ? tid - NV : 0;                                     // the lane's equation
+    const bool e_real = e < NB;
+    const int ebus = e_real ? e : e - NB;
+    int gen = -1;
+#pragma unroll
+    for (int j = 0; j < NG; ++j) gen = kSpv[j] == ebus ? j : gen;
+    const bool has_u = is_eq && gen >= 0;                                   // the equation's generator variable: pg / qg
+    const bool is_pg = has_u && e_real;
+    const bool bounded = is_vm || has_u;
+    const int xidx = is_var ? myvar : (has_u ? (e_real ? PG0 + gen : QG0 + gen) : NY);   // w.a component the lane updates (NY: none)
+    float hi = 0.0f, lo = 0.0f;
+    if (is_vm) { hi = w.c[RPO_EVOPF_C_VMAX + vbus]; lo = w.c[RPO_EVOPF_C_VMIN + vbus]; }
+    else if (is_pg) { hi = w.c[RPO_EVOPF_C_PMAX + gen]; lo = w.c[RPO_EVOPF_C_PMIN + gen]; }
+    else if (has_u) { hi = w.c[RPO_EVOPF_C_QMAX + gen]; lo = w.c[RPO_EVOPF_C_QMIN + gen]; }
+    const float c2 = is_pg ? 2.0f * w.c[RPO_EVOPF_C_QUAD + gen] : 0.0f, c1 = is_pg ? w.c[RPO_EVOPF_C_LIN + gen] : 0.0f;
+
+    // ---- flat start
+    {
+        const float x0 = 0.5f * (hi + lo);                                  // (0 for the angles)
+        if (xidx < NY) w.a[xidx] = x0;
+        if (tid < NE) w.a[PE0 + tid] = p.pe ? p.pe[(size_t)i * NE + tid] : 0.0f;
+        if (tid == 32) w.a[VA0] = w.c[RPO_EVOPF_C_VA_INIT];                 // slack_va (bus 0)
+    }
+    float zu = 1.0f, zl = 1.0f, mu_u = 0.0f, mu_l = 0.0f, gamma = kGamma0;
+    if (bounded) {
+        const float x0 = 0.5f * (hi + lo);
+        zu = fmaxf(hi - x0, kZ0); zl = fmaxf(x0 - lo, kZ0);
+        mu_u = gamma / zu; mu_l = gamma / zl;
+    }
+    sync();
+
+    int it = 0;
+    bool converged = false;
+    float resid = 0.0f;
+    for (;;) {
+        flows(w);
+        eq_resid(w);                                             // g in w.eq
+        const float x = w.a[xidx];
+        const float hu = bounded ? x - hi : -1.0f, hl = bounded ? lo - x : -1.0f;
+        // bound terms: Sigma, the barrier part of N, mu_u - mu_l
+        const float sig = bounded ? mu_u / zu + mu_l / zl : 0.0f;
+        const float nbar = bounded ? (mu_u * hu + gamma) / zu - (mu_l * hl + gamma) / zl : 0.0f;
+        const float dmu = mu_u - mu_l;
+        // generator variable of an equation lane: L_x, D, N of that variable; its column is eliminated into the lane's diagonal
+        const float lam_e = w.dir[e], g_e = is_eq ? w.eq[e] : 0.0f;
+        const float lxu = has_u ? (c2 * x + c1) + lam_e + dmu : 0.0f;
+        const float du = has_u ? c2 + sig : 1.0f;
+        const float nu = lxu + nbar;
+        const float kdiag = has_u ? -1.0f / du : 0.0f;
+
+        // Hessian coefficients of the lane's bus m against every bus n
+        float csn[NB], ddn[NB], vmag[NB], csv = 0.0f, dv = 0.0f;
+        const float vm_m = w.a[VM0 + vbus];
+        {
+            const float lpm = w.dir[vbus], lqm = w.dir[NB + vbus], cm = w.cs[vbus], sm = w.sn[vbus];
+#pragma unroll
+            for (int n = 0; n < NB; ++n) {
+                const bool same = vbus == n;
+                const float cn = w.cs[n], sn = w.sn[n];
+                const float C = same ? 1.0f : cm * cn + sm * sn, S = same ? 0.0f : sm * cn - cm * sn;
+                const float gmn = Yr(w, n, vbus), bmn = Yi(w, n, vbus), gnm = Yr(w, vbus, n), bnm = Yi(w, vbus, n);
+                const float amn = gmn * C + bmn * S, bbmn = gmn * S - bmn * C;
+                const float anm = gnm * C - bnm * S, bbnm = -gnm * S - bnm * C;
+                const float lpn = w.dir[n], lqn = w.dir[NB + n];
+                const float cmn = lpm * amn + lqm * bbmn, cnm = lpn * anm + lqn * bbnm;
+                const float dmn = -lpm * bbmn + lqm * amn, dnm = -lpn * bbnm + lqn * anm;
+                csn[n] = cmn + cnm;
+                ddn[n] = dmn - dnm;
+                vmag[n] = w.a[VM0 + n];
+                csv = fmaf(csn[n], vmag[n], csv);
+                dv = fmaf(ddn[n], vmag[n], dv);
+            }
+        }
+
+        // ---- the lane's row of [[H_vv + Sigma, J_v^T], [J_v, -S D^-1 S^T]] | rhs
+        float row[NK + 1];
+#pragma unroll
+        for (int c = 0; c < NV; ++c) {
+            const bool col_vm = c < NB;
+            const int n = col_vm ? c : c - (NB - 1);
+            const int var = col_vm ? VM0 + n : VA0 + n;
+            float v = 0.0f;
+            if (is_var) {                                        // minus the second derivatives of F
+                const bool same = vbus == n;
+                if (is_vm) v = col_vm ? -csn[n] : (same ? -dv : vmag[n] * ddn[n]);
+                else v = col_vm ? -((same ? dv : 0.0f) + vm_m * ddn[n]) : (same ? vm_m * csv : 0.0f) - vm_m * vmag[n] * csn[n];
+                if (is_vm && tid == c) v += sig;
+            } else if (is_eq) {
+                v = jac_entry(w, e, var);
+            }
+            row[c] = v;
+        }
+        float jtl = 0.0f;                                        // (J^T lambda) of the lane's voltage unknown
+#pragma unroll
+        for (int c = NV; c < NK; ++c) {
+            float v = 0.0f;
+            if (is_var) {
+                v = jac_entry(w, c - NV, myvar);
+                jtl = fmaf(v, w.dir[c - NV], jtl);
+            } else if (tid == c) {
+                v = kdiag;
+            }
+            row[c] = v;
+        }
+        const float lxv = is_var ? jtl + (is_vm ? dmu : 0.0f) : 0.0f;          // L_x of the voltage unknown
+        const float nv = lxv + (is_vm ? nbar : 0.0f);
+        row[NK] = is_var ? -nv : (is_eq ? (has_u ? nu / du - g_e : -g_e) : 0.0f);
+
+        // ---- stop test: max(|g|_inf, max h), |L_x|_inf, z^T mu
+        const float feas_l = fmaxf(fabsf(g_e), bounded ? fmaxf(hu, hl) : 0.0f);
+        const float grad_l = is_var ? fabsf(lxv) : fabsf(lxu);
+        const float comp_l = bounded ? zu * mu_u + zl * mu_l : 0.0f;
+        const float comp = rpo_wave_sum_rows(comp_l);
+        const bool nan_l = g_e != g_e || hu != hu || lxv != lxv || lxu != lxu || comp != comp;
+        const bool any_nan = __builtin_amdgcn_ballot_w64(nan_l) != 0ull;
+        resid = fmaxf(fmaxf(rpo_wave_max_nonneg(fmaxf(feas_l, 0.0f)), rpo_wave_max_nonneg(grad_l)), comp);
+        if (any_nan) resid = __builtin_nanf("");
+        converged = !any_nan && resid < p.tol;
+        if (converged || it >= p.max_iters) break;
+
+        // ---- (dv, dlambda), then the eliminated generator steps, slacks and multipliers
+        int mycol;
+        const float mypiv = gj_wave(row, mycol);
+        if (tid < NK) w.vec[mycol] = row[NK] / mypiv;
+        sync();
+        const float delta = w.vec[tid < NK ? tid : 0];
+        const float dlam = is_eq ? delta : 0.0f;
+        const float dx = is_var ? delta : (has_u ? (-nu - dlam) / du : 0.0f);
+        const float dzu = -hu - zu - dx, dzl = -hl - zl + dx;                   // dz = -h - z - dh
+        const float dmu_u = -mu_u + (gamma - mu_u * dzu) / zu, dmu_l = -mu_l + (gamma - mu_l * dzl) / zl;
+        // step lengths to the boundary times xi, capped at 1: xi * min(z / -dz) = xi / max(-dz / z)
+        const float qp = rpo_wave_max_nonneg(bounded ? fmaxf(fmaxf(-dzu / zu, -dzl / zl), 0.0f) : 0.0f);
+        const float qd = rpo_wave_max_nonneg(bounded ? fmaxf(fmaxf(-dmu_u / mu_u, -dmu_l / mu_l), 0.0f) : 0.0f);
+        const float alpha_p = qp > 0.0f ? fminf(kXi / qp, 1.0f) : 1.0f;
+        const float alpha_d = qd > 0.0f ? fminf(kXi / qd, 1.0f) : 1.0f;
+        if (xidx < NY) w.a[xidx] = x + alpha_p * dx;
+        if (is_eq) w.dir[e] = lam_e + alpha_d * dlam;
+        if (bounded) {
+            zu += alpha_p * dzu; zl += alpha_p * dzl;
+            mu_u += alpha_d * dmu_u; mu_l += alpha_d * dmu_l;
+        }
+        gamma = kSigma * rpo_wave_sum_rows(bounded ? zu * mu_u + zl * mu_l : 0.0f) / (float)NBOUND;
+        sync();
+        ++it;
+    }
+
+    // ---- outputs: the full 43-vector (slack angle and pe as given) and (cost, residual, iterations, converged)
+    float part = 0.0f;
+    if (tid < NG) {
+        const float pg = w.a[PG0 + tid];
+        part = w.c[RPO_EVOPF_C_QUAD + tid] * pg * pg + w.c[RPO_EVOPF_C_LIN + tid] * pg;
+    }
+    const float cost = rpo_wave_sum_rows(part) + w.c[RPO_EVOPF_C_CONST];
+    if (tid < NY) p.action[(size_t)i * NY + tid] = w.a[tid];
+    if (tid < 4) p.info[(size_t)i * 4 + tid] = tid == 0 ? cost : (tid == 1 ? resid : (tid == 2 ? (float)it : (converged ? 1.0f : 0.0f)));
+}
+
+}  // namespace
+
+extern "C" int rpo_evopf_opf(int n, const float* obs, int obs_stride, const float* pe, float* action_out, float* info_out, float tol,
+                             int max_iters, const float* consts_dev, void* stream) {
+    if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < 2 * NB) return RPO_ERR_ARG;
+    if (!obs || !action_out || !info_out || !consts_dev) return RPO_ERR_NULL;
+    const OpfArgs args{n, obs, obs_stride, pe, action_out, info_out, tol, max_iters, consts_dev};
+    return launch(evopf_opf_kernel, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
+}

@@ -9,7 +9,14 @@ HIP kernels of rpo_amd/csrc/evopf.hip (one wavefront per env lane); this class h
 
 Differences to the reference, all stated in DESIGN.md: the loaders' random day (np.random.dirichlet / rand / randn,
 data/demand.py:53-62, data/price.py:41-43) comes from the build's Philox streams keyed by (seed, lane, episode);
-``render`` (igraph) and ``opt_solve`` (pypower's interior-point OPF) are not part of the hot path.
+``render`` (igraph) is not part of the hot path.
+
+The optimal power flow: ``opf(state, pe)`` solves every row's single-step AC-OPF -- the cheapest (pg, qg, vm, va) that meets the
+power balance and the bounds, for the row's demand and a GIVEN battery power -- on the device (rpo_amd/csrc/evopf_opf.hip: a
+primal-dual interior point method, one wavefront per state) and returns an ``OpfResult`` of device tensors.  ``opt_solve(X)`` is
+the reference's method of that name (there: pypower's interior-point OPF, one state at a time on the CPU) on top of it, and
+``EvalTrajectory.opf_gap(env)`` (rpo_amd/algo/evaluation.py) the optimality gap of a recorded evaluation.  There is no CPU
+path: on the oracle backend or a CPU device the three raise NotImplementedError with that reason.
 """
 import numpy as np
 import torch
@@ -275,5 +282,98 @@ class EVOPFEnv(HardConstraintEnv):
         s = torch.as_tensor(np.asarray(state), dtype=torch.float32, device=self.device).view(1, -1)
         return self.eq_resid(s, a).detach().cpu().numpy()
 
-    def opt_solve(self, *a, **k):
-        raise NotImplementedError("pypower's interior-point OPF baseline (evopf.py:729-759) is outside the RPO hot path")
+    # ------------------------------------------------------------------------------------------ optimal power flow
+    def _opf_kernel(self):
+        """The backend's single-step OPF kernel, or NotImplementedError with the reason there is none."""
+        fn = getattr(self._backend, "evopf_opf", None)
+        if fn is None:
+            raise NotImplementedError("this backend has no evopf_opf kernel: the AC-OPF solver exists as the HIP kernel "
+                                      "rpo_evopf_opf only (the CPU oracle backend has none; pypower is not a dependency)")
+        if self.device.type != "cuda":
+            raise NotImplementedError("the AC-OPF solver is the HIP kernel rpo_evopf_opf and needs a GPU device, got %s: "
+                                      "there is no CPU path" % self.device)
+        return fn
+
+    def opf(self, state, pe=None, tol=1e-4, max_iters=40, out=None):
+        """The cheapest dispatch of every row's single-step AC-OPF, on the device (rpo_evopf_opf, csrc/evopf_opf.hip).
+
+        ``state`` [n, 57] observations or [n, 28] demands (pd, qd); ``pe`` [n, 5] battery power, a PARAMETER of the problem
+        (None: zero, the reference's ``opt_solve``; a policy's own pe for optimality gaps).  Minimises ``obj_fn`` over (pg, qg,
+        vm, va) subject to ``eq_resid = 0`` and the bounds on pg, qg, vm by a primal-dual interior point method from the flat
+        start; stops when the primal infeasibility, |L_x|_inf and z^T mu are all below ``tol``, or after ``max_iters``
+        iterations (``converged`` False: infeasible single-step problems exist, and end this way).  Returns an ``OpfResult`` of
+        device tensors; nothing synchronises with the host.  ``out``: an earlier result of the same n, whose buffers are
+        reused."""
+        fn = self._opf_kernel()
+        tol, iters = float(tol), int(max_iters)
+        if not tol > 0.0 or iters != max_iters or iters < 0:
+            raise ValueError("opf: tol must be > 0 and max_iters an integer >= 0, got %r and %r" % (tol, max_iters))
+        state = self._t(state)
+        if state.dim() == 1:
+            state = state.view(1, -1)
+        if state.dim() != 2 or state.shape[0] < 1 or state.shape[1] not in (self.state_dim, 2 * self.nbus):
+            raise ValueError("opf: state must be [n, %d] observations or [n, %d] demands, got %s"
+                             % (self.state_dim, 2 * self.nbus, tuple(state.shape)))
+        if state.stride(1) != 1:
+            state = state.contiguous()
+        n = state.shape[0]
+        if pe is not None:
+            pe = self._t(pe)
+            pe = (pe.view(1, -1) if pe.dim() == 1 else pe).contiguous()
+            if tuple(pe.shape) != (n, self.ne):
+                raise ValueError("opf: pe must be [%d, %d], got %s" % (n, self.ne, tuple(pe.shape)))
+        if out is None:
+            out = OpfResult(torch.empty(n, self._ydim, device=state.device), torch.empty(n, 4, device=state.device))
+        elif not isinstance(out, OpfResult) or tuple(out.action.shape) != (n, self._ydim) or tuple(out.info.shape) != (n, 4) \
+                or out.action.device != state.device or out.info.device != state.device \
+                or not (out.action.is_contiguous() and out.info.is_contiguous()) \
+                or out.action.dtype != torch.float32 or out.info.dtype != torch.float32:
+            raise ValueError("opf: out must be an OpfResult of %d rows on %s" % (n, state.device))
+        fn(self.kernels, state, pe, out.action, out.info, tol, iters)
+        return out
+
+    def opt_solve(self, X, solver_type="hip", tol=1e-4):
+        """The reference's ``opt_solve`` (evopf.py:729-759) on the device: demands X [n, 28] -> (Y [n, 38] numpy = (pg, qg, vm,
+        va) of the optimal dispatch with pe = 0, total time, time per state) in seconds of wall clock, kernel and copy-back.
+        Rows whose problem did not converge (``opf``) are NaN.  ``solver_type``: "hip"; the reference's "pypower" is refused."""
+        if solver_type != "hip":
+            raise NotImplementedError("opt_solve(solver_type=%r): pypower is not a dependency of this build; the solver is "
+                                      "the HIP kernel behind solver_type='hip' (EVOPFEnv.opf)" % (solver_type,))
+        self._opf_kernel()
+        import time
+        X = X.detach() if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != 2 * self.nbus:
+            raise ValueError("opt_solve: X must be [n, %d] demands, got %s" % (2 * self.nbus, tuple(X.shape)))
+        start = time.perf_counter()
+        res = self.opf(X, tol=tol).numpy()
+        total = time.perf_counter() - start
+        Y = res["action"][:, :self.pe_start_yidx].astype(np.float64)
+        Y[~res["converged"]] = np.nan
+        return Y, total, total / X.shape[0]
+
+
+class OpfResult(object):
+    """What ``EVOPFEnv.opf`` returns: device tensors, row i for state i.  ``action`` [n, 43]: the full action vector (va at the
+    slack bus = slack_va, pe as given), so ``eq_resid`` / ``ineq_resid`` / ``obj_fn`` apply to it; ``cost`` [n] = its ``obj_fn``;
+    ``residual`` [n]: the largest of the three stop quantities at exit (NaN if one of them was); ``iters`` [n] int32;
+    ``converged`` [n] bool.  The last four are views of / elementwise ops on ``info`` [n, 4], the kernel's own output."""
+
+    def __init__(self, action, info):
+        self.action, self.info = action, info
+
+    cost = property(lambda self: self.info[:, 0])
+    residual = property(lambda self: self.info[:, 1])
+    iters = property(lambda self: self.info[:, 2].to(torch.int32))
+    converged = property(lambda self: self.info[:, 3] > 0.5)
+
+    def numpy(self):
+        """dict of numpy arrays (one device-to-host copy per buffer; this synchronises)."""
+        info = self.info.detach().cpu().numpy()
+        return dict(action=self.action.detach().cpu().numpy(), cost=info[:, 0].copy(), residual=info[:, 1].copy(),
+                    iters=info[:, 2].astype(np.int32), converged=info[:, 3] > 0.5)
+
+    def converged_rate(self):
+        return float((self.info[:, 3] > 0.5).float().mean())
+
+    def __repr__(self):
+        return "OpfResult(n=%d)" % self.action.shape[0]

@@ -807,6 +807,27 @@ def evopf_project_profile(kernels, obs, ap_raw, action, iters, max_steps, corr_l
         _act_profile(profile, n, max_steps), _stream()), "rpo_evopf_project_profile")
 
 
+OPF_DEMAND = 2 * 14                  # floats of an observation row the OPF reads: pd[14], qd[14]
+
+
+def evopf_opf(kernels, obs, pe, action, info, tol, max_iters):
+    """Single-step AC-OPF of every row (rpo_evopf_opf): obs [n, >= 28] float32 rows with unit column stride (observations, demands
+    alone, or a column slice of something wider: only the first 28 floats of a row are read), pe [n, 5] or None (zeros) -> action
+    [n, 43], info [n, 4] = (cost, largest stop quantity at exit, iterations, converged).  ``kernels``: an EvopfKernels (constant
+    table).  A function of the backend like ``evopf_evaluate``, not a method: the env kernel classes keep their public methods."""
+    if action is None or action.dim() != 2 or action.shape[1] != kernels.action_dim or action.shape[0] < 1:
+        raise RpoHipError("evopf_opf: action must be [n >= 1, %d], got %s" % (kernels.action_dim, None if action is None else tuple(action.shape)))
+    n = action.shape[0]
+    if obs is None or obs.dim() != 2 or obs.shape[0] != n or obs.shape[1] < OPF_DEMAND or obs.stride(1) != 1:
+        raise RpoHipError("evopf_opf: obs must be [%d, >= %d] rows with unit column stride, got %s"
+                          % (n, OPF_DEMAND, None if obs is None else (tuple(obs.shape), obs.stride())))
+    if info is None or tuple(info.shape) != (n, 4) or (pe is not None and tuple(pe.shape) != (n, 5)):
+        raise RpoHipError("evopf_opf: info must be [%d, 4] and pe [%d, 5] or None" % (n, n))
+    stride = int(obs.stride(0)) if n > 1 else int(obs.shape[1])
+    check(_lib.load().rpo_evopf_opf(n, _p(obs, contiguous=False), stride, _p(pe, allow_none=True), _p(action), _p(info), float(tol),
+                                    int(max_iters), kernels._c(action), _stream()), "rpo_evopf_opf")
+
+
 class PendulumKernels(_FusedEnvKernels):
     """HIP kernels of SpringPendulum-v0."""
 
