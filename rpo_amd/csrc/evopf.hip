@@ -205,27 +205,29 @@ __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_complete_bwd_kerne
     sync();
     // step 1 (:889-891): d_int = inv(J_newton)^T dl_dy_total[newton vars]
     const bool force_dyn = w.c[RPO_EVOPF_C_FLAGS] != RPO_EVOPF_STATIC_OK;
+    // (the row is written out in both branches: built by one helper function or lambda, the gradient came out with other last
+    //  bits on the device -- the kernel is then 4.7 KB shorter, the second build reuses values of the first; no further cause found)
     bool solved = false;
-    float dint = 0.0f;
+    float num = 0.0f, piv = 1.0f;                                       // d_int = num / piv of the unknown `mycol`
     int mycol = tid;
     if (!force_dyn) {                                                   // static order (evopf_dev.h), accepted by its pivots
         float row[NN + 1];                                              // row tid of [J_newton^T | rhs]
 #pragma unroll
         for (int c = 0; c < NN; ++c) row[c] = tid < NN ? jac_entry(w, kKeep[c], kNewtonVars[tid]) : 0.0f;
         row[NN] = tid < NN ? w.vec[kNewtonVars[tid] - VM0] : 0.0f;
-        const float mypiv = gauss_jordan_static<NN, NN + 1, 0, TabNewtonT>(row);
-        solved = pivots_ok<NN, 0>(mypiv);
-        dint = row[NN] / mypiv;
+        piv = gj_static<0, NN, 0, 0, NN + 1, TabNewtonT, true>(row);    // (with the exact reciprocal)
+        solved = pivots_ok<NN, 0>(piv);
+        num = row[NN];
     }
     if (!solved) {                                                      // partial pivoting
         float row[NN + 1];
 #pragma unroll
         for (int c = 0; c < NN; ++c) row[c] = tid < NN ? jac_entry(w, kKeep[c], kNewtonVars[tid]) : 0.0f;
         row[NN] = tid < NN ? w.vec[kNewtonVars[tid] - VM0] : 0.0f;
-        float mypiv;
-        gauss_jordan_rows<NN, NN + 1, 0>(row, mycol, mypiv);
-        dint = row[NN] / mypiv;
+        piv = gj_dynamic<0, NN, 0, NN + 1>(row, mycol);
+        num = row[NN];
     }
+    const float dint = num / piv;
     sync();
     if (tid < NN) w.old[mycol] = dint;                                  // d_int, indexed like kKeep
     sync();
@@ -374,9 +376,7 @@ __global__ __launch_bounds__(RPO_BLOCK) void evopf_lagrangian_kernel(int n, cons
 // Box of basic action j of row i straight from global memory (EVOPFEnv.update, evopf.py:769-783)
 __device__ __forceinline__ void row_box(const float* __restrict__ state, int state_stride, const float* __restrict__ consts,
                                         int i, int j, float& lo, float& hi) {
-    if (j < 4) { lo = consts[RPO_EVOPF_C_PMIN + 1 + j]; hi = consts[RPO_EVOPF_C_PMAX + 1 + j]; }
-    else if (j < 9) { lo = consts[RPO_EVOPF_C_VMIN + kSpv[j - 4]]; hi = consts[RPO_EVOPF_C_VMAX + kSpv[j - 4]]; }
-    else battery_bounds(state[(size_t)i * state_stride + 2 * NB + j - 9], hi, lo);
+    basic_box(consts, state + (size_t)i * state_stride + 2 * NB, j, lo, hi);
 }
 
 // Squashed-Gaussian policy head with the state-dependent box (GaussianSharedPolicy.forward, model/policy.py:53-66, with
@@ -438,9 +438,7 @@ __global__ __launch_bounds__(RPO_BLOCK) void evopf_tanh_box_bwd_kernel(int n, co
     for (int idx = blockIdx.x * RPO_BLOCK + threadIdx.x; idx < n * NP; idx += gridDim.x * RPO_BLOCK) {
         const int i = idx / NP, j = idx - i * NP;
         float lo, hi;
-        if (j < 4) { lo = consts[RPO_EVOPF_C_PMIN + 1 + j]; hi = consts[RPO_EVOPF_C_PMAX + 1 + j]; }
-        else if (j < 9) { lo = consts[RPO_EVOPF_C_VMIN + kSpv[j - 4]]; hi = consts[RPO_EVOPF_C_VMAX + kSpv[j - 4]]; }
-        else battery_bounds(state[(size_t)i * state_stride + 2 * NB + j - 9], hi, lo);
+        row_box(state, state_stride, consts, i, j, lo, hi);
         const float scale = (hi - lo) * 0.5f;
         const float th = tanhf(raw[idx]);
         float g = dap[idx] * scale * (1.0f - th * th);

@@ -12,9 +12,17 @@
 // thread 16 us (the serial pivot search and the predicated row swaps ran in every thread); one ROW per thread with a DPP
 // pivot search 8.6 us (round 3); round 4: a STATIC elimination order with case14's sparsity compiled in (no search, 154
 // instead of 561 row-update pairs; partial pivoting remains as the fallback of a pivot-ratio test) and the whole iteration in
-// registers / wave-uniform values ("v2" at the end of this file): 3.4 us -- see tools/evopf_probe.py.  The v1 helpers (flows,
-// eq_resid, ineq_resid through LDS; gauss_jordan_rows) still serve the step / residual kernels, PFFunction.backward and the
-// fallback.  Workgroup = 4 waves = 4 env lanes, a workspace each: the barriers below only order LDS traffic of one wave.
+// registers / wave-uniform values ("v2" below): 3.4 us -- see tools/evopf_probe.py.
+// Two families of helpers live here:
+//   * the LDS path -- flows, eq_resid, ineq_resid, jac_entry: every intermediate in the workspace -- for what runs once per
+//     launch: evopf_resid_kernel, evopf_step_lane, evopf_eq_vjp_kernel, evopf_complete_bwd_kernel, profile_entry and
+//     evopf_opf_kernel (evopf_opf.hip);
+//   * the register path -- RowLane, own_volt, bus_uniforms, row_residual, jacobian_row -- for the iterations of
+//     complete_partial_v2 and grg_iteration_v2 (evopf_act_project_kernel, evopf_project_profile_kernel, evopf_ipg_kernel, the
+//     fused evaluation of evopf_eval.hip).
+// Both eliminate with the same two routines: gj_static (the compiled-in order) and gj_dynamic (partial pivoting: the fallback
+// of the static order, and evopf_opf_kernel's KKT system with its own pivot picker).
+// Workgroup = 4 waves = 4 env lanes, a workspace each: the barriers below only order LDS traffic of one wave.
 //
 // The network is the IEEE 14-bus case exactly like the reference (case14 hard-wired at evopf.py:211, eq_num = 28 and
 // ineq_num = 58 hard-coded at :336-337): the bus classification is compiled in, every number (admittances, limits, costs,
@@ -52,7 +60,7 @@ __device__ constexpr int kPartialActions[NP] = {1, 2, 3, 4, 10, 11, 12, 15, 17, 
 // Accuracy: on 1500 sampled Jacobians (solved states, GRG-like and gross perturbations, Newton's flat start) the static order's
 // inverse is as close to the float64 one as partial pivoting's (median 1.5e-7, same p99) whenever min|pivot| / max|pivot| >
 // 2^-6; below that (gross perturbations only: near-singular Jacobians) the wave falls back to the partial-pivoting elimination
-// (gauss_jordan_rows) -- a wave-uniform branch, see pivots_ok().  RPO_EVOPF_C_FLAGS != RPO_EVOPF_STATIC_OK forces the fallback
+// (gj_dynamic) -- a wave-uniform branch, see pivots_ok().  RPO_EVOPF_C_FLAGS != RPO_EVOPF_STATIC_OK forces the fallback
 // (the default of a table nobody validated; A/B tests).
 // The first six "other" variables (slack pg, qg) appear in exactly one equation each with coefficient 1 (P at the slack bus,
 // Q at the generator buses): with these rows first the leading 6 x 6 block is the identity and the elimination starts at 6.
@@ -156,54 +164,22 @@ __device__ __forceinline__ void battery_bounds(float soc, float& p_max, float& p
     p_min = kEtaOut * fmaxf(kBPmin, kBLow - soc);
 }
 
-// Box of basic action j of the lane whose observation is in w.s (EVOPFEnv.update, evopf.py:769-783)
-__device__ __forceinline__ void partial_box(const Ws& w, int j, float& lo, float& hi) {
-    if (j < 4) { lo = w.c[RPO_EVOPF_C_PMIN + 1 + j]; hi = w.c[RPO_EVOPF_C_PMAX + 1 + j]; }
-    else if (j < 9) { lo = w.c[RPO_EVOPF_C_VMIN + kSpv[j - 4]]; hi = w.c[RPO_EVOPF_C_VMAX + kSpv[j - 4]]; }
-    else battery_bounds(w.s[2 * NB + j - 9], hi, lo);
+// Box of basic action j (EVOPFEnv.update, evopf.py:769-783) from the constants table `c` and the five states of charge `soc`:
+// the one definition, wherever the two live (partial_box: the workspace; row_box of evopf.hip: global memory)
+__device__ __forceinline__ void basic_box(const float* c, const float* soc, int j, float& lo, float& hi) {
+    if (j < 4) { lo = c[RPO_EVOPF_C_PMIN + 1 + j]; hi = c[RPO_EVOPF_C_PMAX + 1 + j]; }
+    else if (j < 9) { lo = c[RPO_EVOPF_C_VMIN + kSpv[j - 4]]; hi = c[RPO_EVOPF_C_VMAX + kSpv[j - 4]]; }
+    else battery_bounds(soc[j - 9], hi, lo);
 }
+// ... of the lane whose observation is in w.s
+__device__ __forceinline__ void partial_box(const Ws& w, int j, float& lo, float& hi) { basic_box(w.c, w.s + 2 * NB, j, lo, hi); }
 
-// Ybus operands a thread needs again in every Newton / GRG iteration, kept in registers (they are constants; read from LDS they
-// were two reads per Jacobian entry and four per term of the admittance products, behind LDS stores the compiler cannot move
-// them across): column `tid` for flows(), row `i` for the Jacobian row of the equation a thread owns.  Same values, same
-// operations.
+// Ybus operands a row lane needs again in every Newton / GRG iteration, kept in registers (they are constants; read from LDS
+// they were two reads per Jacobian entry and four per term of the admittance products, behind LDS stores the compiler cannot
+// move them across): the row and the column of the lane's bus (RowLane below).
 struct YVec {
     float yr[NB], yi[NB];
 };
-__device__ __forceinline__ YVec y_column(const Ws& w, int k) {
-    YVec y;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) { y.yr[i] = Yr(w, i, k); y.yi[i] = Yi(w, i, k); }
-    return y;
-}
-__device__ __forceinline__ YVec y_row(const Ws& w, int i) {
-    YVec y;
-#pragma unroll
-    for (int k = 0; k < NB; ++k) { y.yr[k] = Yr(w, i, k); y.yi[k] = Yi(w, i, k); }
-    return y;
-}
-
-// flows() with the thread's Ybus column in registers (y_column(w, tid < NB ? tid : 0))
-__device__ __forceinline__ void flows(Ws& w, const YVec& yc) {
-    const int tid = lane_id();
-    if (tid < NB) {
-        float sn, cs;
-        sincosf(w.a[VA0 + tid], &sn, &cs);
-        const float vm = w.a[VM0 + tid];
-        w.cs[tid] = cs; w.sn[tid] = sn; w.vr[tid] = vm * cs; w.vi[tid] = vm * sn;
-    }
-    sync();
-    if (tid < NB) {
-        float t1 = 0.0f, t2 = 0.0f;
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {                       // row vector @ matrix, as written at :527-528
-            t1 += w.vr[i] * yc.yr[i] - w.vi[i] * yc.yi[i];
-            t2 += w.vr[i] * yc.yi[i] + w.vi[i] * yc.yr[i];
-        }
-        w.t1[tid] = t1; w.t2[tid] = t2;
-    }
-    sync();
-}
 
 // cos / sin / rectangular voltages and the two admittance products of eq_resid / eq_jac (evopf.py:523-528,623-630)
 __device__ __forceinline__ void flows(Ws& w) {
@@ -304,110 +280,6 @@ __device__ __forceinline__ unsigned half_wave_umax(unsigned key) {
     return (unsigned)__builtin_amdgcn_readlane((int)key, 31);
 }
 
-// Per-thread view of the equation (Jacobian row) a thread owns: everything of eq_jac (evopf.py:614-661) that does not
-// depend on the column.  With A = Yr[i][k] p_k - Yi[i][k] q_k and B = Yi[i][k] p_k + Yr[i][k] q_k, where (p, q) =
-// d(vr_k, vi_k)/d var = (cos, sin) for vm_k and (-vi, vr) for va_k:
-//   real row      d/dvar = -(vr_i A + vi_i B) - [i == k] (p_i t1_i + q_i t2_i)
-//   reactive row  d/dvar =  (vr_i B - vi_i A) + [i == k] (p_i t2_i - q_i t1_i)
-struct RowCoef {
-    int i;            // bus of the equation
-    bool real;        // active (true) or reactive power balance
-    float ca, cb;     // coefficients of A and B
-    float dg_vm, dg_va;   // diagonal terms for the vm / va column of the same bus
-};
-
-__device__ __forceinline__ RowCoef row_coef(const Ws& w, int eq) {
-    RowCoef c;
-    c.real = eq < NB;
-    c.i = c.real ? eq : eq - NB;
-    const float vr = w.vr[c.i], vi = w.vi[c.i], cs = w.cs[c.i], sn = w.sn[c.i], t1 = w.t1[c.i], t2 = w.t2[c.i];
-    c.ca = c.real ? -vr : -vi;
-    c.cb = c.real ? -vi : vr;
-    c.dg_vm = c.real ? -(cs * t1 + sn * t2) : (cs * t2 - sn * t1);
-    c.dg_va = c.real ? -(-vi * t1 + vr * t2) : (-vi * t2 - vr * t1);
-    return c;
-}
-
-// eq_jac entry (this thread's equation, variable `var`); `var` is a compile-time constant at every call site, so only
-// the block it names survives.  Battery columns carry the reference's sign (hazard E1).
-__device__ __forceinline__ float jac_row_entry(const Ws& w, const RowCoef& c, int var, const YVec& yrow) {
-    if (var < QG0) return (c.real && kSpv[var] == c.i) ? 1.0f : 0.0f;
-    if (var < VM0) return (!c.real && kSpv[var - QG0] == c.i) ? 1.0f : 0.0f;
-    if (var >= PE0) return (c.real && kSpv[var - PE0] == c.i) ? -1.0f : 0.0f;
-    const bool dvm = var < VA0;
-    const int k = dvm ? var - VM0 : var - VA0;
-    const float yr = yrow.yr[k], yi = yrow.yi[k];              // (k is a compile-time constant at every call site)
-    const float p = dvm ? w.cs[k] : -w.vi[k], q = dvm ? w.sn[k] : w.vr[k];
-    const float A = yr * p - yi * q, B = yi * p + yr * q;
-    return c.ca * A + c.cb * B + (c.i == k ? (dvm ? c.dg_vm : c.dg_va) : 0.0f);
-}
-__device__ __forceinline__ float jac_row_entry(const Ws& w, const RowCoef& c, int var) {
-    if (var < QG0) return (c.real && kSpv[var] == c.i) ? 1.0f : 0.0f;
-    if (var < VM0) return (!c.real && kSpv[var - QG0] == c.i) ? 1.0f : 0.0f;
-    if (var >= PE0) return (c.real && kSpv[var - PE0] == c.i) ? -1.0f : 0.0f;
-    const bool dvm = var < VA0;
-    const int k = dvm ? var - VM0 : var - VA0;
-    const float yr = Yr(w, c.i, k), yi = Yi(w, c.i, k);
-    const float p = dvm ? w.cs[k] : -w.vi[k], q = dvm ? w.sn[k] : w.vr[k];
-    const float A = yr * p - yi * q, B = yi * p + yr * q;
-    return c.ca * A + c.cb * B + (c.i == k ? (dvm ? c.dg_vm : c.dg_va) : 0.0f);
-}
-
-// Gauss-Jordan with partial pivoting on an N x NC system distributed one ROW per thread (threads >= N pass zeros).
-// Rows are not swapped and pivot rows are not normalised: on return thread r's row solves unknown `mycol` and
-// row[c] / mypiv (c >= N) is entry [mycol][c] of inv(A) @ (the trailing columns).  The first K0 rows must be the unit
-// rows e_0 .. e_{K0-1} within the first K0 columns, and the other rows zero there.
-template <int N, int NC, int K0>
-__device__ __forceinline__ void gauss_jordan_rows(float (&row)[NC], int& mycol, float& mypiv) {
-    const int lane = lane_id();
-    bool used = lane < K0 || lane >= N;
-    mycol = lane < K0 ? lane : 0;
-    mypiv = 1.0f;
-#pragma unroll
-    for (int k = K0; k < N; ++k) {
-        const unsigned key = used ? 0u : ((__float_as_uint(fabsf(row[k])) & ~31u) | (unsigned)lane);
-        const int p = (int)(half_wave_umax(key) & 31u);
-        const float piv = lane_bcast(row[k], p);
-        const bool is_p = lane == p;
-        const float f = is_p ? 0.0f : -row[k] * (1.0f / piv);
-        if (is_p) { used = true; mycol = k; mypiv = piv; }
-        // two columns per instruction (v_pk_fma_f32: the same IEEE fma per component; the pivot row's pair sits in an SGPR pair).
-        // Pairs are (even, odd) columns whatever k is: 64-bit register operands must be even-aligned, a pairing that moved with
-        // k made the compiler re-pack the row with v_pk_mov_b32 at every pivot.
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const f32x2 f2 = {f, f};
-        const int start = (k + 2) & ~1;                              // first even column behind the pivot column
-        if ((k + 1) & 1) row[k + 1] = fmaf(f, lane_bcast(row[k + 1], p), row[k + 1]);
-#pragma unroll
-        for (int c = start; c + 1 < NC; c += 2) {
-            const f32x2 pv = {lane_bcast(row[c], p), lane_bcast(row[c + 1], p)};
-            f32x2 rv = {row[c], row[c + 1]};
-            rv = __builtin_elementwise_fma(f2, pv, rv);
-            row[c] = rv.x; row[c + 1] = rv.y;
-        }
-        if ((NC & 1) && start < NC) row[NC - 1] = fmaf(f, lane_bcast(row[NC - 1], p), row[NC - 1]);
-    }
-}
-
-// Gauss-Jordan in the STATIC order: pivot k is row k (lane k), column k; only the columns Tab::live(k, c) marks are
-// touched.  Rows are not normalised: on return thread r's row solves unknown r and row[c] / pivot (c >= N) is entry [r][c]
-// of inv(A) @ (the trailing columns); the return value is the thread's pivot.  Same K0 convention as gauss_jordan_rows.
-template <int N, int NC, int K0, typename Tab>
-__device__ __forceinline__ float gauss_jordan_static(float (&row)[NC]) {
-    const int lane = lane_id();
-    float mypiv = 1.0f;
-#pragma unroll
-    for (int k = K0; k < N; ++k) {
-        const float piv = lane_bcast(row[k], k);                     // v_readlane with an immediate lane
-        const float f = lane == k ? 0.0f : -row[k] * (1.0f / piv);
-        mypiv = lane == k ? piv : mypiv;
-#pragma unroll
-        for (int c = k + 1; c < NC; ++c)
-            if (Tab::live(k, c)) row[c] = fmaf(f, lane_bcast(row[c], k), row[c]);
-    }
-    return mypiv;
-}
-
 // The static order's acceptance test (wave-uniform): every pivot within 2^-6 of the largest one.  NaN / zero / infinite
 // pivots fail it.  Lanes [K0, N) hold the pivots.
 template <int N, int K0>
@@ -423,9 +295,9 @@ __device__ __forceinline__ bool pivots_ok(float mypiv) {
 // =====================================================================================================================
 // v2 of the equation solver and the GRG projection (round 4): the whole iteration in registers and wave-uniform values.
 //
-// v1 (rounds 1-3; its solver functions were removed in round 4, its helpers above remain) handed every intermediate over through LDS (cos / sin / rectangular voltages -> admittance products -> residuals
-// -> Jacobian rows -> D -> two products with D), each a store, a wave barrier and dependent loads: with ONE resident wave
-// nothing hides those round trips.  Here:
+// v1 (rounds 1-3; removed: only the LDS-path helpers above remain) handed every intermediate over through LDS (cos / sin /
+// rectangular voltages -> admittance products -> residuals -> Jacobian rows -> D -> two products with D), each a store, a wave
+// barrier and dependent loads: with ONE resident wave nothing hides those round trips.  Here:
 //   * lane r < 28 owns equation kRowOrder[r] (both systems: Newton's 22 x 22 is the block of rows / columns 6..27), lanes
 //     32..45 own bus lane - 32; every lane takes cos / sin of the angle of ITS bus, so the 4 x 14 per-bus values every row
 //     needs are wave-uniform v_readlane results (scalar operands of the FMAs), not LDS traffic;
@@ -563,10 +435,12 @@ __device__ __forceinline__ void jacobian_row(const RowLane& L, const Volt& v, co
     }
 }
 
-// Static-order Gauss-Jordan on columns [OFF, OFF + NC) of the 28-row system held one row per lane (array index = column -
-// OFF): pivots KB .. KE-1, pivot k = lane k; pivots below KUNIT are exactly 1 (the slack / qg equations).  Returns the
-// lane's pivot (1 for lanes that own none).
-template <int KB, int KE, int KUNIT, int OFF, int NC, typename Tab>
+// Static-order Gauss-Jordan on columns [OFF, OFF + NC) of a system held one row per lane (array index = column - OFF):
+// pivots KB .. KE-1, pivot k = lane k, column k; only the columns Tab::live marks are touched; pivots below KUNIT are exactly
+// 1 (the slack / qg equations of the 28-row systems).  Rows are not normalised: on return lane r's row solves unknown r and
+// row[c] / pivot is entry [r][c] of inv(A) @ (the trailing columns).  Returns the lane's pivot (1 for lanes that own none).
+// EXACT_RCP: the multiplier with a correctly rounded 1 / pivot instead of the hardware reciprocal (PFFunction.backward).
+template <int KB, int KE, int KUNIT, int OFF, int NC, typename Tab, bool EXACT_RCP = false>
 __device__ __forceinline__ float gj_static(float (&row)[NC]) {
     const int lane = lane_id();
     float mypiv = 1.0f;
@@ -584,7 +458,7 @@ __device__ __forceinline__ float gj_static(float (&row)[NC]) {
             // multiplier with the hardware reciprocal (1 ulp): an error of the multiplier only leaves a residue of that relative
             // size in the eliminated entry -- the size of the elimination's own rounding errors -- and takes the twelve
             // dependent instructions of a correctly rounded division off each of the 22 links of the chain
-            f = lane == k ? 0.0f : -row[j] * RPO_EVOPF_RCP(piv);
+            f = lane == k ? 0.0f : -row[j] * (EXACT_RCP ? 1.0f / piv : RPO_EVOPF_RCP(piv));
             mypiv = lane == k ? piv : mypiv;
         }
 #pragma unroll
@@ -594,9 +468,29 @@ __device__ __forceinline__ float gj_static(float (&row)[NC]) {
     return mypiv;
 }
 
-// The same pivots by partial pivoting (the fallback of the static order): rows are not swapped, `mycol` = the pivot a
-// lane ended up owning (its own lane index where it owns none); lanes outside [KB, KE) are never chosen but are updated.
-template <int KB, int KE, int OFF, int NC>
+// Pivot pickers of gj_dynamic: the (wave-uniform) lane whose entry `x` becomes the pivot, among the lanes not yet `used`.
+struct PickKey32 {       // rows in lanes 0..31: the largest key (|x| bits & ~31) | lane -- magnitudes equal but for their last
+                         // five mantissa bits count as equal and the HIGHEST lane among them wins
+    static __device__ __forceinline__ int pick(bool used, float x) {
+        const unsigned key = used ? 0u : ((__float_as_uint(fabsf(x)) & ~31u) | (unsigned)lane_id());
+        return (int)(half_wave_umax(key) & 31u);
+    }
+};
+struct PickExact64 {     // rows in lanes 0..63: the largest |x|, compared exactly, the LOWEST lane among equals; if every
+                         // candidate is a NaN, the lowest candidate lane (the caller never asks with no row free)
+    static __device__ __forceinline__ int pick(bool used, float x) {
+        const float mag = used ? 0.0f : fabsf(x);
+        const float top = rpo_wave_max_nonneg(mag);
+        unsigned long long cand = __builtin_amdgcn_ballot_w64(!used && mag == top);
+        if (cand == 0ull) cand = __builtin_amdgcn_ballot_w64(!used);
+        return (int)__builtin_ctzll(cand);
+    }
+};
+
+// The same pivots by partial pivoting (the fallback of the static order, and the AC-OPF's KKT system): rows are not swapped,
+// `mycol` = the pivot a lane ended up owning (its own lane index where it owns none); lanes outside [KB, KE) are never chosen
+// but are updated.  The multiplier takes a correctly rounded 1 / pivot.
+template <int KB, int KE, int OFF, int NC, typename Pick = PickKey32>
 __device__ __forceinline__ float gj_dynamic(float (&row)[NC], int& mycol) {
     const int lane = lane_id();
     bool used = lane < KB || lane >= KE;
@@ -605,8 +499,7 @@ __device__ __forceinline__ float gj_dynamic(float (&row)[NC], int& mycol) {
 #pragma unroll
     for (int k = KB; k < KE; ++k) {
         const int j = k - OFF;
-        const unsigned key = used ? 0u : ((__float_as_uint(fabsf(row[j])) & ~31u) | (unsigned)lane);
-        const int p = (int)(half_wave_umax(key) & 31u);
+        const int p = Pick::pick(used, row[j]);
         const float piv = lane_bcast(row[j], p);
         const bool is_p = lane == p;
         const float f = is_p ? 0.0f : -row[j] * (1.0f / piv);
@@ -615,6 +508,13 @@ __device__ __forceinline__ float gj_dynamic(float (&row)[NC], int& mycol) {
         for (int c = j + 1; c < NC; ++c) row[c] = fmaf(f, lane_bcast(row[c], p), row[c]);
     }
     return mypiv;
+}
+
+// The lane's row of Newton's system: columns 6..27 of its Jacobian row | g
+__device__ __forceinline__ void newton_row(const RowLane& L, const Volt& v, const Uniforms& u, float t1, float t2, float resid,
+                                           float (&row)[NN + 1]) {
+    jacobian_row<6, NN>(L, v, u, t1, t2, row);
+    row[NN] = resid;
 }
 
 // complete_partial v2 (PFFunction.forward, evopf.py:789-855): Newton on rows / columns 6..27 with the lane's own stop test,
@@ -637,21 +537,21 @@ __device__ __forceinline__ int complete_partial_v2(Ws& w, const RowLane& L, floa
         const Uniforms u = bus_uniforms(v);
         float t1, t2;
         const float resid = row_residual(w, L, v, u, t1, t2);
+        // (the quotient delta = inv(J) g (:832) stands in each branch, not once behind both: behind the join the completed action
+        //  of 2 rows in 65 came out with other last bits on the device -- the same arithmetic as written, the cause was not found)
         float delta = 0.0f;
         int unknown = L.own_var;                               // w.a index of the unknown this lane's pivot solves
         bool solved = false;
         if (!force_dyn) {
-            float row[NN + 1];                                 // columns 6..27 of the row | g
-            jacobian_row<6, NN>(L, v, u, t1, t2, row);
-            row[NN] = resid;
+            float row[NN + 1];
+            newton_row(L, v, u, t1, t2, resid, row);
             const float mypiv = gj_static<6, NEQ, 6, 6, NN + 1, TabNewton>(row);
             solved = pivots_ok<NEQ, 6>(mypiv);
-            delta = row[NN] / mypiv;                           // delta = inv(J) g (:832), unknown `tid`
+            delta = row[NN] / mypiv;
         }
         if (!solved) {                                         // partial pivoting (near-singular Jacobians, or forced)
             float row[NN + 1];
-            jacobian_row<6, NN>(L, v, u, t1, t2, row);
-            row[NN] = resid;
+            newton_row(L, v, u, t1, t2, resid, row);
             int mycol;
             const float mypiv = gj_dynamic<6, NEQ, 6, NN + 1>(row, mycol);
             delta = row[NN] / mypiv;
@@ -673,6 +573,16 @@ __device__ __forceinline__ int complete_partial_v2(Ws& w, const RowLane& L, floa
         sync();
     }
     return it;
+}
+
+// The lane's row of [J_other | J_partial] for the GRG direction; the extra row (lane 28) takes [g_o^T | g_p^T] from w.vec.
+// (A function, not a lambda of grg_iteration_v2: as a lambda it cost the kernels that loop over the iteration 16 VGPRs.)
+__device__ __forceinline__ void grg_row(const Ws& w, const RowLane& L, const Volt& v, const Uniforms& u, float t1, float t2,
+                                        float (&row)[NY]) {
+    const float isx = L.is_extra ? 1.0f : 0.0f;
+    jacobian_row<0, NY>(L, v, u, t1, t2, row);
+#pragma unroll
+    for (int c = 0; c < NY; ++c) row[c] = fmaf(isx, w.vec[c], row[c]);
 }
 
 // One evaluation of the reduced gradient at w.a (ineq_partial_grad, evopf.py:590-612) and -- when `lr_step` -- the GRG step
@@ -709,51 +619,30 @@ __device__ __forceinline__ bool grg_iteration_v2(Ws& w, const RowLane& L, bool f
     w.vec[L.colpos] = g;                                       // (lanes >= NY park a zero in slot NY: never read)
     sync();
     const bool force_dyn = w.c[RPO_EVOPF_C_FLAGS] != RPO_EVOPF_STATIC_OK;
-    const float isx = L.is_extra ? 1.0f : 0.0f;
-    float fp[NPV];
-    float dsum = 0.0f;                                         // row lanes: sum_p row[NO + p] fp[p] / pivot = (D fp)[mycol]
+    float row[NY], mypiv = 1.0f;
     int mycol = tid;
     bool solved = false;
     if (!force_dyn) {
-        float row[NY];
-        jacobian_row<0, NY>(L, v, u, t1, t2, row);
-#pragma unroll
-        for (int c = 0; c < NY; ++c) row[c] = fmaf(isx, w.vec[c], row[c]);       // lane 28: [g_o^T | g_p^T]
-        const float mypiv = gj_static<0, NEQ, 6, 0, NY, TabGrg0>(row);
+        grg_row(w, L, v, u, t1, t2, row);
+        mypiv = gj_static<0, NEQ, 6, 0, NY, TabGrg0>(row);
         solved = pivots_ok<NEQ, 6>(mypiv);
-        if (solved) {
-            if (L.is_extra) {
-#pragma unroll
-                for (int p = 0; p < NPV; ++p) w.fp[p] = row[NO + p];             // g_p - D^T g_o (:603-606)
-            }
-            sync();
-#pragma unroll
-            for (int p = 0; p < NPV; ++p) fp[p] = w.fp[p];
-            float acc = 0.0f;
-#pragma unroll
-            for (int p = 0; p < NPV; ++p) acc = fmaf(row[NO + p], fp[p], acc);
-            dsum = acc / mypiv;
-        }
     }
     if (!solved) {                                             // partial pivoting (near-singular Jacobians, or forced)
-        float row[NY];
-        jacobian_row<0, NY>(L, v, u, t1, t2, row);
-#pragma unroll
-        for (int c = 0; c < NY; ++c) row[c] = fmaf(isx, w.vec[c], row[c]);
+        grg_row(w, L, v, u, t1, t2, row);
         gj_static<0, 6, 6, 0, NY, TabGrg0>(row);               // the six unit pivots (only the extra row has entries there)
-        const float mypiv = gj_dynamic<6, NEQ, 0, NY>(row, mycol);
-        if (L.is_extra) {
-#pragma unroll
-            for (int p = 0; p < NPV; ++p) w.fp[p] = row[NO + p];
-        }
-        sync();
-#pragma unroll
-        for (int p = 0; p < NPV; ++p) fp[p] = w.fp[p];
-        float acc = 0.0f;
-#pragma unroll
-        for (int p = 0; p < NPV; ++p) acc = fmaf(row[NO + p], fp[p], acc);
-        dsum = acc / mypiv;
+        mypiv = gj_dynamic<6, NEQ, 0, NY>(row, mycol);
     }
+    if (L.is_extra) {
+#pragma unroll
+        for (int p = 0; p < NPV; ++p) w.fp[p] = row[NO + p];                     // g_p - D^T g_o (:603-606)
+    }
+    sync();
+    float fp[NPV], acc = 0.0f;
+#pragma unroll
+    for (int p = 0; p < NPV; ++p) fp[p] = w.fp[p];
+#pragma unroll
+    for (int p = 0; p < NPV; ++p) acc = fmaf(row[NO + p], fp[p], acc);
+    const float dsum = acc / mypiv;                            // row lanes: sum_p row[NO + p] fp[p] / pivot = (D fp)[mycol]
     // full gradient by component (:608-610): partial components = fp (lanes 32..46), other components = -(D fp) (row lanes:
     // the unknown of the pivot they own)
     int var = L.own_var;

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(RPO_WAVE * kWaves) void evopf_eval_kernel(EvalArgs 
                     raw[hd] = (((red_s[hd][0][tid][wave] + red_s[hd][1][tid][wave]) + red_s[hd][2][tid][wave]) + red_s[hd][3][tid][wave]) +
                               gemm_bias(hd ? net.b1b : net.b1, tid);
                 float lo, hi;
-                partial_box(w, tid, lo, hi);                     // (== row_box of the Gaussian head kernel: the same table and state)
+                partial_box(w, tid, lo, hi);                     // (basic_box, as row_box of the Gaussian head kernel: the same table and state)
                 if (GAUSS) {
                     const float scale = (hi - lo) * 0.5f;
                     z = rpo_head_dev::gauss_head_row(raw[0], raw[GAUSS], 0.0f, scale, lo + scale, lo, hi, 1, nullptr);

@@ -15,8 +15,9 @@
 // (Hessian row from the textbook second derivatives of the polar power-flow equations; the Jacobian entries are evopf_dev.h's
 // jac_entry, read by row in the equation lanes and by column in the variable lanes), keeps it in 56 registers and the wave
 // eliminates it by Gauss-Jordan with a dynamic pivot per column (the matrix is symmetric indefinite and its (2, 2) block has
-// zeros on the diagonal at the load buses), as gj_dynamic does for 28 rows: rows are not swapped, every lane remembers the
-// unknown its row ended up solving.  The lane that owns a bounded variable (vm lanes; the equation lane of a generator bus owns
+// zeros on the diagonal at the load buses): evopf_dev.h's gj_dynamic, the routine of the 28-row systems' fallback, with the
+// pivot picker for rows in all 64 lanes (PickExact64) -- rows are not swapped, every lane remembers the unknown its row ended
+// up solving.  The lane that owns a bounded variable (vm lanes; the equation lane of a generator bus owns
 // that generator's pg or qg) keeps its two slacks and two multipliers in registers; x lives in w.a, lambda in w.dir, the
 // solution passes through w.vec.  Nothing else is shared, and nothing outside the workspace is written but the two outputs.
 //
@@ -53,31 +54,6 @@ struct OpfArgs {
     int max_iters;
     const float* consts;
 };
-
-// Gauss-Jordan on the NK x (NK + 1) system held one row per lane, the pivot of column k = the largest |entry| among the rows
-// that own no pivot yet (lowest lane among equals; if every candidate is a NaN, the lowest candidate lane).  Rows are neither
-// swapped nor normalised: on return the lane's row solves unknown `mycol` and row[NK] / (return value) is its value.
-__device__ __forceinline__ float gj_wave(float (&row)[NK + 1], int& mycol) {
-    const int lane = lane_id();
-    bool used = lane >= NK;
-    mycol = lane;
-    float mypiv = 1.0f;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        const float mag = used ? 0.0f : fabsf(row[k]);
-        const float top = rpo_wave_max_nonneg(mag);
-        unsigned long long cand = __builtin_amdgcn_ballot_w64(!used && mag == top);
-        if (cand == 0ull) cand = __builtin_amdgcn_ballot_w64(!used);     // (NK - k rows are free: never empty)
-        const int p = (int)__builtin_ctzll(cand);
-        const float piv = lane_bcast(row[k], p);
-        const bool is_p = lane == p;
-        const float f = is_p ? 0.0f : -row[k] * (1.0f / piv);
-        if (is_p) { used = true; mycol = k; mypiv = piv; }
-#pragma unroll
-        for (int c = k + 1; c < NK + 1; ++c) row[c] = fmaf(f, lane_bcast(row[c], p), row[c]);
-    }
-    return mypiv;
-}
 
 __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs p) {
     __shared__ Ws wss[kOpfWaves];
@@ -215,8 +191,10 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         if (converged || it >= p.max_iters) break;
 
         // ---- (dv, dlambda), then the eliminated generator steps, slacks and multipliers
+        // (the pivot of column k: the largest |entry| among the rows that own none yet, PickExact64; on return the lane's row
+        //  solves unknown `mycol`)
         int mycol;
-        const float mypiv = gj_wave(row, mycol);
+        const float mypiv = gj_dynamic<0, NK, 0, NK + 1, PickExact64>(row, mycol);
         if (tid < NK) w.vec[mycol] = row[NK] / mypiv;
         sync();
         const float delta = w.vec[tid < NK ? tid : 0];

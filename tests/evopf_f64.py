@@ -764,7 +764,7 @@ def emu_jac_v2(f, eqs, vars_, mut=()):
 
 
 def emu_gj_static(m, kb, ke, kunit, live, rcp=True):
-    """gj_static / gauss_jordan_static on [n, R, NC] (rows beyond the pivots ride along); returns the pivots [n, R] (1 where none)."""
+    """gj_static (either reciprocal) on [n, R, NC] (rows beyond the pivots ride along); returns the pivots [n, R] (1 where none)."""
     n, rows, nc = m.shape
     piv = np.ones((n, rows), np.float32)
     with np.errstate(all="ignore"):
@@ -791,7 +791,7 @@ def emu_pivots_ok(piv, k0, ke):
 
 
 def emu_gj_dynamic(m, kb, ke):
-    """gj_dynamic / gauss_jordan_rows: partial pivoting among rows [kb, ke) by the key (|value| bits & ~31) | row, rows not
+    """gj_dynamic with PickKey32: partial pivoting among rows [kb, ke) by the key (|value| bits & ~31) | row, rows not
     swapped.  Returns (pivots [n, R], mycol [n, R])."""
     n, rows, nc = m.shape
     piv = np.ones((n, rows), np.float32)
