@@ -943,6 +943,17 @@ int rpo_evopf_evaluate(const rpo_mlp* actor_host, int gauss, int n_envs, float* 
 int rpo_evopf_opf(int n, const float* obs, int obs_stride, const float* pe, float* action_out, float* info_out, float tol,
                   int max_iters, const float* consts_dev, void* stream);
 
+/* The same kernel with its iterate visible: rpo_evopf_opf plus state_in / state_out [n, RPO_EVOPF_OPF_STATE] floats, either may
+ * be NULL (both NULL: rpo_evopf_opf).  A row is
+ *     action[43] | lambda[28] | z_u[24] | z_l[24] | mu_u[24] | mu_l[24] | gamma[1]
+ * with the bounded variables in the order pg[5], qg[5], vm[14].  With state_in the row replaces the flat start entirely (x with pe
+ * and the slack angle, lambda, slacks, multipliers, gamma) and iterations count from it; pe must then be NULL (RPO_ERR_ARG, before
+ * any HIP call, like the other refusals).  state_out receives the state at exit, the one the stop test was last evaluated on
+ * (state_out[:, :43] = action_out).  For holding the solver one iteration at a time (tests/test_evopf_opf_f64_gpu.py). */
+#define RPO_EVOPF_OPF_STATE 168
+int rpo_evopf_opf_state(int n, const float* obs, int obs_stride, const float* pe, float* action_out, float* info_out, float tol,
+                        int max_iters, const float* consts_dev, const float* state_in, float* state_out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused pipelines of one RPO iteration (rpo_amd/csrc/fused.hip): the row-local stages chained
  * inside one workgroup of 16 rows, because at 4096 lanes / batch 256 every launch is dominated by dispatch + cold-start

@@ -19,7 +19,9 @@
 // pivot picker for rows in all 64 lanes (PickExact64) -- rows are not swapped, every lane remembers the unknown its row ended
 // up solving.  The lane that owns a bounded variable (vm lanes; the equation lane of a generator bus owns
 // that generator's pg or qg) keeps its two slacks and two multipliers in registers; x lives in w.a, lambda in w.dir, the
-// solution passes through w.vec.  Nothing else is shared, and nothing outside the workspace is written but the two outputs.
+// solution passes through w.vec.  Nothing else is shared, and nothing outside the workspace is written but the two outputs --
+// and, through rpo_evopf_opf_state, the iterate itself: state_in replaces the flat start, state_out receives the state at exit
+// (two wave-uniform branches outside the loop), which is how tests/test_evopf_opf_f64_gpu.py holds the loop one iteration at a time.
 //
 // eq_resid is injection minus flow: with F = lambda_p^T P + lambda_q^T Q = sum_ik V_i V_k c_ik, the Hessian of lambda^T g is -F''.
 //   th = va_i - va_k,  G_ik = Yr[k][i], B_ik = Yi[k][i] (flows() multiplies the voltage ROW vector into Ybus)
@@ -53,7 +55,13 @@ struct OpfArgs {
     float tol;
     int max_iters;
     const float* consts;
+    const float* state_in;    // [n, RPO_EVOPF_OPF_STATE] or NULL (the flat start)
+    float* state_out;         // [n, RPO_EVOPF_OPF_STATE] or NULL
 };
+// a row of the state: action[43] | lambda[28] | z_u[24] | z_l[24] | mu_u[24] | mu_l[24] | gamma, the bounded variables in the
+// order pg[5], qg[5], vm[14]
+constexpr int kStLam = NY, kStZu = kStLam + NEQ, kStBnd = NBOUND / 2, kStGamma = kStZu + 4 * kStBnd;
+static_assert(kStGamma + 1 == RPO_EVOPF_OPF_STATE, "layout of the state row");
 
 __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs p) {
     __shared__ Ws wss[kOpfWaves];
@@ -84,6 +92,7 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
     if (is_vm) { hi = w.c[RPO_EVOPF_C_VMAX + vbus]; lo = w.c[RPO_EVOPF_C_VMIN + vbus]; }
     else if (is_pg) { hi = w.c[RPO_EVOPF_C_PMAX + gen]; lo = w.c[RPO_EVOPF_C_PMIN + gen]; }
     else if (has_u) { hi = w.c[RPO_EVOPF_C_QMAX + gen]; lo = w.c[RPO_EVOPF_C_QMIN + gen]; }
+    const int bidx = is_vm ? 2 * NG + vbus : (is_pg ? gen : NG + gen);    // the lane's bounded variable in the state row's order
     const float c2 = is_pg ? 2.0f * w.c[RPO_EVOPF_C_QUAD + gen] : 0.0f, c1 = is_pg ? w.c[RPO_EVOPF_C_LIN + gen] : 0.0f;
 
     // ---- flat start
@@ -98,6 +107,16 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         const float x0 = 0.5f * (hi + lo);
         zu = fmaxf(hi - x0, kZ0); zl = fmaxf(x0 - lo, kZ0);
         mu_u = gamma / zu; mu_l = gamma / zl;
+    }
+    if (p.state_in) {                                           // a given state replaces the flat start entirely
+        const float* st = p.state_in + (size_t)i * RPO_EVOPF_OPF_STATE;
+        if (tid < NY) w.a[tid] = st[tid];
+        if (tid < NEQ) w.dir[tid] = st[kStLam + tid];
+        if (bounded) {
+            zu = st[kStZu + bidx]; zl = st[kStZu + kStBnd + bidx];
+            mu_u = st[kStZu + 2 * kStBnd + bidx]; mu_l = st[kStZu + 3 * kStBnd + bidx];
+        }
+        gamma = st[kStGamma];
     }
     sync();
 
@@ -227,14 +246,30 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
     const float cost = rpo_wave_sum_rows(part) + w.c[RPO_EVOPF_C_CONST];
     if (tid < NY) p.action[(size_t)i * NY + tid] = w.a[tid];
     if (tid < 4) p.info[(size_t)i * 4 + tid] = tid == 0 ? cost : (tid == 1 ? resid : (tid == 2 ? (float)it : (converged ? 1.0f : 0.0f)));
+    if (p.state_out) {                                          // the state the stop test was last evaluated on
+        float* st = p.state_out + (size_t)i * RPO_EVOPF_OPF_STATE;
+        if (tid < NY) st[tid] = w.a[tid];
+        if (tid < NEQ) st[kStLam + tid] = w.dir[tid];
+        if (bounded) {
+            st[kStZu + bidx] = zu; st[kStZu + kStBnd + bidx] = zl;
+            st[kStZu + 2 * kStBnd + bidx] = mu_u; st[kStZu + 3 * kStBnd + bidx] = mu_l;
+        }
+        if (tid == 0) st[kStGamma] = gamma;
+    }
 }
 
 }  // namespace
 
 extern "C" int rpo_evopf_opf(int n, const float* obs, int obs_stride, const float* pe, float* action_out, float* info_out, float tol,
                              int max_iters, const float* consts_dev, void* stream) {
-    if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < 2 * NB) return RPO_ERR_ARG;
+    return rpo_evopf_opf_state(n, obs, obs_stride, pe, action_out, info_out, tol, max_iters, consts_dev, nullptr, nullptr, stream);
+}
+
+extern "C" int rpo_evopf_opf_state(int n, const float* obs, int obs_stride, const float* pe, float* action_out, float* info_out,
+                                   float tol, int max_iters, const float* consts_dev, const float* state_in, float* state_out,
+                                   void* stream) {
+    if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < 2 * NB || (state_in && pe)) return RPO_ERR_ARG;
     if (!obs || !action_out || !info_out || !consts_dev) return RPO_ERR_NULL;
-    const OpfArgs args{n, obs, obs_stride, pe, action_out, info_out, tol, max_iters, consts_dev};
+    const OpfArgs args{n, obs, obs_stride, pe, action_out, info_out, tol, max_iters, consts_dev, state_in, state_out};
     return launch(evopf_opf_kernel, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
 }

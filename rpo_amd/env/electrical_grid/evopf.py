@@ -294,7 +294,7 @@ class EVOPFEnv(HardConstraintEnv):
                                       "there is no CPU path" % self.device)
         return fn
 
-    def opf(self, state, pe=None, tol=1e-4, max_iters=40, out=None):
+    def opf(self, state, pe=None, tol=1e-4, max_iters=40, out=None, state_in=None, state_out=None):
         """The cheapest dispatch of every row's single-step AC-OPF, on the device (rpo_evopf_opf, csrc/evopf_opf.hip).
 
         ``state`` [n, 57] observations or [n, 28] demands (pd, qd); ``pe`` [n, 5] battery power, a PARAMETER of the problem
@@ -303,7 +303,10 @@ class EVOPFEnv(HardConstraintEnv):
         start; stops when the primal infeasibility, |L_x|_inf and z^T mu are all below ``tol``, or after ``max_iters``
         iterations (``converged`` False: infeasible single-step problems exist, and end this way).  Returns an ``OpfResult`` of
         device tensors; nothing synchronises with the host.  ``out``: an earlier result of the same n, whose buffers are
-        reused."""
+        reused.  ``state_in`` / ``state_out``: contiguous float32 device tensors [n, 168] (action[43] | lambda[28] | z_u[24] |
+        z_l[24] | mu_u[24] | mu_l[24] | gamma, bounded variables in the order pg, qg, vm) -- the interior-point state to start
+        from in place of the flat start (it carries pe: ``pe`` must then be None; ``iters`` counts from it) and the state at
+        exit, written in place."""
         fn = self._opf_kernel()
         tol, iters = float(tol), int(max_iters)
         if not tol > 0.0 or iters != max_iters or iters < 0:
@@ -329,7 +332,16 @@ class EVOPFEnv(HardConstraintEnv):
                 or not (out.action.is_contiguous() and out.info.is_contiguous()) \
                 or out.action.dtype != torch.float32 or out.info.dtype != torch.float32:
             raise ValueError("opf: out must be an OpfResult of %d rows on %s" % (n, state.device))
-        fn(self.kernels, state, pe, out.action, out.info, tol, iters)
+        for name, st in (("state_in", state_in), ("state_out", state_out)):
+            if st is not None and (not isinstance(st, torch.Tensor) or tuple(st.shape) != (n, 168) or st.dtype != torch.float32
+                                   or st.device != state.device or not st.is_contiguous()):
+                raise ValueError("opf: %s must be a contiguous float32 tensor [%d, 168] on %s" % (name, n, state.device))
+        if state_in is not None and pe is not None:
+            raise ValueError("opf: state_in carries pe (columns 38..42): pe must be None with it")
+        if state_in is None and state_out is None:
+            fn(self.kernels, state, pe, out.action, out.info, tol, iters)
+        else:
+            fn(self.kernels, state, pe, out.action, out.info, tol, iters, state_in=state_in, state_out=state_out)
         return out
 
     def opt_solve(self, X, solver_type="hip", tol=1e-4):

@@ -810,11 +810,16 @@ def evopf_project_profile(kernels, obs, ap_raw, action, iters, max_steps, corr_l
 OPF_DEMAND = 2 * 14                  # floats of an observation row the OPF reads: pd[14], qd[14]
 
 
-def evopf_opf(kernels, obs, pe, action, info, tol, max_iters):
+OPF_STATE = 168                      # RPO_EVOPF_OPF_STATE: action[43] | lambda[28] | z_u[24] | z_l[24] | mu_u[24] | mu_l[24] | gamma
+
+
+def evopf_opf(kernels, obs, pe, action, info, tol, max_iters, state_in=None, state_out=None):
     """Single-step AC-OPF of every row (rpo_evopf_opf): obs [n, >= 28] float32 rows with unit column stride (observations, demands
     alone, or a column slice of something wider: only the first 28 floats of a row are read), pe [n, 5] or None (zeros) -> action
     [n, 43], info [n, 4] = (cost, largest stop quantity at exit, iterations, converged).  ``kernels``: an EvopfKernels (constant
-    table).  A function of the backend like ``evopf_evaluate``, not a method: the env kernel classes keep their public methods."""
+    table).  A function of the backend like ``evopf_evaluate``, not a method: the env kernel classes keep their public methods.
+    ``state_in`` / ``state_out`` [n, 168] contiguous float32 or None (rpo_evopf_opf_state): the interior-point state to start
+    from instead of the flat start (``pe`` must then be None: the row carries it) and the state at exit."""
     if action is None or action.dim() != 2 or action.shape[1] != kernels.action_dim or action.shape[0] < 1:
         raise RpoHipError("evopf_opf: action must be [n >= 1, %d], got %s" % (kernels.action_dim, None if action is None else tuple(action.shape)))
     n = action.shape[0]
@@ -823,9 +828,20 @@ def evopf_opf(kernels, obs, pe, action, info, tol, max_iters):
                           % (n, OPF_DEMAND, None if obs is None else (tuple(obs.shape), obs.stride())))
     if info is None or tuple(info.shape) != (n, 4) or (pe is not None and tuple(pe.shape) != (n, 5)):
         raise RpoHipError("evopf_opf: info must be [%d, 4] and pe [%d, 5] or None" % (n, n))
+    for name, st in (("state_in", state_in), ("state_out", state_out)):
+        if st is not None and (tuple(st.shape) != (n, OPF_STATE) or st.dtype != torch.float32 or not st.is_contiguous()):
+            raise RpoHipError("evopf_opf: %s must be a contiguous float32 [%d, %d] or None, got %s %s"
+                              % (name, n, OPF_STATE, tuple(st.shape), st.dtype))
+    if state_in is not None and pe is not None:
+        raise RpoHipError("evopf_opf: state_in carries pe (columns 38..42 of its rows): pe must be None with it")
     stride = int(obs.stride(0)) if n > 1 else int(obs.shape[1])
-    check(_lib.load().rpo_evopf_opf(n, _p(obs, contiguous=False), stride, _p(pe, allow_none=True), _p(action), _p(info), float(tol),
-                                    int(max_iters), kernels._c(action), _stream()), "rpo_evopf_opf")
+    if state_in is None and state_out is None:
+        check(_lib.load().rpo_evopf_opf(n, _p(obs, contiguous=False), stride, _p(pe, allow_none=True), _p(action), _p(info),
+                                        float(tol), int(max_iters), kernels._c(action), _stream()), "rpo_evopf_opf")
+        return
+    check(_lib.load().rpo_evopf_opf_state(n, _p(obs, contiguous=False), stride, _p(pe, allow_none=True), _p(action), _p(info),
+                                          float(tol), int(max_iters), kernels._c(action), _p(state_in, allow_none=True),
+                                          _p(state_out, allow_none=True), _stream()), "rpo_evopf_opf_state")
 
 
 class PendulumKernels(_FusedEnvKernels):

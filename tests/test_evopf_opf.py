@@ -1,8 +1,14 @@
 """The single-step AC-OPF of EVOPF-v0 without a GPU: the float64 yardstick (tests/evopf_opf_f64.py) against finite differences
 and against scipy's SLSQP answers in tests/golden/evopf_opf.npz; the public surface (``EVOPFEnv.opf`` / ``opt_solve``,
 ``EvalTrajectory.opf_gap``) over a stand-in for the backend function; the C-ABI entry point ``rpo_evopf_opf`` and its refusals.
-The kernel itself: tests/test_evopf_opf_gpu.py."""
+The kernel itself: tests/test_evopf_opf_gpu.py.
+
+One iteration at a time (tests/test_evopf_opf_f64_gpu.py on the device): the float32 emulation ``emu_opf`` passes every checker
+of ``step_ref`` on the trajectory states of the 70 fixture rows and on the synthetic states under both constants tables, the
+constants C_REF are what it measures there, every seeded mutation fails a checker on those same inputs, ``step_ref`` iterated is
+``solve()`` as it was before the refactor, and the state seam's entry point and keywords refuse what they must."""
 import ctypes
+import functools
 import inspect
 import os
 
@@ -89,9 +95,9 @@ class FakeOpf(object):
     def __init__(self):
         self.calls = []
 
-    def __call__(self, kernels, obs, pe, action, info, tol, max_iters):
+    def __call__(self, kernels, obs, pe, action, info, tol, max_iters, state_in=None, state_out=None):
         self.calls.append(dict(obs=obs[:, :28].clone(), pe=None if pe is None else pe.clone(), tol=tol, max_iters=max_iters,
-                               width=obs.shape[1], action=action, info=info))
+                               width=obs.shape[1], action=action, info=info, state_in=state_in, state_out=state_out))
         action.zero_()
         action[:, :5] = obs[:, :5]
         if pe is not None:
@@ -260,7 +266,8 @@ def test_not_implemented_with_a_reason_without_the_kernel():
 # ------------------------------------------------------------------------------------------------ binding and C ABI
 def test_binding_is_a_backend_function():
     assert callable(ops.evopf_opf) and not hasattr(ops.EvopfKernels, "opf") and not hasattr(ops.EvopfKernels, "evopf_opf")
-    assert list(inspect.signature(ops.evopf_opf).parameters) == ["kernels", "obs", "pe", "action", "info", "tol", "max_iters"]
+    assert list(inspect.signature(ops.evopf_opf).parameters) == ["kernels", "obs", "pe", "action", "info", "tol", "max_iters", "state_in",
+                                                                        "state_out"]
     assert not hasattr(ob, "evopf_opf")
     env = EVOPFEnv(device="cpu")
     with pytest.raises(_lib.RpoHipError):                        # CPU tensors are refused like by every other op
@@ -299,3 +306,246 @@ def test_entry_point_is_declared_exported_and_refuses_before_any_launch():
             assert call(**dict(full, **{name: None})) == NULL, name
         assert call(**dict(full, n=0)) == ARG and call(**dict(full, obs_stride=27)) == ARG
         assert call(**dict(full, pe=None)) not in (0, ARG, NULL)     # pe may be NULL: this one reaches the launch, and fails there
+
+
+# ------------------------------------------------------------------------------------------------ one iteration at a time
+def _solve_before_refactor(demand, pe=None, tol=1e-4, max_iters=40, grid=opf64.GRID):
+    """``evopf_opf_f64.solve`` as it stood before ``ip_eval`` / ``ip_advance`` were cut out of it, kept verbatim: what
+    test_step_ref_iterated_is_solve holds the refactored helper to, bit for bit (both run on the same LAPACK)."""
+    ev_, NBND, NG, NX, NEQ, XIDX = ev, opf64.NBND, opf64.NG, opf64.NX, opf64.NEQ, opf64.XIDX
+    XMAX, XMIN, COST1, COST2, Z0, GAMMA0, XI, SIGMA = (opf64.XMAX, opf64.XMIN, opf64.COST1, opf64.COST2, opf64.Z0, opf64.GAMMA0,
+                                                       opf64.XI, opf64.SIGMA)
+    s = np.asarray(demand, dtype=np.float64)[None, :2 * opf64.NB]
+    pe = np.zeros(grid.ne) if pe is None else np.asarray(pe, dtype=np.float64)
+    a = opf64.flat_start(pe, grid)
+    h = np.concatenate([a[:NBND] - XMAX, XMIN - a[:NBND]])
+    z = np.maximum(-h, Z0)
+    gamma = GAMMA0
+    mu = gamma / z
+    lam = np.zeros(NEQ)
+    it, converged = 0, False
+    while True:
+        g = ev_.eq_resid(s, a[None], grid)[0]
+        J = ev_.eq_jac(a[None], grid)[0][:, XIDX]
+        h = np.concatenate([a[:NBND] - XMAX, XMIN - a[:NBND]])
+        df = np.zeros(NX)
+        df[:NG] = COST2 * a[:NG] + COST1
+        dmu = np.zeros(NX)
+        dmu[:NBND] = mu[:NBND] - mu[NBND:]
+        lx = df + J.T @ lam + dmu
+        with np.errstate(all="ignore"):
+            residual = max(np.abs(g).max(), h.max(), np.abs(lx).max(), float(z @ mu))
+        if residual < tol:
+            converged = True
+            break
+        if it >= max_iters:
+            break
+        with np.errstate(all="ignore"):
+            M = opf64.lagr_hessian(a, lam, grid)[np.ix_(XIDX, XIDX)]
+            M[np.arange(NG), np.arange(NG)] += COST2
+            M[np.arange(NBND), np.arange(NBND)] += mu[:NBND] / z[:NBND] + mu[NBND:] / z[NBND:]
+            N = lx.copy()
+            N[:NBND] += (mu[:NBND] * h[:NBND] + gamma) / z[:NBND] - (mu[NBND:] * h[NBND:] + gamma) / z[NBND:]
+            K = np.zeros((NX + NEQ, NX + NEQ))
+            K[:NX, :NX], K[:NX, NX:], K[NX:, :NX] = M, J.T, J
+            try:
+                sol = np.linalg.solve(K, np.concatenate([-N, -g]))
+            except np.linalg.LinAlgError:
+                sol = np.full(NX + NEQ, np.nan)
+            dx, dlam = sol[:NX], sol[NX:]
+            dh = np.concatenate([dx[:NBND], -dx[:NBND]])
+            dz = -h - z - dh
+            dm = -mu + (gamma - mu * dz) / z
+            neg = dz < 0
+            alpha_p = min(XI * np.min(z[neg] / -dz[neg]), 1.0) if neg.any() else 1.0
+            neg = dm < 0
+            alpha_d = min(XI * np.min(mu[neg] / -dm[neg]), 1.0) if neg.any() else 1.0
+            a[XIDX] += alpha_p * dx
+            z = z + alpha_p * dz
+            lam = lam + alpha_d * dlam
+            mu = mu + alpha_d * dm
+            gamma = SIGMA * float(z @ mu) / (2 * NBND)
+        it += 1
+    return dict(action=a, cost=float(ev_.obj_fn(a[None], grid)[0]), iters=it, converged=converged, residual=float(residual))
+
+
+def test_step_ref_iterated_is_solve():
+    """``step_ref`` on the reference's float64 case, iterated from the flat start, walks ``solve()``'s iterates -- and ``solve()``
+    itself, which now runs on the same two functions, returns what it did before, bit for bit."""
+    demand, pe = opf64.fixture_states()
+    for i in (0, 50, 100, 191, 383):
+        old = _solve_before_refactor(demand[i], pe[i], tol=TOL, max_iters=40)
+        new = opf64.solve(demand[i], pe[i], tol=TOL, max_iters=40)
+        for k in ("action", "cost", "iters", "converged", "residual"):
+            assert np.array_equal(old[k], new[k], equal_nan=True), (i, k)
+        state = opf64.join_state(*opf64.flat_state(pe[i]))[None]
+        for it in range(old["iters"] + 1):
+            r = opf64.step_ref(None, demand[i][None], state, bound=False)
+            assert (r["stop"][0, 3] < TOL) == (it == old["iters"] and bool(old["converged"])), (i, it)
+            if it < old["iters"]:
+                state = r["state"]
+        assert np.array_equal(state[0, :43], old["action"]) and r["stop"][0, 3] == old["residual"], i
+
+
+OPF_SEED, OPF_N, KMAX = 3, 65, 12
+
+
+@functools.lru_cache(maxsize=None)
+def opf_inputs():
+    """The inputs of the GPU file with the emulation in the kernel's place: name -> (table, demand, states [n, 168], step_ref
+    there); the trajectory states k = 0 .. 12 of the 70 fixture rows stacked (910 rows) and opf_states under both tables."""
+    import evopf_f64 as E
+    tab = E.consts_table()
+    shifted = opf64.shifted_table(tab)
+    demand, pe = opf64.fixture_rows()
+
+    def run(state, iters):
+        return opf64.emu_opf(tab, demand, pe if state is None else state, 1e-30, iters)["state"]
+    traj = opf64.trajectory_states(run, KMAX).reshape(-1, opf64.OPF_STATE)
+    out = {"trajectory": (tab, np.tile(demand, (KMAX + 1, 1)), traj)}
+    for name, t in (("synthetic", tab), ("synthetic_shifted", shifted)):
+        d, st = opf64.opf_states(OPF_N, OPF_SEED, t)
+        out[name] = (t, d, st)
+    return {k: v + (opf64.step_ref(*v),) for k, v in out.items()}
+
+
+def emulation_ratios(mut=()):
+    """One emulated step (and the stop quantities and the cost) from every input state against step_ref -> ({group: worst ratio},
+    {name: rows not judged}, violations of the pivot rule)."""
+    worst, left, picks = {}, {}, 0
+    for name, (tab, demand, states, ref) in opf_inputs().items():
+        out = opf64.emu_opf(tab, demand, states, 1e-30, 1, mut)
+        at = opf64.emu_opf(tab, demand, states, 1e-30, 0, mut)
+        r, unj = opf64.check_step(ref, out["state"])
+        r["opf_stop"], _ = opf64.check_stop(ref, np.concatenate([at["stop"], at["info"][:, 1:2]], axis=1))
+        rc, uc = opf64.ratios("opf_cost", out["info"][:, 0], *opf64.cost_ref(tab, out["action"]))
+        r["opf_cost"] = float(rc[~uc].max())
+        for g, v in r.items():
+            worst[g] = max(worst.get(g, 0.0), v)
+        left[name], picks = unj, picks + out["picks"]
+    return worst, left, picks
+
+
+@functools.lru_cache(maxsize=None)
+def emulation():
+    return emulation_ratios()
+
+
+def test_emulation_passes_every_checker():
+    worst, left, picks = emulation()
+    print({g: round(v, 3) for g, v in worst.items()}, {k: int(v.sum()) for k, v in left.items()})
+    assert set(worst) == set(opf64.C_REF) and picks == 0
+    for group, ratio in worst.items():
+        assert ratio <= 1.0, (group, ratio)
+    # rows not judged: the NaN row; late iterates (and only late ones, k >= 4) of the trajectories, the five infeasible rows from
+    # k = 8 on; of the synthetic states the wide odd rows -- never one of the rows built for a purpose
+    traj = left["trajectory"].reshape(KMAX + 1, 70)
+    assert not traj[:4].any() and not traj[:10, :65].any() and traj[:, :65].mean() <= 0.05
+    for name in ("synthetic", "synthetic_shifted"):
+        rows = np.nonzero(left[name])[0]
+        assert 9 in rows and not (set(rows) - {9}) & set(range(opf64.N_SPECIAL)) and (rows[rows != 9] % 2 == 1).all()
+        assert len(rows) <= 0.4 * OPF_N
+    print("not judged: trajectory %s per k, synthetic %s" % (traj.sum(axis=1).tolist(), [int(left[k].sum()) for k in ("synthetic", "synthetic_shifted")]))
+
+
+def test_yardstick_constants():
+    """C_REF[group] is the emulation's own worst error in units of eps32 * bound (ratio * MARGIN * C_REF) on these inputs: not
+    above it, and not below 0.9 of it."""
+    worst, _, _ = emulation()
+    for group, c in opf64.C_REF.items():
+        measured = worst[group] * opf64.MARGIN * c
+        print("%-10s measured %.4f  C_REF %.3f" % (group, measured, c))
+        assert 0.9 * c <= measured <= c, (group, measured, c)
+
+
+@pytest.mark.parametrize("mut", opf64.MUTATIONS)
+def test_mutation_fails_a_checker(mut):
+    worst, _, picks = emulation_ratios((mut,))
+    print(mut, {g: round(v, 2) for g, v in worst.items()}, "pivot rule violations", picks)
+    assert max(worst.values()) > 1.0 or picks > 0, mut
+
+
+# ------------------------------------------------------------------------------------------------ the state seam: keywords, ABI
+def test_opf_state_keywords_pass_through_and_are_checked(fake_env):
+    env, fake = fake_env
+    s = states(4)
+    st_in, st_out = torch.zeros(4, 168), torch.empty(4, 168)
+    res = env.opf(s, state_in=st_in, state_out=st_out, max_iters=1)
+    assert isinstance(res, OpfResult) and fake.calls[-1]["state_in"] is st_in and fake.calls[-1]["state_out"] is st_out
+    assert fake.calls[-1]["pe"] is None and fake.calls[-1]["max_iters"] == 1
+    env.opf(s, state_out=st_out)
+    assert fake.calls[-1]["state_in"] is None and fake.calls[-1]["state_out"] is st_out
+    env.opf(s, pe=np.zeros((4, 5), np.float32), state_out=st_out)                  # pe with state_out alone is fine
+    env.opf(s)
+    assert fake.calls[-1]["state_in"] is None and fake.calls[-1]["state_out"] is None
+    n = len(fake.calls)
+    bad = (torch.zeros(3, 168), torch.zeros(4, 167), torch.zeros(4, 168, dtype=torch.float64), torch.zeros(4, 336)[:, ::2],
+           torch.zeros(168), np.zeros((4, 168), np.float32))
+    for name in ("state_in", "state_out"):
+        for t in bad:
+            with pytest.raises(ValueError, match=name):
+                env.opf(s, **{name: t})
+    with pytest.raises(ValueError, match="pe"):
+        env.opf(s, pe=np.zeros((4, 5), np.float32), state_in=st_in)
+    assert len(fake.calls) == n                                                   # refused before the backend was called
+
+
+def test_binding_checks_the_state_arguments():
+    env = EVOPFEnv(device="cpu")
+    base = dict(obs=torch.zeros(2, 57), pe=None, action=torch.zeros(2, 43), info=torch.zeros(2, 4))
+
+    def call(**kw):
+        a = dict(base, **kw)
+        ops.evopf_opf(env.kernels, a["obs"], a["pe"], a["action"], a["info"], 1e-4, 40, state_in=a.get("state_in"),
+                      state_out=a.get("state_out"))
+    assert ops.OPF_STATE == _lib.CONST["RPO_EVOPF_OPF_STATE"] == opf64.OPF_STATE == 168
+    for name in ("state_in", "state_out"):
+        for t in (torch.zeros(3, 168), torch.zeros(2, 167), torch.zeros(2, 168, dtype=torch.float64), torch.zeros(2, 336)[:, ::2]):
+            with pytest.raises(_lib.RpoHipError, match="evopf_opf: %s" % name):
+                call(**{name: t})
+    with pytest.raises(_lib.RpoHipError, match="pe must be None"):
+        call(pe=torch.zeros(2, 5), state_in=torch.zeros(2, 168))
+    with pytest.raises(_lib.RpoHipError):                        # well-formed CPU tensors: refused like by every other op
+        call(state_in=torch.zeros(2, 168), state_out=torch.zeros(2, 168))
+
+
+def test_state_entry_point_is_declared_exported_and_refuses_before_any_launch():
+    V, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    assert _lib.PROTOTYPES["rpo_evopf_opf_state"] == [I, V, I, V, V, V, F, I, V, V, V, V]
+    assert _lib.PROTOTYPES["rpo_evopf_opf"] == [I, V, I, V, V, V, F, I, V, V]        # the existing entry point keeps its signature
+    assert _lib.CONST["RPO_ABI_VERSION"] == 6                                        # an added entry point: no new ABI version
+    lib = _lib.load()
+    assert hasattr(lib, "rpo_evopf_opf_state")
+    good = dict(n=4, obs=None, obs_stride=57, pe=None, action_out=None, info_out=None, tol=1e-4, max_iters=40, consts_dev=None,
+                state_in=None, state_out=None, stream=None)
+
+    def call(**kw):
+        return lib.rpo_evopf_opf_state(*dict(good, **kw).values())
+    for kw in (dict(n=0), dict(n=-2), dict(max_iters=-1), dict(tol=0.0), dict(tol=-1e-4), dict(tol=float("nan")), dict(obs_stride=27)):
+        assert call(**kw) == ARG, kw
+    assert call() == NULL and call(max_iters=0) == NULL
+    buf = (ctypes.c_float * 1024)()
+    r = ctypes.c_void_p(ctypes.addressof(buf))                   # (compared against NULL only; a refusal dereferences nothing)
+    assert call(pe=r, state_in=r) == ARG                          # pe together with state_in: before the NULL checks, before a launch
+    assert call(pe=r, state_out=r) == NULL and call(state_in=r, state_out=r) == NULL
+    if torch.cuda.device_count() == 0:
+        full = dict(obs=r, action_out=r, info_out=r, consts_dev=r, state_in=r, state_out=r)
+        for name in ("obs", "action_out", "info_out", "consts_dev"):
+            assert call(**dict(full, **{name: None})) == NULL, name
+        assert call(**dict(full, pe=r)) == ARG
+        assert call(**full) not in (0, ARG, NULL)                 # complete arguments reach the launch, and fail there without a GPU
+
+
+def test_iteration_classes_hold_a_third_of_the_converged_rows():
+    """The rows the GPU file holds to EQUAL iteration counts (float64 residual outside [tol / 2, 2 tol] at every iterate): at least
+    a third of the converging ones, on its 70 rows and on the fixture's first 70 states."""
+    demand, pe = opf64.fixture_rows()
+    iters, conv, decisive = opf64.iteration_classes(demand, pe, TOL)
+    ref = opf64.solve_many(demand.astype(np.float64), pe.astype(np.float64), tol=TOL, max_iters=40)
+    assert np.array_equal(iters, ref["iters"]) and np.array_equal(conv, ref["converged"])
+    first = opf64.fixture_states()
+    _, conv0, decisive0 = opf64.iteration_classes(first[0][:70], first[1][:70], TOL)
+    print("decisive: %d of %d converged (the GPU file's rows), %d of %d (the fixture's first 70)"
+          % ((decisive & conv).sum(), conv.sum(), (decisive0 & conv0).sum(), conv0.sum()))
+    assert conv.sum() == 65 and (decisive & conv).sum() * 3 >= conv.sum()
+    assert conv0.sum() == 69 and (decisive0 & conv0).sum() * 3 >= conv0.sum()
