@@ -954,6 +954,21 @@ int rpo_evopf_opf(int n, const float* obs, int obs_stride, const float* pe, floa
 int rpo_evopf_opf_state(int n, const float* obs, int obs_stride, const float* pe, float* action_out, float* info_out, float tol,
                         int max_iters, const float* consts_dev, const float* state_in, float* state_out, void* stream);
 
+/* The single-step AC-OPF with the battery power a VARIABLE (EVOPFEnv.opf(pe="free"), evaluate_opf; the free-pe instance of the
+ * same kernel): for each of n observations (obs_stride >= 57 floats between rows: the demand, the five states of charge and the
+ * current price of the row are read) minimise obj_fn(pg) + sum_j pe_cost[j] pe[j] over (pg, qg, vm, va, pe[5]) subject to
+ * eq_resid = 0, the 48 bounds on pg, qg, vm and the 10 battery bounds battery_bounds(soc) that ineq_resid uses.  pe_cost [n,5], or
+ * NULL: (we / wg) * price of the row in every component, with which the optimum maximises the env's one-step reward.  pe enters
+ * the real-power equation of its generator bus with derivative +1, as eq_resid adds it (not eq_jac's -1).  Same method, flat
+ * start (pe at the middle of its box), stop test and outputs as rpo_evopf_opf with 58 inequalities; action_out [n,43] carries
+ * the optimal pe in columns 38..42, info_out [n,4] column 0 stays obj_fn of the returned point.  An empty battery box (a state of
+ * charge far outside its band) ends as not converged at max_iters.  No state seam.  A row's output does not depend on the other
+ * rows of the launch.  Reads obs, pe_cost and consts_dev, writes the two outputs, nothing else.
+ * Refused before any HIP call, sizes before pointers: n <= 0, max_iters < 0, tol <= 0 (or NaN), obs_stride < 57 (RPO_ERR_ARG); a
+ * NULL obs, action_out, info_out or consts_dev (RPO_ERR_NULL). */
+int rpo_evopf_opf_free(int n, const float* obs, int obs_stride, const float* pe_cost, float* action_out, float* info_out, float tol,
+                       int max_iters, const float* consts_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused pipelines of one RPO iteration (rpo_amd/csrc/fused.hip): the row-local stages chained
  * inside one workgroup of 16 rows, because at 4096 lanes / batch 256 every launch is dominated by dispatch + cold-start

@@ -56,6 +56,12 @@ the groups run side by side, each padded to whole 64-lane tiles, as S x padded l
 (``rpo_<env>_evaluate_noise_sweep``: the fused kernel's NSW instances read their group's sigma out of a device table and key the
 draw by the episode within the group, not by the lane); every other configuration runs the S calls ("sweep").
 
+The OPF controller (``evaluate_opf(episodes, seed=...)`` -> ``EvalResult`` with ``path`` "opf", EVOPF-v0 on a GPU only): the stepwise
+loop on ``evaluate()``'s episodes -- the same ``_initial_env``, so the same days and initial states of charge under the same seed --
+with the single-step AC-OPF of the lane's observation in the policy's place (``_run_stepwise(producer=)``: one launch of
+``rpo_evopf_opf_free``, or of ``rpo_evopf_opf`` with idle batteries, straight into the env's action rows), a hard-feasible
+baseline whose per-episode differences to a policy's result are paired; ``opf_iters`` / ``opf_converged`` [episode, step].
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
 does not record trajectories and produces no per-constraint reports.  With the trainer argument ``keep_best`` every point's
@@ -87,7 +93,10 @@ class EvalResult(object):
     whose max inequality violation exceeds the vector env's ``viol_thresh``; ``proj_iters``: GRG iterations summed over the
     episode; ``nonfinite``: a live step produced a non-finite reward or violation.  ``path``: "fused" or "stepwise".
     ``trajectory`` / ``constraints``: the ``EvalTrajectory`` of ``record=`` / the ``ConstraintReport`` of ``constraints=True``,
-    else None.  ``obs_noise``: the float32 sigma vector [obs_dim] of ``obs_noise=``, None for a clean evaluation."""
+    else None.  ``obs_noise``: the float32 sigma vector [obs_dim] of ``obs_noise=``, None for a clean evaluation.
+    ``evaluate_opf`` (``path`` "opf"; ``proj_iters`` sums the solver's iterations): ``opf_iters`` int32 / ``opf_converged`` bool
+    [episode, step], the solver's iteration count and stop flag of every live step (0 / False past the episode's end); None
+    otherwise."""
 
     FIELDS = ("ret", "length", "mean_ineq", "mean_eq", "max_ineq", "max_eq", "viol_steps", "proj_iters", "nonfinite")
 
@@ -107,6 +116,7 @@ class EvalResult(object):
         self.trajectory = trajectory
         self.constraints = constraints
         self.obs_noise = None if obs_noise is None else np.array(obs_noise, dtype=np.float32)
+        self.opf_iters = self.opf_converged = None               # evaluate_opf: [episode, step]
 
     @property
     def episodes(self):
@@ -190,9 +200,9 @@ class EvalTrajectory(object):
         with np.load(path) as z:
             return cls(float(z["viol_thresh"]), **{name: z[name] for name in cls.ARRAYS})
 
-    def opf_gap(self, env, tol=1e-4, max_iters=40):
+    def opf_gap(self, env, tol=1e-4, max_iters=40, pe="policy"):
         """The optimality gap of every recorded step of an EVOPF-v0 evaluation (``opf_gap`` below) -> ``OpfGap``."""
-        return opf_gap(self, env, tol=tol, max_iters=max_iters)
+        return opf_gap(self, env, tol=tol, max_iters=max_iters, pe=pe)
 
     def __repr__(self):
         return "EvalTrajectory(episodes=%d, horizon=%d, steps=%d)" % (self.episodes, self.horizon, int(self.valid.sum()))
@@ -249,11 +259,16 @@ class OpfGap(object):
         return "OpfGap(steps=%d, converged=%.3f, mean gap=%.4g)" % (int(self.valid.sum()), self.converged_rate(), self.mean())
 
 
-def opf_gap(trajectory, env, tol=1e-4, max_iters=40):
+def opf_gap(trajectory, env, tol=1e-4, max_iters=40, pe="policy"):
     """For every valid step of ``trajectory`` (``trainer.evaluate(..., record=...)`` on EVOPF-v0): ``env.opf`` at the step's
     recorded observation with the recorded action's pe, in one launch over all steps, against ``env.obj_fn`` of the recorded
     action -> ``OpfGap``.  ``env``: an EVOPFEnv on a GPU device (NotImplementedError otherwise, with the reason).  With
-    ``evaluate(obs_noise=)`` the recorded observation is the noisy one the policy saw."""
+    ``evaluate(obs_noise=)`` the recorded observation is the noisy one the policy saw.  ``pe="free"``: against the optimum over the
+    full action, ``env.opf(obs, pe="free")`` -- ``cost_policy`` and ``cost_opt`` then hold ``obj_fn + pe_cost . pe`` with the
+    default ``pe_cost`` ((we / wg) * the step's price: minus the step's reward over wg) of the recorded action and of the free
+    optimum in the recorded observation, and ``gap`` is their DIFFERENCE (that objective has no sign to divide by)."""
+    if pe not in ("policy", "free"):
+        raise ValueError("opf_gap: pe must be 'policy' (the recorded battery power on both sides) or 'free', got %r" % (pe,))
     if not hasattr(env, "opf"):
         raise TypeError("opf_gap: env must be an EVOPFEnv, got %s" % type(env).__name__)
     obs, action, valid = np.asarray(trajectory.obs), np.asarray(trajectory.action), np.asarray(trajectory.valid, dtype=bool)
@@ -265,12 +280,20 @@ def opf_gap(trajectory, env, tol=1e-4, max_iters=40):
     if valid.any():
         o = np.ascontiguousarray(obs[valid], dtype=np.float32)
         a = np.ascontiguousarray(action[valid], dtype=np.float32)
-        res = env.opf(o, pe=a[:, -env.ne:], tol=tol, max_iters=max_iters).numpy()
-        cost_policy[valid] = env.obj_fn(a).detach().cpu().numpy().astype(np.float64)
+        if pe == "free":
+            out = env.opf(o, pe="free", tol=tol, max_iters=max_iters)
+            res = out.numpy()
+            policy = env.obj_fn(a) + (out.pe_cost * env._t(a[:, -env.ne:])).sum(dim=1)
+            cost_policy[valid] = policy.detach().cpu().numpy().astype(np.float64)
+            res["cost"] = res["objective"]
+        else:
+            res = env.opf(o, pe=a[:, -env.ne:], tol=tol, max_iters=max_iters).numpy()
+            cost_policy[valid] = env.obj_fn(a).detach().cpu().numpy().astype(np.float64)
         converged[valid] = res["converged"]
         cost_opt[valid] = np.where(res["converged"], res["cost"].astype(np.float64), np.nan)
     with np.errstate(all="ignore"):
-        gap = (cost_policy - cost_opt) / cost_opt
+        # (free pe: the objective carries pe_cost . pe and has no sign; the gap is the difference, in units of obj_fn)
+        gap = cost_policy - cost_opt if pe == "free" else (cost_policy - cost_opt) / cost_opt
     violation = np.where(valid, np.maximum(np.asarray(trajectory.ineq, dtype=np.float64), np.asarray(trajectory.eq, dtype=np.float64)), np.nan)
     return OpfGap(tol, max_iters, cost_policy=cost_policy, cost_opt=cost_opt, gap=gap, converged=converged, valid=valid,
                   violation=violation)
@@ -648,6 +671,72 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     return res
 
 
+def evaluate_opf(tr, episodes=10, seed=None, horizon=None, init_states=None, record=False, constraints=False, pe="free",
+                 pe_cost=None, tol=1e-4, max_iters=40):
+    """See ``RPOTrainerBase.evaluate_opf``."""
+    if pe not in ("free", "zero"):
+        raise ValueError("evaluate_opf: pe must be 'free' (the battery power is dispatched too) or 'zero' (idle batteries), got %r"
+                         % (pe,))
+    if pe_cost is not None and pe != "free":
+        raise ValueError("evaluate_opf: pe_cost is the linear cost of the free battery power: pass pe='free' with it")
+    env = tr.base_env
+    if getattr(tr.kernels, "name", None) != "EVOPF-v0" or not hasattr(env, "opf"):
+        raise NotImplementedError("evaluate_opf: the OPF controller is the single-step AC-OPF of EVOPF-v0; this trainer's env is %s"
+                                  % getattr(tr.kernels, "name", type(env).__name__))
+    fn = env._opf_free_kernel() if pe == "free" else env._opf_kernel()          # NotImplementedError: oracle backend, CPU device
+    tol, iters_cap = float(tol), int(max_iters)
+    if not tol > 0.0 or iters_cap != max_iters or iters_cap < 0:
+        raise ValueError("evaluate_opf: tol must be > 0 and max_iters an integer >= 0, got %r and %r" % (tol, max_iters))
+    n = check_episodes(episodes)
+    want_con = check_constraints(constraints)
+    R = check_record(record, n)
+    H = check_horizon(tr, horizon, "evaluate_opf")
+    k = tr.kernels
+    idx = torch.as_tensor(np.asarray(env.partial_actions), dtype=torch.int64, device=tr.device)
+    dims = (k.obs_dim, int(idx.numel()), k.action_dim)
+    if R:
+        nbytes = 4 * H * R * hip_ops.trace_layout(*dims)[1]
+        if nbytes > hip_ops.TRACE_MAX_BYTES:
+            raise ValueError("evaluate_opf: record=%r needs a trace buffer of %d bytes, above the cap of %d bytes; record fewer "
+                             "episodes (record=k)" % (record, nbytes, hip_ops.TRACE_MAX_BYTES))
+    if pe_cost is not None:
+        pe_cost = torch.as_tensor(pe_cost, dtype=torch.float32, device=tr.device)
+        if pe_cost.dim() == 0 or (pe_cost.dim() == 1 and pe_cost.shape[0] == env.ne):
+            pe_cost = pe_cost.expand(n, env.ne)
+        if tuple(pe_cost.shape) != (n, env.ne):
+            raise ValueError("evaluate_opf: pe_cost must be None, a number, [%d] or [episodes, %d], got %s"
+                             % (env.ne, env.ne, tuple(pe_cost.shape)))
+        pe_cost = pe_cost.contiguous()
+    init_states = check_init_states(tr, init_states, n, "evaluate_opf")
+    seed = fresh_seed(tr) if seed is None else int(seed)
+    v = _initial_env(tr, n, seed, init_states)
+    acc = torch.zeros(n, 8, device=tr.device)
+    trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
+    con = torch.empty(n, hip_ops.con_width(k.ineq_num, k.eq_num), device=tr.device) if want_con else None
+    info = torch.empty(n, 4, device=tr.device)
+    log = torch.zeros(H, n, 2, device=tr.device)                 # (iterations, converged) of every step's launch
+
+    def producer(v, iters, step):
+        # one launch on the observation, straight into the env's action rows (pe = None: zeros, the idle battery)
+        fn(k, v.obs, pe_cost, v.action, info, tol, iters_cap)
+        iters.copy_(info[:, 2])
+        log[step].copy_(info[:, 2:])
+        return v.action.index_select(1, idx) if R else None      # (the proposal is read by the record alone)
+
+    with torch.no_grad():
+        _run_stepwise(tr, v, acc, H, trace=trace, con=con, producer=producer)
+    res = EvalResult(acc.cpu().numpy(), "opf", H, seed)
+    live = np.arange(H)[None, :] < res.length[:, None]           # filled while the episode is live
+    log = log.cpu().numpy().transpose(1, 0, 2)
+    res.opf_iters = np.where(live, log[:, :, 0], 0).astype(np.int32)
+    res.opf_converged = live & (log[:, :, 1] > 0.5)
+    if want_con:
+        res.constraints = _constraint_report(tr, con.cpu().numpy(), res.length, v.viol_thresh)
+    if R:
+        res.trajectory = EvalTrajectory.from_trace(trace.cpu().numpy(), dims, res.length[:R], v.viol_thresh)
+    return res
+
+
 #: the env kernels' method of a ``variant`` of _run_fused -> what is said to a record or a noise next to it
 _VARIANT_REFUSALS = {"evaluate_budgets": "per-lane budgets run without a record and without observation noise",
                      "evaluate_policies": "policy groups run without a record and without observation noise",
@@ -702,14 +791,16 @@ def _run_fused_evopf(tr, v, acc, H, trace=None, budget=(None, None), con=None, n
                                   tr.corr_momentum, v.max_episode_steps, v.viol_thresh, v.seed, v.env_id_base, con=con)
 
 
-def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, noise=None):
+def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, noise=None, producer=None):
     """eval()'s loop: the trainer's deterministic action + projection, one env step without auto-reset, the accumulator
     update.  Finished lanes keep stepping (as in eval()); their rows no longer change.  ``trace``: the zeroed record
     [H, R, W]; the step's row goes in before the accumulator update (which ends the lanes the step finished), from a copy
     of the observation the policy read (the step overwrites it).  ``con``: the per-constraint report [n, W], updated before
     the accumulators for the same reason.  ``noise``: (sigma, seed) of ``obs_noise=``: step i's noisy observation goes into a
     buffer of its own (never into the env's rows: CartSafe-v0's observation IS its state), which the policy, the projection
-    and the record read; the env steps what it holds."""
+    and the record read; the env steps what it holds.  ``producer``: ``producer(v, iters, step)`` in the place of the
+    trainer's ``_eval_action`` -- it writes v.action from v.obs and ``iters``, and returns the proposal to record
+    (``evaluate_opf``: the OPF controller); without it nothing here differs."""
     k = tr.kernels
     rows = torch.zeros(v.n, k.ring_floats, device=tr.device)
     iters = torch.zeros(v.n, dtype=torch.int32, device=tr.device)
@@ -731,7 +822,7 @@ def _run_stepwise(tr, v, acc, H, trace=None, budget=(None, None), con=None, nois
                 obs_noise_torch(tr, v.obs, sigma, seed, i, obs_in)
         elif trace is not None:
             obs_in.copy_(v.obs)
-        proposal = tr._eval_action(v, iters=iters, **kw)
+        proposal = tr._eval_action(v, iters=iters, **kw) if producer is None else producer(v, iters, i)
         v.step(v.action, rows=rows, cap_steps=1, auto_reset=False)
         if trace is not None:
             record(rows, k.cols, obs_in, proposal, v.action, iters, i, acc, trace)

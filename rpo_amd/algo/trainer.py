@@ -1616,6 +1616,24 @@ class RPOTrainerBase(object):
         return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record,
                         eval_steps=eval_steps, eval_lr=eval_lr, constraints=constraints, obs_noise=obs_noise)
 
+    def evaluate_opf(self, episodes=10, seed=None, horizon=None, init_states=None, record=False, constraints=False, pe="free",
+                     pe_cost=None, tol=1e-4, max_iters=40):
+        """The OPF controller on ``evaluate()``'s episodes -> ``EvalResult`` with ``path == "opf"``: at every step the action is
+        the single-step AC-OPF of the lane's observation (``EVOPFEnv.opf``: ``pe="free"`` dispatches the batteries too and
+        maximises the step's reward, ``pe="zero"`` leaves them idle), a hard-feasible baseline to put next to a policy's result.
+        EVOPF-v0 on a GPU only (NotImplementedError elsewhere, with the reason).  ``episodes``, ``seed``, ``horizon``,
+        ``init_states``, ``record`` and ``constraints`` are ``evaluate()``'s: with the same ``seed`` episode i sees the same day
+        and initial state of charge as ``evaluate(seed=seed)``, so per-episode differences are paired.  Per step: one solver
+        launch on the env's observations into its action rows, the env step, the accumulators; no host synchronisation inside
+        the loop.  A row whose problem did not converge steps the solver's last iterate, and its violations show in the result.
+        ``result.opf_iters`` / ``result.opf_converged`` [episode, step]; ``proj_iters`` sums the iterations.  The record's
+        ``proposal`` is the OPF action's components at ``env.partial_actions`` and ``iters`` the solver's iteration count:
+        ``result.trajectory.save()`` of such a run is a set of expert demonstrations.  ``pe_cost`` (with ``pe="free"``): None, a
+        number, [5] or [episodes, 5]; ``tol`` / ``max_iters``: the solver's.  No trainer state changes."""
+        from .evaluation import evaluate_opf
+        return evaluate_opf(self, episodes=episodes, seed=seed, horizon=horizon, init_states=init_states, record=record,
+                            constraints=constraints, pe=pe, pe_cost=pe_cost, tol=tol, max_iters=max_iters)
+
     def evaluate_budgets(self, episodes=10, eval_steps=None, eval_lr=None, horizon=None, seed=None, init_states=None,
                          constraints=False):
         """Evaluate the current policy under B projection budgets at once -> ``BudgetSweep``: which ``eval_steps`` does a

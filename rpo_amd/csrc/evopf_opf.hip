@@ -42,14 +42,15 @@ constexpr int kOpfWaves = 4;                 // states per workgroup, one wave e
 constexpr int NV = 2 * NB - 1;               // voltage unknowns: vm[14], va at the 13 non-slack buses (bus 0 is the slack)
 constexpr int NK = NV + NEQ;                 // order of the reduced KKT system
 constexpr int NBOUND = 2 * (2 * NG + NB);    // 48 inequalities
+constexpr int NBOUND_FREE = NBOUND + 2 * NE; // ... and the 10 battery bounds of the free-pe instance: 58
 constexpr float kSigma = 0.1f, kXi = 0.99995f, kZ0 = 1.0f, kGamma0 = 1.0f;
-static_assert(NK <= RPO_WAVE, "one row of the reduced KKT system per lane");
+static_assert(NK + NE <= RPO_WAVE, "one row of the reduced KKT system per lane, and a lane per battery behind them");
 
 struct OpfArgs {
     int n;
     const float* obs;
     int obs_stride;
-    const float* pe;          // [n, 5] or NULL (zeros)
+    const float* pe;          // [n, 5] or NULL (zeros); the free-pe instance: pe_cost [n, 5] or NULL ((kWe / kWg) * price of the row)
     float* action;            // [n, 43]
     float* info;              // [n, 4]: cost, largest stop quantity at exit, iterations, converged
     float tol;
@@ -63,13 +64,31 @@ struct OpfArgs {
 constexpr int kStLam = NY, kStZu = kStLam + NEQ, kStBnd = NBOUND / 2, kStGamma = kStZu + 4 * kStBnd;
 static_assert(kStGamma + 1 == RPO_EVOPF_OPF_STATE, "layout of the state row");
 
+// kSpv[j] for a lane-dependent j.  Selects on literals, not a read of kSpv: a second kind of use of that table in this module
+// moves the compiler's choices in the fixed-pe instance too (its instructions are pinned, see below).
+__device__ __forceinline__ int bus_of_battery(int j) {
+    static_assert(NE == 5 && kSpv[0] == 0 && kSpv[1] == 1 && kSpv[2] == 2 && kSpv[3] == 5 && kSpv[4] == 7, "battery j sits at bus kSpv[j]");
+    return j == 4 ? 7 : (j == 3 ? 5 : j);
+}
+
+// FREE_PE: the battery power is a variable too (rpo_evopf_opf_free).  pe_j enters g like pg_j -- linearly, in the real-power
+// equation of bus kSpv[j] alone, with d g / d pe = +1 (eq_resid adds pg + pe; NOT jac_entry's -1, the reference's eq_jac sign,
+// DESIGN hazard E1) -- has no Hessian and a box, battery_bounds(soc) of the row's observation: it is eliminated by hand like the
+// generator variables.  Lane NK + j owns pe_j (x, box, the four slack / multiplier registers every bounded lane has);
+// L_x = pe_cost_j + lambda_e + (mu_u - mu_l), D = Sigma, N = L_x + barrier part.  The equation lane of that bus, which owns pg_j,
+// reads 1 / D_pe and N_pe / D_pe from it (two lane reads) for kdiag = -(1 / D_pg + 1 / D_pe) and rhs = N_pg / D_pg + N_pe / D_pe
+// - g_e; after the solve lane NK + j reads dlambda_e from w.vec and forms dpe = (-N_pe - dlambda_e) / D_pe.  58 inequalities.
+// No state seam (state_in / state_out are not read).  The FREE_PE = false instance is the kernel as it stood, instruction for
+// instruction: every addition below folds away on a compile-time false.
+template <bool FREE_PE>
 __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs p) {
     __shared__ Ws wss[kOpfWaves];
     Ws& w = wss[threadIdx.x / RPO_WAVE];
     const int i = blockIdx.x * kOpfWaves + threadIdx.x / RPO_WAVE, tid = lane_id();
     if (i >= p.n) return;                                       // (whole waves: only wave-level hand-overs below)
     load_consts(w, p.consts);
-    load_row(w.s, p.obs + (size_t)i * p.obs_stride, 2 * NB);    // pd, qd: all the problem reads of the observation
+    // pd, qd: all the fixed-pe problem reads of the observation; free pe: the whole row (state of charge, current price)
+    load_row(w.s, p.obs + (size_t)i * p.obs_stride, FREE_PE ? NS : 2 * NB);
     if (tid <= NY) w.a[tid] = 0.0f;
     if (tid < NEQ) w.dir[tid] = 0.0f;                           // lambda
     sync();
@@ -78,7 +97,10 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
     const bool is_var = tid < NV, is_vm = tid < NB, is_eq = tid >= NV && tid < NK;
     const int vbus = is_vm ? tid : (is_var ? tid - (NB - 1) : 0);          // bus of the lane's voltage unknown
     const int myvar = is_vm ? VM0 + vbus : VA0 + vbus;
-    const int e = is_eq ? tid - NV : 0;                                     // the lane's equation
+    const bool is_pe = FREE_PE && tid >= NK && tid < NK + NE;               // free pe: lane NK + j owns pe_j ...
+    const int bat = is_pe ? tid - NK : 0;
+    // the lane's equation (a battery lane: the real-power equation of its bus)
+    const int e = is_eq ? tid - NV : (FREE_PE ? (is_pe ? bus_of_battery(bat) : 0) : 0);
     const bool e_real = e < NB;
     const int ebus = e_real ? e : e - NB;
     int gen = -1;
@@ -86,20 +108,25 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
     for (int j = 0; j < NG; ++j) gen = kSpv[j] == ebus ? j : gen;
     const bool has_u = is_eq && gen >= 0;                                   // the equation's generator variable: pg / qg
     const bool is_pg = has_u && e_real;
-    const bool bounded = is_vm || has_u;
-    const int xidx = is_var ? myvar : (has_u ? (e_real ? PG0 + gen : QG0 + gen) : NY);   // w.a component the lane updates (NY: none)
+    const bool elim = has_u || is_pe;                                       // the lane owns a variable eliminated by hand
+    const bool bounded = is_vm || elim;
+    const int xidx = is_var ? myvar : (has_u ? (e_real ? PG0 + gen : QG0 + gen) : (is_pe ? PE0 + bat : NY));   // w.a component the lane updates (NY: none)
     float hi = 0.0f, lo = 0.0f;
     if (is_vm) { hi = w.c[RPO_EVOPF_C_VMAX + vbus]; lo = w.c[RPO_EVOPF_C_VMIN + vbus]; }
     else if (is_pg) { hi = w.c[RPO_EVOPF_C_PMAX + gen]; lo = w.c[RPO_EVOPF_C_PMIN + gen]; }
     else if (has_u) { hi = w.c[RPO_EVOPF_C_QMAX + gen]; lo = w.c[RPO_EVOPF_C_QMIN + gen]; }
+    else if (is_pe) battery_bounds(w.s[2 * NB + bat], hi, lo);
     const int bidx = is_vm ? 2 * NG + vbus : (is_pg ? gen : NG + gen);    // the lane's bounded variable in the state row's order
-    const float c2 = is_pg ? 2.0f * w.c[RPO_EVOPF_C_QUAD + gen] : 0.0f, c1 = is_pg ? w.c[RPO_EVOPF_C_LIN + gen] : 0.0f;
+    const float c2 = is_pg ? 2.0f * w.c[RPO_EVOPF_C_QUAD + gen] : 0.0f;
+    // linear cost: pe_cost_j of the battery lanes, by default what the env's reward charges for a unit of pe in units of obj_fn
+    const float c1 = is_pg ? w.c[RPO_EVOPF_C_LIN + gen]
+                           : (is_pe ? (p.pe ? p.pe[(size_t)i * NE + bat] : (kWe / kWg) * w.s[2 * NB + NE]) : 0.0f);
 
     // ---- flat start
     {
         const float x0 = 0.5f * (hi + lo);                                  // (0 for the angles)
         if (xidx < NY) w.a[xidx] = x0;
-        if (tid < NE) w.a[PE0 + tid] = p.pe ? p.pe[(size_t)i * NE + tid] : 0.0f;
+        if (!FREE_PE && tid < NE) w.a[PE0 + tid] = p.pe ? p.pe[(size_t)i * NE + tid] : 0.0f;
         if (tid == 32) w.a[VA0] = w.c[RPO_EVOPF_C_VA_INIT];                 // slack_va (bus 0)
     }
     float zu = 1.0f, zl = 1.0f, mu_u = 0.0f, mu_l = 0.0f, gamma = kGamma0;
@@ -108,7 +135,7 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         zu = fmaxf(hi - x0, kZ0); zl = fmaxf(x0 - lo, kZ0);
         mu_u = gamma / zu; mu_l = gamma / zl;
     }
-    if (p.state_in) {                                           // a given state replaces the flat start entirely
+    if (!FREE_PE && p.state_in) {                               // a given state replaces the flat start entirely
         const float* st = p.state_in + (size_t)i * RPO_EVOPF_OPF_STATE;
         if (tid < NY) w.a[tid] = st[tid];
         if (tid < NEQ) w.dir[tid] = st[kStLam + tid];
@@ -134,8 +161,8 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         const float dmu = mu_u - mu_l;
         // generator variable of an equation lane: L_x, D, N of that variable; its column is eliminated into the lane's diagonal
         const float lam_e = w.dir[e], g_e = is_eq ? w.eq[e] : 0.0f;
-        const float lxu = has_u ? (c2 * x + c1) + lam_e + dmu : 0.0f;
-        const float du = has_u ? c2 + sig : 1.0f;
+        const float lxu = elim ? (c2 * x + c1) + lam_e + dmu : 0.0f;
+        const float du = elim ? c2 + sig : 1.0f;
         const float nu = lxu + nbar;
         const float kdiag = has_u ? -1.0f / du : 0.0f;
 
@@ -196,6 +223,16 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         const float lxv = is_var ? jtl + (is_vm ? dmu : 0.0f) : 0.0f;          // L_x of the voltage unknown
         const float nv = lxv + (is_vm ? nbar : 0.0f);
         row[NK] = is_var ? -nv : (is_eq ? (has_u ? nu / du - g_e : -g_e) : 0.0f);
+        if constexpr (FREE_PE) {
+            // the pg lane of bus kSpv[j] takes pe_j's share from lane NK + j (two lane reads): kdiag = -(1 / D_pg + 1 / D_pe),
+            // rhs = N_pg / D_pg + N_pe / D_pe - g_e.  Here, after the rows are built, where fewer registers are live.
+            const int src = (NK + (is_pg ? gen : 0)) << 2;
+            const float inv_pe = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(1.0f / du)));
+            const float n_pe = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(nu / du)));
+#pragma unroll
+            for (int j = 0; j < NE; ++j) row[NV + bus_of_battery(j)] -= (is_pg && gen == j) ? inv_pe : 0.0f;
+            row[NK] += is_pg ? n_pe : 0.0f;
+        }
 
         // ---- stop test: max(|g|_inf, max h), |L_x|_inf, z^T mu
         const float feas_l = fmaxf(fabsf(g_e), bounded ? fmaxf(hu, hl) : 0.0f);
@@ -216,9 +253,9 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         const float mypiv = gj_dynamic<0, NK, 0, NK + 1, PickExact64>(row, mycol);
         if (tid < NK) w.vec[mycol] = row[NK] / mypiv;
         sync();
-        const float delta = w.vec[tid < NK ? tid : 0];
-        const float dlam = is_eq ? delta : 0.0f;
-        const float dx = is_var ? delta : (has_u ? (-nu - dlam) / du : 0.0f);
+        const float delta = w.vec[tid < NK ? tid : (is_pe ? NV + e : 0)];
+        const float dlam = (is_eq || is_pe) ? delta : 0.0f;
+        const float dx = is_var ? delta : (elim ? (-nu - dlam) / du : 0.0f);
         const float dzu = -hu - zu - dx, dzl = -hl - zl + dx;                   // dz = -h - z - dh
         const float dmu_u = -mu_u + (gamma - mu_u * dzu) / zu, dmu_l = -mu_l + (gamma - mu_l * dzl) / zl;
         // step lengths to the boundary times xi, capped at 1: xi * min(z / -dz) = xi / max(-dz / z)
@@ -232,12 +269,12 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
             zu += alpha_p * dzu; zl += alpha_p * dzl;
             mu_u += alpha_d * dmu_u; mu_l += alpha_d * dmu_l;
         }
-        gamma = kSigma * rpo_wave_sum_rows(bounded ? zu * mu_u + zl * mu_l : 0.0f) / (float)NBOUND;
+        gamma = kSigma * rpo_wave_sum_rows(bounded ? zu * mu_u + zl * mu_l : 0.0f) / (float)(FREE_PE ? NBOUND_FREE : NBOUND);
         sync();
         ++it;
     }
 
-    // ---- outputs: the full 43-vector (slack angle and pe as given) and (cost, residual, iterations, converged)
+    // ---- outputs: the full 43-vector (slack angle as given; pe as given, or the optimal one) and (cost, residual, iterations, converged)
     float part = 0.0f;
     if (tid < NG) {
         const float pg = w.a[PG0 + tid];
@@ -246,7 +283,7 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
     const float cost = rpo_wave_sum_rows(part) + w.c[RPO_EVOPF_C_CONST];
     if (tid < NY) p.action[(size_t)i * NY + tid] = w.a[tid];
     if (tid < 4) p.info[(size_t)i * 4 + tid] = tid == 0 ? cost : (tid == 1 ? resid : (tid == 2 ? (float)it : (converged ? 1.0f : 0.0f)));
-    if (p.state_out) {                                          // the state the stop test was last evaluated on
+    if (!FREE_PE && p.state_out) {                                     // the state the stop test was last evaluated on
         float* st = p.state_out + (size_t)i * RPO_EVOPF_OPF_STATE;
         if (tid < NY) st[tid] = w.a[tid];
         if (tid < NEQ) st[kStLam + tid] = w.dir[tid];
@@ -271,5 +308,13 @@ extern "C" int rpo_evopf_opf_state(int n, const float* obs, int obs_stride, cons
     if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < 2 * NB || (state_in && pe)) return RPO_ERR_ARG;
     if (!obs || !action_out || !info_out || !consts_dev) return RPO_ERR_NULL;
     const OpfArgs args{n, obs, obs_stride, pe, action_out, info_out, tol, max_iters, consts_dev, state_in, state_out};
-    return launch(evopf_opf_kernel, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
+    return launch(evopf_opf_kernel<false>, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
+}
+
+extern "C" int rpo_evopf_opf_free(int n, const float* obs, int obs_stride, const float* pe_cost, float* action_out, float* info_out,
+                                  float tol, int max_iters, const float* consts_dev, void* stream) {
+    if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < NS) return RPO_ERR_ARG;
+    if (!obs || !action_out || !info_out || !consts_dev) return RPO_ERR_NULL;
+    const OpfArgs args{n, obs, obs_stride, pe_cost, action_out, info_out, tol, max_iters, consts_dev, nullptr, nullptr};
+    return launch(evopf_opf_kernel<true>, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
 }

@@ -15,8 +15,11 @@ The optimal power flow: ``opf(state, pe)`` solves every row's single-step AC-OPF
 power balance and the bounds, for the row's demand and a GIVEN battery power -- on the device (rpo_amd/csrc/evopf_opf.hip: a
 primal-dual interior point method, one wavefront per state) and returns an ``OpfResult`` of device tensors.  ``opt_solve(X)`` is
 the reference's method of that name (there: pypower's interior-point OPF, one state at a time on the CPU) on top of it, and
-``EvalTrajectory.opf_gap(env)`` (rpo_amd/algo/evaluation.py) the optimality gap of a recorded evaluation.  There is no CPU
-path: on the oracle backend or a CPU device the three raise NotImplementedError with that reason.
+``EvalTrajectory.opf_gap(env)`` (rpo_amd/algo/evaluation.py) the optimality gap of a recorded evaluation.  ``opf(state,
+pe="free")`` dispatches the batteries too: it minimises ``obj_fn + pe_cost . pe`` over all 43 components with the battery box of
+the row's state of charge, by default at the price that makes the optimum the best one-step reward (``reward_fn``); it is the
+controller of ``trainer.evaluate_opf`` and the reference of ``opf_gap(pe="free")``.  There is no CPU path: on the oracle backend or
+a CPU device all of these raise NotImplementedError with that reason.
 """
 import numpy as np
 import torch
@@ -294,7 +297,56 @@ class EVOPFEnv(HardConstraintEnv):
                                       "there is no CPU path" % self.device)
         return fn
 
-    def opf(self, state, pe=None, tol=1e-4, max_iters=40, out=None, state_in=None, state_out=None):
+    def _opf_free_kernel(self):
+        """The backend's free-pe OPF kernel, or NotImplementedError with the reason there is none."""
+        self._opf_kernel()
+        fn = getattr(self._backend, "evopf_opf_free", None)
+        if fn is None:
+            raise NotImplementedError("this backend has no evopf_opf_free kernel: the free-pe AC-OPF solver exists as the HIP "
+                                      "kernel rpo_evopf_opf_free only")
+        return fn
+
+    def default_pe_cost(self, state):
+        """The price of a unit of battery power in units of ``obj_fn`` under the env's reward, per row of observations [n, 57]
+        -> [n, 5]: (we / wg) * the row's current price in every component (what rpo_evopf_opf_free uses for a NULL pe_cost)."""
+        price = state[:, 2 * self.nbus + self.ne:2 * self.nbus + self.ne + 1]
+        return ((self.we / self.wg) * price).expand(-1, self.ne).contiguous()
+
+    def reward_fn(self, state, action):
+        """The env step's reward formula (evopf.py:348-366) for rows of observations [n, 57] and actions [n, 43] -> [n]:
+        wg * (-obj_fn(action)) - we * price * sum(pe), price the row's current price.  Torch tensors in, a tensor out; arrays in,
+        a float64 array out."""
+        col = 2 * self.nbus + self.ne
+        if isinstance(state, torch.Tensor) or isinstance(action, torch.Tensor):
+            state, action = self._t(state), self._t(action)
+            state = state.view(1, -1) if state.dim() == 1 else state
+            action = action.view(1, -1) if action.dim() == 1 else action
+            return self.wg * (-self.obj_fn(action)) - self.we * state[:, col] * action[:, -self.ne:].sum(dim=1)
+        state, action = np.atleast_2d(np.asarray(state, dtype=np.float64)), np.atleast_2d(np.asarray(action, dtype=np.float64))
+        pg_mw = action[:, :self.ng] * self.genbase
+        cost = ((case14.GENCOST[:, 4] * pg_mw ** 2).sum(axis=1) + (case14.GENCOST[:, 5] * pg_mw).sum(axis=1)
+                + float(case14.GENCOST[:, 6].sum())) / float(self.genbase.mean() ** 2)
+        return self.wg * (-cost) - self.we * state[:, col] * action[:, -self.ne:].sum(axis=1)
+
+    def _opf_free(self, fn, state, pe_cost, tol, iters, out):
+        """``opf(pe="free")`` behind the checks the two forms share."""
+        if state.shape[1] != self.state_dim:
+            raise ValueError("opf: pe='free' needs [n, %d] observations -- demands alone carry neither the state of charge (the "
+                             "battery box) nor the price (the default pe_cost), got %s" % (self.state_dim, tuple(state.shape)))
+        n = state.shape[0]
+        if pe_cost is not None:
+            pe_cost = self._t(pe_cost)
+            if pe_cost.dim() == 0 or (pe_cost.dim() == 1 and pe_cost.shape[0] == self.ne):
+                pe_cost = pe_cost.expand(n, self.ne)
+            if tuple(pe_cost.shape) != (n, self.ne):
+                raise ValueError("opf: pe_cost must be None, a number, [%d] or [%d, %d], got %s"
+                                 % (self.ne, n, self.ne, tuple(pe_cost.shape)))
+            pe_cost = pe_cost.to(torch.float32).contiguous()
+        fn(self.kernels, state, pe_cost, out.action, out.info, tol, iters)
+        out.pe_cost = self.default_pe_cost(state) if pe_cost is None else pe_cost
+        return out
+
+    def opf(self, state, pe=None, tol=1e-4, max_iters=40, out=None, state_in=None, state_out=None, pe_cost=None):
         """The cheapest dispatch of every row's single-step AC-OPF, on the device (rpo_evopf_opf, csrc/evopf_opf.hip).
 
         ``state`` [n, 57] observations or [n, 28] demands (pd, qd); ``pe`` [n, 5] battery power, a PARAMETER of the problem
@@ -306,8 +358,21 @@ class EVOPFEnv(HardConstraintEnv):
         reused.  ``state_in`` / ``state_out``: contiguous float32 device tensors [n, 168] (action[43] | lambda[28] | z_u[24] |
         z_l[24] | mu_u[24] | mu_l[24] | gamma, bounded variables in the order pg, qg, vm) -- the interior-point state to start
         from in place of the flat start (it carries pe: ``pe`` must then be None; ``iters`` counts from it) and the state at
-        exit, written in place."""
-        fn = self._opf_kernel()
+        exit, written in place.
+
+        ``pe="free"``: the battery power is a variable too (rpo_evopf_opf_free) -- minimise ``obj_fn + sum_j pe_cost[j] pe[j]`` over
+        (pg, qg, vm, va, pe) with the 10 battery bounds ``battery_bounds(soc)`` of the row's observation added (58 inequalities).
+        ``state`` must then be [n, 57] observations; ``pe_cost`` None ((we / wg) * the row's current price: the optimum maximises
+        the env's one-step reward), a number, [5] or [n, 5]; ``state_in`` / ``state_out`` are refused.  The result's ``action``
+        carries the optimal pe, ``cost`` stays ``obj_fn`` of the point, ``pe_cost`` / ``objective`` what was minimised."""
+        free = isinstance(pe, str)
+        if free and pe != "free":
+            raise ValueError("opf: pe must be None, [n, %d] or the string 'free', got %r" % (self.ne, pe))
+        if free and (state_in is not None or state_out is not None):
+            raise ValueError("opf: pe='free' has no state seam: state_in / state_out must be None")
+        if pe_cost is not None and not free:
+            raise ValueError("opf: pe_cost is the linear cost of the free battery power: pass pe='free' with it")
+        fn = self._opf_free_kernel() if free else self._opf_kernel()
         tol, iters = float(tol), int(max_iters)
         if not tol > 0.0 or iters != max_iters or iters < 0:
             raise ValueError("opf: tol must be > 0 and max_iters an integer >= 0, got %r and %r" % (tol, max_iters))
@@ -320,7 +385,7 @@ class EVOPFEnv(HardConstraintEnv):
         if state.stride(1) != 1:
             state = state.contiguous()
         n = state.shape[0]
-        if pe is not None:
+        if pe is not None and not free:
             pe = self._t(pe)
             pe = (pe.view(1, -1) if pe.dim() == 1 else pe).contiguous()
             if tuple(pe.shape) != (n, self.ne):
@@ -338,6 +403,9 @@ class EVOPFEnv(HardConstraintEnv):
                 raise ValueError("opf: %s must be a contiguous float32 tensor [%d, 168] on %s" % (name, n, state.device))
         if state_in is not None and pe is not None:
             raise ValueError("opf: state_in carries pe (columns 38..42): pe must be None with it")
+        if free:
+            return self._opf_free(fn, state, pe_cost, tol, iters, out)
+        out.pe_cost = None
         if state_in is None and state_out is None:
             fn(self.kernels, state, pe, out.action, out.info, tol, iters)
         else:
@@ -368,21 +436,33 @@ class OpfResult(object):
     """What ``EVOPFEnv.opf`` returns: device tensors, row i for state i.  ``action`` [n, 43]: the full action vector (va at the
     slack bus = slack_va, pe as given), so ``eq_resid`` / ``ineq_resid`` / ``obj_fn`` apply to it; ``cost`` [n] = its ``obj_fn``;
     ``residual`` [n]: the largest of the three stop quantities at exit (NaN if one of them was); ``iters`` [n] int32;
-    ``converged`` [n] bool.  The last four are views of / elementwise ops on ``info`` [n, 4], the kernel's own output."""
+    ``converged`` [n] bool.  The last four are views of / elementwise ops on ``info`` [n, 4], the kernel's own output.
+    ``pe_cost``: the [n, 5] linear cost of pe that ``opf(pe="free")`` minimised with, None for a fixed-pe result; ``objective`` [n]
+    = ``cost + (pe_cost * pe).sum(1)``, what was minimised (``cost`` itself when ``pe_cost`` is None)."""
 
-    def __init__(self, action, info):
-        self.action, self.info = action, info
+    def __init__(self, action, info, pe_cost=None):
+        self.action, self.info, self.pe_cost = action, info, pe_cost
 
     cost = property(lambda self: self.info[:, 0])
     residual = property(lambda self: self.info[:, 1])
     iters = property(lambda self: self.info[:, 2].to(torch.int32))
     converged = property(lambda self: self.info[:, 3] > 0.5)
 
+    @property
+    def objective(self):
+        if self.pe_cost is None:
+            return self.cost
+        return self.cost + (self.pe_cost * self.action[:, -self.pe_cost.shape[1]:]).sum(dim=1)
+
     def numpy(self):
-        """dict of numpy arrays (one device-to-host copy per buffer; this synchronises)."""
+        """dict of numpy arrays (one device-to-host copy per buffer; this synchronises); a free-pe result adds ``pe_cost`` and
+        ``objective``."""
         info = self.info.detach().cpu().numpy()
-        return dict(action=self.action.detach().cpu().numpy(), cost=info[:, 0].copy(), residual=info[:, 1].copy(),
+        host = dict(action=self.action.detach().cpu().numpy(), cost=info[:, 0].copy(), residual=info[:, 1].copy(),
                     iters=info[:, 2].astype(np.int32), converged=info[:, 3] > 0.5)
+        if self.pe_cost is not None:                             # a free-pe result carries what it minimised as well
+            host.update(pe_cost=self.pe_cost.detach().cpu().numpy(), objective=self.objective.detach().cpu().numpy())
+        return host
 
     def converged_rate(self):
         return float((self.info[:, 3] > 0.5).float().mean())

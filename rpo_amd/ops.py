@@ -844,6 +844,28 @@ def evopf_opf(kernels, obs, pe, action, info, tol, max_iters, state_in=None, sta
                                           _p(state_out, allow_none=True), _stream()), "rpo_evopf_opf_state")
 
 
+OPF_OBS = 57                         # floats of an observation row the free-pe OPF reads: demand, state of charge, current price
+
+
+def evopf_opf_free(kernels, obs, pe_cost, action, info, tol, max_iters):
+    """Single-step AC-OPF of every row with the battery power a variable (rpo_evopf_opf_free): obs [n, >= 57] float32 observation
+    rows with unit column stride (demand, state of charge and current price are read), pe_cost [n, 5] contiguous or None ((we / wg)
+    * price of the row) -> action [n, 43] with the optimal pe, info [n, 4] = (obj_fn of the point, largest stop quantity at exit,
+    iterations, converged).  A function of the backend like ``evopf_opf``."""
+    if action is None or action.dim() != 2 or action.shape[1] != kernels.action_dim or action.shape[0] < 1:
+        raise RpoHipError("evopf_opf_free: action must be [n >= 1, %d], got %s"
+                          % (kernels.action_dim, None if action is None else tuple(action.shape)))
+    n = action.shape[0]
+    if obs is None or obs.dim() != 2 or obs.shape[0] != n or obs.shape[1] < OPF_OBS or obs.stride(1) != 1:
+        raise RpoHipError("evopf_opf_free: obs must be [%d, >= %d] rows with unit column stride, got %s"
+                          % (n, OPF_OBS, None if obs is None else (tuple(obs.shape), obs.stride())))
+    if info is None or tuple(info.shape) != (n, 4) or (pe_cost is not None and tuple(pe_cost.shape) != (n, 5)):
+        raise RpoHipError("evopf_opf_free: info must be [%d, 4] and pe_cost [%d, 5] or None" % (n, n))
+    stride = int(obs.stride(0)) if n > 1 else int(obs.shape[1])
+    check(_lib.load().rpo_evopf_opf_free(n, _p(obs, contiguous=False), stride, _p(pe_cost, allow_none=True), _p(action), _p(info),
+                                         float(tol), int(max_iters), kernels._c(action), _stream()), "rpo_evopf_opf_free")
+
+
 class PendulumKernels(_FusedEnvKernels):
     """HIP kernels of SpringPendulum-v0."""
 
