@@ -1407,6 +1407,29 @@ int rpo_gauss_head(int n, const float* raw, const float* eps, float scale, float
 int rpo_gauss_head_bwd(int n, const float* raw, const float* eps, const float* dap, float dlogp, float scale,
                        float base, float lo, float hi, float* draw, void* stream);
 
+/* Behaviour-cloning head (trainer.pretrain, rpo_amd/algo/pretrain.py; csrc/bc.hip): the loss of the actor's tanh-box output
+ * against a demonstrated basic action, in box-normalised coordinates, and its gradient w.r.t. the RAW actor output.
+ * raw [n, heads * P] from rpo_mlp_forward without a box (heads = 1: RPODDPG; heads = 2: RPOSAC's (mean | log-std), the mean half is
+ * read), target [n, P] with rows target_stride >= P floats apart (columns of a gathered batch), P <= 16.  Per row i, component j:
+ *   scale = (hi - lo) / 2, base = lo + scale;  u = clamp((target - base) / scale, -clip, clip), 0 < clip <= 1;  y = tanh(raw)
+ *   L = 1 / (n P) sum_ij w_j (y - u)^2;        draw_ij = 2 w_j / (n P) (y - u) (1 - y^2)
+ * A term with scale <= 1e-6 (an empty box) contributes 0 to both; the denominator stays n P.  draw [n, heads * P] is written in
+ * full: for heads = 2 the log-std half receives exactly 0.  loss_parts [(n + 15) / 16]: loss_parts[g] is the share of rows
+ * [16 g, 16 g + 16) in L, summing them in index order gives L.  The bits of draw and loss_parts depend on neither the grid size
+ * nor any arrival order (one writer per word, fixed summation order, no atomics).  NaN: as in the heads above, a NaN in raw
+ * reaches draw and the loss (in a term of an empty box it is dropped with the term); the clamp of u keeps a NaN target.
+ * lo_host / hi_host / weights_host: HOST pointers to P floats, copied into the launch's arguments (weights_host NULL: all 1;
+ * a negative or NaN weight is RPO_ERR_ARG). */
+int rpo_bc_head(int n, int P, int heads, const float* raw, const float* target, int target_stride, const float* lo_host,
+                const float* hi_host, const float* weights_host, float clip, float* draw, float* loss_parts, void* stream);
+
+/* The same for EVOPF-v0 (P = RPO_EVOPF_PARTIAL): the box of (i, j) is the state-dependent one of row i's observation
+ * (state [n, >= RPO_EVOPF_STATE] with rows state_stride floats apart; EVOPFEnv.update, what rpo_evopf_tanh_box_bwd and the
+ * projection use), so a battery whose state of charge is out of band has an empty box and its term is 0. */
+int rpo_evopf_bc_head(int n, int heads, const float* state, int state_stride, const float* raw, const float* target,
+                      int target_stride, const float* weights_host, float clip, float* draw, float* loss_parts,
+                      const float* consts_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1634,6 +1634,34 @@ class RPOTrainerBase(object):
         return evaluate_opf(self, episodes=episodes, seed=seed, horizon=horizon, init_states=init_states, record=record,
                             constraints=constraints, pe=pe, pe_cost=pe_cost, tol=tol, max_iters=max_iters)
 
+    def pretrain(self, demos, steps=1000, batch_size=None, lr=None, seed=None, weights=None, clip=0.98, sync_targets=True,
+                 idx=None):
+        """Clone the actor from ``demos`` (``Demonstrations``: observations and the demonstrated basic actions, e.g.
+        ``Demonstrations.from_trajectory(b.trajectory, tr.base_env, mask=b.opf_converged)`` of ``b = tr.evaluate_opf(1024,
+        seed=1, record=True)``) -> ``PretrainResult`` (``loss`` numpy [steps], read back once after the loop; ``steps``,
+        ``batch_size``, ``lr``, ``seed``, ``rows``).  Loss of a minibatch: L = 1 / (B P) sum w_j (tanh(raw) - u*)^2 in
+        box-normalised coordinates, u* = clamp((a* - base) / scale, -clip, clip) with the actor's own box of that row (EVOPF-v0:
+        the state-of-charge dependent one; an empty box contributes 0); RPOSAC clones the mean head, the log-std head receives
+        gradient 0.  One step = gather the minibatch from the device-resident table, actor forward, the head (rpo_bc_head /
+        rpo_evopf_bc_head), actor backward, clip + Adam on the actor's range of the flat buffer: five launches, no host
+        synchronisation inside the loop; with hipGraphs the steps run in captured windows of kernel nodes, bit-equal to eager.
+        ``batch_size``: None (the trainer's) or a positive multiple of 16; ``lr``: None (``lr_actor``) or a finite number > 0;
+        sampling is uniform with replacement from the project's Philox keyed by (``seed``, step) -- None: a fresh seed per call
+        from the trainer seed and a call counter of pretrain's own; the same (demos, seed, steps, batch_size, lr) on the same
+        weights gives the same bits.  ``weights``: None or P numbers >= 0; ``clip`` in (0, 1]; ``idx``: int64 [steps,
+        batch_size] replaces the draws (parity tests).  The optimiser state is the call's own (a fresh Adam with the actor
+        optimiser's weight decay and clip threshold): what changes is the actor's range of ``flat.data`` -- with
+        ``shared_param=True`` including the shared state embedding, as an actor step does -- and, with ``sync_targets=True``, the
+        actor target (set to the actor) and the shared slice of the critic target (set to the embedding).  Nothing else changes:
+        critic-only parameters, multipliers, every optimiser's moments and counters, the gradient buffer (restored bit for
+        bit), ctrl, env lanes, replay, Philox counters of training and evaluation, the graphs of ``run_steps``.  ``steps=0`` is
+        a no-op with an empty ``loss``.  Data-parallel runs: no collective -- replicas stay identical if every rank passes the
+        same arguments.  ValueError for a bad argument; NotImplementedError (with the reason) without the fused actor, on a
+        backend without the head kernels, or on a CPU device.  See rpo_amd/algo/pretrain.py."""
+        from .pretrain import pretrain
+        return pretrain(self, demos, steps=steps, batch_size=batch_size, lr=lr, seed=seed, weights=weights, clip=clip,
+                        sync_targets=sync_targets, idx=idx)
+
     def evaluate_budgets(self, episodes=10, eval_steps=None, eval_lr=None, horizon=None, seed=None, init_states=None,
                          constraints=False):
         """Evaluate the current policy under B projection budgets at once -> ``BudgetSweep``: which ``eval_steps`` does a

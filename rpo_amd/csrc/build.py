@@ -14,7 +14,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["cartsafe.hip", "pendulum.hip", "evopf.hip", "replay.hip", "train_ops.hip", "mlp.hip", "fused.hip", "nsplit.hip",
-           "rollout_stream.hip", "mlp_bwd_stream.hip", "evaluate.hip", "act.hip", "act_stream.hip", "evopf_eval.hip", "evopf_opf.hip"]
+           "rollout_stream.hip", "mlp_bwd_stream.hip", "evaluate.hip", "act.hip", "act_stream.hip", "evopf_eval.hip", "evopf_opf.hip", "bc.hip"]
 # per-file flags: the streaming rollout, the streaming backward and the streaming policy_act are compiled without SLP
 # vectorisation (see their headers)
 FILE_FLAGS = {"rollout_stream.hip": ["-fno-slp-vectorize"], "mlp_bwd_stream.hip": ["-fno-slp-vectorize"],

@@ -1110,6 +1110,54 @@ def gauss_head_bwd(raw, eps, dap, dlogp, scale, base, lo, hi, draw):
                                          _stream()), "rpo_gauss_head_bwd")
 
 
+def _bc_weights(weights, P):
+    """``weights`` of the cloning heads -> (host pointer or None, the array that must outlive the call)."""
+    if weights is None:
+        return None, None
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if w.shape[0] != P:
+        raise RpoHipError("expected %d weights, got %d" % (P, w.shape[0]))
+    return _host_ptr(w), w
+
+
+def _bc_shapes(raw, target, draw, loss_parts):
+    n, P = target.shape
+    heads = raw.shape[1] // P
+    if raw.dim() != 2 or raw.shape[0] != n or raw.shape[1] != heads * P or tuple(draw.shape) != tuple(raw.shape):
+        raise RpoHipError("bc_head: raw / draw must be [n, P] or [n, 2 P] for target [n, P], got %s / %s / %s"
+                          % (tuple(raw.shape), tuple(draw.shape), tuple(target.shape)))
+    if loss_parts.numel() != (n + 15) // 16:
+        raise RpoHipError("bc_head: loss_parts must hold (n + 15) // 16 = %d floats, got %d" % ((n + 15) // 16, loss_parts.numel()))
+    return n, P, heads
+
+
+def bc_head(raw, target, lo, hi, weights, clip, draw, loss_parts):
+    """Behaviour-cloning head with a constant box (rpo_bc_head): raw [n, heads * P], target a [n, P] row view, lo / hi P host
+    numbers, weights None or P host numbers >= 0 -> draw (like raw) and loss_parts [(n + 15) // 16]."""
+    n, P, heads = _bc_shapes(raw, target, draw, loss_parts)
+    tp, ts = _row_view(target, P)
+    lo, hi = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (lo, hi))
+    if lo.shape[0] != P or hi.shape[0] != P:
+        raise RpoHipError("bc_head: lo / hi must hold %d numbers" % P)
+    wp, w = _bc_weights(weights, P)
+    check(_lib.load().rpo_bc_head(n, P, heads, _p(raw), tp, ts, _host_ptr(lo), _host_ptr(hi), wp, clip, _p(draw), _p(loss_parts),
+                                  _stream()), "rpo_bc_head")
+
+
+def evopf_bc_head(kernels, obs, raw, target, weights, clip, draw, loss_parts):
+    """Behaviour-cloning head with the state-dependent box of ``obs`` (rpo_evopf_bc_head; see ``bc_head``).  ``obs`` is taken as
+    ``EvopfKernels.tanh_box_bwd`` takes it: a [n, obs_dim] row view."""
+    n, P, heads = _bc_shapes(raw, target, draw, loss_parts)
+    if P != kernels.partial_dim or obs.shape[0] != n:
+        raise RpoHipError("evopf_bc_head: needs target [n, %d] and obs [n, %d], got %s / %s"
+                          % (kernels.partial_dim, kernels.obs_dim, tuple(target.shape), tuple(obs.shape)))
+    sp, ss = _row_view(obs, kernels.obs_dim)
+    tp, ts = _row_view(target, P)
+    wp, w = _bc_weights(weights, P)
+    check(_lib.load().rpo_evopf_bc_head(n, heads, sp, ss, _p(raw), tp, ts, wp, clip, _p(draw), _p(loss_parts), kernels._c(raw),
+                                        _stream()), "rpo_evopf_bc_head")
+
+
 def mlp_backward_pair(desc1, desc2, s, a, x0_1, h1_1, dout_1, dh_1, dx0_1, da_1, x0_2, h1_2, dout_2, dh_2, dx0_2, da_2,
                       param_grads=True, first_layer_state_only=False, gradmax=None, td1=None, td2=None):
     sp, ss = _row_view(s, desc1.S)
