@@ -102,6 +102,7 @@ extern "C" {
 #define RPO_EVOPF_C_QSIGN 518
 #define RPO_EVOPF_C_PRICE 532
 #define RPO_EVOPF_CONSTS_LEN 560
+#define RPO_EVOPF_SCEN_DAY 720 /* floats per day of a scenario table: price[48] | 24 x (pd[14] qd[14]); 2880 bytes */
 
 #define RPO_CTRL_LEN 288
 #define RPO_CTRL_T 0        /* vector steps completed */
@@ -830,6 +831,29 @@ int rpo_evopf_step(int n_envs, float* state, const float* action, int* ep_len, f
                    float* rows, long long cap_steps, float* stats, int stats_cap, long long* ctrl, int max_episode_steps,
                    int auto_reset, float viol_thresh, const float* consts_dev, unsigned long long seed,
                    unsigned env_id_base, void* stream);
+
+/* Scenarios: a caller's days instead of the Philox draws (an evaluation seam; additive, RPO_ABI_VERSION stays 6).  A scenario
+ * table is float [days, RPO_EVOPF_SCEN_DAY]: floats [0, 48) of a day = the price of hours 0..47 in the observation's units
+ * (24..47: the look-ahead past midnight), floats [48 + 28 t, 48 + 28 t + 28) = (pd[14], qd[14]) of hour t per unit; day [n]
+ * (int) = the table row lane i plays.  Hour t < 24 of the observation: [0, 28) = demand[t], [33 + k] = price[t + k]; t >= 24:
+ * zero.  A day[i] outside [0, days) never indexes the table: the lane's observation becomes NaN (ctrl[RPO_CTRL_NONFINITE]).
+ * Refused before any launch: n <= 0, days <= 0 (RPO_ERR_ARG), a NULL among the required pointers (RPO_ERR_NULL), and what
+ * rpo_evopf_step refuses. */
+
+/* The day lane env_id_base + i is dealt in episode ep_count[i] (NULL: 0) under `seed`, written in the table layout by the device
+ * function rpo_evopf_reset / rpo_evopf_step draw with (the same bits); price hours 24..47 are zero.  table_out [n, 720]. */
+int rpo_evopf_scenario_table(int n, float* table_out, const unsigned* ep_count, const float* consts_dev, unsigned long long seed,
+                             unsigned env_id_base, void* stream);
+
+/* rpo_evopf_reset with hour 0 of table row day[i]; state of charge as there. */
+int rpo_evopf_reset_scenario(int n_envs, float* state, int* ep_len, float* ep_ret, const float* table, int days, const int* day,
+                             const float* consts_dev, void* stream);
+
+/* rpo_evopf_step with the next hour read from table row day[i]; never auto-resets (ep_count is left as it is).  Everything else
+ * is that step: violations, reward, battery, transition row, statistics, failure flag. */
+int rpo_evopf_step_scenario(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count,
+                            float* rows, long long cap_steps, float* stats, int stats_cap, long long* ctrl, int max_episode_steps,
+                            float viol_thresh, const float* consts_dev, const float* table, int days, const int* day, void* stream);
 
 /* take_action's noise + clip to the state-dependent box (agent/ddpg_pa.py:101-112; EVOPFEnv.update evopf.py:769-783)
  * -> complete_partial = Newton power flow (PFFunction.forward, evopf.py:789-855; newton_tol 1e-5, newton_max_iters 50)

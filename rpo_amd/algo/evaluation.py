@@ -96,7 +96,7 @@ class EvalResult(object):
     else None.  ``obs_noise``: the float32 sigma vector [obs_dim] of ``obs_noise=``, None for a clean evaluation.
     ``evaluate_opf`` (``path`` "opf"; ``proj_iters`` sums the solver's iterations): ``opf_iters`` int32 / ``opf_converged`` bool
     [episode, step], the solver's iteration count and stop flag of every live step (0 / False past the episode's end); None
-    otherwise."""
+    otherwise.  ``days``: int array [episodes], the day of ``scenarios=`` every episode played; None without scenarios."""
 
     FIELDS = ("ret", "length", "mean_ineq", "mean_eq", "max_ineq", "max_eq", "viol_steps", "proj_iters", "nonfinite")
 
@@ -117,6 +117,7 @@ class EvalResult(object):
         self.constraints = constraints
         self.obs_noise = None if obs_noise is None else np.array(obs_noise, dtype=np.float32)
         self.opf_iters = self.opf_converged = None               # evaluate_opf: [episode, step]
+        self.days = None                                         # scenarios=: int64 [episodes], the day each episode played
 
     @property
     def episodes(self):
@@ -610,14 +611,34 @@ def check_init_states(tr, init_states, n, what="evaluate"):
     return init_states
 
 
-def _make_vec(tr, n, seed):
+def check_scenarios(tr, scenarios, n, what="evaluate"):
+    """``scenarios`` of evaluate() / evaluate_opf() -> (None, None), or ((table, day) on the trainer's device: the vector env's
+    ``scenario``, days int64 numpy [n]): episode e plays day e % len(scenarios).  NotImplementedError naming EVOPF-v0 on another
+    env, backend or device; TypeError for anything but a ``Scenarios``."""
+    if scenarios is None:
+        return None, None
+    if getattr(tr.kernels, "name", None) != "EVOPF-v0" or not isinstance(tr.kernels, hip_ops.EvopfKernels) \
+            or tr.device.type != "cuda":
+        raise NotImplementedError("%s: scenarios are played by the HIP step kernel of EVOPF-v0 on a GPU (rpo_evopf_step_scenario) "
+                                  "only; this trainer's env is %s (%s) on %s"
+                                  % (what, getattr(tr.kernels, "name", "?"), type(tr.kernels).__name__, tr.device))
+    from ..env.electrical_grid.scenarios import Scenarios
+    if not isinstance(scenarios, Scenarios):
+        raise TypeError("%s: scenarios must be a Scenarios, got %s" % (what, type(scenarios).__name__))
+    days = np.arange(n, dtype=np.int64) % len(scenarios)
+    return (scenarios.table(tr.device), torch.as_tensor(days.astype(np.int32), device=tr.device)), days
+
+
+def _make_vec(tr, n, seed, scenario=None):
+    kw = {} if scenario is None else dict(scenario=scenario)
     return tr.base_env.make_vec(n, seed=seed, env_id_base=0, max_episode_steps=tr.max_episode_steps, device=tr.device,
-                                stats_cap=2, viol_thresh=tr.vec.viol_thresh)
+                                stats_cap=2, viol_thresh=tr.vec.viol_thresh, **kw)
 
 
-def _initial_env(tr, n, seed, init_states):
-    """The initial env of ``evaluate()``: n lanes reset under ``seed``, then the injection of ``init_states``."""
-    v = _make_vec(tr, n, seed)
+def _initial_env(tr, n, seed, init_states, scenario=None):
+    """The initial env of ``evaluate()``: n lanes reset under ``seed`` -- or to hour 0 of their day of ``scenario`` -- then the
+    injection of ``init_states``."""
+    v = _make_vec(tr, n, seed, scenario)
     v.reset()
     if init_states is not None:
         v.set_internal(init_states)
@@ -631,9 +652,10 @@ def _constraint_report(tr, con, length, viol_thresh):
 
 
 def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
-             constraints=False, obs_noise=None):
+             constraints=False, obs_noise=None, scenarios=None):
     """See ``RPOTrainerBase.evaluate``."""
     n = check_episodes(episodes)
+    scenario, days = check_scenarios(tr, scenarios, n)
     want_con = check_constraints(constraints)
     sigma = check_obs_noise(obs_noise, tr.kernels.obs_dim)
     if sigma is not None and not sigma.any():                    # 0 and all-zero: the clean evaluation, nothing new runs
@@ -643,7 +665,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     H = check_horizon(tr, horizon)
     k = tr.kernels
     fused = fused_ok(tr)
-    fused_evopf = not fused and fused_evopf_ok(tr, n, R, sigma)
+    fused_evopf = not fused and scenario is None and fused_evopf_ok(tr, n, R, sigma)   # (the fused kernel has no table-fed instance)
     dims = (k.obs_dim, k.partial_dim if fused else tr._eval_proposal_dim(), k.action_dim)
     if R:
         nbytes = 4 * H * R * hip_ops.trace_layout(*dims)[1]
@@ -653,7 +675,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
                              % (record, nbytes, H, R, hip_ops.trace_layout(*dims)[1], hip_ops.TRACE_MAX_BYTES))
     init_states = check_init_states(tr, init_states, n)
     seed = fresh_seed(tr) if seed is None else int(seed)
-    v = _initial_env(tr, n, seed, init_states)
+    v = _initial_env(tr, n, seed, init_states, scenario)
     acc = torch.zeros(n, 8, device=tr.device)
     # the record: zeroed here (the kernels write live lanes' rows only and never clear it), [step, episode, W]
     trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
@@ -664,6 +686,7 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
     with torch.no_grad():
         run(tr, v, acc, H, trace=trace, budget=budget, con=con, **noise)
     res = EvalResult(acc.cpu().numpy(), path, H, seed, obs_noise=sigma)
+    res.days = days
     if want_con:
         res.constraints = _constraint_report(tr, con.cpu().numpy(), res.length, v.viol_thresh)
     if R:
@@ -672,8 +695,9 @@ def evaluate(tr, episodes=10, horizon=None, seed=None, init_states=None, record=
 
 
 def evaluate_opf(tr, episodes=10, seed=None, horizon=None, init_states=None, record=False, constraints=False, pe="free",
-                 pe_cost=None, tol=1e-4, max_iters=40):
-    """See ``RPOTrainerBase.evaluate_opf``."""
+                 pe_cost=None, tol=1e-4, max_iters=40, scenarios=None):
+    """See ``RPOTrainerBase.evaluate_opf``, whose parameters these are; ``scenarios`` (here only: the method's parameter list is
+    fixed) is ``evaluate()``'s -- a ``Scenarios``, episode e plays day e % len(scenarios), ``result.days`` records it."""
     if pe not in ("free", "zero"):
         raise ValueError("evaluate_opf: pe must be 'free' (the battery power is dispatched too) or 'zero' (idle batteries), got %r"
                          % (pe,))
@@ -688,6 +712,7 @@ def evaluate_opf(tr, episodes=10, seed=None, horizon=None, init_states=None, rec
     if not tol > 0.0 or iters_cap != max_iters or iters_cap < 0:
         raise ValueError("evaluate_opf: tol must be > 0 and max_iters an integer >= 0, got %r and %r" % (tol, max_iters))
     n = check_episodes(episodes)
+    scenario, days = check_scenarios(tr, scenarios, n, "evaluate_opf")
     want_con = check_constraints(constraints)
     R = check_record(record, n)
     H = check_horizon(tr, horizon, "evaluate_opf")
@@ -709,7 +734,7 @@ def evaluate_opf(tr, episodes=10, seed=None, horizon=None, init_states=None, rec
         pe_cost = pe_cost.contiguous()
     init_states = check_init_states(tr, init_states, n, "evaluate_opf")
     seed = fresh_seed(tr) if seed is None else int(seed)
-    v = _initial_env(tr, n, seed, init_states)
+    v = _initial_env(tr, n, seed, init_states, scenario)
     acc = torch.zeros(n, 8, device=tr.device)
     trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
     con = torch.empty(n, hip_ops.con_width(k.ineq_num, k.eq_num), device=tr.device) if want_con else None
@@ -726,6 +751,7 @@ def evaluate_opf(tr, episodes=10, seed=None, horizon=None, init_states=None, rec
     with torch.no_grad():
         _run_stepwise(tr, v, acc, H, trace=trace, con=con, producer=producer)
     res = EvalResult(acc.cpu().numpy(), "opf", H, seed)
+    res.days = days
     live = np.arange(H)[None, :] < res.length[:, None]           # filled while the episode is live
     log = log.cpu().numpy().transpose(1, 0, 2)
     res.opf_iters = np.where(live, log[:, :, 0], 0).astype(np.int32)

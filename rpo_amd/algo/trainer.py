@@ -1583,7 +1583,7 @@ class RPOTrainerBase(object):
         return tuple(out)
 
     def evaluate(self, episodes=10, horizon=None, seed=None, init_states=None, record=False, eval_steps=None, eval_lr=None,
-                 constraints=False, obs_noise=None):
+                 constraints=False, obs_noise=None, scenarios=None):
         """Evaluate the current policy on ``episodes`` independent episodes -> ``EvalResult`` (per-episode arrays; ``summary()``
         is eval()'s 10-tuple).  The policy, projection and horizon are eval()'s: deterministic actor (RPOSAC: the mean head),
         ``eval_steps`` / ``eval_lr`` / ``corr_eps`` / ``corr_momentum``, at most min(500, max_episode_steps, the env's
@@ -1611,10 +1611,15 @@ class RPOTrainerBase(object):
         ``result.trajectory.obs`` holds the noisy observation, ``result.obs_noise`` the float32 sigma vector.  A column with
         sigma 0 keeps its bits; None, 0 and all-zero are the clean evaluation (the same launches and bits as without the
         argument, ``result.obs_noise`` None).  ``eval()``, curve mode, ``keep_best``, ``act()``, training and checkpoints
-        never see noise.  See rpo_amd/algo/evaluation.py."""
+        never see noise.  ``scenarios`` (EVOPF-v0 on a GPU; NotImplementedError naming it elsewhere): a ``Scenarios``
+        (rpo_amd/env/electrical_grid/scenarios.py) -- episode e plays the caller's day ``e % len(scenarios)`` instead of the day the
+        Philox streams deal, from hour 0 with an empty battery (``init_states`` still overrides hour 0 afterwards, e.g. the state
+        of charge); ``result.days`` [episodes] records it; ``seed`` then only keys ``obs_noise``; every other argument works as on
+        the stepwise path, which such a call always takes (``path == "stepwise"``, whatever ``fused_eval_evopf`` says).  The
+        sweeps and curve mode take no scenarios; the OPF controller takes them as ``rpo_amd.algo.evaluate_opf(trainer, scenarios=)``.  See rpo_amd/algo/evaluation.py."""
         from .evaluation import evaluate
         return evaluate(self, episodes=episodes, horizon=horizon, seed=seed, init_states=init_states, record=record,
-                        eval_steps=eval_steps, eval_lr=eval_lr, constraints=constraints, obs_noise=obs_noise)
+                        eval_steps=eval_steps, eval_lr=eval_lr, constraints=constraints, obs_noise=obs_noise, scenarios=scenarios)
 
     def evaluate_opf(self, episodes=10, seed=None, horizon=None, init_states=None, record=False, constraints=False, pe="free",
                      pe_cost=None, tol=1e-4, max_iters=40):
@@ -1629,7 +1634,10 @@ class RPOTrainerBase(object):
         ``result.opf_iters`` / ``result.opf_converged`` [episode, step]; ``proj_iters`` sums the iterations.  The record's
         ``proposal`` is the OPF action's components at ``env.partial_actions`` and ``iters`` the solver's iteration count:
         ``result.trajectory.save()`` of such a run is a set of expert demonstrations.  ``pe_cost`` (with ``pe="free"``): None, a
-        number, [5] or [episodes, 5]; ``tol`` / ``max_iters``: the solver's.  No trainer state changes."""
+        number, [5] or [episodes, 5]; ``tol`` / ``max_iters``: the solver's.  No trainer state changes.  On the caller's days
+        (``evaluate(scenarios=S)``): this method's parameter list is fixed, so the keyword lives on the function behind it --
+        ``rpo_amd.algo.evaluate_opf(trainer, ..., scenarios=S)`` is this call with it; the same ``Scenarios`` through both gives
+        the same ``result.days`` and hour-0 observations, the paired comparison on the caller's days."""
         from .evaluation import evaluate_opf
         return evaluate_opf(self, episodes=episodes, seed=seed, horizon=horizon, init_states=init_states, record=record,
                             constraints=constraints, pe=pe, pe_cost=pe_cost, tol=tol, max_iters=max_iters)

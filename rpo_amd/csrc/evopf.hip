@@ -44,6 +44,53 @@ __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_step_kernel(StepAr
     rpo_step_epilogue(p.ctrl, t, p.stats, p.stats_cap);
 }
 
+// ---------------------------------------------------------------------------------------------------- scenarios
+// The day lane env_id_base + i is dealt in episode ep_count[i] (NULL: 0), in the table layout: episode_obs itself for every
+// hour, so the bits are the ones the reset and the step draw.  Price: the hour-0 window; hours 24..47 are zero.
+__global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_scenario_table_kernel(int n, float* __restrict__ table,
+                                                                        const unsigned* __restrict__ ep_count,
+                                                                        const float* __restrict__ consts, uint64_t seed,
+                                                                        uint32_t env_id_base) {
+    __shared__ Ws wss[kActWaves];
+    Ws& w = wss[threadIdx.x / RPO_WAVE];
+    const int i = blockIdx.x * kActWaves + threadIdx.x / RPO_WAVE, tid = lane_id();
+    if (i >= n) return;
+    load_consts(w, consts);
+    sync();
+    float* day = table + (size_t)i * RPO_EVOPF_SCEN_DAY;
+    const unsigned ep = ep_count ? ep_count[i] : 0u;
+    for (int t = 0; t < T; ++t) {
+        episode_obs(w, w.s, seed, env_id_base + (uint32_t)i, ep, t);
+        if (tid < 2 * NB) day[2 * NAHEAD + t * 2 * NB + tid] = w.s[tid];
+        if (t == 0 && tid < NAHEAD) { day[tid] = w.s[2 * NB + NE + tid]; day[NAHEAD + tid] = 0.0f; }
+        sync();
+    }
+}
+
+// rpo_evopf_reset from a table: hour 0 of day[i], state of charge kBInit
+__global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_reset_scenario_kernel(int n, float* __restrict__ state, int* __restrict__ ep_len,
+                                                                        float* __restrict__ ep_ret, TableDays days) {
+    __shared__ Ws wss[kActWaves];
+    Ws& w = wss[threadIdx.x / RPO_WAVE];
+    const int i = blockIdx.x * kActWaves + threadIdx.x / RPO_WAVE, tid = lane_id();
+    if (i >= n) return;
+    scenario_obs(w, w.s, days.table, days.days, days.day[i], 0);
+    if (tid < NE) w.s[2 * NB + tid] = kBInit;
+    sync();
+    for (int k = tid; k < NS; k += RPO_WAVE) state[(size_t)i * NS + k] = w.s[k];
+    if (tid == 0) { ep_len[i] = 0; ep_ret[i] = 0.0f; }
+}
+
+// evopf_step_kernel with the table as the data source (p.auto_reset = 0: an evaluation seam)
+__global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_step_scenario_kernel(StepArgs p, TableDays days) {
+    __shared__ Ws wss[kActWaves];
+    __shared__ __align__(16) float rows_s[kActWaves][RPO_EVOPF_ROW];
+    const int wave = threadIdx.x / RPO_WAVE, i = blockIdx.x * kActWaves + wave;
+    const long long t = p.ctrl ? p.ctrl[RPO_CTRL_T] : 0;
+    if (i < p.n) evopf_step_lane(p, wss[wave], rows_s[wave], i, t, days);
+    rpo_step_epilogue(p.ctrl, t, p.stats, p.stats_cap);
+}
+
 // ------------------------------------------------------------------------------- explore + complete + project
 struct ActArgs {
     int n;
@@ -483,6 +530,35 @@ int rpo_evopf_step(int n_envs, float* state, const float* action, int* ep_len, f
     StepArgs p{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl, max_episode_steps,
                auto_reset, viol_thresh, consts_dev, (uint64_t)seed, (uint32_t)env_id_base};
     return launch(evopf_step_kernel, lane_grid(n_envs), kActThreads, 0, stream, p);
+}
+
+int rpo_evopf_scenario_table(int n, float* table_out, const unsigned* ep_count, const float* consts_dev, unsigned long long seed,
+                             unsigned env_id_base, void* stream) {
+    if (n <= 0) return RPO_ERR_ARG;
+    if (!table_out || !consts_dev) return RPO_ERR_NULL;
+    return launch(evopf_scenario_table_kernel, lane_grid(n), kActThreads, 0, stream, n, table_out, ep_count, consts_dev, (uint64_t)seed,
+                  (uint32_t)env_id_base);
+}
+
+int rpo_evopf_reset_scenario(int n_envs, float* state, int* ep_len, float* ep_ret, const float* table, int days, const int* day,
+                             const float* consts_dev, void* stream) {
+    if (int e = check_common(n_envs, state, ep_len, consts_dev)) return e;
+    if (days <= 0) return RPO_ERR_ARG;
+    if (!ep_ret || !table || !day) return RPO_ERR_NULL;
+    return launch(evopf_reset_scenario_kernel, lane_grid(n_envs), kActThreads, 0, stream, n_envs, state, ep_len, ep_ret,
+                  TableDays{table, days, day});
+}
+
+int rpo_evopf_step_scenario(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count,
+                            float* rows, long long cap_steps, float* stats, int stats_cap, long long* ctrl, int max_episode_steps,
+                            float viol_thresh, const float* consts_dev, const float* table, int days, const int* day, void* stream) {
+    if (int e = check_common(n_envs, state, action, consts_dev)) return e;
+    if (days <= 0) return RPO_ERR_ARG;
+    if (!ep_len || !ep_ret || !ep_count || !table || !day) return RPO_ERR_NULL;
+    if (max_episode_steps <= 0 || (rows && cap_steps <= 0) || (stats && stats_cap <= 0)) return RPO_ERR_ARG;
+    StepArgs p{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl, max_episode_steps,
+               0, viol_thresh, consts_dev, 0ull, 0u};
+    return launch(evopf_step_scenario_kernel, lane_grid(n_envs), kActThreads, 0, stream, p, TableDays{table, days, day});
 }
 
 int rpo_evopf_act_project(int n, const float* state, int state_stride, const float* ap_raw, const float* noise, float* action, int* iters,

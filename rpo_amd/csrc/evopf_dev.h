@@ -796,6 +796,23 @@ __device__ __forceinline__ void episode_obs(Ws& w, float* out, uint64_t seed, ui
     sync();
 }
 
+// The same hour read from a caller's table instead (layout RPO_EVOPF_SCEN_DAY, rpo_hip.h: price of hours 0..47, then (pd[14],
+// qd[14]) per hour): out[0..28) = demand[t], out[33 + k] = price[t + k] -- the look-ahead runs past midnight into hours 24..47,
+// which the Philox days leave zero -- and all zero when t >= 24, as above.  A day outside [0, days) never indexes the table:
+// the lane's observation becomes NaN, which the step's failure word reports.  The barriers of episode_obs (its first one orders
+// w.vec, which nothing writes here).
+__device__ __forceinline__ void scenario_obs(Ws& w, float* out, const float* __restrict__ table, int days, int day, int t) {
+    const int tid = lane_id();
+    const bool over = t >= T, known = day >= 0 && day < days;
+    const float* d = table + (size_t)(known ? day : 0) * RPO_EVOPF_SCEN_DAY;
+    const float fill = known ? 0.0f : __builtin_nanf("");
+    const bool read = known && !over;
+    sync();
+    if (tid < 2 * NB) out[tid] = read ? d[2 * NAHEAD + t * 2 * NB + tid] : fill;
+    if (tid < NAHEAD) out[2 * NB + NE + tid] = read ? d[t + tid] : fill;
+    sync();
+}
+
 __device__ __forceinline__ void load_row(float* dst, const float* __restrict__ src, int n) {
     for (int i = lane_id(); i < n; i += RPO_WAVE) dst[i] = src[i];
 }
@@ -828,10 +845,28 @@ struct StepArgs {
     uint32_t env_id_base;
 };
 
+// Where a stepping lane takes its episode data from: hour t of episode `ep` of lane i (env id `env_id`) into out (state of
+// charge untouched).
+struct PhiloxDays {       // the loaders' draws, keyed by (p.seed, env_id, ep)
+    __device__ __forceinline__ void obs(const StepArgs& p, Ws& w, float* out, int, uint32_t env_id, unsigned ep, int t) const {
+        episode_obs(w, out, p.seed, env_id, ep, t);
+    }
+};
+struct TableDays {        // row day[i] of a scenario table [days, RPO_EVOPF_SCEN_DAY], whatever the episode
+    const float* table;
+    int days;
+    const int* day;
+    __device__ __forceinline__ void obs(const StepArgs&, Ws& w, float* out, int i, uint32_t, unsigned, int t) const {
+        scenario_obs(w, out, table, days, day[i], t);
+    }
+};
+
 // EVOPFEnv.step (evopf.py:348-366) + Battery.step (:74-102) + the bookkeeping of the run loop (rpo_ddpg.py:120-145):
 // violations of the pre-step observation, reward, next hour of the episode data, replay scatter, statistics, auto-reset.
 // Shared by evopf_step_kernel (evopf.hip) and the fused evaluation (evopf_eval.hip: rows = stats = NULL, auto_reset = 0).
-__device__ __forceinline__ void evopf_step_lane(const StepArgs& p, Ws& w, float* row, int i, long long t) {
+// `days`: the source of the episode data -- the Philox draws, or evopf_step_scenario_kernel's table.
+template <typename Days = PhiloxDays>
+__device__ __forceinline__ void evopf_step_lane(const StepArgs& p, Ws& w, float* row, int i, long long t, const Days& days = Days{}) {
     RPO_FP_STRICT
     const int tid = lane_id();
     load_consts(w, p.consts);
@@ -862,7 +897,7 @@ __device__ __forceinline__ void evopf_step_lane(const StepArgs& p, Ws& w, float*
     for (int k = tid; k < NS; k += RPO_WAVE) row[k] = w.s[k];
     if (tid < NY) row[NS + tid] = w.a[tid];
     float* nxt = row + NS + NY;
-    episode_obs(w, nxt, p.seed, env_id, ep, len);
+    days.obs(p, w, nxt, i, env_id, ep, len);
     if (tid < NE) {                                                    // Battery.step :86-97
         const float soc = w.s[2 * NB + tid];
         float p_max, p_min;
@@ -890,7 +925,7 @@ __device__ __forceinline__ void evopf_step_lane(const StepArgs& p, Ws& w, float*
     // the lane continues from the next observation, or from a fresh episode (env.reset() after a done, rpo_ddpg.py:142)
     const float ret = p.ep_ret[i] + reward;
     if (done && p.auto_reset) {
-        episode_obs(w, w.s, p.seed, env_id, ep + 1u, 0);
+        days.obs(p, w, w.s, i, env_id, ep + 1u, 0);
         if (tid < NE) w.s[2 * NB + tid] = kBInit;
         sync();
         for (int k = tid; k < NS; k += RPO_WAVE) p.state[(size_t)i * NS + k] = w.s[k];

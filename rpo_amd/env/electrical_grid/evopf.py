@@ -306,6 +306,27 @@ class EVOPFEnv(HardConstraintEnv):
                                       "kernel rpo_evopf_opf_free only")
         return fn
 
+    # ------------------------------------------------------------------------------------------ scenarios
+    def scenarios(self, n, seed=0, env_id_base=0, episode=0):
+        """The ``Scenarios`` (scenarios.py) that lanes ``env_id_base .. env_id_base + n - 1`` are dealt under ``seed`` in episode
+        ``episode``: the Philox days, written by the device function the reset and step kernels draw with
+        (rpo_evopf_scenario_table), so playing them back gives those kernels' bits.  There is no CPU path."""
+        fn = getattr(self._backend, "evopf_scenario_table", None)
+        if fn is None:
+            raise NotImplementedError("this backend has no evopf_scenario_table kernel: the days the Philox streams deal are "
+                                      "written by the HIP kernel rpo_evopf_scenario_table only (the CPU oracle backend has none)")
+        if self.device.type != "cuda":
+            raise NotImplementedError("the scenario table is written by the HIP kernel rpo_evopf_scenario_table and needs a GPU "
+                                      "device, got %s: there is no CPU path" % self.device)
+        for name, x in (("n", n), ("env_id_base", env_id_base), ("episode", episode)):
+            if isinstance(x, bool) or int(x) != x or x < (1 if name == "n" else 0):
+                raise ValueError("scenarios: %s must be an integer >= %d, got %r" % (name, 1 if name == "n" else 0, x))
+        from .scenarios import Scenarios
+        table = torch.empty(int(n), hip_ops.CONST["RPO_EVOPF_SCEN_DAY"], device=self.device)
+        ep = torch.full((int(n),), int(episode), dtype=torch.int32, device=self.device) if episode else None
+        fn(self.kernels, table, ep, int(seed), int(env_id_base))
+        return Scenarios.from_table(table.cpu().numpy())
+
     def default_pe_cost(self, state):
         """The price of a unit of battery power in units of ``obj_fn`` under the env's reward, per row of observations [n, 57]
         -> [n, 5]: (we / wg) * the row's current price in every component (what rpo_evopf_opf_free uses for a NULL pe_cost)."""

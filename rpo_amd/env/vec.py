@@ -11,7 +11,7 @@ from .. import ops as hip_ops
 class VecEnv(object):
 
     def __init__(self, kernels, n_envs, device, seed=0, env_id_base=0, max_episode_steps=None, viol_thresh=1e-3,
-                 stats_cap=4096, ctrl=None):
+                 stats_cap=4096, ctrl=None, scenario=None):
         self.k = kernels
         self.n = int(n_envs)
         self.device = device
@@ -31,8 +31,17 @@ class VecEnv(object):
         self.stats = hip_ops.new_stats(stats_cap, device)
         self.ctrl = ctrl if ctrl is not None else torch.zeros(hip_ops.CTRL_LEN, dtype=torch.int64, device=device)
         self.steps_host = 0
+        # (table [days, SCEN_DAY] float32, day [n] int32) on the device: the lanes play the caller's days, not the Philox draws
+        # (EVOPF-v0 only: ops.evopf_reset_scenario / evopf_step_scenario; an evaluation seam -- no auto-reset)
+        self.scenario = scenario
+        if scenario is not None and not isinstance(kernels, hip_ops.EvopfKernels):
+            raise NotImplementedError("scenarios are built for the HIP kernels of EVOPF-v0 only (its step kernel reads the "
+                                      "table), not %s" % type(kernels).__name__)
 
     def reset(self):
+        if self.scenario is not None:
+            hip_ops.evopf_reset_scenario(self.k, self.internal, self.ep_len, self.ep_ret, *self.scenario)
+            return self.obs
         self.k.reset(self.internal, self.obs, self.ep_len, self.ep_ret, self.ep_count, self.seed, self.env_id_base)
         return self.obs
 
@@ -48,6 +57,13 @@ class VecEnv(object):
 
     def step(self, action, rows=None, cap_steps=1, auto_reset=True):
         """One fused vector step; scatters the transitions into ``rows`` (the replay ring) when given."""
+        if self.scenario is not None:
+            if auto_reset:
+                raise ValueError("a VecEnv with a scenario never auto-resets: step(auto_reset=False)")
+            hip_ops.evopf_step_scenario(self.k, self.internal, action, self.ep_len, self.ep_ret, self.ep_count, rows, cap_steps,
+                                        self.stats, self.ctrl, self.max_episode_steps, self.viol_thresh, *self.scenario)
+            self.steps_host += 1
+            return self.obs
         self.k.step(self.internal, self.obs, action, self.ep_len, self.ep_ret, self.ep_count, rows, cap_steps,
                     self.stats, self.ctrl, self.max_episode_steps, auto_reset, self.viol_thresh, self.seed,
                     self.env_id_base)

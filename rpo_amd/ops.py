@@ -866,6 +866,55 @@ def evopf_opf_free(kernels, obs, pe_cost, action, info, tol, max_iters):
                                          float(tol), int(max_iters), kernels._c(action), _stream()), "rpo_evopf_opf_free")
 
 
+SCEN_DAY = CONST["RPO_EVOPF_SCEN_DAY"]    # floats per day of a scenario table: price[48] | 24 x (pd[14], qd[14])
+
+
+def _scenario(table, day, n):
+    """(table pointer, days, day pointer) of a scenario: table [days >= 1, SCEN_DAY] contiguous float32, day [n] int32, both on
+    the lanes' device."""
+    if table is None or table.dim() != 2 or table.shape[1] != SCEN_DAY or table.shape[0] < 1 or table.dtype != torch.float32 \
+            or not table.is_contiguous():
+        raise RpoHipError("scenario table must be a contiguous float32 [days >= 1, %d], got %s"
+                          % (SCEN_DAY, None if table is None else (tuple(table.shape), table.dtype)))
+    if day is None or tuple(day.shape) != (n,) or day.dtype != torch.int32 or not day.is_contiguous():
+        raise RpoHipError("scenario day must be a contiguous int32 [%d], got %s"
+                          % (n, None if day is None else (tuple(day.shape), day.dtype)))
+    return _p(table), int(table.shape[0]), _p(day, torch.int32)
+
+
+def evopf_scenario_table(kernels, table_out, ep_count, seed, env_id_base):
+    """The days lanes env_id_base .. env_id_base + n - 1 are dealt under ``seed`` in episode ep_count[i] (None: 0), in the scenario
+    table layout (rpo_evopf_scenario_table): table_out [n, SCEN_DAY] contiguous float32.  A function of the backend like
+    ``evopf_opf``, not a method: the env kernel classes keep their public methods."""
+    if table_out is None or table_out.dim() != 2 or table_out.shape[1] != SCEN_DAY or table_out.shape[0] < 1 \
+            or table_out.dtype != torch.float32 or not table_out.is_contiguous():
+        raise RpoHipError("evopf_scenario_table: table_out must be a contiguous float32 [n >= 1, %d]" % SCEN_DAY)
+    n = table_out.shape[0]
+    if ep_count is not None and (tuple(ep_count.shape) != (n,) or ep_count.dtype != torch.int32):
+        raise RpoHipError("evopf_scenario_table: ep_count must be int32 [%d] or None" % n)
+    check(_lib.load().rpo_evopf_scenario_table(n, _p(table_out), _p(ep_count, torch.int32, allow_none=True),
+                                               kernels._c(table_out), int(seed), int(env_id_base), _stream()),
+          "rpo_evopf_scenario_table")
+
+
+def evopf_reset_scenario(kernels, internal, ep_len, ep_ret, table, day):
+    """``kernels.reset`` with hour 0 of table row day[i] (rpo_evopf_reset_scenario)."""
+    tp, days, dp = _scenario(table, day, internal.shape[0])
+    check(_lib.load().rpo_evopf_reset_scenario(internal.shape[0], _p(internal), _p(ep_len, torch.int32), _p(ep_ret), tp, days, dp,
+                                               kernels._c(internal), _stream()), "rpo_evopf_reset_scenario")
+
+
+def evopf_step_scenario(kernels, internal, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, ctrl, max_episode_steps,
+                        viol_thresh, table, day):
+    """``kernels.step`` with the next hour read from table row day[i]; never auto-resets (rpo_evopf_step_scenario)."""
+    tp, days, dp = _scenario(table, day, internal.shape[0])
+    check(_lib.load().rpo_evopf_step_scenario(
+        internal.shape[0], _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32),
+        _ring(rows, kernels.ring_floats), cap_steps, _p(stats, allow_none=True), 0 if stats is None else stats.shape[0],
+        _p(ctrl, torch.int64, allow_none=True), max_episode_steps, viol_thresh, kernels._c(internal), tp, days, dp, _stream()),
+        "rpo_evopf_step_scenario")
+
+
 class PendulumKernels(_FusedEnvKernels):
     """HIP kernels of SpringPendulum-v0."""
 
