@@ -423,13 +423,19 @@ def cart_lagrangian_t64(table, partial, action, nu, scale):
     return row.detach().numpy(), dist.detach().numpy(), ga.numpy()
 
 
-def cart_lagrangian(A, table, partial, action, nu, scale, mask=None):
+def _cols(A, x, exact):
+    """The columns of x as inputs of ``A``.  ``exact`` (B64 only; tests/update_f64.py): float64 values are taken as they are
+    instead of through their float32 rounding -- the value a float64 chain hands on, not a kernel's output."""
+    x = np.asarray(x, np.float64 if exact else np.float32)
+    return [V(x[..., i]) if exact else A.inp(x[..., i]) for i in range(x.shape[-1])]
+
+
+def cart_lagrangian(A, table, partial, action, nu, scale, mask=None, exact=False):
     """lagrangian_row + the scale of the elementwise launch, with bounds: dict(dist [6], g0, g1, margins [6]); ``mask`` [n,6]
-    overrides the predicates g_j > 0 of the gradient."""
+    overrides the predicates g_j > 0 of the gradient.  ``exact``: see ``_cols``."""
     with np.errstate(all="ignore"):
         c = CartTab(A, table, partial)
-        a = np.asarray(action, np.float32)
-        h, g = cart_eq_ineq(A, c, A.inp(a[:, 0]), A.inp(a[:, 1]))
+        h, g = cart_eq_ineq(A, c, *_cols(A, action, exact))
         nu = [A.inp(np.float32(v)) for v in nu]
         g0 = g1 = None
         for j in range(6):
@@ -440,14 +446,14 @@ def cart_lagrangian(A, table, partial, action, nu, scale, mask=None):
         return dict(dist=[A.maximum(gj, A.k(0.0)) for gj in g], g0=s * g0, g1=s * g1, margins=g)
 
 
-def cart_complete_bwd(A, table, partial, ga):
-    """d/d ap of the loss through complete_partial (cartpole.py:369-373): g_p + (-(C_p C_o_inv)) g_o."""
+def cart_complete_bwd(A, table, partial, ga, exact=False):
+    """d/d ap of the loss through complete_partial (cartpole.py:369-373): g_p + (-(C_p C_o_inv)) g_o.  ``exact``: see ``_cols``."""
     with np.errstate(all="ignore"):
         c = CartTab(A, table, partial)
-        ga = np.asarray(ga, np.float32)
-        gp, go = cart_split(partial, ga)
+        g0, g1 = _cols(A, ga, exact)
+        gp, go = (g0, g1) if partial == 0 else (g1, g0)
         k = -(c.C_p * c.C_o_inv)
-        return A.inp(gp) + k * A.inp(go)
+        return gp + k * go
 
 
 def cart_complete_bwd_fd(table, partial, ga):
@@ -700,21 +706,22 @@ def pend_lagrangian_t64(action, nu0, scale):
     return dist.detach().numpy(), ga.numpy()
 
 
-def pend_lagrangian(A, action, nu0, scale, mask=None):
-    """lagrangian_row: dict(dist, g0, g1, margin g); ``mask`` [n] overrides the predicate g > 0 of the gradient."""
+def pend_lagrangian(A, action, nu0, scale, mask=None, exact=False):
+    """lagrangian_row: dict(dist, g0, g1, margin g); ``mask`` [n] overrides the predicate g > 0 of the gradient.  ``exact``: see
+    ``_cols``."""
     with np.errstate(all="ignore"):
-        a = np.asarray(action, np.float32)
-        ax, ay = A.inp(a[:, 0]), A.inp(a[:, 1])
+        ax, ay = _cols(A, action, exact)
         g = ax * ax + ay * ay - A.k(opd.MAX_SUMMATION)
         k = A.where(A.val(g) > 0 if mask is None else np.asarray(mask), A.k(2.0) * A.inp(np.float32(scale)) * A.inp(np.float32(nu0)), A.k(0.0))
         return dict(dist=A.maximum(g, A.k(0.0)), g0=k * ax, g1=k * ay, margin=g)
 
 
-def pend_complete_bwd(A, obs, ga):
-    """d a_y / d a_x = -C_p C_o_inv (pendulum.py:256-262): g0 - g1 (sin (1 / cos))."""
+def pend_complete_bwd(A, obs, ga, exact=False):
+    """d a_y / d a_x = -C_p C_o_inv (pendulum.py:256-262): g0 - g1 (sin (1 / cos)).  ``exact`` (the gradient only): see ``_cols``."""
     with np.errstate(all="ignore"):
-        obs, ga = np.asarray(obs, np.float32), np.asarray(ga, np.float32)
-        return A.inp(ga[:, 0]) - A.inp(ga[:, 1]) * (A.inp(obs[:, 1]) * (A.k(1.0) / A.inp(obs[:, 0])))
+        obs = np.asarray(obs, np.float32)
+        g0, g1 = _cols(A, ga, exact)
+        return g0 - g1 * (A.inp(obs[:, 1]) * (A.k(1.0) / A.inp(obs[:, 0])))
 
 
 def pend_complete_bwd_fd(obs, ga):
