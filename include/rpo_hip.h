@@ -217,6 +217,7 @@ extern "C" {
 #define RPO_STREAM_EVOPF_DEMAND 5 /* episode load profile: Dirichlet + power factors (data/demand.py:53-62) */
 #define RPO_STREAM_EVOPF_PRICE 6  /* episode price profile: magnitude + hourly noise   (data/price.py:41-43)  */
 #define RPO_STREAM_EVAL_OBS 7     /* evaluate(obs_noise=): counter (episode, step, this + 0x100 * column, 0), words 0 and 1 */
+#define RPO_STREAM_EVOPF_DAY 8    /* scenario bank, deal "uniform": counter (env, episode, this, 0), word 0 -> the day of the episode */
 
 int rpo_abi_version(void);
 
@@ -854,6 +855,32 @@ int rpo_evopf_reset_scenario(int n_envs, float* state, int* ep_len, float* ep_re
 int rpo_evopf_step_scenario(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count,
                             float* rows, long long cap_steps, float* stats, int stats_cap, long long* ctrl, int max_episode_steps,
                             float viol_thresh, const float* consts_dev, const float* table, int days, const int* day, void* stream);
+
+/* Scenario bank: TRAINING on a caller's days (additive, RPO_ABI_VERSION stays 6).  `table` is a scenario table as above, used as
+ * a bank: lane env_id_base + i plays in episode e the row
+ *   deal RPO_EVOPF_DEAL_UNIFORM: umulhi(word 0 of Philox(seed; env id, e, RPO_STREAM_EVOPF_DAY, 0), days)
+ *   deal RPO_EVOPF_DEAL_CYCLE:   (env id + (64-bit) e * stride) mod days, stride = the run's total lane count
+ * -- a pure function of (seed, env id, episode): no per-lane day array exists, ep_count is the whole state.  Refused before any
+ * launch: n <= 0, days < 1, a deal other than these two, stride < 1 with the cycle (RPO_ERR_ARG), a NULL among the required
+ * pointers (RPO_ERR_NULL; ep_count may be NULL where rpo_evopf_reset allows it: episode 0), and what rpo_evopf_step refuses. */
+#define RPO_EVOPF_DEAL_UNIFORM 0
+#define RPO_EVOPF_DEAL_CYCLE 1
+
+/* rpo_evopf_reset with hour 0 of the day dealt for episode ep_count[i]; state of charge as there. */
+int rpo_evopf_reset_bank(int n_envs, float* state, int* ep_len, float* ep_ret, const unsigned* ep_count, const float* table, int days,
+                         int deal, int stride, unsigned long long seed, unsigned env_id_base, void* stream);
+
+/* rpo_evopf_step (its whole argument list, auto_reset included) with the episode data read from the bank: the next hour from the
+ * day of episode ep_count[i], and at done && auto_reset hour 0 of the day of episode ep_count[i] + 1. */
+int rpo_evopf_step_bank(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count, float* rows,
+                        long long cap_steps, float* stats, int stats_cap, long long* ctrl, int max_episode_steps, int auto_reset,
+                        float viol_thresh, const float* consts_dev, unsigned long long seed, unsigned env_id_base, const float* table,
+                        int days, int deal, int stride, void* stream);
+
+/* day_out[i] (int [n]) = the bank row lane env_id_base + i plays in episode ep_count[i] (NULL: 0): what the two kernels above
+ * compute, for the host to ask which day a lane is on. */
+int rpo_evopf_bank_days(int n, const unsigned* ep_count, int days, int deal, int stride, unsigned long long seed, unsigned env_id_base,
+                        int* day_out, void* stream);
 
 /* take_action's noise + clip to the state-dependent box (agent/ddpg_pa.py:101-112; EVOPFEnv.update evopf.py:769-783)
  * -> complete_partial = Newton power flow (PFFunction.forward, evopf.py:789-855; newton_tol 1e-5, newton_max_iters 50)

@@ -20,7 +20,7 @@ class RPODDPG(RPOTrainerBase):
                  init_nju=0.0, fixed=False, clip_thres="inf", partial=False, partial_idx=None,
                  device=torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"),
                  num_envs=None, seed=None, backend=None, use_graph=None, updates_per_step=None, schedule=None,
-                 eval_episodes=None, keep_best=None):
+                 eval_episodes=None, keep_best=None, scenarios=None, deal="uniform"):
         base = getattr(env, "unwrapped", env)
         agent = PDDDPG_PA(
             base.state_dim, base.action_dim, base.eq_num, base.ineq_num, embed_dim=embed_dim, hidden_dim=hidden_dim,
@@ -32,7 +32,7 @@ class RPODDPG(RPOTrainerBase):
             partial_idx=base.partial_actions if partial_idx is None else partial_idx, device=device, backend=backend,
             clip_thres=clip_thres)
         self._setup(env, work_dir, name, logger, agent, hyperparameters(locals()), device, num_envs, seed, backend, use_graph,
-                    updates_per_step, schedule=schedule)
+                    updates_per_step, schedule=schedule, scenarios=scenarios, deal=deal)
 
     # ---- rollout policy (rpo_ddpg.py:98-106, agent/ddpg_pa.py:101-112) ----------------------------------------
     def _actor_out(self, name, obs, save=False, tag=None):

@@ -22,7 +22,7 @@ class RPOSAC(RPOTrainerBase):
                  clip_thres="inf", partial=False, partial_idx=None,
                  device=torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"),
                  num_envs=None, seed=None, backend=None, use_graph=None, updates_per_step=None, schedule=None,
-                 eval_episodes=None, keep_best=None):
+                 eval_episodes=None, keep_best=None, scenarios=None, deal="uniform"):
         base = getattr(env, "unwrapped", env)
         agent = PDSAC_PA(
             automatic_entropy_tuning, base.state_dim, base.action_dim, base.eq_num, base.ineq_num,
@@ -36,7 +36,7 @@ class RPOSAC(RPOTrainerBase):
             backend=backend, clip_thres=clip_thres)
         self.automatic_entropy_tuning = automatic_entropy_tuning
         self._setup(env, work_dir, name, logger, agent, hyperparameters(locals()), device, num_envs, seed, backend, use_graph,
-                    updates_per_step, schedule=schedule)
+                    updates_per_step, schedule=schedule, scenarios=scenarios, deal=deal)
         self._act_kw = {}        # the Gaussian head kernels emit finished (boxed, clipped) basic actions, never raw ones
 
     _gauss_policy = True

@@ -301,6 +301,24 @@ _HP_NAMES = ("max_steps", "corr_lr", "eval_lr", "corr_eps", "corr_momentum", "co
              "eval_episodes", "keep_best")
 
 
+def _check_bank(scenarios, deal, base_env, device):
+    """``scenarios`` / ``deal`` of a trainer's constructor -> the ``Scenarios`` to train on, or None.  TypeError for anything but a
+    ``Scenarios``, ValueError for an unknown ``deal``, NotImplementedError naming EVOPF-v0 where its HIP step kernel does not run."""
+    from ..env.electrical_grid.scenarios import Scenarios
+    if scenarios is not None and not isinstance(scenarios, Scenarios):
+        raise TypeError("scenarios must be a Scenarios (rpo_amd.env.electrical_grid), got %s" % type(scenarios).__name__)
+    if not isinstance(deal, str) or deal not in hip_ops.DEALS:
+        raise ValueError("deal must be one of %s, got %r" % (sorted(hip_ops.DEALS), deal))
+    if scenarios is None:
+        return None
+    k = base_env.kernels
+    if getattr(k, "name", None) != "EVOPF-v0" or not isinstance(k, hip_ops.EvopfKernels) or torch.device(device).type != "cuda":
+        raise NotImplementedError("scenarios=: a scenario bank is played by the HIP step kernel of EVOPF-v0 on a GPU "
+                                  "(rpo_evopf_step_bank) only; this trainer's env is %s (%s) on %s"
+                                  % (getattr(k, "name", "?"), type(k).__name__, device))
+    return scenarios
+
+
 def hyperparameters(args):
     """The trainer attributes `_setup` takes from a constructor's arguments (``args``: its ``locals()``)."""
     return {k: args[k] for k in _HP_NAMES}
@@ -322,8 +340,9 @@ class RPOTrainerBase(object):
     _HOST_STATE = tuple(_HOST_STATE_DEFAULTS)
 
     def _setup(self, env, work_dir, name, logger, agent, hp, device, num_envs=None, seed=None, backend=None,
-               use_graph=None, updates_per_step=None, fused=None, schedule=None):
+               use_graph=None, updates_per_step=None, fused=None, schedule=None, scenarios=None, deal="uniform"):
         self.env, self.agent, self.device = env, agent, device
+        self.scenarios, self.deal = _check_bank(scenarios, deal, getattr(env, "unwrapped", env), device), deal
         self.schedule = parse_schedule(schedule)
         if fused is not None:
             self.schedule["fused_mlp"] = int(bool(fused))
@@ -365,8 +384,15 @@ class RPOTrainerBase(object):
             seed = self.dist.sync_initial_state(seed, agent, device)
         self.seed = int(seed)
         self.max_episode_steps = getattr(env, "_max_episode_steps", None)
+        # scenarios=: the training lanes play the caller's days -- every episode of lane (rank * n_local + i) is dealt a day of the
+        # bank by `deal`, a function of (seed, global lane id, episode) with stride = the GLOBAL lane count, so data-parallel
+        # ranks play disjoint lanes of one deal.  Only this VecEnv changes: eval(), curve mode, evaluate() and act() play what
+        # they play without a bank (held-out days: evaluate(scenarios=S_test)).
+        bank = {} if self.scenarios is None else dict(bank=(self.scenarios.table(device), deal, self.num_envs))
+        self._bank_state = None if self.scenarios is None else dict(days=len(self.scenarios), deal=deal, stride=self.num_envs,
+                                                                    digest=self.scenarios.digest())
         self.vec = self.base_env.make_vec(self.n_local, seed=self.seed, env_id_base=self.dist.rank * self.n_local,
-                                          max_episode_steps=self.max_episode_steps, device=device)
+                                          max_episode_steps=self.max_episode_steps, device=device, **bank)
         self.buffer = agent.attach_env(self.kernels, self.n_local, self.seed + 7919 * (self.dist.rank + 1), self.vec.ctrl)
         self._batch = torch.zeros(self.batch_size, self.kernels.row_floats, device=device)
         P = self.kernels.partial_dim                                    # basic actions per env (1, 1, 14)
@@ -1796,6 +1822,16 @@ class RPOTrainerBase(object):
             print(f"lambda: {self.agent.lamb}, nju: {self.agent.nju}")
         print("============================\n")
 
+    def scenario_days(self):
+        """The day of the bank every local lane is on now -> int64 numpy [n_local] (``rpo_evopf_bank_days`` on the live episode
+        counters); None for a trainer without ``scenarios=``."""
+        if self.scenarios is None:
+            return None
+        v = self.vec
+        out = torch.empty(v.n, dtype=torch.int32, device=self.device)
+        hip_ops.evopf_bank_days(out, v.ep_count, len(self.scenarios), self.deal, self.num_envs, v.seed, v.env_id_base)
+        return out.cpu().numpy().astype(np.int64)
+
     # ------------------------------------------------------------------------------------------ checkpoints
     def save(self, replay=True):
         """Checkpoint for an exact resume (the reference's save/load, agent/ddpg_pa.py:92-99, stores
@@ -1819,6 +1855,8 @@ class RPOTrainerBase(object):
                      env=self.kernels.name, projection_mode=self.projection_mode)
         if self._curve is not None:                                 # (an additional entry: older checkpoints load without it;
             state["eval_curve"] = self._curve.state()               #  keep_best: + the kept span, its row and its point index)
+        if self._bank_state is not None:                            # (likewise additional: the bank the lanes are dealt from; the day
+            state["bank"] = dict(self._bank_state)                  #  a lane is on follows from seed, lane id and ep_count alone)
         torch.save(state, os.path.join(d, "trainer_state.pth"))
 
     def load(self, weights_only=False):
@@ -1836,6 +1874,8 @@ class RPOTrainerBase(object):
                         row_floats=self.kernels.row_floats, algo=type(self).__name__, env=self.kernels.name,
                         projection_mode=self.projection_mode)
             diff = {k: (st[k], v) for k, v in mine.items() if k in st and st[k] != v}
+            if st.get("bank") != self._bank_state:                  # bank or no bank, and days, deal, stride, digest
+                diff["bank"] = (st.get("bank"), self._bank_state)
             if diff:
                 raise ValueError("checkpoint does not match this trainer (checkpoint, trainer): %s" % diff)
             if st["rows"] is None and st["t"] > 0:

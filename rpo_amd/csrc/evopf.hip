@@ -91,6 +91,43 @@ __global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_step_scenario_kern
     rpo_step_epilogue(p.ctrl, t, p.stats, p.stats_cap);
 }
 
+// ------------------------------------------------------------------------------------------------ scenario bank
+// Training on the caller's days: the table is a bank, and a lane is dealt a row of it anew for every episode (bank_day,
+// evopf_dev.h).  rpo_evopf_reset from the bank: hour 0 of the day dealt for episode ep_count[i] (NULL: 0).
+__global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_reset_bank_kernel(int n, float* __restrict__ state, int* __restrict__ ep_len,
+                                                                    float* __restrict__ ep_ret,
+                                                                    const unsigned* __restrict__ ep_count, BankDays days,
+                                                                    uint64_t seed, uint32_t env_id_base) {
+    __shared__ Ws wss[kActWaves];
+    Ws& w = wss[threadIdx.x / RPO_WAVE];
+    const int i = blockIdx.x * kActWaves + threadIdx.x / RPO_WAVE, tid = lane_id();
+    if (i >= n) return;
+    const int day = bank_day(seed, env_id_base + (uint32_t)i, ep_count ? ep_count[i] : 0u, days.days, days.deal, days.stride);
+    scenario_obs(w, w.s, days.table, days.days, day, 0);
+    if (tid < NE) w.s[2 * NB + tid] = kBInit;
+    sync();
+    for (int k = tid; k < NS; k += RPO_WAVE) state[(size_t)i * NS + k] = w.s[k];
+    if (tid == 0) { ep_len[i] = 0; ep_ret[i] = 0.0f; }
+}
+
+// evopf_step_kernel with the bank as the data source; p.auto_reset is the caller's: a finished lane goes on with its next deal
+__global__ __launch_bounds__(RPO_WAVE * kActWaves) void evopf_step_bank_kernel(StepArgs p, BankDays days) {
+    __shared__ Ws wss[kActWaves];
+    __shared__ __align__(16) float rows_s[kActWaves][RPO_EVOPF_ROW];
+    const int wave = threadIdx.x / RPO_WAVE, i = blockIdx.x * kActWaves + wave;
+    const long long t = p.ctrl ? p.ctrl[RPO_CTRL_T] : 0;
+    if (i < p.n) evopf_step_lane(p, wss[wave], rows_s[wave], i, t, days);
+    rpo_step_epilogue(p.ctrl, t, p.stats, p.stats_cap);
+}
+
+// Which day every lane is on: day[i] = bank_day of episode ep_count[i] (NULL: 0).  One thread per lane.
+__global__ __launch_bounds__(RPO_BLOCK) void evopf_bank_days_kernel(int n, const unsigned* __restrict__ ep_count, int days, int deal,
+                                                                    uint32_t stride, uint64_t seed, uint32_t env_id_base,
+                                                                    int* __restrict__ day) {
+    for (long long i = (long long)blockIdx.x * RPO_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * RPO_BLOCK)
+        day[i] = bank_day(seed, env_id_base + (uint32_t)i, ep_count ? ep_count[i] : 0u, days, deal, stride);
+}
+
 // ------------------------------------------------------------------------------- explore + complete + project
 struct ActArgs {
     int n;
@@ -507,6 +544,14 @@ int check_common(int n, const void* a, const void* b, const float* consts) {
     return 0;
 }
 
+// a bank's words: days >= 1, deal 0 "uniform" or 1 "cycle", and a stride >= 1 for the cycle (bank_day divides by days)
+int check_deal(int days, int deal, int stride) {
+    if (days < 1 || deal < RPO_EVOPF_DEAL_UNIFORM || deal > RPO_EVOPF_DEAL_CYCLE) return RPO_ERR_ARG;
+    if (deal == RPO_EVOPF_DEAL_CYCLE && stride < 1) return RPO_ERR_ARG;
+    return 0;
+}
+int check_bank(const float* table, int days, int deal, int stride) { return table ? check_deal(days, deal, stride) : RPO_ERR_NULL; }
+
 }  // namespace
 
 // ====================================================================================================== C ABI
@@ -559,6 +604,37 @@ int rpo_evopf_step_scenario(int n_envs, float* state, const float* action, int* 
     StepArgs p{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl, max_episode_steps,
                0, viol_thresh, consts_dev, 0ull, 0u};
     return launch(evopf_step_scenario_kernel, lane_grid(n_envs), kActThreads, 0, stream, p, TableDays{table, days, day});
+}
+
+int rpo_evopf_reset_bank(int n_envs, float* state, int* ep_len, float* ep_ret, const unsigned* ep_count, const float* table, int days,
+                         int deal, int stride, unsigned long long seed, unsigned env_id_base, void* stream) {
+    if (n_envs <= 0) return RPO_ERR_ARG;
+    if (!state || !ep_len || !ep_ret) return RPO_ERR_NULL;
+    if (int e = check_bank(table, days, deal, stride)) return e;
+    return launch(evopf_reset_bank_kernel, lane_grid(n_envs), kActThreads, 0, stream, n_envs, state, ep_len, ep_ret, ep_count,
+                  BankDays{table, days, deal, (uint32_t)stride}, (uint64_t)seed, (uint32_t)env_id_base);
+}
+
+int rpo_evopf_step_bank(int n_envs, float* state, const float* action, int* ep_len, float* ep_ret, unsigned* ep_count, float* rows,
+                        long long cap_steps, float* stats, int stats_cap, long long* ctrl, int max_episode_steps, int auto_reset,
+                        float viol_thresh, const float* consts_dev, unsigned long long seed, unsigned env_id_base, const float* table,
+                        int days, int deal, int stride, void* stream) {
+    if (int e = check_common(n_envs, state, action, consts_dev)) return e;
+    if (!ep_len || !ep_ret || !ep_count) return RPO_ERR_NULL;
+    if (int e = check_bank(table, days, deal, stride)) return e;
+    if (max_episode_steps <= 0 || (rows && cap_steps <= 0) || (stats && stats_cap <= 0)) return RPO_ERR_ARG;
+    StepArgs p{n_envs, state, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, stats_cap, ctrl, max_episode_steps,
+               auto_reset, viol_thresh, consts_dev, (uint64_t)seed, (uint32_t)env_id_base};
+    return launch(evopf_step_bank_kernel, lane_grid(n_envs), kActThreads, 0, stream, p, BankDays{table, days, deal, (uint32_t)stride});
+}
+
+int rpo_evopf_bank_days(int n, const unsigned* ep_count, int days, int deal, int stride, unsigned long long seed, unsigned env_id_base,
+                        int* day_out, void* stream) {
+    if (n <= 0) return RPO_ERR_ARG;
+    if (!day_out) return RPO_ERR_NULL;
+    if (int e = check_deal(days, deal, stride)) return e;
+    return launch(evopf_bank_days_kernel, dim3(rpo_grid_for(n)), RPO_BLOCK, 0, stream, n, ep_count, days, deal, (uint32_t)stride,
+                  (uint64_t)seed, (uint32_t)env_id_base, day_out);
 }
 
 int rpo_evopf_act_project(int n, const float* state, int state_stride, const float* ap_raw, const float* noise, float* action, int* iters,

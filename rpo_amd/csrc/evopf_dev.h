@@ -813,6 +813,16 @@ __device__ __forceinline__ void scenario_obs(Ws& w, float* out, const float* __r
     sync();
 }
 
+// The row of a scenario BANK [days, RPO_EVOPF_SCEN_DAY] that lane `env_id` plays in episode `episode`: a pure function of
+// (seed, env id, episode), so a lane keeps no day of its own -- ep_count is the whole state.  deal 0 "uniform": word x of
+// Philox(seed; env_id, episode, RPO_STREAM_EVOPF_DAY, 0) scaled to [0, days); deal 1 "cycle": (env_id + episode * stride) mod
+// days, stride = the run's total lane count (every day equally often when stride and days are coprime).  days >= 1, and
+// stride >= 1 for deal 1: the entry points refuse anything else, so the result always lies in [0, days).
+__device__ __forceinline__ int bank_day(uint64_t seed, uint32_t env_id, uint32_t episode, int days, int deal, uint32_t stride) {
+    if (deal == 0) return (int)__umulhi(rpo_philox(seed, env_id, episode, RPO_STREAM_EVOPF_DAY, 0u).x, (uint32_t)days);
+    return (int)(((uint64_t)env_id + (uint64_t)episode * stride) % (uint64_t)(uint32_t)days);
+}
+
 __device__ __forceinline__ void load_row(float* dst, const float* __restrict__ src, int n) {
     for (int i = lane_id(); i < n; i += RPO_WAVE) dst[i] = src[i];
 }
@@ -860,11 +870,24 @@ struct TableDays {        // row day[i] of a scenario table [days, RPO_EVOPF_SCE
         scenario_obs(w, out, table, days, day[i], t);
     }
 };
+struct BankDays {         // row bank_day(p.seed, env_id, ep) of a scenario bank: every episode of a lane is dealt a day anew
+    const float* table;
+    int days;
+    int deal;
+    uint32_t stride;
+    __device__ __forceinline__ void obs(const StepArgs& p, Ws& w, float* out, int, uint32_t env_id, unsigned ep, int t) const {
+        // (one wave per lane: env id and episode are the same in all 64 threads, and saying so keeps the Philox block of the
+        //  uniform deal -- 40 quarter-rate 32-bit multiplies in front of the table's loads -- on the scalar unit)
+        const uint32_t id = __builtin_amdgcn_readfirstlane(env_id), e = __builtin_amdgcn_readfirstlane(ep);
+        scenario_obs(w, out, table, days, bank_day(p.seed, id, e, days, deal, stride), t);
+    }
+};
 
 // EVOPFEnv.step (evopf.py:348-366) + Battery.step (:74-102) + the bookkeeping of the run loop (rpo_ddpg.py:120-145):
 // violations of the pre-step observation, reward, next hour of the episode data, replay scatter, statistics, auto-reset.
 // Shared by evopf_step_kernel (evopf.hip) and the fused evaluation (evopf_eval.hip: rows = stats = NULL, auto_reset = 0).
-// `days`: the source of the episode data -- the Philox draws, or evopf_step_scenario_kernel's table.
+// `days`: the source of the episode data -- the Philox draws, evopf_step_scenario_kernel's table, or evopf_step_bank_kernel's
+// bank, whose obs(.., ep + 1, 0) at the auto-reset is the lane's next deal.
 template <typename Days = PhiloxDays>
 __device__ __forceinline__ void evopf_step_lane(const StepArgs& p, Ws& w, float* row, int i, long long t, const Days& days = Days{}) {
     RPO_FP_STRICT

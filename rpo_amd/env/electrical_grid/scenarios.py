@@ -5,6 +5,8 @@ demand of the 14 buses for each of the 24 hours, and the price of 48 hours in th
 look-ahead past midnight, which the observation's 24-hour price window reads from hour 1 on.  ``Scenarios`` holds D such days on
 the host; ``table()`` lays them out as the step kernel reads them (include/rpo_hip.h, RPO_EVOPF_SCEN_DAY) and
 ``trainer.evaluate(scenarios=S)`` / ``rpo_amd.algo.evaluate_opf(trainer, scenarios=S)`` play them: episode e plays day e % len(S).
+``RPODDPG(..., scenarios=S, deal=)`` / ``RPOSAC`` TRAIN on them: S is a bank, and every episode of a training lane is dealt one of
+its days (rpo_evopf_step_bank); ``split`` parts a bank into the days to train on and the days to hold out.
 
 Where days come from: ``Scenarios(demand, price)`` (any source), ``Scenarios.from_system_days(env, load, price)`` (system-level
 load curves and prices, split over the buses the way the reference's ``DemandLoader.process`` does -- the reference's
@@ -100,6 +102,24 @@ class Scenarios(object):
         if not parts or not all(isinstance(p, Scenarios) for p in parts):
             raise TypeError("Scenarios.concat: a non-empty sequence of Scenarios")
         return Scenarios(np.concatenate([p.demand for p in parts]), np.concatenate([p.price for p in parts]))
+
+    def split(self, frac, seed=0):
+        """A disjoint random split -> (train, test): round(frac * D) days drawn by ``numpy.random.default_rng(seed)`` go to the
+        first part, the others to the second, each in the order they have here.  ValueError when a part would hold no day: train
+        on the one (``RPODDPG(..., scenarios=train)``), hold the other out (``evaluate(scenarios=test)``)."""
+        if isinstance(frac, bool) or not isinstance(frac, (int, float, np.integer, np.floating)) or not 0.0 < float(frac) < 1.0:
+            raise ValueError("Scenarios.split: frac must be a number in (0, 1), got %r" % (frac,))
+        D = len(self)
+        k = int(round(float(frac) * D))
+        if k < 1 or k > D - 1:
+            raise ValueError("Scenarios.split: frac=%r of %d day(s) leaves a part empty (%d / %d)" % (frac, D, k, D - k))
+        perm = np.random.default_rng(seed).permutation(D)
+        return self[np.sort(perm[:k])], self[np.sort(perm[k:])]
+
+    def digest(self):
+        """sha1 of the float32 table bytes: what a checkpoint records of the bank a trainer was trained on."""
+        import hashlib
+        return hashlib.sha1(np.ascontiguousarray(self.table(), dtype=np.float32).tobytes()).hexdigest()
 
     def scale_demand(self, f):
         """Demand (pd and qd) times ``f``: a number, [D] per day or [24] per hour.  A new object."""

@@ -11,7 +11,7 @@ from .. import ops as hip_ops
 class VecEnv(object):
 
     def __init__(self, kernels, n_envs, device, seed=0, env_id_base=0, max_episode_steps=None, viol_thresh=1e-3,
-                 stats_cap=4096, ctrl=None, scenario=None):
+                 stats_cap=4096, ctrl=None, scenario=None, bank=None):
         self.k = kernels
         self.n = int(n_envs)
         self.device = device
@@ -38,7 +38,24 @@ class VecEnv(object):
             raise NotImplementedError("scenarios are built for the HIP kernels of EVOPF-v0 only (its step kernel reads the "
                                       "table), not %s" % type(kernels).__name__)
 
+        # (table [days, SCEN_DAY] float32 on the device, deal "uniform" | "cycle", stride = the run's total lane count): a scenario
+        # BANK -- lane env_id_base + i is dealt one of the caller's days anew for every episode, a function of (seed, env id,
+        # ep_count[i]) alone (ops.evopf_reset_bank / evopf_step_bank; auto-resets like the Philox days: the training seam)
+        self.bank = None if bank is None else tuple(bank)
+        if bank is not None and scenario is not None:
+            raise ValueError("VecEnv takes scenario= (one fixed day per lane, evaluation) or bank= (a day per episode, training), "
+                             "not both")
+        if bank is not None and not isinstance(kernels, hip_ops.EvopfKernels):
+            raise NotImplementedError("a scenario bank is built for the HIP kernels of EVOPF-v0 only (its step kernel reads the "
+                                      "table), not %s" % type(kernels).__name__)
+        if bank is not None and len(self.bank) != 3:
+            raise ValueError("bank must be (table, deal, stride)")
+
     def reset(self):
+        if self.bank is not None:
+            hip_ops.evopf_reset_bank(self.k, self.internal, self.ep_len, self.ep_ret, self.ep_count, self.seed, self.env_id_base,
+                                     *self.bank)
+            return self.obs
         if self.scenario is not None:
             hip_ops.evopf_reset_scenario(self.k, self.internal, self.ep_len, self.ep_ret, *self.scenario)
             return self.obs
@@ -57,6 +74,12 @@ class VecEnv(object):
 
     def step(self, action, rows=None, cap_steps=1, auto_reset=True):
         """One fused vector step; scatters the transitions into ``rows`` (the replay ring) when given."""
+        if self.bank is not None:
+            hip_ops.evopf_step_bank(self.k, self.internal, action, self.ep_len, self.ep_ret, self.ep_count, rows, cap_steps,
+                                    self.stats, self.ctrl, self.max_episode_steps, auto_reset, self.viol_thresh, self.seed,
+                                    self.env_id_base, *self.bank)
+            self.steps_host += 1
+            return self.obs
         if self.scenario is not None:
             if auto_reset:
                 raise ValueError("a VecEnv with a scenario never auto-resets: step(auto_reset=False)")

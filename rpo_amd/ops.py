@@ -915,6 +915,76 @@ def evopf_step_scenario(kernels, internal, action, ep_len, ep_ret, ep_count, row
         "rpo_evopf_step_scenario")
 
 
+STREAM_EVOPF_DAY = CONST["RPO_STREAM_EVOPF_DAY"]
+DEALS = {"uniform": CONST["RPO_EVOPF_DEAL_UNIFORM"], "cycle": CONST["RPO_EVOPF_DEAL_CYCLE"]}    # how a bank deals its days
+
+
+def _deal(days, deal, stride, what):
+    """(days, deal, stride) of a scenario bank as the C ABI takes them; ``deal``: a name of ``DEALS`` or its number."""
+    code = DEALS.get(deal, deal) if isinstance(deal, str) else deal
+    if isinstance(code, bool) or not isinstance(code, int) or code not in DEALS.values():
+        raise RpoHipError("%s: deal must be one of %s, got %r" % (what, sorted(DEALS), deal))
+    if int(days) < 1 or (code == DEALS["cycle"] and int(stride) < 1) or not 0 <= int(stride) < 2 ** 31:
+        raise RpoHipError("%s: a bank needs days >= 1 and 1 <= stride < 2^31 (the run's lane count), got %r / %r" % (what, days, stride))
+    return int(days), code, int(stride)
+
+
+def _bank(table, deal, stride, what):
+    """(table pointer, days, deal, stride) of a scenario bank: table [days >= 1, SCEN_DAY] contiguous float32 on the device."""
+    if table is None or table.dim() != 2 or table.shape[1] != SCEN_DAY or table.shape[0] < 1 or table.dtype != torch.float32 \
+            or not table.is_contiguous():
+        raise RpoHipError("%s: the bank's table must be a contiguous float32 [days >= 1, %d], got %s"
+                          % (what, SCEN_DAY, None if table is None else (tuple(table.shape), table.dtype)))
+    words = _deal(table.shape[0], deal, stride, what)
+    return (_p(table),) + words
+
+
+def _lane_ints(t, n, what, allow_none=False):
+    """``t`` checked as a contiguous int32 [n] (or None); the pointer is taken by the caller's ``_p``."""
+    if t is None and allow_none:
+        return None
+    if t is None or tuple(t.shape) != (n,) or t.dtype != torch.int32 or not t.is_contiguous():
+        raise RpoHipError("%s must be a contiguous int32 [%d], got %s" % (what, n, None if t is None else (tuple(t.shape), t.dtype)))
+    return t
+
+
+def evopf_reset_bank(kernels, internal, ep_len, ep_ret, ep_count, seed, env_id_base, table, deal, stride):
+    """``kernels.reset`` with hour 0 of the bank day lane i is dealt in episode ep_count[i] (rpo_evopf_reset_bank).  A function of
+    the backend like ``evopf_reset_scenario``, not a method: the env kernel classes keep their public methods."""
+    n = internal.shape[0]
+    _lane_ints(ep_count, n, "evopf_reset_bank: ep_count")
+    tp, days, code, stride = _bank(table, deal, stride, "evopf_reset_bank")
+    check(_lib.load().rpo_evopf_reset_bank(n, _p(internal), _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32), tp, days,
+                                           code, stride, int(seed), int(env_id_base), _stream()), "rpo_evopf_reset_bank")
+
+
+def evopf_step_bank(kernels, internal, action, ep_len, ep_ret, ep_count, rows, cap_steps, stats, ctrl, max_episode_steps, auto_reset,
+                    viol_thresh, seed, env_id_base, table, deal, stride):
+    """``kernels.step`` with the episode data read from a scenario bank: a lane whose episode ends is dealt its next day when
+    ``auto_reset`` (rpo_evopf_step_bank)."""
+    n = internal.shape[0]
+    _lane_ints(ep_count, n, "evopf_step_bank: ep_count")
+    tp, days, code, stride = _bank(table, deal, stride, "evopf_step_bank")
+    check(_lib.load().rpo_evopf_step_bank(
+        n, _p(internal), _p(action), _p(ep_len, torch.int32), _p(ep_ret), _p(ep_count, torch.int32),
+        _ring(rows, kernels.ring_floats), cap_steps, _p(stats, allow_none=True), 0 if stats is None else stats.shape[0],
+        _p(ctrl, torch.int64, allow_none=True), max_episode_steps, int(auto_reset), viol_thresh, kernels._c(internal), int(seed),
+        int(env_id_base), tp, days, code, stride, _stream()), "rpo_evopf_step_bank")
+
+
+def evopf_bank_days(day_out, ep_count, days, deal, stride, seed, env_id_base):
+    """day_out[i] (int32 [n] on the device) = the bank row lane env_id_base + i plays in episode ep_count[i] (int32 [n], or None:
+    episode 0) of a bank of ``days`` days (rpo_evopf_bank_days): the deal of the two kernels above, for the host to ask."""
+    if day_out is None or day_out.dim() != 1 or day_out.shape[0] < 1:
+        raise RpoHipError("evopf_bank_days: day_out must be a contiguous int32 [n >= 1]")
+    n = day_out.shape[0]
+    _lane_ints(day_out, n, "evopf_bank_days: day_out")
+    _lane_ints(ep_count, n, "evopf_bank_days: ep_count", allow_none=True)
+    days, code, stride = _deal(days, deal, stride, "evopf_bank_days")
+    check(_lib.load().rpo_evopf_bank_days(n, _p(ep_count, torch.int32, allow_none=True), days, code, stride, int(seed), int(env_id_base),
+                                          _p(day_out, torch.int32), _stream()), "rpo_evopf_bank_days")
+
+
 class PendulumKernels(_FusedEnvKernels):
     """HIP kernels of SpringPendulum-v0."""
 
