@@ -248,7 +248,13 @@ int rpo_abi_version(void);
 #define RPO_TUNE_FWD_BF16X3 9      /* EXPERIMENT (default 0 = off): 1: the streaming forward (where RPO_TUNE_FWD_STREAM
                                       applies, nowhere else) runs its hidden layer as a 3 x bf16 split of both operands on
                                       v_mfma_f32_16x16x32_bf16 (mlp_stream_bf16x3.h): f32-accurate, NOT bit-equal to the exact form */
-#define RPO_TUNE_COUNT 10
+#define RPO_TUNE_COUNT 10          /* the keys above: [0, RPO_TUNE_COUNT).  The value is pinned (callers of ABI 6 probe rpo_tuning(RPO_TUNE_COUNT, ..)
+                                      for RPO_ERR_ARG), so index 10 stays no key and later keys follow behind it: */
+#define RPO_TUNE_WGRAD_STAGED 11   /* 1: the hidden-vector blocks (db0, dW1 [, dW1b], db1) of rpo_split_critic_bwd_b /
+                                      rpo_split_policy_e stage their operands in LDS, requested by all four waves in one round trip,
+                                      and pol_e's Lagrangian fold requests its partials up front; 0: one wave fetches them with scalar
+                                      loads -- the same chains, the same bits (rpo_split_critic_bwd_b_ride, bound by its lane blocks,
+                                      always has the one-wave form) */
 int rpo_tuning(int key, int value);
 
 /* ---------------------------------------------------------------------------------------------------------------

@@ -19,7 +19,9 @@
 
 // Kernel-variant switches (include/rpo_hip.h: rpo_tuning, RPO_TUNE_*): one process-wide table, defined in train_ops.hip,
 // read by the launch code on every call (no getenv in the library).
-extern int g_rpo_tune[RPO_TUNE_COUNT];
+// Slots: the keys [0, RPO_TUNE_COUNT) and the keys added behind it (RPO_TUNE_WGRAD_STAGED; slot RPO_TUNE_COUNT itself is no key).
+constexpr int kRpoTuneSlots = RPO_TUNE_WGRAD_STAGED + 1;
+extern int g_rpo_tune[kRpoTuneSlots];
 static inline int rpo_tune(int key) { return g_rpo_tune[key]; }
 
 // relu as ONE instruction: the integer maximum of the bit pattern with 0 (positive floats order like their bits, negative

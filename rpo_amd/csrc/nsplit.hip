@@ -783,6 +783,7 @@ __device__ __forceinline__ float ns_dw0_tile(const Mlp& net, float* gW0, const f
 
 // Hidden-layer vectors of 16 columns: thread = (column, batch range); 64 threads of the workgroup work, each a sequential
 // chain over its B / 4 rows (the order of mlp_bwd_weights_body); block 0 also sums d_k over the batch for db1_k.
+// This is the one-wave form: rpo_tuning(RPO_TUNE_WGRAD_STAGED, 0), and always in the riding bwd_b (ns_hv_block_staged below).
 __device__ __forceinline__ float ns_hv_block(const Mlp& net, const MlpGrad& gr, const float* __restrict__ h1, const float* dglob,
                                              int dstride, bool two, int B, int rb, float* smem) {
     constexpr int H = 256;
@@ -863,7 +864,7 @@ __device__ __forceinline__ float ns_hv_block(const Mlp& net, const MlpGrad& gr, 
             gmax = fmaxf(gmax, fabsf(nw1b));
         }
     }
-    if (rb == 0) {
+    if (rb == 0 && !(RPO_NS_SKIP & 4)) {
         // db1_k = sum_b d_k[b]: strided per-thread partials, wave reduction, 4 wave partials added in order
         __syncthreads();
         float s0 = 0.0f, s1 = 0.0f;
@@ -889,12 +890,187 @@ __device__ __forceinline__ float ns_hv_block(const Mlp& net, const MlpGrad& gr, 
     return gmax;
 }
 
+// ---- The same block with its operands staged in LDS (rpo_tuning(RPO_TUNE_WGRAD_STAGED), the default).  Above, ONE wave
+//      fetches the block's operands: 128 scalar loads per thread, each h1 instruction touching four 64-byte segments (row
+//      stride 1 KB, 16 columns) and each d instruction a value that 16 lanes share.  Here all four waves request them together,
+//      straight-line and before anything waits: the h1 rows with 16-byte loads (four lanes per 64-byte row segment), the rows'
+//      d values once and coalesced, block 0's db1 terms in the same round trip.  The same 64 (column, range) threads then run
+//      the same sequential chains from LDS, so no sum changes its order.  A pass stages kHvRows rows of each of the four batch
+//      ranges (16 KB); batches above 256 rows take more passes.
+constexpr int kHvRows = 64;
+constexpr int kHvLdPart = kHvRows * 16 + 16;        // floats between two ranges' h1 rows: a chain read of the wave (4 ranges x 16
+                                                    // columns, row u) then covers 64 consecutive banks
+constexpr int kHvLdD = kHvRows + 4;                 // ... and its 16-byte reads of four rows' d values (one address per range,
+                                                    // broadcast) four different bank groups
+constexpr int kHvSmem = 4 * kHvLdPart + 2 * 4 * kHvLdD + 4 * 3 * 16 + 8;
+constexpr int kWeightSmem = kHvSmem > 4 * 16 * 16 ? kHvSmem : 4 * 16 * 16;      // floats a weight role's workgroup needs
+
+struct HvStage { f32x4 h[4]; float d0, d1; };
+
+// request pass c0 of the block: thread (row r = tid / 4, quarter q = tid % 4) one 16-byte piece of row r of every range,
+// thread (range tid / 64, row tid % 64) that row's d values; rows past the batch are clamped (the chain masks them)
+__device__ __forceinline__ void ns_hv_stage_load(HvStage& s, const float* __restrict__ h1, const float* dglob, int dstride, bool two,
+                                                 int B, int rb, int c0) {
+    constexpr int H = 256;
+    const int tid = threadIdx.x, r = tid >> 2, q = tid & 3, last = B - 1;
+#pragma unroll
+    for (int part = 0; part < 4; ++part) {
+        const int bb = (int)(((long long)B * part) / 4) + c0 + r, bc = bb < last ? bb : last;
+        s.h[part] = *reinterpret_cast<const f32x4*>(&h1[(size_t)bc * H + rb * 16 + q * 4]);
+    }
+    const int bb = (int)(((long long)B * (tid >> 6)) / 4) + c0 + (tid & 63), bc = bb < last ? bb : last;
+    s.d0 = dglob[(size_t)bc * dstride];
+    s.d1 = two ? dglob[(size_t)bc * dstride + 1] : 0.0f;
+}
+
+// N staged rows of one (column, range) chain: every LDS read is requested first, then the rows are added in order.  TWO is a
+// template parameter so that no row of the chain stands behind a branch (as a run-time flag it put one between the rows' reads).
+template <bool TWO, int N>
+__device__ __forceinline__ void ns_hv_chain(const float* hcol, const float* dr0, const float* dr1, int len, float w1a, float w1b,
+                                            float& gb0, float& gw1a, float& gw1b) {
+    static_assert(N % 4 == 0, "16-byte reads of the d values");
+    float hl[N], a0l[N], a1l[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) hl[u] = hcol[u * 16];
+#pragma unroll
+    for (int u = 0; u < N; u += 4) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(&dr0[u]);
+        f32x4 v1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (TWO) v1 = *reinterpret_cast<const f32x4*>(&dr1[u]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { a0l[u + i] = v0[i]; a1l[u + i] = v1[i]; }
+    }
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const bool ok = u < len;
+        const float h = ok ? hl[u] : 0.0f, a0 = ok ? a0l[u] : 0.0f, a1 = (TWO && ok) ? a1l[u] : 0.0f;
+        gb0 += ns_dh(h, a0, a1, w1a, w1b);
+        const float hr = fmaxf(h, 0.0f);
+        gw1a = fmaf(a0, hr, gw1a);
+        gw1b = fmaf(a1, hr, gw1b);
+    }
+}
+
+__device__ __forceinline__ float ns_hv_block_staged(const Mlp& net, const MlpGrad& gr, const float* __restrict__ h1,
+                                                    const float* dglob, int dstride, bool two, int B, int rb, float* smem) {
+    static_assert(kBwdMaxB <= 4 * kThreads, "db1: at most four rows per thread");
+    const int tid = threadIdx.x;
+    float* hs = smem;                                                          // [4][kHvRows][16], ranges kHvLdPart apart
+    float* d0s = smem + 4 * kHvLdPart;                                         // [4][kHvRows], ranges kHvLdD apart
+    float* d1s = d0s + 4 * kHvLdD;
+    float (*partial)[3][16] = reinterpret_cast<float (*)[3][16]>(d1s + 4 * kHvLdD);   // [4][3][16]
+    float* red = d1s + 4 * kHvLdD + 4 * 3 * 16;                                // [4][2]: db1's wave partials
+    float gmax = 0.0f;
+    float cur_b0 = 0.0f, cur_w1 = 0.0f, cur_w1b = 0.0f, cur_b1 = 0.0f, cur_b1b = 0.0f;
+    if (tid < 16) {
+        cur_b0 = gr.b0[rb * 16 + tid];
+        cur_w1 = gr.W1[rb * 16 + tid];
+        if (two) cur_w1b = gr.W1b[rb * 16 + tid];
+    }
+    if (rb == 0 && tid == 0) {
+        cur_b1 = gr.b1[0];
+        if (two) cur_b1b = gr.b1b[0];
+    }
+    const int o = tid & 15, part = (tid >> 4) & 3;
+    const int b_lo = (int)(((long long)B * part) / 4), b_hi = (int)(((long long)B * (part + 1)) / 4);
+    float w1a = 0.0f, w1b = 0.0f;
+    if (tid < 64) {
+        w1a = net.W1[rb * 16 + o];
+        if (two) w1b = net.W1b[rb * 16 + o];
+    }
+    // block 0, db1_k = sum_b d_k[b]: the terms of thread tid are rows tid, tid + 256, ... (requested with the staging)
+    float dv0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, dv1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const bool db1 = rb == 0 && !(RPO_NS_SKIP & 4);
+    if (db1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b2 = tid + i * kThreads, bc = b2 < B ? b2 : B - 1;
+            dv0[i] = dglob[(size_t)bc * dstride];
+            if (two) dv1[i] = dglob[(size_t)bc * dstride + 1];
+        }
+    }
+    HvStage st;
+    ns_hv_stage_load(st, h1, dglob, dstride, two, B, rb, 0);
+    if (db1) {
+        // strided per-thread partials, wave reduction, 4 wave partials added in order (by thread 0, below)
+        float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (tid + i * kThreads < B) {
+                s0 += dv0[i];
+                if (two) s1 += dv1[i];
+            }
+        }
+        { float ss[2] = {s0, s1}; rpo_wave_reduce_many(ss, 0u); s0 = ss[0]; s1 = ss[1]; }
+        if ((tid & 63) == 0) { red[(tid >> 6) * 2] = s0; red[(tid >> 6) * 2 + 1] = s1; }
+    }
+    float gb0 = 0.0f, gw1a = 0.0f, gw1b = 0.0f;
+    const int nmax = (B + 3) / 4;                                              // rows of the longest range
+    for (int c0 = 0;;) {
+#pragma unroll
+        for (int pp = 0; pp < 4; ++pp) *reinterpret_cast<f32x4*>(&hs[pp * kHvLdPart + tid * 4]) = st.h[pp];
+        d0s[(tid >> 6) * kHvLdD + (tid & 63)] = st.d0;
+        if (two) d1s[(tid >> 6) * kHvLdD + (tid & 63)] = st.d1;
+        __syncthreads();
+        if (tid < 64) {
+            const int len = b_hi - b_lo - c0;                                  // rows of this thread's range in the pass (may be <= 0)
+            const float* hcol = hs + part * kHvLdPart + o;
+            const float* dr0 = d0s + part * kHvLdD;
+            const float* dr1 = d1s + part * kHvLdD;
+            if (two) {                                                         // (two halves: 3 x 32 values in registers)
+                ns_hv_chain<true, kHvRows / 2>(hcol, dr0, dr1, len, w1a, w1b, gb0, gw1a, gw1b);
+                ns_hv_chain<true, kHvRows / 2>(hcol + kHvRows / 2 * 16, dr0 + kHvRows / 2, dr1 + kHvRows / 2, len - kHvRows / 2, w1a,
+                                               w1b, gb0, gw1a, gw1b);
+            } else {
+                ns_hv_chain<false, kHvRows>(hcol, dr0, dr1, len, w1a, w1b, gb0, gw1a, gw1b);
+            }
+        }
+        c0 += kHvRows;
+        if (c0 >= nmax) break;
+        __syncthreads();                                                       // the chains have read the pass
+        ns_hv_stage_load(st, h1, dglob, dstride, two, B, rb, c0);
+    }
+    if (tid < 64) { partial[part][0][o] = gb0; partial[part][1][o] = gw1a; partial[part][2][o] = gw1b; }
+    __syncthreads();
+    if (tid < 16) {
+        const int j = rb * 16 + o;
+        const float nb0 = cur_b0 + (((partial[0][0][o] + partial[1][0][o]) + partial[2][0][o]) + partial[3][0][o]);
+        const float nw1 = cur_w1 + (((partial[0][1][o] + partial[1][1][o]) + partial[2][1][o]) + partial[3][1][o]);
+        gr.b0[j] = nb0;
+        gr.W1[j] = nw1;
+        gmax = fmaxf(fabsf(nb0), fabsf(nw1));
+        if (two) {
+            const float nw1b = cur_w1b + (((partial[0][2][o] + partial[1][2][o]) + partial[2][2][o]) + partial[3][2][o]);
+            gr.W1b[j] = nw1b;
+            gmax = fmaxf(gmax, fabsf(nw1b));
+        }
+    }
+    if (db1 && tid == 0) {
+        const float nb1 = cur_b1 + (((red[0] + red[2]) + red[4]) + red[6]);
+        gr.b1[0] = nb1;
+        gmax = fmaxf(gmax, fabsf(nb1));
+        if (two) {
+            const float nb1b = cur_b1b + (((red[1] + red[3]) + red[5]) + red[7]);
+            gr.b1b[0] = nb1b;
+            gmax = fmaxf(gmax, fabsf(nb1b));
+        }
+    }
+    return gmax;
+}
+
 // block w < kW0Tiles: dW0 tile, else hidden-vector block.  The rows' head gradients d0 [, d1] were left in global memory by
-// the dx0 launch before this one (row stride `dstride` floats).
+// the dx0 launch before this one (row stride `dstride` floats).  smem: kWeightSmem floats.
 __device__ __forceinline__ float ns_weight_role(const Mlp& net, const MlpGrad& gr, const float* h1, const float* x0,
-                                                const float* dglob, int dstride, bool two, int B, int w, float* smem) {
-    if (w < kW0Tiles) return ns_dw0_tile(net, gr.W0, h1, x0, dglob, dstride, two, B, w, smem);
+                                                const float* dglob, int dstride, bool two, int B, int w, float* smem, bool staged) {
+    if (w < kW0Tiles) return (RPO_NS_SKIP & 32) ? 0.0f : ns_dw0_tile(net, gr.W0, h1, x0, dglob, dstride, two, B, w, smem);
+    if (RPO_NS_SKIP & 2) return 0.0f;
+    if (staged) return ns_hv_block_staged(net, gr, h1, dglob, dstride, two, B, w - kW0Tiles, smem);
     return ns_hv_block(net, gr, h1, dglob, dstride, two, B, w - kW0Tiles, smem);
+}
+
+// the staged form reads h1 with 16-byte loads
+bool wgrad_staged(const float* h1_0, const float* h1_1) {
+    return rpo_tune(RPO_TUNE_WGRAD_STAGED) != 0 && !(((uintptr_t)h1_0 | (uintptr_t)h1_1) & 15u);
 }
 
 // ---- bwd_a: TD target + Huber (from the slab partials) -> dh = dLoss/dQ * W1 * 1[h1 > 0] (on the fly) -> dx0 of one
@@ -999,15 +1175,17 @@ __device__ __forceinline__ void bwd_b_bookkeeping(const SplitArgs& p) {
 
 // own blocks: [0, kWeightBlocks) weight roles | first-layer blocks | (k == 0, when asked for) one bookkeeping block
 template <class L>
-__device__ __forceinline__ void bwd_b_role(const SplitArgs& p, float* smem, int bx, int k, int own_blocks) {
+__device__ __forceinline__ void bwd_b_role(const SplitArgs& p, float* smem, int bx, int k, int own_blocks, bool staged) {
     if ((p.prep_step || p.clock_out || p.updates_out) && bx == own_blocks - 1) {
-        if (k == 0) bwd_b_bookkeeping(p);
+        if (k == 0 && !(RPO_NS_SKIP & 8)) bwd_b_bookkeeping(p);
         return;
     }
     if (bx < kWeightBlocks) {
-        gradmax_flush(p.gradmax, ns_weight_role(p.critic[k], p.critic_grad[k], p.h1[k], p.x0[k], p.dq[k], 1, false, p.B, bx, smem));
+        gradmax_flush(p.gradmax, ns_weight_role(p.critic[k], p.critic_grad[k], p.h1[k], p.x0[k], p.dq[k], 1, false, p.B, bx, smem,
+                                                staged));
         return;
     }
+    if (RPO_NS_SKIP & 64) return;
     BwdArgs a{};
     a.net = p.critic[k];
     a.g = p.critic_grad[k];
@@ -1021,9 +1199,9 @@ __device__ __forceinline__ void bwd_b_role(const SplitArgs& p, float* smem, int 
 }
 
 template <class L>
-__global__ __launch_bounds__(kThreads) void split_critic_bwd_b_kernel(SplitArgs p) {
-    __shared__ __attribute__((aligned(16))) float smem[4 * 16 * 16];
-    bwd_b_role<L>(p, smem, blockIdx.x, blockIdx.y, gridDim.x);
+__global__ __launch_bounds__(kThreads) void split_critic_bwd_b_kernel(SplitArgs p, int staged) {
+    __shared__ __attribute__((aligned(16))) float smem[kWeightSmem];
+    bwd_b_role<L>(p, smem, blockIdx.x, blockIdx.y, gridDim.x, staged != 0);
 }
 
 // bwd_b + explore / project / step / scatter of the lanes: grid (own_blocks + lane blocks, K); the extra x-blocks of plane 0
@@ -1031,8 +1209,9 @@ __global__ __launch_bounds__(kThreads) void split_critic_bwd_b_kernel(SplitArgs 
 template <class L>
 __global__ __launch_bounds__(kThreads) void split_critic_bwd_b_ride_kernel(SplitArgs p, CartConsts c, RideArgs<typename L::Env> r,
                                                                            int own_blocks) {
+    // (the one-wave form of the hidden-vector blocks: the lane blocks bound this launch -- 8.23 us with either form, measured)
     __shared__ __attribute__((aligned(16))) float smem[4 * 16 * 16];
-    if ((int)blockIdx.x < own_blocks) bwd_b_role<L>(p, smem, blockIdx.x, blockIdx.y, own_blocks);
+    if ((int)blockIdx.x < own_blocks) bwd_b_role<L>(p, smem, blockIdx.x, blockIdx.y, own_blocks, false);
     else if (blockIdx.y == 0) ride_tail<typename L::Env>(r, c, smem, blockIdx.x - own_blocks, gridDim.x - own_blocks);
 }
 
@@ -1778,31 +1957,44 @@ __global__ __launch_bounds__(kThreads) void split_policy_front_kernel(SplitArgs 
 //      gradients (left by pol_d) and the saved activations; then the first-layer gradients from dx0_a; one more workgroup
 //      folds the Lagrangian partials (value, d/d nu).
 template <class ENV>
-__global__ __launch_bounds__(kThreads) void split_policy_e_kernel(SplitArgs p, int fl_blocks) {
+__global__ __launch_bounds__(kThreads) void split_policy_e_kernel(SplitArgs p, int fl_blocks, int staged) {
     typedef typename ENV::L L;
-    __shared__ __attribute__((aligned(16))) float smem[4 * 16 * 16];
+    __shared__ __attribute__((aligned(16))) float smem[kWeightSmem];
     if (blockIdx.x < kWeightBlocks) {
         gradmax_flush(p.gradmax, ns_weight_role(p.actor, p.actor_grad, p.h1_a, p.x0_a, p.dout, 2, p.actor.n_out > 1, p.B,
-                                                blockIdx.x, smem));
+                                                blockIdx.x, smem, staged != 0));
         return;
     }
     const int fb = blockIdx.x - kWeightBlocks;
     if (fb == fl_blocks) {
         const int tid = threadIdx.x, T = (p.B + kRows - 1) / kRows;
-        if (tid < 8) {
+        if (tid < 8 && !(RPO_NS_SKIP & 16)) {
             float sacc = 0.0f;
-            for (int g = 0; g < T; ++g) sacc += p.lag_partial[g * 8 + tid];
+            if (staged) {
+                // every tile's partial is requested up front (T <= kBwdMaxB / kRows, clamped loads), added in the same order
+                constexpr int kMaxT = kBwdMaxB / kRows;
+                float lv[kMaxT];
+#pragma unroll
+                for (int g = 0; g < kMaxT; ++g) lv[g] = p.lag_partial[(g < T ? g : T - 1) * 8 + tid];
+#pragma unroll
+                for (int g = 0; g < kMaxT; ++g)
+                    if (g < T) sacc += lv[g];
+            } else {
+                for (int g = 0; g < T; ++g) sacc += p.lag_partial[g * 8 + tid];
+            }
             const float inv_b = 1.0f / (float)p.B;
             if (tid == 0) p.lag_out[0] = inv_b * sacc;
             else if (tid == 7) { if (!p.twin) p.lag_out[1] = inv_b * sacc; }
             else if (tid - 1 < ENV::NI) p.nu_grad[tid - 1] += inv_b * sacc;
         }
         // bookkeeping for the rpo_adam_step_multi(prepared) launch behind the policy step (nothing in this launch reads it)
+        if (RPO_NS_SKIP & 8) return;
         if (tid >= 64 && tid < 67 && p.prep2_step[tid - 64]) adam_prepare(p.prep2_step[tid - 64], p.prep2_beta1[tid - 64], p.prep2_beta2[tid - 64]);
         if (tid == 128 && p.clock_out) p.clock_out[0] += 1;
         if (tid == 192 && p.updates_out) p.updates_out[RPO_CTRL_UPDATES] += 1;
         return;
     }
+    if (RPO_NS_SKIP & 64) return;
     BwdArgs a{};
     a.net = p.actor;
     a.g = p.actor_grad;
@@ -2107,11 +2299,11 @@ int bwd_b(const rpo_split_update* u, const rpo_rollout_rider* r, Variant v, void
     if (int e = ride_checks(u, r, v, false)) return e;
     if (int e = to_args(u, kNeedCritics | kNeedCriticGrads | actor_need(v), a, c)) return e;
     if (!a.batch_out || !critic_bufs(a, kBufBwd)) return RPO_ERR_NULL;
-    const int own = bwd_b_blocks(a);
+    const int own = bwd_b_blocks(a), staged = wgrad_staged(a.h1[0], a.twin ? a.h1[1] : nullptr) ? 1 : 0;
     if (v == kRide)                                               // the step of every lane behind the stage's own blocks
         return launch_env(kBwdBRide, u->env, dim3(own + (r->n_envs + kThreads - 1) / kThreads, critics(a)), kThreads, stream, a, c,
                           Ride{a, r}, own);
-    return launch_env(kBwdB, u->env, dim3(own, critics(a)), kThreads, stream, a);
+    return launch_env(kBwdB, u->env, dim3(own, critics(a)), kThreads, stream, a, staged);
 }
 
 // policy_b alone, or as the fused policy launch: [policy_a +] policy_b + policy_c + the first half of policy_d
@@ -2214,7 +2406,8 @@ int rpo_split_policy_e(const rpo_split_update* u, void* stream) {
     if (int e = to_args(u, kNeedActor | kNeedActorGrad, a, c)) return e;
     if (!a.batch_out || !a.dx0_a || !a.lag_partial || !a.lag_out || !a.nu_grad || !a.dout || !a.x0_a || !a.h1_a) return RPO_ERR_NULL;
     const int fl_blocks = mlp_fl_blocks(a.actor.E * (a.actor.S + 1));
-    return launch_env(kPolicyE, u->env, dim3(kWeightBlocks + fl_blocks + 1), kThreads, stream, a, fl_blocks);
+    return launch_env(kPolicyE, u->env, dim3(kWeightBlocks + fl_blocks + 1), kThreads, stream, a, fl_blocks,
+                      wgrad_staged(a.h1_a, nullptr) ? 1 : 0);
 }
 
 int rpo_xcc_probe(int gx, int gy, int gz, int threads, int* out, void* stream) {

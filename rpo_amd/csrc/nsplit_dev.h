@@ -83,6 +83,9 @@ __device__ __forceinline__ void ns_load_weights(const Mlp& net, int g, NsWeights
 #ifndef RPO_NS_SKIP
 #define RPO_NS_SKIP 0              // timing-only builds: 1 = no first-layer fmaf loops in the column-split stages
 #endif
+// further bits, the roles of the all-rows launches bwd_b / pol_e (nsplit.hip; tools/probe/wgrad_roles.py): 2 = no hidden-vector
+// blocks, 4 = no db1 in block 0 of them, 8 = no bookkeeping (adam_prepare, the clocks), 16 = no Lagrangian fold in pol_e,
+// 32 = no dW0 tiles, 64 = no first-layer blocks
 // (acc1: the four C tiles of the lane, acc1[4 t + i] = x0[row li][64 w + 16 t + 4 lg + i] so far)
 template <int EIN>
 __device__ __forceinline__ void ns_layer1_state(const Mlp& net, const NsWeights<EIN>& w, const NsLds<EIN>& lds, float (&acc1)[kRows]) {

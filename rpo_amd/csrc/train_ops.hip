@@ -229,9 +229,11 @@ __global__ __launch_bounds__(RPO_BLOCK) void philox_normal_kernel(int n, float* 
 }  // namespace
 
 // defaults of the kernel-variant switches (RPO_TUNE_* order)
-int g_rpo_tune[RPO_TUNE_COUNT] = {/* FWD_STREAM */ 1, /* FWD_STREAM_WAVES */ 16, /* BWD_ONEPASS */ 1, /* GEMM_KSPLIT */ 1,
+int g_rpo_tune[kRpoTuneSlots] = {/* FWD_STREAM */ 1, /* FWD_STREAM_WAVES */ 16, /* BWD_ONEPASS */ 1, /* GEMM_KSPLIT */ 1,
                                   /* MLP_GEMM */ 1, /* ROLLOUT_WIDE: 2 = by size */ 2, /* BWD_STREAM */ 1,
-                                  /* L1_MFMA */ 1, /* EVOPF_PLACE */ 0, /* FWD_BF16X3 */ 0};
+                                  /* L1_MFMA */ 1, /* EVOPF_PLACE */ 0, /* FWD_BF16X3 */ 0, /* (RPO_TUNE_COUNT: no key) */ 0,
+                                  /* WGRAD_STAGED */ 1};
+static_assert(RPO_TUNE_COUNT == 10 && RPO_TUNE_WGRAD_STAGED == 11, "the table above follows the keys' indices");
 
 extern "C" {
 
@@ -248,7 +250,7 @@ int rpo_philox_normal(int n, float* out, unsigned long long seed, unsigned id_ba
 int rpo_abi_version(void) { return RPO_ABI_VERSION; }
 
 int rpo_tuning(int key, int value) {
-    if (key < 0 || key >= RPO_TUNE_COUNT) return RPO_ERR_ARG;
+    if (key < 0 || (key >= RPO_TUNE_COUNT && key != RPO_TUNE_WGRAD_STAGED)) return RPO_ERR_ARG;
     const int old = g_rpo_tune[key];
     if (value >= 0) g_rpo_tune[key] = value;
     return old;

@@ -6,6 +6,11 @@ set -e
 cd $(dirname $0)/../../rpo_amd/csrc
 for N in "$@"; do
   GEMM_SKIP=0
+  if [ "${KIND:-fwd}" = ns ]; then    # roles of the column-split stages (RPO_NS_SKIP bits, csrc/nsplit_dev.h); every other object as built
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DRPO_NS_SKIP=$N -c nsplit.hip -o /tmp/nsplit_skip$N.o
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o librpo_hip_skip$N.so $(ls *.o | grep -v '^nsplit\.o$') /tmp/nsplit_skip$N.o
+    continue
+  fi
   if [ "${KIND:-fwd}" = rollout ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DRPO_ROLLOUT_SKIP=${ROLL:-$N} -DRPO_TILE_SKIP=${TILE:-0} -c fused.hip -o /tmp/fused_skip$N.o
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o librpo_hip_skip$N.so cartsafe.o pendulum.o evopf.o replay.o train_ops.o mlp.o /tmp/fused_skip$N.o nsplit.o rollout_stream.o mlp_bwd_stream.o
