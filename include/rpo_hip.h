@@ -582,7 +582,10 @@ int rpo_mlp_supported(int E, int H, int cat);
  * the same wherever inf * 0 or inf - inf arises (a zero weight is enough).  Rows are independent: no other row changes a bit.
  * This holds for rpo_mlp_forward in every form (row tile, first layer on either unit, x0 / h1 saved or not, layer by layer),
  * rpo_mlp_forward_multi and rpo_mlp_forward_split + rpo_mlp_split_head, which agree on such rows as on all others; the failure
- * flag (RPO_CTRL_NONFINITE) relies on it.  The streaming forms of n >= 12288 rows keep a NaN only when its sign bit is clear. */
+ * flag (RPO_CTRL_NONFINITE) relies on it.  The streaming forms (n >= 12288 rows here; the streaming rollout and policy_act, which
+ * share that forward) keep a NaN of either sign like every other form: tests/test_nonfinite_gpu.py pins the launches that train,
+ * act and evaluate.  One exception, stated: the opt-in 3 x bf16 hidden layer (RPO_TUNE_FWD_BF16X3) still takes its relu as an
+ * integer maximum and keeps a NaN only when its sign bit is clear. */
 int rpo_mlp_forward(const rpo_mlp* net_host, int n, const float* s, int s_stride, const float* a, int a_stride,
                     float* out, float* x0_save, float* h1_save, int out_mode, float scale, float base, void* stream);
 

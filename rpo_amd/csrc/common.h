@@ -26,13 +26,16 @@ static inline int rpo_tune(int key) { return g_rpo_tune[key]; }
 
 // relu as ONE instruction: the integer maximum of the bit pattern with 0 (positive floats order like their bits, negative
 // floats and -0.0 are negative integers).  fmaxf(x, 0.0f) compiles to two v_max_f32 -- the first quiets a signalling NaN the
-// value could be -- which matters next to f32 MFMAs: vector instructions share their lanes.  Same bits for every non-NaN x.
+// value could be -- which matters next to f32 MFMAs: vector instructions share their lanes.  Same bits for every non-NaN x; a NaN
+// whose sign bit is set becomes 0.  Only where no failure flag rests on the value: the relu the streaming backward recomputes from
+// saved pre-activations (mlp_bwd_stream.h) and the opt-in 3 x bf16 forward (mlp_stream_bf16x3.h).  Every forward that feeds an
+// action uses rpo_relu below -- the streaming forward (mlp_stream.h) too, at the same instruction count.
 __device__ __forceinline__ float rpo_relu_bits(float x) {
     const int b = __float_as_int(x);
     return __int_as_float(b > 0 ? b : 0);
 }
 
-// relu of the forward kernels (row tile, column split, layer by layer): IEEE 754-2019 maximum(x, 0), which returns the NaN when x
+// relu of the forward kernels (row tile, column split, layer by layer, streaming): IEEE 754-2019 maximum(x, 0), which returns the NaN when x
 // is one, whatever its sign -- a NaN pre-activation stays NaN and reaches the row's output (include/rpo_hip.h, rpo_mlp_forward; the
 // failure flag of DESIGN 4.7 rests on it).  fmaxf(x, 0.0f) returns 0 for a NaN.  ONE v_maximum3_f32 on gfx950 where fmaxf is two
 // v_max_f32 (the first quiets a signalling NaN); the same bits as fmaxf for every non-NaN x (maximum(-0.0, +0.0) = +0.0).

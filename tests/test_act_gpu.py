@@ -201,9 +201,10 @@ def test_schedule_key_residuals_and_out(hip, algo, envname):
             assert torch.equal(getattr(again, f), ref[f]), f
         with pytest.raises(ValueError):
             tr.act(x[:999], out=full)
-    # a NaN observation is no error: both paths agree on its row, the other rows keep their bits, no flag is raised.  (Whether
-    # the NaN reaches the action is the MLP kernels' business: their ReLU is the hardware maximum, which returns the non-NaN
-    # operand, so a NaN input is dropped behind the first layer; SpringPendulum's projection reads the observation itself.)
+    # a NaN observation is no error: both paths agree on its row, the other rows keep their bits, no flag is raised.  The NaN
+    # REACHES the row's outputs (include/rpo_hip.h, rpo_mlp_forward: the relu of every forward keeps a NaN pre-activation, so
+    # the proposal is NaN; Complete and the residuals are arithmetic on it; the GRG loop leaves after its one unconditional
+    # iteration, NaN comparing false with corr_eps) -- every form and every plant: tests/test_nonfinite_gpu.py.
     ref = tr.act(x[:64].contiguous())
     bad = x[:64].clone()
     bad[9, 2] = float("nan")
@@ -215,6 +216,9 @@ def test_schedule_key_residuals_and_out(hip, algo, envname):
         assert torch.equal(getattr(fused, f)[keep], getattr(ref, f)[keep]), f
     if envname == "pendulum":
         assert torch.isnan(fused.action[9, 1]) and torch.isnan(fused.ineq_resid[9]).all()      # (Complete: a_y depends on the row)
+    for r in (fused, step):                                     # what the NaN row holds
+        assert torch.isnan(r.proposal[9]).all() and torch.isnan(r.action[9]).all() and int(r.iters[9]) == 1
+        assert torch.isnan(r.eq_resid[9]).all() and torch.isnan(r.ineq_resid[9]).all()
     assert int(tr.vec.ctrl[hip.CONST["RPO_CTRL_NONFINITE"]]) == 0
 
 
