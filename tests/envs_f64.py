@@ -734,19 +734,24 @@ def pend_complete_bwd_fd(obs, ga):
         return ga[:, 0] + ga[:, 1] * d
 
 
-def project_b64(env, ap_in, K, lr, corr_eps, momentum, table=None, partial=None, obs=None):
+def project_b64(env, ap_in, K, lr, corr_eps, momentum, table=None, partial=None, obs=None, exact=False, trace=None, stop_guard=True):
     """The whole per-lane loop in float64 WITH momentum, the running bound carried through every iteration (each adds at most one
     single-step bound: the accumulated m is the K-step tolerance).  Returns (a_p V, a_o V, iters [n], clean [n]): ``clean`` rows met
-    no ambiguous mask or stop predicate on the way -- only those say anything about a float32 trajectory."""
+    no ambiguous mask or stop predicate on the way -- only those say anything about a float32 trajectory.  ``exact``: the float64
+    proposal as it is (``project_interval``); ``trace``: a list that receives, per iteration, the decisions of the rows that took
+    it as [n, 1 + predicates] booleans (the stop test, then the masks), False where the row had stopped.  ``stop_guard=False``: a stop
+    test within its guard does not spoil a row -- the float64 decision stands and a launch that decided otherwise shows as an
+    error, not as an exemption.  (SpringPendulum's |h| after Complete is 0 with a magnitude sum of 54: the guard, MARGIN * C_REF =
+    2 eps32 m = 1.3e-5, is wider than corr_eps = 1e-5 on EVERY row, while a float32 |h| stays below 0.5 eps32 m = 3.2e-6.)"""
     with np.errstate(all="ignore"):
         eps = float(np.float32(corr_eps))
         if env == "cart":
             c = CartTab(B64, table, partial)
-            ap = B64.inp(ap_in)
+            ap = B64X.inp(ap_in) if exact else B64.inp(ap_in)
             ao = cart_complete(B64, c, ap)
         else:
             e = pend_eq_of_obs(B64, obs)
-            ap = B64.inp(ap_in)
+            ap = B64X.inp(ap_in) if exact else B64.inp(ap_in)
             ao = pend_complete(B64, e, ap)
         n = ap.v.shape[0]
         old = (V(np.zeros(n)), V(np.zeros(n)))
@@ -762,20 +767,60 @@ def project_b64(env, ap_in, K, lr, corr_eps, momentum, table=None, partial=None,
                     amb |= ambiguous(V(gj.v - eps, gj.m), "stop_pred")
                 nap, nao, stp, margins = cart_grg_step(B64, c, partial, ap, ao, lr, momentum, old)
                 mamb = np.any([ambiguous(mg, "cart_pred") for mg in margins], axis=0)
+                on = np.stack([mg.v > 0 for mg in margins], axis=1)
             else:
                 h, g = pend_resid(B64, e, ap, ao)
                 viol = (np.abs(h.v) > eps) | (g.v > eps)
                 amb = ambiguous(V(np.abs(h.v) - eps, h.m), "stop_pred") | ambiguous(V(g.v - eps, g.m), "stop_pred")
                 nap, nao, stp, bm = pend_grg_step(B64, e, ap, ao, lr, momentum, old)
                 mamb = ambiguous(bm, "pend_pred")
+                on = (bm.v > 0)[:, None]
             if k > 0:
-                clean &= ~(live & amb)
+                if stop_guard:
+                    clean &= ~(live & amb)
                 live = live & viol
             clean &= ~(live & mamb)
+            if trace is not None:
+                trace.append(np.concatenate([live[:, None], on & live[:, None]], axis=1))
             ap, ao = B64.where(live, nap, ap), B64.where(live, nao, ao)
             old = (B64.where(live, stp[0], old[0]), B64.where(live, stp[1], old[1]))
             iters += live
         return ap, ao, iters, clean
+
+
+def project_interval(env, ap, delta, K, lr, corr_eps, lo, hi, table=None, partial=None, obs=None):
+    """Complete + the per-lane loop (corr_momentum = 0) of a float64 proposal ``ap`` that the launch held to within ``delta``:
+    the loop in float64 at clip(ap - delta), clip(ap) and clip(ap + delta).  A row whose clip decision, iteration count, stop test or
+    any mask differs among the three points, or meets an ambiguous mask at one of them, is AMBIGUOUS: the launch may have taken
+    another branch (the stop test is held to the float64 decision at the three points: project_b64, stop_guard).  On every other row the map ap -> a is smooth over the interval (affine for CartSafe, whose masks only pick
+    constants; quadratic terms for SpringPendulum), a few float32 ulps wide: the action moves by at most 2 x the larger deviation of
+    the end points from the centre (the factor 2 covers the curvature), and the float32 loop adds its own bound, tol_c(<env>_act) *
+    eps32 * the magnitude sum carried through the iterations (the convention of check_explore for the budget-0 action).
+    Returns (a [n,2] in the action's column order, bound [n,2], ambiguous [n], iters [n], path): ``path`` holds the actions at the
+    two end points (``ends``) and the float32 loop's own share of the bound (``own`` [n,2]) -- the proposal is one scalar per row,
+    so what follows can be carried along that one-dimensional path."""
+    ap, delta = np.asarray(ap, np.float64).reshape(-1), np.asarray(delta, np.float64).reshape(-1)
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    runs, inside = [], []
+    for pt in (ap - delta, ap, ap + delta):
+        inside.append(np.stack([pt >= lo, pt <= hi], axis=1))
+        tr = []
+        p, o, it, clean = project_b64(env, np.clip(pt, lo, hi), K, lr, corr_eps, 0.0, table=table, partial=partial, obs=obs,
+                                      exact=True, trace=tr, stop_guard=False)
+        runs.append((p, o, it, clean, np.stack(tr, axis=0) if tr else np.zeros((0, ap.size, 1), bool)))
+    c = runs[1]
+    amb = np.zeros(ap.size, bool)
+    for k in (0, 2):
+        amb |= (inside[k] != inside[1]).any(axis=1) | (runs[k][2] != c[2]) | (runs[k][4] != c[4]).any(axis=(0, 2))
+    for r in runs:
+        amb |= ~r[3]
+    with np.errstate(all="ignore"):
+        dev = [np.maximum(np.abs(runs[0][j].v - c[j].v), np.abs(runs[2][j].v - c[j].v)) for j in (0, 1)]
+        own = [tol_c(env + "_act") * EPS32 * B64.mag(c[j]) for j in (0, 1)]
+        bp, bo = (2.0 * dev[j] + own[j] + TINY for j in (0, 1))
+    join = (lambda p_, o_: cart_join(partial, p_, o_)) if env == "cart" else (lambda p_, o_: np.stack([p_, o_], axis=1))
+    path = dict(ends=[join(runs[k][0].v, runs[k][1].v) for k in (0, 2)], own=join(own[0] + TINY, own[1] + TINY))
+    return join(c[0].v, c[1].v), join(bp, bo), amb, c[2], path
 
 
 def batch_project_b64(obs, ap, K, lr, corr_eps, momentum):

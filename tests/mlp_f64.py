@@ -96,6 +96,29 @@ class Mlp64(object):
         a2 = torch.cat([a1 @ w.abs().t() + b.abs() for w, b in zip(ws, bs)], 1)
         return out, a2, L0 + L1 + L2
 
+    def forward_running(self, s, a=None, a_err=None):
+        """The whole network in float64 with the running bound of a float32 forward of the same inputs carried layer by layer:
+        (out, err) with |out32 - out| <= err.  forward_bound pushes the first layer's |.| expression through |W0| and |W1| and
+        multiplies by gamma of the whole chain; here every layer adds gamma_L of ITS OWN |.| expression at the float64
+        activations (widened by the error they carry) to |W| applied to the error it was handed (relu is 1-Lipschitz):
+            e0 = gamma_L0 A0 (+ |Wa| a_err),   e1 = e0 |W0| + gamma_L1 ((relu(x0) + e0) |W0| + |b0|),   e2 likewise.
+        The same inequalities, a factor of some tens tighter at 256 -> 256.  ``a_err`` [n, A]: a bound on what the launch read in
+        place of ``a``, every weight in absolute value (valid through the relu; a first-order gradient is not)."""
+        g = lambda L: L * U / (1.0 - L * U)                                       # noqa: E731
+        x0, a0, L0 = self.first_layer(s, a)
+        e0 = g(L0) * a0
+        if a_err is not None:
+            ea = self._f64(a_err) @ self.p["Wa"].abs().t()
+            e0 = e0 + (torch.cat([torch.zeros_like(ea), ea], 1) if self.cat else ea) * (1.0 + g(L0))
+        h1, _, L1 = self.hidden(x0)
+        w0 = self.p["W0"].abs().t()
+        e1 = e0 @ w0 + g(L1) * ((x0.clamp_min(0.0) + e0) @ w0 + self.p["b0"].abs())
+        out, _, L2 = self.head(h1)
+        ws, bs = self._heads()
+        r1 = h1.clamp_min(0.0) + e1
+        e2 = torch.cat([e1 @ w.abs().t() + g(L2) * (r1 @ w.abs().t() + b.abs()) for w, b in zip(ws, bs)], 1)
+        return out, e2 + TINY
+
     # ----------------------------------------------------------------------------------------------------- backward
     def backward(self, s, a, x0, h1, dout, param_grads=True, first_layer_state_only=False):
         """What rpo_mlp_backward computes from the kernel's saved x0 / h1 and a float32 dout [n, n_out * hd]:

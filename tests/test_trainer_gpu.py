@@ -484,7 +484,18 @@ _ROLLOUT_CASES = [pytest.param(a, e, n, 128, id="%s-%s-%s" % (a, e, name)) for n
                   for a, e in CASES] + [pytest.param(a, e, 100, 256, id="%s-%s-embed_256" % (a, e)) for a, e in CASES[:4]]
 # The largest |difference| the parent commit left between the two forms at embed_dim = 256, case by case; the bound is twice
 # that.  No entry: the parent is bitwise there, and so is the assertion.  "stats": the per-step statistics that miss rtol 1e-5
-# (sums of residuals near zero).  The cause of the RPOSAC differences has not been looked for.
+# (sums of residuals near zero).
+# Where the RPOSAC differences come from (read from the code, not from a run): the two forms run the actor's forward through
+# different kernels with another order of the k sums.  The pipeline runs mlp_tile_forward (fused.hip, rollout_tile: out_mode
+# `gauss ? 0 : 1`).  The stepwise sequence calls FusedNets.forward, which at E = 256 and n <= 16384 hands rpo_mlp_forward scratch
+# for x0 / h1 also on an inference call; with out_mode == 0 -- RPOSAC's raw heads (RPOSAC._gauss) -- that is gemm_path_ok
+# (mlp_gemm.h), so the forward goes layer by layer through gemm_forward, whose hidden layer (K = 256) takes the k-split kernel:
+# four quarter chains added as ((q0 + q1) + q2) + q3, not the tile kernel's one chain.  RPODDPG's proposal asks for the tanh box
+# (RPODDPG._actor_out: out_mode 1), which gemm_path_ok refuses: it stays on mlp_forward_kernel<256, 256>, the same mlp_tile.h
+# code as the pipeline, and is bitwise.  The update side (_CRITIC_MAX_256) differs in all four cases for the same reason: the
+# generic launches' forward_multi / forward of the critics and targets (saved or scratch x0 / h1, out_mode 0) take the GEMM path,
+# the pipelines mlp_tile_forward.  Both forms are held to float64 on their own by tests/test_embed256_f64_gpu.py; the figures
+# below stay what they were.
 _ROLLOUT_MAX_256 = {
     ("sac", "cart"): {"env state": 2.86102295e-06, "obs": 2.86102295e-06, "replay rows": 2.86102295e-06, "actions": 1.54972076e-06,
                       "parameters": 1.45286322e-07, "stats": 5.122274e-07},

@@ -1,6 +1,9 @@
 """The float64 chain of the constrained policy update (tests/update_f64.py) and the harness that reads ``agent.flat.grad`` between
 the backward launches and the optimiser step, on the CPU: the chain against torch autograd, the harness on the oracle backend
 (tests/oracle_backend.py: the generic launches' call order), and planted errors that the post-Adam checks of the suite let pass.
+At embed_dim = hidden_dim = 256, the trainers' default width: the harness again, the target chain of the launches that keep their
+next actions (update_f64.cart_target_chain) and the rollout's actions (update_f64.rollout_actions) on the oracle backend at the
+seeds of tests/test_embed256_f64_gpu.py, and errors planted into a float32 stand-in of that chain.
 """
 import numpy as np
 import pytest
@@ -353,6 +356,182 @@ def test_planted_errors_are_found_in_the_flat_gradient(what, algo, envname, kw):
     near = dict(dq_row="dq", padded_batch="dq", shared_embedding="dq", lagrangian_da="g_act", alpha_over_b="logp")[what]
     assert bad[near] == clean[near] <= 1.0, (near, bad[near], clean[near])
     assert _grad_ratio(bad) > 1.0, "the planted error stays inside the bound: %.3g" % _grad_ratio(bad)
+
+
+# ================================================================================== the 256-wide networks (the default width)
+E256 = dict(embed_dim=256, hidden_dim=256)
+HARNESS_256 = [(a, e, dict(kw, batch_size=b)) for a, e, kw in (("ddpg", "cart", {}), ("sac", "cart", {}), ("sac", "pendulum", {}))
+               for b in (100, 17)]
+
+
+@pytest.mark.parametrize("algo,envname,kw", HARNESS_256, ids=[_case_id(c) for c in HARNESS_256])
+def test_harness_on_the_oracle_backend_at_256(algo, envname, kw):
+    """The harness at embed_dim = hidden_dim = 256, the trainers' default width, on the oracle backend (the generic chain): what
+    test_harness_on_the_oracle_backend judges, and on CartSafe qn against the recomputed target chain as well
+    (update_f64.cart_target_chain, the form in which the launches that keep their next actions are judged), with the TD chain
+    run from it."""
+    tr = _trainer(algo, envname, **dict(E256, **kw))
+    assert tr.fused.descs["actor"].E == 256
+    snap = uf.run_update(tr)
+    assert snap["path"] == ("generic", "generic")
+    worst, info = uf.check_update(tr, snap, target_chain=(envname == "cart"))
+    uf.report("oracle backend, 256 wide, %s" % _case_id((algo, envname, kw)), worst)
+    assert ("qn target chain" in worst) == (envname == "cart")
+    assert max(worst.values()) <= 1.0
+
+
+# the seeds, lanes, warm-up steps and batches of tests/test_embed256_f64_gpu.py: the reference alone must stay within AMBIG_CAP there
+CAP_UPDATE = [(a, dict(kw, batch_size=b)) for a, kw in (("ddpg", {}), ("ddpg", dict(shared_param=False)), ("sac", {}))
+              for b in (256, 250, 100, 17, 1)]
+
+
+@pytest.mark.parametrize("algo,kw", CAP_UPDATE, ids=[_case_id((c[0], "cart", c[1])) for c in CAP_UPDATE])
+def test_target_chain_ambiguity_on_the_oracle_backend(algo, kw):
+    """CartSafe at 256: the share of rows whose target-chain projection is ambiguous (a clip, stop or mask decision that differs
+    over ap +- delta) on the oracle backend at the GPU cases' seeds and batches, under AMBIG_CAP -- a condition on the reference
+    and the seeds, known to hold before a device is asked -- and the oracle backend's own qn within the chain's bound."""
+    tr = _trainer(algo, "cart", **dict(E256, **kw))
+    snap = uf.run_update(tr, critic_only=True)
+    chain = uf.cart_target_chain(tr, snap, uf.EnvRef.of(tr.kernels), uf.trainer_box(tr))
+    share = float(chain["ambiguous"].double().mean())
+    r = uf.target_qn_ratio(chain, [c["qn"] for c in snap["critic"]]) if share < 1.0 else 0.0
+    print("target chain %s: ambiguous share %.3g (cap %.3g), iterations up to %d, qn ratio %.3g"
+          % (_case_id((algo, "cart", kw)), share, uf.AMBIG_CAP, int(chain["iters"].max()), r))
+    assert share <= uf.AMBIG_CAP and r <= 1.0
+
+
+ROLL = [(a, e, n) for a, e in (("sac", "cart"), ("sac", "pendulum"), ("ddpg", "cart")) for n in (1, 17, 100)]
+
+
+@pytest.mark.parametrize("algo,envname,n", ROLL, ids=["%s-%s-%d" % c for c in ROLL])
+def test_rollout_actions_on_the_oracle_backend(algo, envname, n):
+    """update_f64.rollout_actions on the oracle backend's vector step (the stepwise sequence) at 256, at the lanes and steps of
+    the GPU cases: the stored actions within the bound, the ambiguous share within AMBIG_CAP."""
+    tr = _rollout_trainer(algo, envname, n)
+    obs, t, sub, params = tr.vec.obs.clone(), int(tr.vec.ctrl[0]), int(tr.vec.ctrl[2]), uf.read_params(tr)
+    tr._rollout(False)
+    res = uf.rollout_actions(tr, params, obs, tr.vec.action, t, sub, tr.vec.env_id_base)
+    share = float(res["ambiguous"].mean())
+    print("rollout %s %s n=%d t=%d: ratio %.3g, ambiguous share %.3g" % (algo, envname, n, t, res["ratio"], share))
+    assert t >= 1 and share <= uf.AMBIG_CAP and res["ratio"] <= 1.0
+
+
+def _rollout_trainer(algo, envname, n, steps=3):
+    torch.set_num_threads(1)
+    torch.manual_seed(5)
+    tr = build_trainer(algo, envname, ob, CPU, fused=True, num_envs=n, use_graph=False, batch_size=16, **E256)
+    tr.vec.reset()
+    tr.run_steps(steps)
+    return tr
+
+
+def _mlp32(p, s, a=None, drop_rows=None, drop_cols=None):
+    """A network in plain float32 torch (the stand-in of a launch).  drop_rows / drop_cols: the hidden layer of those rows leaves
+    those embedding columns out -- one k-step of a tile lost."""
+    x0 = s @ p["Ws"].t() + p["bs"]
+    if a is not None:
+        x0 = x0 + a @ p["Wa"].t() + p["ba"]
+    r0 = torch.relu(x0)
+    h1 = r0 @ p["W0"].t() + p["b0"]
+    if drop_rows is not None:
+        keep = torch.ones(r0.shape[1], dtype=torch.bool)
+        keep[drop_cols] = False
+        h1[drop_rows] = r0[drop_rows][:, keep] @ p["W0"][:, keep].t() + p["b0"]
+    r1 = torch.relu(h1)
+    out = [r1 @ p["W1"].view(1, -1).t() + p["b1"]]
+    if p.get("W1b") is not None:
+        out.append(r1 @ p["W1b"].view(1, -1).t() + p["b1b"])
+    return torch.cat(out, dim=1)
+
+
+def _proposal32(tr, p, obs, eps, box, plant, name):
+    """The basic action in float32: the tanh box of the deterministic actor (+ the caller's exploration) or the Gaussian head at the
+    draw ``eps``.  plant "ls_from_mean": the head reads its log-std from the mean's column."""
+    scale, base, lo, hi = box
+    raw = _mlp32(p[name], obs)
+    if tr.sac:
+        ls = raw[:, 0 if plant == "ls_from_mean" else 1]
+        return hf.gauss_head(raw[:, 0], ls, eps, scale, base, lo, hi, dtype=torch.float32)["ap"].numpy()
+    return (np.float32(scale) * torch.tanh(raw[:, 0]) + np.float32(base)).numpy()
+
+
+def _target_qn32(tr, snap, plant=None):
+    """The target chain pi(s') -> head -> Complete -> Proj -> Q_targ in float32 (plain torch and envs_f64.cart_project_f32: a
+    stand-in of the launch that shares no code with the float64 chain), with ONE error planted:
+      k_step        Q_targ's hidden layer leaves 4 of the 256 embedding columns out for the rows of the second tile
+      uncompleted   the rows of the ragged last tile keep a' = (ap, 0): neither completed nor projected
+      ls_from_mean  RPOSAC: the Gaussian head reads its log-std from the mean's column
+      q_at_s        Q_targ is evaluated at (s, a') in place of (s', a')"""
+    state, _, next_state = snap["cols"][:3]
+    p0, env, box = snap["params0"], uf.EnvRef.of(tr.kernels), uf.trainer_box(tr)
+    B, K = state.shape[0], int(tr.max_steps)
+    ap = _proposal32(tr, p0, next_state, snap["rec"].get("eps_next"), box, plant, "actor" if tr.sac else "actor_target")
+    planes, _ = ef.cart_project_f32(env.table, env.partial, ap, K, tr.corr_lr, tr.corr_eps, 0.0)
+    a = planes[K][:, :2].copy()
+    if plant == "uncompleted":
+        last = np.arange(16 * (B // 16), B)
+        assert 0 < last.size < 16
+        a[last] = ef.cart_join(env.partial, ap[last], np.zeros(last.size, np.float32))
+    a = torch.from_numpy(a)
+    at = state if plant == "q_at_s" else next_state
+    drop = dict(drop_rows=torch.arange(16, 32), drop_cols=torch.arange(128, 132)) if plant == "k_step" else {}
+    return [_mlp32(p0[t], at, a, **drop).view(-1) for _, t in uf.critic_names(tr)]
+
+
+TARGET_PLANTS = [("k_step", "ddpg"), ("uncompleted", "ddpg"), ("ls_from_mean", "sac"), ("q_at_s", "ddpg")]
+
+
+@pytest.mark.parametrize("what,algo", TARGET_PLANTS, ids=[p[0] for p in TARGET_PLANTS])
+def test_planted_errors_are_found_in_the_target_values(what, algo):
+    """Four errors of the kind a row-tile pipeline makes in the chain it keeps to itself, planted into a float32 stand-in of the
+    launch's qn (never into the repository's kernels) on CartSafe at 256 wide, 100 rows: each lands above 1 x the bound of
+    update_f64.cart_target_chain while the unplanted stand-in -- and the oracle backend's own qn -- stay below it.
+    Measured, worst |qn - float64| / bound, unplanted -> planted, under the four forms of the bound (update_f64.cart_target_chain):
+
+                      "path" (asserted)     "corners"            "running"            "chain" (the first form)
+      k_step          0.00014 -> 21         0.00009 -> 11        5.8e-7 -> 0.068      9.9e-8 -> 0.013
+      uncompleted     0.00014 -> 1.7        0.00009 -> 0.93      5.8e-7 -> 0.0043     9.9e-8 -> 0.0007
+      ls_from_mean    0.00019 -> 21         0.00014 -> 13        6.0e-7 -> 0.10       8.6e-8 -> 0.016
+      q_at_s          0.00014 -> 690        0.00009 -> 369       5.8e-7 -> 1.4        9.9e-8 -> 0.29
+
+    The chain form lets every one of them pass and the running form three: the sensitivity with every weight in absolute value,
+    |W1| |W0| |Wa| delta_a, is some hundred times the network's response to delta_a.  The corners of the box a' +- delta_a leave
+    the path Complete keeps a' on, and let the uncompleted rows pass (the critic of a fresh trainer hardly answers to a').  Hence
+    "path".  The uncompleted rows stay the thinnest: 4 rows, an a' that is off by 0.1 to 0.3 where delta_a is 0.003 to 0.006."""
+    tr = _trainer(algo, "cart", **dict(E256, batch_size=100))
+    snap = uf.run_update(tr, critic_only=True)
+    env, box = uf.EnvRef.of(tr.kernels), uf.trainer_box(tr)
+    clean32, bad32 = _target_qn32(tr, snap), _target_qn32(tr, snap, what)
+    line = []
+    for bounds in ("path", "corners", "running", "chain"):
+        chain = uf.cart_target_chain(tr, snap, env, box, bounds=bounds)
+        assert float(chain["ambiguous"].double().mean()) <= uf.AMBIG_CAP
+        own = uf.target_qn_ratio(chain, [c["qn"] for c in snap["critic"]])
+        clean, bad = uf.target_qn_ratio(chain, clean32), uf.target_qn_ratio(chain, bad32)
+        line.append("%s %.3g -> %.3g" % (bounds, clean, bad))
+        assert own <= 1.0 and clean <= 1.0, (bounds, own, clean)
+        if bounds == uf.TARGET_BOUNDS:
+            assert bad > 1.0, "the planted error stays inside the bound: %.3g" % bad
+    print("planted %-13s qn ratio unplanted -> planted: %s" % (what, " | ".join(line)))
+
+
+def test_planted_log_std_column_is_found_in_the_rollout_actions():
+    """RPOSAC's rollout on CartSafe at 256 wide, 17 lanes: a float32 stand-in of the vector step's policy whose Gaussian head reads
+    its log-std from the mean's column lands above 1 x the bound of update_f64.rollout_actions, the unplanted stand-in and the
+    oracle backend's own actions below it.  Measured: 0.00008 -> 52."""
+    tr = _rollout_trainer("sac", "cart", 17)
+    obs, t, sub, params = tr.vec.obs.clone(), int(tr.vec.ctrl[0]), int(tr.vec.ctrl[2]), uf.read_params(tr)
+    tr._rollout(False)
+    env, box = uf.EnvRef.of(tr.kernels), uf.trainer_box(tr)
+    eps = uf.rollout_noise(tr, 17, t, sub, tr.vec.env_id_base)
+    got = {}
+    for plant in (None, "ls_from_mean"):
+        ap = _proposal32(tr, params, obs, eps, box, plant, "actor")
+        planes, _ = ef.cart_project_f32(env.table, env.partial, ap, int(tr.max_steps), tr.corr_lr, tr.corr_eps, 0.0)
+        got[plant] = uf.rollout_actions(tr, params, obs, planes[int(tr.max_steps)][:, :2], t, sub, tr.vec.env_id_base)["ratio"]
+    own = uf.rollout_actions(tr, params, obs, tr.vec.action, t, sub, tr.vec.env_id_base)["ratio"]
+    print("planted ls_from_mean  rollout action ratio %.3g -> %.3g (the oracle backend's own %.3g)" % (got[None], got["ls_from_mean"], own))
+    assert own <= 1.0 and got[None] <= 1.0 < got["ls_from_mean"]
 
 
 # ============================================================================================================ EVOPF-v0

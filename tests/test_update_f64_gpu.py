@@ -11,15 +11,17 @@ the completed actions, g_act; RPOSAC's log pi(a'|s') on every path) layer-locall
 Paths, chosen with RPO_SCHEDULE and asserted per case: the generic launches, the row-tile pipelines (fused.hip), the column-split
 stages (nsplit.hip) with the front launches and with one launch per stage.  CartSafe's row-tile pipelines and split stages complete
 and project the next actions inside the launch that evaluates the target critics and do not export them (SpringPendulum's hand
-them over through memory: wrapped _project_batch, split.next_actions): their q / qn are held bit for bit to the generic launches'
-on the same parameters, ring and draws instead; the split stages with and without front launches leave the same bits in flat.grad
-after each half.
+them over through memory: wrapped _project_batch, split.next_actions): their qn is judged against the target chain recomputed in
+float64 (update_f64.cart_target_chain; the TD chain runs from that value and bound), and their q / qn are held bit for bit to the
+generic launches' on the same parameters, ring and draws as well; the split stages with and without front launches leave the same
+bits in flat.grad after each half.  The 256-wide networks: tests/test_embed256_f64_gpu.py.
 
 Worst |err| / bound measured on an MI355X, per group (every case prints its own under -s; the gradient bounds are worst-case
 chains over B + 20 additions, so a correct kernel sits far inside them -- the planted errors of test_update_f64.py, 0.4 % of a
 gradient, land at 13 to 580):
     CartSafe, generic launches       critic slice 0.0002, shared slice 0.0002, actor slice 0.0006, losses 0.0014, log_alpha 0.01
-    CartSafe, row-tile pipelines     critic 0.026, shared 0.0002, actor 0.0006, losses 0.024 (qn is the launch's own: no target bound)
+    CartSafe, row-tile pipelines     critic 0.026, shared 0.0002, actor 0.0006, losses 0.024 (the TD chain from the launch's own qn, which
+                                     is judged against the target chain: 0.0005; from qn64 and its bound: critic 0.001, losses 0.0001)
     CartSafe, split, front / none    critic 0.026, shared 0.0002, actor 0.0004, losses 0.023, log_alpha 0.01
     SpringPendulum, every path       critic 0.00006, actor 0.0004 (split 0.0003), d nu 0.05, losses 0.0009
     *_viol, row-tile and split       critic 0.025 / 0.007, actor 0.0011 / 0.0026, d nu 0.0026 / 0.0013 (cart / pendulum)
@@ -167,7 +169,8 @@ EQUAL = [(a, dict(kw, batch_size=b)) for a, _, kw in CART for b in (256, 250, 10
 @pytest.mark.parametrize("path", ["row-tile", "split", "split-nofront"])
 def test_cart_targets_equal_the_generic_launches(hip, monkeypatch, path, algo, kw):
     """CartSafe's row-tile critic pipeline and its split stages keep the next actions inside the launch, so their qn cannot be held
-    against float64 at them.  Instead: q and qn (and dq, and RPOSAC's log pi(a'|s')) of those launches are bit for bit those of the
+    against float64 at them (above it is held against the recomputed target chain, whose bound carries the proposal's interval).
+    Beside that: q and qn (and dq, and RPOSAC's log pi(a'|s')) of those launches are bit for bit those of the
     generic launches -- whose next actions and qn ARE held against float64 above -- on the same parameters, targets and ring
     (copied over) and the same Philox draws (same seed and clock: the sampled batch is asserted equal); every CartSafe case of
     the matrix above: shared and separate embeddings, RPOSAC, 256 / 250 / 100 rows."""

@@ -1,6 +1,7 @@
 """The constrained policy update as ONE float64 chain: what ``agent.flat.grad`` must hold between the backward launches and the
 optimiser step, with a bound beside every element.  Not collected; used by test_update_f64.py (CPU: the chain against autograd,
-the harness on the oracle backend, planted errors) and test_update_f64_gpu.py (every update path of the trainers on the device).
+the harness on the oracle backend, planted errors), test_update_f64_gpu.py (every update path of the trainers on the device) and
+test_embed256_f64_gpu.py (the 256-wide networks; the rollout's actions through policy_proposal and envs_f64.project_interval).
 
 Nothing here is new arithmetic.  The chain composes the restatements the kernel tests already use, stage by stage:
 
@@ -168,6 +169,154 @@ def critic_chain(net, state, action, x0, h1, q, qn, qn_err, reward, done, gamma,
     rows = dq.numel()
     grads = {k: param_allowed(res, res_b, k, rows) for k in mf.FIELDS if k in res}
     return grads, (loss, loss_b), (dq, dq_b)
+
+
+TARGET_BOUNDS = "path"
+
+
+def _forward(net, obs, bounds, a=None):
+    """(out, bound) of a float32 forward against float64: Mlp64.forward_bound ("chain": gamma of the whole chain on the |.|
+    expression pushed through every layer) or Mlp64.forward_running (the running bound, layer by layer)."""
+    if bounds == "chain":
+        out, absval, L = net.forward_bound(obs, a)
+        return out, mf.bound(absval, L)
+    return net.forward_running(obs, a)
+
+
+def _spread(net, obs, centre, points):
+    """max over ``points`` of |Q64(obs, point) - centre|, per row."""
+    out = torch.zeros_like(centre)
+    for pt in points:
+        out = torch.maximum(out, (net.forward(obs, pt)[0] - centre).abs())
+    return out
+
+
+def policy_proposal(tr, params, box, obs, eps=None, target=True, det_noise=None, eps_t=0.0, bounds=None):
+    """The basic action the policy proposes at ``obs`` in float64 and a bound on the launch's float32 one: (ap, delta, heads).
+    RPODDPG: the target actor (``target``) or the live one through the tanh box, heads_f64.C_REF_BOX_FWD on the box and |scale|
+    times the forward bound of the head (tanh is 1-Lipschitz), plus eps_t x ``det_noise`` (the rollout's exploration: its product
+    and its sum round once each).  RPOSAC: the live actor through the Gaussian head at the draw ``eps``, heads_f64.C_REF_AP on the
+    head and |d ap / d heads| (autograd of heads_f64.gauss_head) on the forward bound of the two heads -- the sensitivity
+    check_update's "log pi(a'|s')" branch uses.  The clip to the box is left to the caller (envs_f64.project_interval:
+    continuous, its seam a predicate)."""
+    scale, base, lo, hi = box
+    n = obs.shape[0]
+    bounds = TARGET_BOUNDS if bounds is None else bounds
+    if tr.sac:
+        out, rb = _forward(net64(tr, params, "actor"), obs, bounds)
+        fw = hf.gauss_head(out[:, 0], out[:, 1], eps, scale, base, -1e30, 1e30, dap=torch.ones(n, dtype=F64), dlogp=0.0)
+        mg = hf.gauss_mags(out[:, 0], out[:, 1], eps, scale, base)
+        delta = hf.MARGIN * hf.C_REF_AP * hf.EPS32 * mg["ap"] + fw["g_mean"].abs() * rb[:, 0] + fw["g_ls"].abs() * rb[:, 1] + mf.TINY
+        return fw["ap"], delta, out
+    out, o_b = _forward(net64(tr, params, "actor_target" if target else "actor"), obs, bounds)
+    o, o_b = out.view(-1), o_b.view(-1)
+    ap = scale * torch.tanh(o) + base
+    delta = hf.MARGIN * hf.C_REF_BOX_FWD * hf.EPS32 * hf.tanh_box_fwd_mags(o, scale, base) + abs(scale) * o_b + mf.TINY
+    if det_noise is not None:
+        nz = t64(det_noise).view(-1) * hf.f32(eps_t)
+        delta = delta + hf.EPS32 * (ap.abs() + 2 * nz.abs())
+        ap = ap + nz
+    return ap, delta, out
+
+
+def cart_target_chain(tr, snap, env, box, bounds=None):
+    """qn of the launches that keep the next actions to themselves (CartSafe's row-tile critic pipelines and split stages),
+    recomputed in float64 from the gathered batch, the parameters before the update and, for RPOSAC, the reproduced draw:
+
+        pi_targ(s') (RPOSAC: pi(s') at eps_next) -> box / Gaussian head      policy_proposal: (ap, delta)
+        -> Complete -> Proj                                                  envs_f64.project_interval at ap - delta, ap, ap + delta:
+                                                                             (a', delta_a), ambiguous rows
+        -> Q_targ(s', a')                                                    its forward bound + its response to the interval
+
+    ``bounds`` (default TARGET_BOUNDS; tests/test_update_f64.py::test_planted_errors_are_found_in_the_target_values measures
+    what each form lets pass):
+      "chain"    Mlp64.forward_bound for both networks and the sensitivity |W1| |W0| |Wa| delta_a, every weight in absolute value:
+                 valid through the relu, which is 1-Lipschitz (a first-order gradient at a' is not a bound).  At 256 -> 256 it allows
+                 qn some units (delta = 0.05 on a proposal of size 1, 3.7 on a qn of 0.4 where the float32 error is 2e-7) and hides
+                 every planted error: kept as the yardstick the tighter forms are shown against.
+      "running"  Mlp64.forward_running for both (the running bound layer by layer: the same inequalities, no looser step) with
+                 delta_a handed to it as the error of the action input -- still every weight in absolute value; hides three of four.
+      "corners"  forward_running for the networks' own rounding, and for delta_a the spread of Q_targ64 over the four corners
+                 a' +- delta_a about the centre, doubled (the map is piecewise linear in a' with relu kinks: the factor covers a
+                 kink inside the box, as project_interval's covers curvature).  The corners leave the line Complete keeps a' on.
+      "path"     the proposal is one scalar per row, so the propagation is one-dimensional: the spread of Q_targ64 over the two
+                 end points a'(ap - delta), a'(ap + delta) about a'(ap), doubled, and the float32 loop's own (ulp-sized) share of
+                 delta_a through forward_running in absolute value.
+    Returns dict(qn [(value, bound)] per target critic, ambiguous [n], next_actions (a', delta_a), ap (ap, delta), iters [n])."""
+    bounds = TARGET_BOUNDS if bounds is None else bounds
+    next_state = snap["cols"][2]
+    p0, rec = snap["params0"], snap["rec"]
+    ap, delta, _ = policy_proposal(tr, p0, box, next_state, eps=rec.get("eps_next"), bounds=bounds)
+    a, a_b, amb, iters, path = ef.project_interval(env.kind, ap.numpy(), delta.numpy(), int(tr.max_steps), tr.corr_lr, tr.corr_eps, box[2],
+                                                   box[3], table=env.table, partial=env.partial, obs=n64(next_state))
+    a, a_b = torch.from_numpy(a), torch.from_numpy(a_b)
+    qn = []
+    for _, tname in critic_names(tr):
+        net = net64(tr, p0, tname)
+        if bounds == "chain":
+            out, own = _forward(net, next_state, bounds, a)
+            ws, _ = net._heads()
+            b = own + (((a_b @ net.p["Wa"].abs().t()) @ net.p["W0"].abs().t()) @ ws[0].abs().t()) * (1.0 + 4 * U)
+        elif bounds == "running":
+            out, b = net.forward_running(next_state, a, a_err=a_b)
+        elif bounds == "corners":
+            out, own = net.forward_running(next_state, a)
+            b = own + 2.0 * _spread(net, next_state, out, [a + a_b * torch.tensor([s0, s1], dtype=F64) for s0 in (-1.0, 1.0) for s1 in (-1.0, 1.0)])
+        else:
+            # along the path: the two end points of the proposal's interval, and around each of the three points the corners of
+            # the float32 loop's own (ulp-sized) box
+            pown = torch.from_numpy(path["own"])
+            out, own = net.forward_running(next_state, a, a_err=pown)
+            b = own + 2.0 * _spread(net, next_state, out, [torch.from_numpy(e) for e in path["ends"]])
+        qn.append((out.view(-1), b.view(-1)))
+    return dict(qn=qn, ambiguous=torch.from_numpy(amb), next_actions=(a, a_b), ap=(ap, delta), iters=iters)
+
+
+def trainer_box(tr):
+    """(scale, base, lo, hi) of the constant action box, as the float32 arguments the launches receive."""
+    return (hf.f32(tr._box_affine[0]), hf.f32(tr._box_affine[1]), hf.f32(tr._box_lo), hf.f32(tr._box_hi))
+
+
+def rollout_noise(tr, n, t, sub=0, env_id_base=0):
+    """The draw of one vector step at clock ``t``, from the Philox oracle at the launch's key: RPODDPG's exploration noise
+    (STREAM_ACT, index t) or RPOSAC's sample (STREAM_POLICY, index t + salt 0, sub-stream ctrl[RPO_CTRL_UPDATES])."""
+    from oracle import philox
+    ids = np.arange(n) + int(env_id_base)
+    if tr.sac:
+        r = philox.draw(tr.seed, ids, int(t) & 0xFFFFFFFF, philox.STREAM_POLICY, int(sub))
+    else:
+        r = philox.draw(tr.seed, ids, int(t), philox.STREAM_ACT)
+    return torch.from_numpy(np.asarray(philox.normal(r[:, 0], r[:, 1]), np.float32))
+
+
+def rollout_actions(tr, params, obs, actions, t, sub=0, env_id_base=0, bounds=None):
+    """The actions of one vector step against float64 from the observation the launch read: actor(obs) -> tanh box + eps_t x the
+    Philox draw and the clip (RPODDPG) or the Gaussian head at the Philox draw (RPOSAC) -> Complete -> Proj, by the three-point
+    scheme of cart_target_chain (policy_proposal, envs_f64.project_interval).  Returns dict(ratio: worst |action - float64| /
+    bound over the rows that are not ambiguous, ambiguous [n], ref (a, bound), iters [n])."""
+    env, box = EnvRef.of(tr.kernels), trainer_box(tr)
+    obs = t64(obs)
+    n = obs.shape[0]
+    noise = rollout_noise(tr, n, t, sub, env_id_base)
+    if tr.sac:
+        ap, delta, _ = policy_proposal(tr, params, box, obs, eps=noise, bounds=bounds)
+    else:
+        eps_t = hf.eps_schedule(tr.eps_start, tr.eps, tr.decay_value, t)
+        ap, delta, _ = policy_proposal(tr, params, box, obs, target=False, det_noise=noise, eps_t=eps_t, bounds=bounds)
+    a, a_b, amb, iters, _ = ef.project_interval(env.kind, ap.numpy(), delta.numpy(), int(tr.max_steps), tr.corr_lr, tr.corr_eps, box[2], box[3],
+                                                table=env.table, partial=env.partial, obs=obs.numpy())
+    got = n64(actions).reshape(n, 2)
+    assert np.isfinite(got).all(), "rollout actions: non-finite"
+    r = np.abs(got - a) / a_b
+    keep = ~amb
+    return dict(ratio=float(r[keep].max()) if keep.any() else 0.0, ambiguous=amb, ref=(a, a_b), iters=iters, noise=noise)
+
+
+def target_qn_ratio(chain, got):
+    """Worst |qn - float64| / bound of the launch's target values ``got`` (one [n] tensor per target critic) over the rows whose
+    projection is not ambiguous."""
+    keep = ~chain["ambiguous"]
+    return max(float(((t64(g).view(-1) - ref).abs() / b)[keep].max()) for g, (ref, b) in zip(got, chain["qn"]))
 
 
 def _critic_da(critics, state, actions, dqs, shared, rows):
@@ -539,11 +688,13 @@ def _cap(tag, rows, worst, key):
     assert share <= AMBIG_CAP, "%s: %.3g of the rows are ambiguous (cap %.3g)" % (tag, share, AMBIG_CAP)
 
 
-def check_update(tr, snap, strict=True):
+def check_update(tr, snap, strict=True, target_chain=False):
     """Judge a snapshot of ``run_update``: every element of the critic, shared and actor slices of flat.grad and of the
     multipliers' gradient within its bound, padding and the other optimiser's private slice exactly 0, the losses within theirs,
     gradmax exact, the launches' intermediates layer-locally within float64.  Returns {what: worst |err| / bound}; with
-    ``strict`` a ratio above 1 fails where it is found, otherwise it is only recorded (the planted-error tests)."""
+    ``strict`` a ratio above 1 fails where it is found, otherwise it is only recorded (the planted-error tests).
+    ``target_chain`` (CartSafe): judge qn against the recomputed target chain (cart_target_chain) and run the TD chain from it even
+    where the launches exported their next actions -- the form every launch that keeps them to itself is judged in."""
     ag, fl, B = tr.agent, tr.agent.flat, tr.batch_size
     worst, fails = {}, []
     evopf = tr.kernels.name.startswith("EVOPF")
@@ -567,19 +718,35 @@ def check_update(tr, snap, strict=True):
     # (CartSafe's pipelines and split stages alone keep the next actions inside their launch)
     assert nxt is not None or (env is not None and env.kind == "cart" and snap["path"][0] != "generic"), "next actions not captured"
     qn64, qn_err = [], []
+    chain = None
+    if nxt is None or target_chain:
+        # CartSafe's pipelines and split stages do not export the next actions: the target chain is recomputed in float64 from the
+        # batch, and qn judged against it (cart_target_chain).  A row whose projection may have branched otherwise in the launch
+        # keeps the launch's own qn (its decision), at most AMBIG_CAP of the batch.
+        chain = cart_target_chain(tr, snap, env, box)
+        amb = chain["ambiguous"]
+        _cap("the target chain's projection", amb, worst, "proj(s')")
+        for (cname, tname), c, (ref, b) in zip(names, snap["critic"], chain["qn"]):
+            got = c["qn"].view(-1).to(F64)
+            judge(tname + " qn", got[~amb], ref[~amb], b[~amb], "qn target chain")
+            qn64.append(torch.where(amb, got, ref))
+            qn_err.append(torch.where(amb, torch.zeros_like(b), b))
     for (cname, tname), c in zip(names, snap["critic"]):
-        t64net = net64(tr, p0, tname)
         if nxt is not None:
-            out, absval, L = t64net.forward_bound(next_state, nxt)
-            qn64.append(out.view(-1))
-            qn_err.append(mf.bound(absval, L).view(-1))
-            judge(tname + " qn", c["qn"].view(-1), qn64[-1], qn_err[-1], "qn")
-        else:                                                   # (CartSafe's pipelines and split stages do not export the next actions:
-            qn64.append(c["qn"].view(-1).to(F64))               #  the launch's qn stands, held bit for bit to the generic path's by its own test)
-            qn_err.append(None)
-    err_min = None if qn_err[0] is None else torch.maximum(qn_err[0], qn_err[-1])
+            out, absval, L = net64(tr, p0, tname).forward_bound(next_state, nxt)
+            if chain is None:
+                qn64.append(out.view(-1))
+                qn_err.append(mf.bound(absval, L).view(-1))
+            judge(tname + " qn", c["qn"].view(-1), out.view(-1), mf.bound(absval, L).view(-1), "qn")
+    # What the TD chain starts from: the float64 target values with their bound (mlp_f64.td, qn_err).  Where the launch keeps its
+    # next actions that bound carries the proposal's interval and is some tens of times wider than a forward bound, so there the
+    # chain is ALSO run from the launch's own qn with no target bound -- what the TD prologue read, judged above -- under the plain
+    # keys, as before the target chain existed; the run from qn64 goes under "... from qn64".
+    sources = [("", qn64, torch.maximum(qn_err[0], qn_err[-1]))]
+    if nxt is None:
+        sources = [("", [c["qn"].view(-1).to(F64) for c in snap["critic"]], None), (" from qn64",) + sources[0][1:]]
     got_c, covered = snap["grad_c"], torch.zeros(fl.total, dtype=torch.bool)
-    loss_ref, loss_b = 0.0, 0.0
+    loss_ref, loss_b = {sfx: 0.0 for sfx, _, _ in sources}, {sfx: 0.0 for sfx, _, _ in sources}
     parts = snap["parts_c"].view(len(names), -1)
     for i, ((cname, tname), c) in enumerate(zip(names, snap["critic"])):
         net = net64(tr, p0, cname)
@@ -601,26 +768,28 @@ def check_update(tr, snap, strict=True):
             mg = hf.gauss_mags(out[:, 0], out[:, 1], rec["eps_next"], box[0], box[1])
             allowed = hf.MARGIN * hf.C_REF_LOGP * hf.EPS32 * mg["logp"] + fw["g_mean"].abs() * rb[:, 0] + fw["g_ls"].abs() * rb[:, 1] + mf.TINY
             judge("log pi(a'|s')", logp.view(-1), fw["logp"], allowed, "logp(s')")
-        grads, (lo_, lo_b), (dq, dq_b) = critic_chain(net, state, action, c["x0"], c["h1"], c["q"], qn64[0], err_min, reward, done,
-                                                        ag.gamma, qn64[1] if tr.sac else None, logp, alpha)
-        judge(cname + " dq", c["dq"].view(-1), dq, dq_b, "dq")
-        got_loss = float(parts[i].double().sum())
-        r = abs(got_loss - lo_) / lo_b
-        worst["loss parts"] = max(worst.get("loss parts", 0.0), r)
-        loss_ref, loss_b = loss_ref + lo_, loss_b + lo_b
-        for k, (off, got) in _slices(tr, cname, got_c).items():
-            ref, allowed = grads[k]
-            judge("%s d%s" % (cname, k), got, ref, allowed, "critic " + k)
-            covered[off:off + got.numel()] = True
+        for sfx, src, err in sources:
+            grads, (lo_, lo_b), (dq, dq_b) = critic_chain(net, state, action, c["x0"], c["h1"], c["q"], src[0], err, reward, done,
+                                                            ag.gamma, src[1] if tr.sac else None, logp, alpha)
+            judge(cname + " dq" + sfx, c["dq"].view(-1), dq, dq_b, "dq" + sfx)
+            got_loss = float(parts[i].double().sum())
+            r = abs(got_loss - lo_) / lo_b
+            worst["loss parts" + sfx] = max(worst.get("loss parts" + sfx, 0.0), r)
+            loss_ref[sfx], loss_b[sfx] = loss_ref[sfx] + lo_, loss_b[sfx] + lo_b
+            for k, (off, got) in _slices(tr, cname, got_c).items():
+                ref, allowed = grads[k]
+                judge("%s d%s%s" % (cname, k, sfx), got, ref, allowed, "critic " + k + sfx)
+                covered[off:off + got.numel()] = True
     lo, hi = fl.critic_range
     assert int(torch.count_nonzero(got_c[lo:hi][~covered[lo:hi]])) == 0, "critic update: padding floats of its slice written"
     assert int(torch.count_nonzero(got_c[hi:])) == 0, "critic update: the actor's private slice or the multipliers written"
-    allowed = loss_b + float(mf.bound(parts.double().abs().sum(), parts.numel()))
-    r = abs(snap["loss_c"] - loss_ref) / allowed
-    worst["critic loss"] = r
-    if r > 1.0:
-        fails.append("critic loss %.9g vs %.9g: %.4g x the bound" % (snap["loss_c"], loss_ref, r))
-        assert not strict, fails[-1]
+    for sfx, _, _ in sources:
+        allowed = loss_b[sfx] + float(mf.bound(parts.double().abs().sum(), parts.numel()))
+        r = abs(snap["loss_c"] - loss_ref[sfx]) / allowed
+        worst["critic loss" + sfx] = r
+        if r > 1.0:
+            fails.append("critic loss%s %.9g vs %.9g: %.4g x the bound" % (sfx, snap["loss_c"], loss_ref[sfx], r))
+            assert not strict, fails[-1]
     if snap["gradmax_c"] is not None:
         assert snap["gradmax_c"] == float(got_c[lo:hi].abs().max()), ("critic gradmax", snap["gradmax_c"], float(got_c[lo:hi].abs().max()))
 
