@@ -5,6 +5,8 @@ logic of the trainers (loop cadence, flat parameter layout, optimiser order, log
 exercised by the CPU suite, and (b) a whole trainer driven by the oracle can be compared with the same trainer driven
 by the HIP kernels.  The product never imports this module; ``rpo_amd`` has no CPU fallback.
 """
+import copy
+
 import numpy as np
 import torch
 
@@ -182,6 +184,14 @@ class EvopfKernels(_EnvKernels):
         self.consts = np.asarray(consts, dtype=np.float32)
         C = CONST
         np.testing.assert_allclose(self.consts[C["RPO_EVOPF_C_YR"]:C["RPO_EVOPF_C_YR"] + 196].reshape(14, 14), oe.GRID.Yr, atol=1e-6)
+        # The Lagrangian's constraint bounds are the float32 table entries the kernels read: a margin a - hi of two float32 values
+        # is exact in float32, so against the case file's float64 bounds (half an eps32 of the bound away) a small violation would
+        # differ by more than any rounding of the kernel.
+        self.grid32 = copy.copy(oe.GRID)
+        for name, n in (("pmax", 5), ("pmin", 5), ("qmax", 5), ("qmin", 5), ("vmax", 14), ("vmin", 14)):
+            off = C["RPO_EVOPF_C_" + name.upper()]
+            np.testing.assert_allclose(self.consts[off:off + n], getattr(oe.GRID, name), rtol=1e-7, atol=1e-30)
+            setattr(self.grid32, name, self.consts[off:off + n].astype(np.float64))
 
     def reset(self, internal, obs, ep_len, ep_ret, ep_count, seed, env_id_base):
         n = internal.shape[0]
@@ -300,7 +310,8 @@ class EvopfKernels(_EnvKernels):
 
     def lagrangian(self, action, nu, scale, loss_out, grad_action, grad_nu, obs=None):
         s, a, v = _np(obs).astype(np.float64), _np(action).astype(np.float64), _np(nu).astype(np.float64)
-        g = oe.ineq_resid(s, a)
+        scale = float(np.float32(scale))                            # (a float argument of the kernel, as train_ops.lagrangian_* take it)
+        g = oe.ineq_resid(s, a, self.grid32)
         dist = np.maximum(g, 0.0)
         loss_out += float(scale * (dist @ v).sum())
         if grad_action is not None:

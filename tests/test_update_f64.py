@@ -222,8 +222,12 @@ def _trainer(algo, envname, backend=ob, seed=5, **kw):
 
 
 # every case of the GPU matrix the oracle backend can run (its launches are the generic chain)
-HARNESS_CASES = [("ddpg", "evopf256", dict(batch_size=64)),
-                 ("ddpg", "cart", {}), ("ddpg", "cart", dict(shared_param=False)), ("sac", "cart", {}),
+NJU = dict(batch_size=64, init_nju=0.1)
+EVOPF_SAC = [NJU, dict(batch_size=50, init_nju=0.1), dict(NJU, alpha=0.2), dict(NJU, automatic_entropy_tuning=True),
+             dict(batch_size=64), dict(batch_size=64, init_nju=0.0)]
+HARNESS_CASES = [("ddpg", "evopf256", dict(batch_size=64)), ("ddpg", "evopf256", dict(batch_size=50))] + \
+                [("sac", "evopf256", kw) for kw in EVOPF_SAC] + \
+                [("ddpg", "cart", {}), ("ddpg", "cart", dict(shared_param=False)), ("sac", "cart", {}),
                  ("ddpg", "pendulum", {}), ("sac", "pendulum", {}), ("ddpg", "cart_viol", {}), ("ddpg", "pendulum_viol", {}),
                  ("sac", "cart", dict(automatic_entropy_tuning=True)),
                  ("ddpg", "cart", dict(batch_size=250)), ("ddpg", "cart", dict(batch_size=100)), ("sac", "cart", dict(batch_size=250)),
@@ -244,7 +248,13 @@ def test_harness_on_the_oracle_backend(algo, envname, kw):
     last_losses within theirs, gradmax exact, the ambiguous rows of every comparison under AMBIG_CAP; the seeds are the GPU
     file's, so the cap is known to hold for them before a device is asked.  (The oracle backend's
     float32 is torch's on the CPU: the ratios say the harness is right, not how good a kernel is -- the worst gradient ratio of
-    any case is 0.005, d/d nu 0.16, the worst layer-local one 0.44, x0.)"""
+    any case is 0.005, d/d nu 0.16, the worst layer-local one 0.44, x0.)
+
+    EVOPF-v0: RPODDPG at 64 and at 50 rows (ragged against the 16 rows per workgroup of the head kernels and the row tile of
+    mlp_gemm), and RPOSAC (update_f64.evopf_sac_actor_chain) with non-zero multipliers at 64 and 50 rows, at alpha = 0.2, with
+    automatic_entropy_tuning, with build_trainer's own arguments (EVOPF_HP: init_nju = 0.1 as well) and with multipliers of
+    zero.  With init_nju given, at least one row violates and g_act, d/d nu in float64 and nju.weight.grad are not zero (42 of
+    50 rows violate after the five iterations at seed 5, the GPU file's).  Worst ratios there: gradients 0.03, d/d nu 0.04."""
     tr = _trainer(algo, envname, **kw)
     snap = uf.run_update(tr)
     assert snap["path"] == ("generic", "generic")
@@ -256,6 +266,16 @@ def test_harness_on_the_oracle_backend(algo, envname, kw):
         assert 0 < int(viol.sum()) < viol.size and float(np.abs(info["gnu"]).max()) > 0 and float(snap["grad_a"].abs().max()) > 0
     if kw.get("automatic_entropy_tuning"):
         assert "log_alpha" in worst and snap["log_alpha_grad"] != 0.0
+    if kw.get("init_nju"):
+        assert_multipliers_act(snap, info)
+
+
+def assert_multipliers_act(snap, info):
+    """Non-zero multipliers and a violated constraint: the Lagrangian's d/d action and d/d nu are not zero, in float64 and in
+    what the launches left."""
+    off = snap["nu_off"]
+    assert int(info["violating"].sum()) > 0 and float(np.abs(info["gnu"]).max()) > 0.0 and info["g_act"] > 0.0
+    assert float(snap["grad_a"][off[0]:off[1]].abs().max()) > 0.0
 
 
 # ================================================================================================================ planted errors
@@ -279,6 +299,12 @@ class _Plant(object):
                     dout[7] = 0.0
                 if plant.what == "padded_batch" and plant.armed:
                     dout *= n / (16.0 * ((n + 15) // 16))
+                if plant.what.startswith("logp_components") and plant.armed:
+                    # log pi(a'|s') with one of its 14 components left out of the sum ("crit.logp", dq_out and the loss
+                    # partials stay right: a second prologue on buffers of its own hands the backward its dq)
+                    lost = inner_td(self.q, self.qn1, self.qn2, self.logp - plant.logp_component(3), self.reward, self.done,
+                                    self.alpha, self.gamma, torch.zeros_like(self.dq_out), torch.zeros_like(self.loss_partial))
+                    dout = inner_td.apply(lost).clone()
                 return dout
         self.Td = Td
         self.armed = False
@@ -300,17 +326,34 @@ class _Plant(object):
     def arm(self, tr):
         """Switch the error on (after the warm-up iterations, which both runs share bit for bit)."""
         self.armed, self.tr = True, tr
-        if self.what == "lagrangian_da":
-            inner = tr.kernels.complete_bwd
+        B, k = tr.batch_size, tr.kernels
+        if self.what in ("lagrangian_da", "lagrangian_da_3way", "twin_da"):
+            inner = k.complete_bwd
 
             def complete_bwd(obs, grad_action, grad_ap, action=None):
-                g_act = tr.fused.buf("g_act", tr.batch_size, tr.kernels.action_dim)
+                if self.what == "twin_da":                       # ((da1 + da2) + g_act: the second critic's share never arrives)
+                    return inner(obs, grad_action - tr.fused.buf("da2", B, k.action_dim), grad_ap, action=action)
+                g_act = tr.fused.buf("g_act", B, k.action_dim)
                 return inner(obs, grad_action + (SCALE - 1.0) * g_act, grad_ap, action=action)   # (da + g_act: the Lagrangian's share scaled)
-            tr.kernels.complete_bwd = complete_bwd
+            k.complete_bwd = complete_bwd
+        if self.what.startswith("alpha_over_b_evopf"):           # (the state-dependent box: the head's backward is the env's own)
+            inner_head = k.gauss_head_bwd
+            k.gauss_head_bwd = lambda obs, raw, eps, dap, dlogp, draw: inner_head(obs, raw, eps, dap, dlogp * SCALE, draw)
+
+    def logp_component(self, j):
+        """Component j of log pi(a'|s') of the critic update that is running, [B] float32: from the heads, the draw and the batch
+        that launch read."""
+        tr = self.tr
+        B = tr.batch_size
+        next_state = tr.buffer.split(tr._batch)["next_state"]
+        head = uf.evopf_gauss(next_state, tr.fused.buf("crit.raw", B, 2 * tr.kernels.partial_dim), tr._noise_b)
+        return head["fw"]["logp"][:, j].float()
 
 
 PLANTS = [("dq_row", "ddpg", "cart", {}), ("lagrangian_da", "ddpg", "cart_viol", {}), ("shared_embedding", "ddpg", "cart", {}),
-          ("padded_batch", "ddpg", "cart", dict(batch_size=250)), ("alpha_over_b", "sac", "cart", {})]
+          ("padded_batch", "ddpg", "cart", dict(batch_size=250)), ("alpha_over_b", "sac", "cart", {})] + \
+         [(w, "sac", "evopf256", dict(NJU, alpha=0.2)) for w in ("twin_da", "lagrangian_da_3way", "alpha_over_b_evopf")] + \
+         [("logp_components", "sac", "evopf256", dict(NJU, alpha=0.2, gamma=0.05)), ("logp_components@0.01", "sac", "evopf256", dict(NJU, alpha=0.01))]
 GRAD_KEYS = ("critic ", "actor ", "shared ", "nu")
 
 
@@ -320,7 +363,7 @@ def _grad_ratio(worst):
 
 @pytest.mark.parametrize("what,algo,envname,kw", PLANTS, ids=[p[0] for p in PLANTS])
 def test_planted_errors_are_found_in_the_flat_gradient(what, algo, envname, kw):
-    """Five errors of the kind hand-written pipelines make, each planted into the backend proxy of an oracle-backend trainer
+    """Errors of the kind hand-written pipelines make, each planted into the backend proxy of an oracle-backend trainer
     behind the buffers the harness reads back, so that ONLY the flat-gradient check can see it -- and it must: the worst
     |err| / bound over the gradient slices goes above 1.  Beside it, the worst parameter shift after the optimiser steps of the
     same update against the unplanted run: what the post-Adam checks of the suite would have had to see, next to their
@@ -335,7 +378,52 @@ def test_planted_errors_are_found_in_the_flat_gradient(what, algo, envname, kw):
       shared_embedding  the critic's share of the shared embedding left out         0.0007 -> 583 (shared dbs) | 1.6e-4
       padded_batch      1 / B taken as 1 / (16 ceil(B / 16)) at B = 250             0.0007 -> 49 (actor dW0) | 3.0e-8
       alpha_over_b      RPOSAC: alpha / B of the Gaussian head's backward x (1 + 2^-8)   0.0017 -> 13 (actor dW1b) | 4.4e-6
+
+    RPOSAC on EVOPF-v0 (init_nju = 0.1, alpha = 0.2, 64 rows), the places where that update differs from everything above:
+
+      twin_da             the second critic's d/d action dropped from complete_bwd     0.03 -> 300 (actor dW1) | 1.7e-4
+      lagrangian_da_3way  the Lagrangian's share of the three-way add x (1 + 2^-8)      0.03 -> 5.1 (actor dW1) | 1.3e-5
+      alpha_over_b_evopf  alpha / B of the 14-wide head's backward x (1 + 2^-8)         0.03 -> 546 (actor dW1b) | 1.3e-5
+                          (printed beside it: the same error at the script's alpha = 0.001 lands at 0.022 -> 59, still found)
+      logp_components     one of the 14 components left out of log pi(a'|s') before Td  0.04 -> 78 (critic dW0) | 3.9e-6
+                          at gamma = 0.05.  At the trainer's default discount, 0.95, this error cannot be found by anything at
+                          alpha = 0.2: alpha log pi(a'|s') is 8.5 to 10.4 (log pi 42 to 52, a component -1.3 to 5.0) against
+                          rewards of -1 to -3 and q of -0.7, so every row's TD error is 8.6 to 11.7, beyond the Huber clamp, and
+                          stays above 7.6 whichever component is left out: dq is +-1 / B whatever log pi is, and the critic
+                          gradients of the planted and the unplanted run are equal bit for bit (printed beside it: 0.03 -> 0.03;
+                          the device shows the same saturation, a dq ratio of 0 in tests/test_update_f64_gpu.py's
+                          alpha = 0.2 case).  The plant needs rows inside the clamp, so this one trainer is built with
+                          gamma = 0.05: gamma alpha log pi is then about 0.5, of the size of the rewards, alpha and the
+                          multipliers as in the three above.
+      logp_components@0.01  the same error at gamma = 0.95 and alpha = 0.01, where rows are inside the clamp   0.02 -> 4.0 (critic dW0)
+                          (at the script's alpha = 0.001 it lands at 0.41: a 14th of alpha log pi is then 0.003 in a TD error
+                          of 0.5 to 2, inside the bound of the chain)
     """
+    runs = _planted_runs(what, algo, envname, kw)
+    clean, bad = runs[False][0], runs[True][0]
+    shift = float((runs[True][1] - runs[False][1]).abs().max())
+    print("planted %-16s gradient ratio %.3g -> %.3g (%s) | worst post-Adam parameter shift %.3g"
+          % (what, _grad_ratio(clean), _grad_ratio(bad), max((k for k in bad if k.startswith(GRAD_KEYS)), key=bad.get), shift))
+    assert _grad_ratio(clean) <= 1.0 and not runs[False][2]
+    # the buffer next to the planted stage is the unplanted launch's: only the gradient can tell
+    near = dict(dq_row="dq", padded_batch="dq", shared_embedding="dq", lagrangian_da="g_act", alpha_over_b="logp", twin_da="g_act",
+                lagrangian_da_3way="g_act", alpha_over_b_evopf="logp", logp_components="logp")[what.split("@")[0]]
+    assert bad[near] == clean[near] <= 1.0, (near, bad[near], clean[near])
+    if what.startswith("logp_components"):                       # (found by the critic slices; dq as the launch left it stays right)
+        assert bad["dq"] == clean["dq"] <= 1.0
+        critic = max(v for k, v in bad.items() if k.startswith("critic "))
+        assert critic > 1.0, "log pi(a'|s') less one component stays inside the critic slices' bound: %.3g (see the docstring)" % critic
+    assert _grad_ratio(bad) > 1.0, "the planted error stays inside the bound: %.3g" % _grad_ratio(bad)
+    if what == "logp_components":                                # (printed only: the same error at the default discount)
+        low = _planted_runs(what, algo, envname, {k: v for k, v in kw.items() if k != "gamma"})
+        print("planted %-16s at gamma = 0.95: gradient ratio %.3g -> %.3g" % (what, _grad_ratio(low[False][0]), _grad_ratio(low[True][0])))
+    if what == "alpha_over_b_evopf":                             # (printed only: the same error at the script's alpha)
+        low = _planted_runs(what, algo, envname, dict(kw, alpha=0.001))
+        print("planted %-16s at alpha = 0.001: gradient ratio %.3g -> %.3g" % (what, _grad_ratio(low[False][0]), _grad_ratio(low[True][0])))
+
+
+def _planted_runs(what, algo, envname, kw):
+    """{planted: (worst, parameters after the optimiser steps, fails)} of the same update without and with the error."""
     runs = {}
     for planted in (False, True):
         backend = _Plant(what)
@@ -347,15 +435,7 @@ def test_planted_errors_are_found_in_the_flat_gradient(what, algo, envname, kw):
         worst, info = uf.check_update(tr, snap, strict=False)
         tr._actor_step(snap["actor_out"])
         runs[planted] = (worst, torch.cat([tr.agent.flat.data.clone(), tr.agent.critic_target_flat.clone()]), info["fails"])
-    clean, bad = runs[False][0], runs[True][0]
-    shift = float((runs[True][1] - runs[False][1]).abs().max())
-    print("planted %-16s gradient ratio %.3g -> %.3g (%s) | worst post-Adam parameter shift %.3g"
-          % (what, _grad_ratio(clean), _grad_ratio(bad), max((k for k in bad if k.startswith(GRAD_KEYS)), key=bad.get), shift))
-    assert _grad_ratio(clean) <= 1.0 and not runs[False][2]
-    # the buffer next to the planted stage is the unplanted launch's: only the gradient can tell
-    near = dict(dq_row="dq", padded_batch="dq", shared_embedding="dq", lagrangian_da="g_act", alpha_over_b="logp")[what]
-    assert bad[near] == clean[near] <= 1.0, (near, bad[near], clean[near])
-    assert _grad_ratio(bad) > 1.0, "the planted error stays inside the bound: %.3g" % _grad_ratio(bad)
+    return runs
 
 
 # ================================================================================== the 256-wide networks (the default width)
@@ -595,4 +675,75 @@ def test_evopf_chain_equals_autograd_around_the_oracle_completion():
     worst = max(_rel(ch["grads"][k][0].reshape(gr.shape), gr) for k, gr in zip(keys, grads))
     wnu = _rel(torch.from_numpy(ch["gnu"][0]), dnu)
     print("evopf chain vs autograd around the oracle's completion: actor gradients %.3g, d/d nu %.3g" % (worst, wnu))
+    assert worst <= 8e-15 and wnu <= 2 * 2.0 ** -52
+
+
+def test_evopf_sac_chain_equals_autograd_around_the_oracle_completion():
+    """evopf_sac_actor_chain (RPOSAC on EVOPF-v0) against torch autograd of mean(alpha log pi - min(Q1, Q2)) + the Lagrangian term:
+    the SAC twin of the test above.  The squashed Gaussian is written out here in plain torch (14 components in the
+    state-dependent box, log pi summed over them), the two concatenating critics and the Lagrangian are differentiated by
+    autograd in the action, Complete's backward is oracle/evopf.py's (complete_partial_bwd), and autograd runs again from the
+    sampled ap and from log pi into the actor's two 14-wide heads.  alpha = 0.25 and B = 32, so alpha / B is a float32 value (the
+    chain rounds it as the kernel's argument).  Achieved: the actor gradients agree to 2.6e-16 of max |gradient|; asserted at the
+    tolerance of the test above (8e-15: the same two solves of the 22 x 22 system), d/d nu within two float64 roundings."""
+    import evopf_f64 as vf
+    from oracle import evopf as oe
+    B, g, alpha, hd = 32, torch.Generator().manual_seed(4), 0.25, 14
+    s32 = oe.reset(7, np.arange(B), np.zeros(B, np.int64)).astype(np.float32)
+    s64 = torch.from_numpy(s32.astype(np.float64))
+    actor = _Net("gauss", 57, 0, 61, n_out=2)
+    u = lambda *shape: (torch.rand(*shape, generator=g, dtype=F64) * 2 - 1) / 16      # noqa: E731
+    for w, b in (("W1", "b1"), ("W1b", "b1b")):
+        actor.leaf[w], actor.leaf[b] = u(hd, 256).requires_grad_(True), u(hd).requires_grad_(True)
+    b1b = actor.leaf["b1b"].detach() - 0.5                      # (log-stds around -3.5: a visible sample spread ...)
+    b1b[:2] += 2.5                                              # (... and two components beyond the upper clamp at -2)
+    actor.leaf["b1b"] = b1b.requires_grad_(True)
+    actor.ref = mf.Mlp64({k: v.detach() for k, v in actor.leaf.items()}, 57, 0, 128, 256, n_out=2, head_dim=hd)
+    cps = [{k: v.to(F64) for k, v in mf.make_params(("c", "cat", 57, 43, 128, 1, 1), 62 + k, zero_col=False).items()} for k in range(2)]
+    critics = [mf.Mlp64(cp, 57, 43, 128, 256, cat=True) for cp in cps]
+    lo, hi, scale, base, _, _ = hf.evopf_box(s32)
+    noise = torch.randn(B, hd, generator=g, dtype=F64).float()
+    x0a, h1a, m0, m1 = actor.masks(s64, None)
+    raw = actor(s64, None, m0, m1)
+    e = noise.to(F64)
+    lsr = raw[:, hd:] - 3.0
+    ls = torch.clamp(lsr, hf.LS_MIN, hf.LS_MAX)
+    assert 0 < int((lsr > hf.LS_MAX).sum()) < lsr.numel()
+    y = torch.tanh(raw[:, :hd] + e * ls.exp())
+    logp = (-0.5 * e * e - ls - hf.HALF_LOG_2PI - torch.log(scale * (1 - y * y) + 1e-6)).sum(1)
+    ap = torch.clamp(scale * y + base, min=lo, max=hi)
+    acts = oe.project(s32.astype(np.float64), ap.detach().numpy(), 0, 0.0, 1e-5, 0.0)[0].astype(np.float32)
+    a_var = torch.from_numpy(acts.astype(np.float64)).requires_grad_(True)
+    nu = (0.05 + 0.2 * torch.rand(58, generator=g)).float().numpy()
+    nu_t = torch.from_numpy(nu.astype(np.float64)).requires_grad_(True)
+    J = torch.from_numpy(oe.ineq_jac())
+    tab = vf.Tab(vf.B64E, vf.consts_table())                    # (the float32 table's bounds on both sides, as above)
+    resid = vf.val(vf.B64E, vf.ineq_resid(vf.B64E, tab, vf.cols(vf.B64E, s32), vf.cols(vf.B64E, acts)))
+    gv = a_var @ J.t() + (torch.from_numpy(resid) - a_var.detach() @ J.t())
+    viol = (gv > 0).detach()
+    assert 0 < int(viol.any(dim=1).sum())
+    qs, saved = [], []
+    for cp in cps:
+        x0c = torch.cat([s64 @ cp["Ws"].t() + cp["bs"], a_var @ cp["Wa"].t() + cp["ba"]], dim=1)
+        h1c = torch.relu(x0c) @ cp["W0"].t() + cp["b0"]
+        qs.append((torch.relu(h1c) @ cp["W1"].t() + cp["b1"]).view(-1))
+        saved.append((x0c.detach(), h1c.detach()))
+    w1 = ((qs[0] < qs[1]).to(F64) + 0.5 * (qs[0] == qs[1]).to(F64)).detach()
+    assert 0 < int(w1.sum()) < B                                # (both critics take rows)
+    lag = ((gv * viol) @ nu_t).mean()
+    ent = (alpha * logp).mean()
+    dl, dnu = torch.autograd.grad((-(w1 * qs[0] + (1 - w1) * qs[1])).mean() + lag, [a_var, nu_t])
+    jac = vf.dense_jac(vf.consts_table(), acts)[0]
+    jn = jac[:, oe.GRID.keep_constr][:, :, oe.GRID.newton_vars]
+    dz = torch.from_numpy(oe.complete_partial_bwd(dl.numpy(), jac, jn))
+    keys = sorted(actor.leaf)
+    grads = torch.autograd.grad([ap, ent], [actor.leaf[k] for k in keys], grad_outputs=[dz, torch.ones((), dtype=F64)])
+    ch = uf.evopf_sac_actor_chain(vf.consts_table(), actor.ref, critics, s64, x0a, h1a, raw.detach(), noise, torch.from_numpy(acts),
+                                  saved, w1, nu, alpha)
+    loss = float((ent + (-(w1 * qs[0] + (1 - w1) * qs[1])).mean() + lag).detach())
+    assert abs(loss - ch["loss"][0]) <= 1e-13 * max(1.0, abs(loss))
+    assert float((ch["logp"][0] - logp.detach()).abs().max()) <= 1e-12 and float((ch["ap"][0] - ap.detach()).abs().max()) <= 1e-14
+    worst = max(_rel(ch["grads"][k][0].reshape(gr.shape), gr) for k, gr in zip(keys, grads))
+    wnu = _rel(torch.from_numpy(ch["gnu"][0]), dnu)
+    print("evopf sac chain vs autograd around the oracle's completion: actor gradients %.3g, d/d nu %.3g" % (worst, wnu))
     assert worst <= 8e-15 and wnu <= 2 * 2.0 ** -52

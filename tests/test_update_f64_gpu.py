@@ -6,7 +6,8 @@ has happened and the ring holds data): flat.grad.zero_() and _critic_update | re
 Per case (update_f64.check_update): every element of the critic, shared and actor slices and of nju.weight.grad within its bound
 (FlatParams.offset), padding floats and the other optimiser's private slice exactly 0, last_losses within theirs, gradmax equal to
 max |slice| where the backward left it, the launches' intermediates (x0 / h1 / q / qn / dq, ap_det or the Gaussian heads and log pi,
-the completed actions, g_act; RPOSAC's log pi(a'|s') on every path) layer-locally within float64, ambiguous rows (relu(g), clip seams, min(Q1, Q2)) under AMBIG_CAP.
+the completed actions, g_act; RPOSAC's log pi(a'|s') on every path, on EVOPF-v0 the sampled ap' as well) layer-locally within
+float64, ambiguous rows (relu(g), clip seams, min(Q1, Q2)) under AMBIG_CAP.
 
 Paths, chosen with RPO_SCHEDULE and asserted per case: the generic launches, the row-tile pipelines (fused.hip), the column-split
 stages (nsplit.hip) with the front launches and with one launch per stage.  CartSafe's row-tile pipelines and split stages complete
@@ -25,11 +26,17 @@ gradient, land at 13 to 580):
     CartSafe, split, front / none    critic 0.026, shared 0.0002, actor 0.0004, losses 0.023, log_alpha 0.01
     SpringPendulum, every path       critic 0.00006, actor 0.0004 (split 0.0003), d nu 0.05, losses 0.0009
     *_viol, row-tile and split       critic 0.025 / 0.007, actor 0.0011 / 0.0026, d nu 0.0026 / 0.0013 (cart / pendulum)
-    EVOPF-v0, generic chain          critic 0.00002, actor 0.0009, d nu 0.027, losses 0.0003
+    EVOPF-v0 RPODDPG, generic chain  critic 0.00002, actor 0.0009, d nu 0.028, losses 0.0004 (64 rows and 50)
+    EVOPF-v0 RPOSAC, generic chain   critic 0.00003, actor 0.0015 (alpha = 0.2: 0.019, the log-std head), d nu 0.05, losses 0.0035
+                                     (alpha = 0.2: 0.010), log_alpha 0.01; log pi and log pi(a'|s') 0.06, the sampled ap and ap' 0.056,
+                                     g_act 0.26 (50 rows), the basic components of the completed actions equal to the head's ap.
+                                     At alpha = 0.2 every row's TD error lies beyond the Huber clamp (alpha log pi(a'|s') is about 10,
+                                     the rewards -1 to -3): dq is +-1 / B exactly, and the critic slices do not depend on log pi there;
+                                     at the script's alpha = 0.001 they do
     layer-local intermediates        x0 0.63, RPOSAC's sampled ap 0.28, completed actions 0.26, g_act 0.23, dq 0.21, log pi 0.18,
                                      log pi(a'|s') of the pipelines 0.0008 (its bound carries the heads' forward bound), the rest below 0.05
 Ambiguous rows per comparison: none for relu(g) and the clip seams, at most 0.4 % (one row of 256) for min(Q1, Q2); none left out.
-95 cases, 5.4 s; the slowest case 0.5 s.
+102 cases, 6.3 s; the slowest case 0.6 s.
 """
 import pytest
 import torch
@@ -136,14 +143,47 @@ def test_log_alpha_gradient(hip, monkeypatch, path):
     assert max(worst.values()) <= 1.0
 
 
-def test_evopf_flat_gradient_matches_float64(hip, monkeypatch):
+def _kw_id(kw):
+    return "-".join("%s=%s" % kv for kv in sorted(kw.items()))
+
+
+@pytest.mark.parametrize("kw", [dict(batch_size=64), dict(batch_size=50)], ids=_kw_id)
+def test_evopf_flat_gradient_matches_float64(hip, monkeypatch, kw):
     """RPODDPG on EVOPF-v0 at the script's network sizes (256 -> 256, a concatenating critic, a 14-wide actor head): the generic
     chain with the kernels' fused adds (rpo_evopf_lagrangian overwrites, rpo_evopf_complete_bwd adds the Lagrangian's d/d action),
-    a batch of 64."""
-    snap, worst, info = _case(hip, monkeypatch, "ddpg", "evopf256", "generic", dict(batch_size=64))
-    uf.report("ddpg evopf256 generic B=64", worst)
+    a batch of 64 and one of 50 (ragged against the 16 rows per workgroup of the head kernels and the row tile of mlp_gemm)."""
+    snap, worst, info = _case(hip, monkeypatch, "ddpg", "evopf256", "generic", kw)
+    uf.report("ddpg evopf256 generic B=%d" % kw["batch_size"], worst)
     assert getattr(hip.EvopfKernels, "fused_adds", False)
     assert 0 < int(info["violating"].sum()) and float(abs(info["gnu"]).max()) > 0.0
+    assert max(worst.values()) <= 1.0
+
+
+# (the cases of tests/test_update_f64.py, which runs them on the oracle backend first: the ambiguous shares are known there)
+NJU = dict(batch_size=64, init_nju=0.1)
+EVOPF_SAC = [NJU, dict(batch_size=50, init_nju=0.1), dict(NJU, alpha=0.2), dict(NJU, automatic_entropy_tuning=True),
+             dict(batch_size=64), dict(batch_size=64, init_nju=0.0)]
+
+
+@pytest.mark.parametrize("kw", EVOPF_SAC, ids=_kw_id)
+def test_evopf_sac_flat_gradient_matches_float64(hip, monkeypatch, kw):
+    """RPOSAC on EVOPF-v0 (scripts/evopf_exp_sac.py's sizes: 256 -> 256, two concatenating critics, two 14-wide actor heads) on
+    the generic chain, as the trainer composes it: the squashed-Gaussian head in the state-dependent box, log pi summed over 14
+    components into the TD prologue of both critics, rpo_min_q_bwd's split of -1 / B between the two mlp_gemm backward passes,
+    the three-way add (da1 + da2) + g_act inside rpo_evopf_complete_bwd, the head's backward with alpha / B.  Non-zero
+    multipliers (the Lagrangian's d/d action and d/d nu are not zero: asserted), 64 rows and a ragged 50, alpha = 0.2 beside
+    the script's 0.001 (where alpha / B d log pi is 1e-6 of the other terms), automatic_entropy_tuning, and multipliers of zero."""
+    snap, worst, info = _case(hip, monkeypatch, "sac", "evopf256", "generic", kw)
+    uf.report("sac evopf256 generic %s" % _kw_id(kw), worst)
+    assert getattr(hip.EvopfKernels, "fused_adds", False)
+    for key in ("ambiguous min", "ambiguous seam", "ambiguous relu(g)"):
+        assert worst[key] <= uf.AMBIG_CAP, (key, worst[key])
+    if kw.get("init_nju"):
+        off = snap["nu_off"]
+        assert int(info["violating"].sum()) > 0 and float(abs(info["gnu"]).max()) > 0.0 and info["g_act"] > 0.0
+        assert float(snap["grad_a"][off[0]:off[1]].abs().max()) > 0.0
+    if kw.get("automatic_entropy_tuning"):
+        assert "log_alpha" in worst and snap["log_alpha_grad"] != 0.0
     assert max(worst.values()) <= 1.0
 
 

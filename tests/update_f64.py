@@ -14,6 +14,8 @@ Nothing here is new arithmetic.  The chain composes the restatements the kernel 
              SAC: the same with heads_f64.gauss_head (forward and backward, alpha / B on log pi) and min(Q1, Q2)
              EVOPF-v0 (DDPG): evopf_f64.lagrangian, evopf_f64.complete_bwd_ref at the float64 Jacobian of the stored action,
              heads_f64.tanh_box on heads_f64.evopf_box
+             EVOPF-v0 (SAC): heads_f64.gauss_head on heads_f64.evopf_box (14 components, log pi their sum), min(Q1, Q2) of two
+             concatenating critics, (da1 + da2) + g in the kernel's association, the same completion backward, alpha / B
 
 The losses are the reference's (rpo_ddpg.py:307-337, rpo_sac.py:321-353):
     critic   mean Huber(Q(s, a) - (r + gamma (1 - d) Q_targ(s', a')))           SAC: min of the twin targets - alpha log pi(a'|s'),
@@ -433,15 +435,13 @@ def sac_actor_chain(env, actor, critics, state, x0a, h1a, raw, noise, box, actio
                 ap=(fw["ap"], hf.MARGIN * hf.C_REF_AP * hf.EPS32 * mags["ap"] + mf.TINY))
 
 
-def evopf_actor_chain(consts, actor, critic, state, x0a, h1a, raw, noise, eps_t, actions, x0c, h1c, nu, g_act=None):
-    """RPODDPG's policy step on EVOPF-v0 (the generic chain; the kernels add the Lagrangian's d/d action inside
-    rpo_evopf_complete_bwd) from the launches' raw actor outputs [n,14], noise and completed actions [n,43]: evopf_f64.lagrangian
-    -> Mlp64.backward of the (concatenating) critic -> evopf_f64.complete_bwd_ref at the float64 Jacobian of the stored action,
-    row by row -> heads_f64.tanh_box with heads_f64.evopf_box -> Mlp64.backward of the actor.  Returns ddpg_actor_chain's dict."""
+def _evopf_lagrangian(consts, s32, a32, nu, g_act=None):
+    """EVOPF-v0's Lagrangian term mean_b nu . relu(g(a_b)) at the launch's float32 states and completed actions
+    (evopf_f64.lagrangian): EnvRef.lagrangian's dict -- g (value, bound) [n,43], gnu (value, bound) [58], loss (value, bound),
+    ambiguous [n], violating [n], ratio [n] (the launch's ``g_act`` in units of the "lag_grad" tolerance).  A row with ambiguous
+    predicates takes the mask under which ``g_act`` agrees best (either value of an ambiguous mask: the launch's decision)."""
     import evopf_f64 as vf
-    B = state.shape[0]
-    s32, a32 = np.asarray(t64(state).numpy(), np.float32), np.asarray(t64(actions).numpy(), np.float32)
-    nu = np.asarray(nu, np.float32).reshape(-1)
+    B = s32.shape[0]
     with np.errstate(all="ignore"):
         c = vf.Tab(vf.B64E, consts)
         S, Ac = vf.cols(vf.B64E, s32), vf.cols(vf.B64E, a32)
@@ -465,20 +465,41 @@ def evopf_actor_chain(consts, actor, critic, state, x0a, h1a, raw, noise, eps_t,
         g_b = vf.tol_c("lag_grad") * ef.EPS32 * gm + ef.TINY
         gnu = np.array([float(x.v) for x in r["grad_nu"]])
         gnu_b = vf.tol_c("lag_sum") * ef.EPS32 * np.array([float(x.m) for x in r["grad_nu"]]) + ef.TINY
-        lag = dict(g=(gv, g_b), gnu=(gnu, gnu_b), ambiguous=amb.any(axis=1), violating=(mv > 0).any(axis=1), ratio=ratio,
-                   loss=(float(r["loss"].v), vf.tol_c("lag_sum") * ef.EPS32 * float(r["loss"].m) + ef.TINY))
+        return dict(g=(gv, g_b), gnu=(gnu, gnu_b), ambiguous=amb.any(axis=1), violating=(mv > 0).any(axis=1), ratio=ratio,
+                    loss=(float(r["loss"].v), vf.tol_c("lag_sum") * ef.EPS32 * float(r["loss"].m) + ef.TINY))
+
+
+def _evopf_complete_bwd(consts, a32, dl, dlm):
+    """evopf_f64.complete_bwd_ref row by row at the float64 Jacobian of the stored actions (evopf_f64.dense_jac): dl [n,43] the
+    summed d/d action, dlm its running bound in units of tol_c("cbwd") * eps32 -> (dap, bound) [n,14] as torch float64."""
+    import evopf_f64 as vf
+    n = a32.shape[0]
+    jv, jm = vf.dense_jac(consts, a32)
+    dap, dap_m = np.zeros((n, vf.NP)), np.zeros((n, vf.NP))
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            dap[i], dap_m[i] = vf.complete_bwd_ref(jv[i], jm[i], dl[i], dlm[i])
+    return torch.from_numpy(dap), torch.from_numpy(vf.tol_c("cbwd") * ef.EPS32 * dap_m + ef.TINY)
+
+
+def evopf_actor_chain(consts, actor, critic, state, x0a, h1a, raw, noise, eps_t, actions, x0c, h1c, nu, g_act=None):
+    """RPODDPG's policy step on EVOPF-v0 (the generic chain; the kernels add the Lagrangian's d/d action inside
+    rpo_evopf_complete_bwd) from the launches' raw actor outputs [n,14], noise and completed actions [n,43]: evopf_f64.lagrangian
+    -> Mlp64.backward of the (concatenating) critic -> evopf_f64.complete_bwd_ref at the float64 Jacobian of the stored action,
+    row by row -> heads_f64.tanh_box with heads_f64.evopf_box -> Mlp64.backward of the actor.  Returns ddpg_actor_chain's dict."""
+    import evopf_f64 as vf
+    B = state.shape[0]
+    s32, a32 = np.asarray(t64(state).numpy(), np.float32), np.asarray(t64(actions).numpy(), np.float32)
+    nu = np.asarray(nu, np.float32).reshape(-1)
+    lag = _evopf_lagrangian(consts, s32, a32, nu, g_act)
+    gv, g_b = lag["g"]
     q, q_abs, Lq = critic.head(h1c)
     dq = torch.full((B,), -1.0 / B, dtype=F64)
     da, da_b, _ = _critic_da([(critic, x0c, h1c)], state, actions, [(dq, U * dq.abs())], False, B)
     dl = da.numpy() + gv
     # (the running bound complete_bwd_ref takes is in units of tol_c * eps32: the incoming bounds in those units + the add's rounding)
     dlm = (da_b.numpy() + g_b) / (vf.tol_c("cbwd") * ef.EPS32) + np.abs(dl)
-    jv, jm = vf.dense_jac(consts, a32)
-    dap, dap_m = np.zeros((B, vf.NP)), np.zeros((B, vf.NP))
-    with np.errstate(all="ignore"):
-        for i in range(B):
-            dap[i], dap_m[i] = vf.complete_bwd_ref(jv[i], jm[i], dl[i], dlm[i])
-    dap, dap_b = torch.from_numpy(dap), torch.from_numpy(vf.tol_c("cbwd") * ef.EPS32 * dap_m + ef.TINY)
+    dap, dap_b = _evopf_complete_bwd(consts, a32, dl, dlm)
     lo, hi, scale, base, scale_mag, base_mag = hf.evopf_box(s32)
     o = t64(raw).view(B, vf.NP)
     nz = t64(noise).view(B, vf.NP)
@@ -498,6 +519,94 @@ def evopf_actor_chain(consts, actor, critic, state, x0a, h1a, raw, noise, eps_t,
     loss_b = lag["loss"][1] + float(qb.mean()) + float(mf.bound(q.abs().mean(), B + 16))
     return dict(grads=grads, gnu=lag["gnu"], loss=(loss, loss_b), lag=lag, do=(do, do_b), dap=(dap, dap_b), seam=seam.any(dim=1),
                 clipped=~inside, q=(q.view(-1), qb))
+
+
+def evopf_gauss(state, raw, noise, dap=None, dlogp=0.0):
+    """The 14-wide squashed-Gaussian head in EVOPF-v0's state-dependent box (heads_f64.gauss_head / gauss_mags at
+    heads_f64.evopf_box(state)) from the launch's raw heads [n,28] -- rpo_evopf_gauss_head's layout: the 14 means, then the 14
+    log-stds -- and the draw [n,14]: dict(fw, mags, box, ap (value, bound) [n,14], logp (value, bound) [n], args).  log pi is the
+    sum over the 14 components; its bound is every component's own plus the rounding of the float32 sum (a 16-lane butterfly:
+    four more additions), the form of tests/test_heads_gpu.py::test_evopf_gauss_head."""
+    n = state.shape[0]
+    s32 = np.asarray(t64(state).numpy(), np.float32)
+    lo, hi, scale, base, scale_mag, base_mag = hf.evopf_box(s32)
+    raw, e = t64(raw).view(n, -1), t64(noise).view(n, -1)
+    P = e.shape[1]
+    assert raw.shape[1] == 2 * P
+    args = (raw[:, :P], raw[:, P:], e, scale, base, lo, hi)
+    fw = hf.gauss_head(*args, dap=dap, dlogp=dlogp)
+    mags = hf.gauss_mags(*args[:5], dap=dap, dlogp=dlogp, scale_mag=scale_mag, base_mag=base_mag)
+    logp = fw["logp"].sum(1)
+    logp_b = hf.MARGIN * hf.C_REF_LOGP * hf.EPS32 * (mags["logp"].sum(1) + 4 * fw["logp"].abs().sum(1)) + mf.TINY
+    ap_b = hf.MARGIN * hf.C_REF_AP * hf.EPS32 * mags["ap"] + mf.TINY
+    return dict(fw=fw, mags=mags, box=(lo, hi, scale, base, scale_mag, base_mag), ap=(fw["ap"], ap_b), logp=(logp, logp_b), args=args)
+
+
+def evopf_sac_actor_chain(consts, actor, critics, state, x0a, h1a, raw, noise, actions, saved, w1, nu, alpha, g_act=None):
+    """RPOSAC's policy step on EVOPF-v0 (the generic chain; rpo_evopf_complete_bwd adds the second critic's and the Lagrangian's
+    d/d action itself) from the launches' raw heads [n,28], the policy step's own draw [n,14] and the completed actions [n,43]:
+
+        heads_f64.gauss_head in heads_f64.evopf_box(state)              ap [n,14], log pi [n] (summed over the 14 components)
+        evopf_f64.lagrangian at the stored actions                      the loss term, g = d/d action, d/d nu (_evopf_lagrangian)
+        Mlp64.head of both (concatenating) critics at those actions     min(Q1, Q2); its split w1 is the launch's (from its dq1)
+        Mlp64.backward of both with dq_k = w_k (-1 / B)                 da1, da2 (_critic_da)
+        (da1 + da2) + g                                                 the association include/rpo_hip.h states for
+                                                                        rpo_evopf_complete_bwd, one rounding per add
+        evopf_f64.complete_bwd_ref at the float64 Jacobian, row by row  d/d ap [n,14]
+        heads_f64.gauss_head backward with alpha / B on log pi          d/d (14 means, 14 log-stds) -> Mlp64.backward of the actor
+
+    critics: [critic1, critic2] (Mlp64); saved: [(x0, h1)] of both at the policy's actions.  Returns sac_actor_chain's dict."""
+    import evopf_f64 as vf
+    B = state.shape[0]
+    s32, a32 = np.asarray(t64(state).numpy(), np.float32), np.asarray(t64(actions).numpy(), np.float32)
+    nu = np.asarray(nu, np.float32).reshape(-1)
+    a_32 = hf.f32(alpha)
+    dlogp = hf.f32(a_32 / B)
+    # ---- the Gaussian head
+    head = evopf_gauss(state, raw, noise)
+    fw, (lo, hi, scale, base, scale_mag, base_mag) = head["fw"], head["box"]
+    logp, logp_b = head["logp"]
+    # ---- the Lagrangian and min(Q1, Q2)
+    lag = _evopf_lagrangian(consts, s32, a32, nu, g_act)
+    gv, g_b = lag["g"]
+    w1 = t64(w1).view(-1)
+    qs = [c.head(h1) for c, (x0, h1) in zip(critics, saved)]
+    qv = [q[0].view(-1) for q in qs]
+    qb = [mf.bound(q[1], q[2]).view(-1) for q in qs]
+    tie = (qv[0] - qv[1]).abs() <= qb[0] + qb[1]                 # min(Q1, Q2): either critic may have been the smaller one
+    # ---- the three-way add
+    dqs = [(w * (-1.0 / B), U * (w * (-1.0 / B)).abs()) for w in (w1, 1.0 - w1)]
+    das = [_critic_da([(c, x0, h1)], state, actions, [dq], False, B)[:2] for c, (x0, h1), dq in zip(critics, saved, dqs)]
+    d12 = (das[0][0] + das[1][0]).numpy()
+    dl = d12 + gv
+    # (complete_bwd_ref's running bound is in units of tol_c * eps32: the three incoming bounds in those units + the rounding of
+    #  each of the two adds)
+    dlm = (das[0][1].numpy() + das[1][1].numpy() + g_b) / (vf.tol_c("cbwd") * ef.EPS32) + np.abs(d12) + np.abs(dl)
+    # ---- backward through the completion and the head
+    dap, dap_b = _evopf_complete_bwd(consts, a32, dl, dlm)
+    back = evopf_gauss(state, raw, noise, dap=dap, dlogp=dlogp)
+    bw, bmag = back["fw"], back["mags"]
+    lin = hf.gauss_head(*head["args"], dap=dap_b, dlogp=0.0)     # |map| on the incoming bound
+    draw = torch.cat([bw["g_mean"], bw["g_ls"]], dim=1)
+    draw_b = torch.cat([hf.MARGIN * hf.C_REF_G_MEAN * hf.EPS32 * bmag["g_mean"] + lin["g_mean"].abs(),
+                        hf.MARGIN * hf.C_REF_G_LS * hf.EPS32 * bmag["g_ls"] + lin["g_ls"].abs()], dim=1) + mf.TINY
+    res = actor.backward(state, None, x0a, h1a, draw)
+    res_b = actor.backward(state, None, x0a, h1a, draw_b)
+    grads = {k: param_allowed(res, res_b, k, B) for k in mf.FIELDS if k in res}
+    # ---- loss and seams
+    qmin = torch.minimum(qv[0], qv[1])
+    term = a_32 * logp - qmin
+    term_b = abs(a_32) * logp_b + torch.maximum(qb[0], qb[1]) + 2 * U * (abs(a_32) * logp.abs() + qmin.abs())
+    loss = lag["loss"][0] + float(term.mean())
+    loss_b = lag["loss"][1] + float(term_b.mean()) + float(mf.bound(term.abs().mean(), B + 16))
+    mean, rls, e = head["args"][:3]
+    ls = rls - 3.0
+    pre = scale * torch.tanh(mean + e * torch.clamp(ls, hf.LS_MIN, hf.LS_MAX).exp()) + base
+    width = hf.EPS32 * (scale_mag + base_mag) * 8                # (the kernel computes the box itself: tests/test_heads_gpu.py)
+    a_seam = hf.near_seam(pre, lo, hi) | ((pre - lo).abs() <= width) | ((pre - hi).abs() <= width)
+    ls_seam = ((ls - hf.LS_MIN).abs() <= 8 * hf.EPS32 * 23) | ((ls - hf.LS_MAX).abs() <= 8 * hf.EPS32 * 3)
+    return dict(grads=grads, gnu=lag["gnu"], loss=(loss, loss_b), lag=lag, logp=(logp, logp_b), draw=(draw, draw_b),
+                dap=(dap, dap_b), seam=(a_seam | ls_seam).any(dim=1), tie=tie, q=list(zip(qv, qb)), ap=head["ap"])
 
 
 def noise_t(noise):
@@ -521,9 +630,10 @@ def _cpu(t):
     return t.detach().to("cpu").clone()
 
 
-def scratch(tr, *names):
-    """The first of the named ``fused.buf(...)`` buffers that exists with batch_size rows, as a CPU copy."""
-    B = tr.batch_size
+def scratch(tr, *names, **kw):
+    """The first of the named ``fused.buf(...)`` buffers that exists with batch_size rows (``rows=``: that many elements in one
+    of its dimensions -- the flat [B * P] buffers of a P-wide head), as a CPU copy."""
+    B = kw.get("rows", tr.batch_size)
     for name in names:
         hit = [v for k, v in tr.fused._scratch.items() if k[0] == name and B in k[1:]]
         if hit:
@@ -615,6 +725,7 @@ def run_update(tr, critic_only=False):
             _sync(tr)
             if not tr._pipelines:
                 rec["raw_next"] = scratch(tr, "crit.raw")
+                rec["ap_next"] = scratch(tr, "crit.ap", rows=tr.batch_size * tr.kernels.partial_dim).view(tr.batch_size, -1)
                 assert torch.equal(rec["eps_next"], _cpu(tr._noise_b).view(-1)), "the reproduced draw is not the update's"
         tr._iter_actor_step = None
         if critic_only:
@@ -633,8 +744,10 @@ def run_update(tr, critic_only=False):
                  g_act=scratch(tr, "g_act"))
         a["critic"] = [dict(x0=scratch(tr, c + ".x0"), h1=scratch(tr, c + ".h1")) for c, _ in names]
         if tr.sac:
-            a["raw"] = scratch(tr, "pi.raw")
+            a["raw"] = scratch(tr, "pi.raw")                      # [B, 2 P]: the P means, then the P log-stds (P = kernels.partial_dim)
             a["logp"] = scratch(tr, "pi.logp")
+            if not tr._actor_pipeline:
+                a["ap"] = scratch(tr, "pi.ap", rows=tr.batch_size * tr.kernels.partial_dim).view(tr.batch_size, -1)
             a["noise"] = _actor_noise(tr, ("act.noise" if split_a else "pi.noise",), tr._noise_pi)
             if split_a:                                          # (the split of min(Q1, Q2) from the head partials, as pol_c reads them)
                 q1, q2 = (split_head(scratch(tr, "split.part_q%d" % k), snap["params1"]["critic%d" % k]["b1"]) for k in (1, 2))
@@ -752,7 +865,16 @@ def check_update(tr, snap, strict=True, target_chain=False):
         net = net64(tr, p0, cname)
         forward_checks(net, state, action, c["x0"], c["h1"], c["q"], worst, cname)
         logp = rec.get("logp_next")
-        if tr.sac and i == 0 and "raw_next" in rec:             # log pi(a'|s'): the generic launches keep the heads it was taken from
+        if tr.sac and i == 0 and evopf:
+            # EVOPF-v0 (generic launches): the 28 heads at s', then log pi(a'|s') and the sampled ap' from those heads at the box of
+            # s' and the critic update's draw.  (The basic components of the next actions are the projected proposal: the
+            # completion and the projection are held by tests/test_evopf_f64_gpu.py.)
+            out, absval, L = net64(tr, p0, "actor").forward_bound(next_state)
+            judge("actor raw(s')", rec["raw_next"], out, mf.bound(absval, L), "raw")
+            hd = evopf_gauss(next_state, rec["raw_next"], rec["eps_next"])
+            judge("log pi(a'|s')", logp.view(-1), hd["logp"][0], hd["logp"][1], "logp")
+            judge("ap(s')", rec["ap_next"], hd["ap"][0], hd["ap"][1], "ap")
+        elif tr.sac and i == 0 and "raw_next" in rec:           # log pi(a'|s'): the generic launches keep the heads it was taken from
             out, absval, L = net64(tr, p0, "actor").forward_bound(next_state)
             judge("actor raw(s')", rec["raw_next"], out, mf.bound(absval, L), "raw")
             rn = rec["raw_next"].to(F64)
@@ -802,7 +924,20 @@ def check_update(tr, snap, strict=True, target_chain=False):
         forward_checks(net, state, a["actions"], sv["x0"], sv["h1"], None, worst, cname + "@pi")
     nu = snap["nu"].numpy()
     eps_t = hf.eps_schedule(tr.eps_start, tr.eps, tr.decay_value, snap["t"])
-    if tr.sac:
+    if tr.sac and evopf:
+        import evopf_f64 as vf
+        w1 = a["w1"].to(F64)
+        ch = evopf_sac_actor_chain(tr.kernels.consts, actor, crit64, state, a["x0"], a["h1"], a["raw"], a["noise"], a["actions"],
+                                   [(sv["x0"], sv["h1"]) for sv in a["critic"]], w1, nu, alpha, g_act=a["g_act"])
+        r, ab, L = actor.head(a["h1"])
+        mf.check("actor raw", a["raw"], r, ab, L, worst)
+        judge("log pi", a["logp"].view(-1), ch["logp"][0], ch["logp"][1], "logp")
+        judge("ap", a["ap"], ch["ap"][0], ch["ap"][1], "ap")
+        # (the basic components of the stored action are the head's sample -- _gauss emits finished actions, hence no noise and
+        #  no clip here; its Newton completion is held by tests/test_evopf_f64_gpu.py)
+        worst["actions"] = vf.check_proposal(tr.kernels.consts, state.numpy(), a["ap"].numpy(), None, vf.NOISE_NONE, False, 0.0, 0,
+                                             np.arange(B), snap["t"], a["actions"].numpy()[:, vf.PARTA])["act"]
+    elif tr.sac:
         w1 = a["w1"].to(F64)
         ch = sac_actor_chain(env, actor, crit64, state, a["x0"], a["h1"], a["raw"], a["noise"], box, a["actions"],
                              [(sv["x0"], sv["h1"]) for sv in a["critic"]], w1, nu, alpha, shared, g_act=a["g_act"])
@@ -811,6 +946,7 @@ def check_update(tr, snap, strict=True, target_chain=False):
         judge("log pi", a["logp"].view(-1), ch["logp"][0], ch["logp"][1], "logp")
         judge("ap", a["actions"][:, env.p], ch["ap"][0], ch["ap"][1], "ap")     # (the basic component: the Gaussian head's sample)
         worst["actions"] = env.check_actions(a["actions"].numpy(), a["actions"].numpy()[:, env.p], None, 0.0, box[2], box[3], state.numpy())
+    if tr.sac:
         _cap("min(Q1, Q2)", ch["tie"], worst, "min")
         decided = ~ch["tie"]
         want = (ch["q"][0][0] < ch["q"][1][0]).to(F64)
@@ -873,7 +1009,7 @@ def check_update(tr, snap, strict=True, target_chain=False):
         assert not strict, fails[-1]
     if snap["gradmax_a"] is not None:
         assert snap["gradmax_a"] == float(got_a[lo:hi].abs().max()), ("actor gradmax", snap["gradmax_a"], float(got_a[lo:hi].abs().max()))
-    info = dict(violating=ch["lag"]["violating"], gnu=gnu, fails=fails)
+    info = dict(violating=ch["lag"]["violating"], gnu=gnu, fails=fails, g_act=float(a["g_act"].abs().max()))
     return worst, info
 
 
