@@ -1029,6 +1029,24 @@ int rpo_evopf_opf_state(int n, const float* obs, int obs_stride, const float* pe
 int rpo_evopf_opf_free(int n, const float* obs, int obs_stride, const float* pe_cost, float* action_out, float* info_out, float tol,
                        int max_iters, const float* consts_dev, void* stream);
 
+/* The safety filter of EVOPF-v0 (EVOPFEnv.nearest_feasible, evaluate_filtered; a third instance of the same kernel; additive,
+ * RPO_ABI_VERSION stays 6): for each of n observations the dispatch NEAREST to a given action that meets eq_resid = 0 and all 58
+ * bounds of ineq_resid -- minimise 0.5 sum_k w_k (y_k - t_k)^2 over (pg, qg, vm, va, pe[5]) with the constraint set of
+ * rpo_evopf_opf_free, k over the 14 components the actor controls in the env's partial_actions order: pg of generators 1..4, vm at
+ * the five generator buses, pe[5].  target [n, >= 43] rows in the layout of an action (target_stride floats between rows); only
+ * those 14 components are read.  weight NULL: w_k = 1 / s_k^2 with s_k the half-width of the variable's own box in this problem (per
+ * row for pe), 0 where s_k <= 1e-6 -- the distance in box units; else a table of 14 floats per row in that order, weight_stride 0
+ * (one row for all) or 14, every value a finite number > 0 (anything else, like a NaN in the row's target or observation, ends
+ * that row as not converged at max_iters and touches no other row).  Same method, flat start (the target is NOT the start), stop
+ * test and signs as rpo_evopf_opf_free; action_out [n,43] the full action vector, info_out [n,4] = (the objective at exit, the
+ * largest of the three stop quantities at exit, iterations, converged 0 / 1).  A row's output does not depend on the other rows of
+ * the launch.  Reads obs, target, weight and consts_dev, writes the two outputs, nothing else.
+ * Refused before any HIP call, sizes before pointers: n <= 0, max_iters < 0, tol <= 0 (or NaN), obs_stride < 57, target_stride <
+ * 43, weight_stride neither 0 nor 14 (RPO_ERR_ARG); a NULL obs, target, action_out, info_out or consts_dev (RPO_ERR_NULL). */
+int rpo_evopf_nearest(int n, const float* obs, int obs_stride, const float* target, int target_stride, const float* weight,
+                      int weight_stride, float* action_out, float* info_out, float tol, int max_iters, const float* consts_dev,
+                      void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Fused pipelines of one RPO iteration (rpo_amd/csrc/fused.hip): the row-local stages chained
  * inside one workgroup of 16 rows, because at 4096 lanes / batch 256 every launch is dominated by dispatch + cold-start

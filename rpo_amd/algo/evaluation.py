@@ -62,6 +62,13 @@ with the single-step AC-OPF of the lane's observation in the policy's place (``_
 ``rpo_evopf_opf_free``, or of ``rpo_evopf_opf`` with idle batteries, straight into the env's action rows), a hard-feasible
 baseline whose per-episode differences to a policy's result are paired; ``opf_iters`` / ``opf_converged`` [episode, step].
 
+The safety filter (``evaluate_filtered(episodes, seed=...)`` -> ``EvalResult`` with ``path`` "filtered", EVOPF-v0 on a GPU only): the
+same loop and episodes with the trainer's own ``_eval_action`` (actor + GRG projection) followed by one launch of
+``rpo_evopf_nearest`` on that action -- the feasible dispatch nearest to what the policy asked for -- into the env's action rows;
+where the solve did not converge the step takes the policy's own action (``fallback="policy"``, a device select on the converged
+flag) or the solver's last iterate (``fallback="last"``); ``filter_iters`` / ``filter_converged`` / ``filter_distance`` [episode,
+step].  "policy", "policy + filter" and "OPF" on one seed are paired.
+
 Curve mode (trainer argument ``eval_episodes=N``): the training loop enqueues such an evaluation where it would call
 ``eval()`` and does not wait for it; ``CurveRunner`` below, results in ``trainer.eval_curve`` (``EvalCurve``).  Curve mode
 does not record trajectories and produces no per-constraint reports.  With the trainer argument ``keep_best`` every point's
@@ -96,7 +103,9 @@ class EvalResult(object):
     else None.  ``obs_noise``: the float32 sigma vector [obs_dim] of ``obs_noise=``, None for a clean evaluation.
     ``evaluate_opf`` (``path`` "opf"; ``proj_iters`` sums the solver's iterations): ``opf_iters`` int32 / ``opf_converged`` bool
     [episode, step], the solver's iteration count and stop flag of every live step (0 / False past the episode's end); None
-    otherwise.  ``days``: int array [episodes], the day of ``scenarios=`` every episode played; None without scenarios."""
+    otherwise.  ``evaluate_filtered`` (``path`` "filtered"; ``proj_iters`` sums the filter's iterations): ``filter_iters`` int32 /
+    ``filter_converged`` bool / ``filter_distance`` float32 [episode, step], the safety filter's iteration count, stop flag and
+    objective at exit of every live step (0 / False past the episode's end); None otherwise.  ``days``: int array [episodes], the day of ``scenarios=`` every episode played; None without scenarios."""
 
     FIELDS = ("ret", "length", "mean_ineq", "mean_eq", "max_ineq", "max_eq", "viol_steps", "proj_iters", "nonfinite")
 
@@ -117,6 +126,7 @@ class EvalResult(object):
         self.constraints = constraints
         self.obs_noise = None if obs_noise is None else np.array(obs_noise, dtype=np.float32)
         self.opf_iters = self.opf_converged = None               # evaluate_opf: [episode, step]
+        self.filter_iters = self.filter_converged = self.filter_distance = None   # evaluate_filtered: [episode, step]
         self.days = None                                         # scenarios=: int64 [episodes], the day each episode played
 
     @property
@@ -756,6 +766,74 @@ def evaluate_opf(tr, episodes=10, seed=None, horizon=None, init_states=None, rec
     log = log.cpu().numpy().transpose(1, 0, 2)
     res.opf_iters = np.where(live, log[:, :, 0], 0).astype(np.int32)
     res.opf_converged = live & (log[:, :, 1] > 0.5)
+    if want_con:
+        res.constraints = _constraint_report(tr, con.cpu().numpy(), res.length, v.viol_thresh)
+    if R:
+        res.trajectory = EvalTrajectory.from_trace(trace.cpu().numpy(), dims, res.length[:R], v.viol_thresh)
+    return res
+
+
+def evaluate_filtered(tr, episodes=10, seed=None, horizon=None, init_states=None, record=False, constraints=False, weight=None,
+                      tol=1e-4, max_iters=40, fallback="policy", eval_steps=None, eval_lr=None, scenarios=None):
+    """See ``RPOTrainerBase.evaluate_filtered``."""
+    if fallback not in ("policy", "last"):
+        raise ValueError("evaluate_filtered: fallback must be 'policy' (a step whose solve did not converge takes the policy's own "
+                         "action) or 'last' (the solver's last iterate), got %r" % (fallback,))
+    env = tr.base_env
+    if getattr(tr.kernels, "name", None) != "EVOPF-v0" or not hasattr(env, "nearest_feasible"):
+        raise NotImplementedError("evaluate_filtered: the safety filter is the nearest-feasible solve of EVOPF-v0; this trainer's "
+                                  "env is %s" % getattr(tr.kernels, "name", type(env).__name__))
+    fn = env._nearest_kernel()                                   # NotImplementedError: oracle backend, CPU device
+    tol, iters_cap = float(tol), int(max_iters)
+    if not tol > 0.0 or iters_cap != max_iters or iters_cap < 0:
+        raise ValueError("evaluate_filtered: tol must be > 0 and max_iters an integer >= 0, got %r and %r" % (tol, max_iters))
+    n = check_episodes(episodes)
+    scenario, days = check_scenarios(tr, scenarios, n, "evaluate_filtered")
+    want_con = check_constraints(constraints)
+    kw = {}
+    if eval_steps is not None or eval_lr is not None:
+        kw["eval_steps"], kw["eval_lr"] = check_budget(tr, eval_steps, eval_lr, "evaluate_filtered")
+    R = check_record(record, n)
+    H = check_horizon(tr, horizon, "evaluate_filtered")
+    k = tr.kernels
+    idx = torch.as_tensor(np.asarray(env.partial_actions), dtype=torch.int64, device=tr.device)
+    dims = (k.obs_dim, int(idx.numel()), k.action_dim)
+    if R:
+        nbytes = 4 * H * R * hip_ops.trace_layout(*dims)[1]
+        if nbytes > hip_ops.TRACE_MAX_BYTES:
+            raise ValueError("evaluate_filtered: record=%r needs a trace buffer of %d bytes, above the cap of %d bytes; record "
+                             "fewer episodes (record=k)" % (record, nbytes, hip_ops.TRACE_MAX_BYTES))
+    weight = env._check_weight(weight, n, "evaluate_filtered")
+    init_states = check_init_states(tr, init_states, n, "evaluate_filtered")
+    seed = fresh_seed(tr) if seed is None else int(seed)
+    v = _initial_env(tr, n, seed, init_states, scenario)
+    acc = torch.zeros(n, 8, device=tr.device)
+    trace = torch.zeros(H, R, hip_ops.trace_layout(*dims)[1], device=tr.device) if R else None
+    con = torch.empty(n, hip_ops.con_width(k.ineq_num, k.eq_num), device=tr.device) if want_con else None
+    info = torch.empty(n, 4, device=tr.device)
+    policy = torch.empty_like(v.action)                          # the policy's own action of the step: the filter's target
+    log = torch.zeros(H, n, 4, device=tr.device)                 # the filter's info row of every step's launch
+
+    def producer(v, iters, step):
+        # the trainer's deterministic action + GRG projection, then one launch that moves it to the nearest feasible dispatch
+        tr._eval_action(v, iters=iters, **kw)
+        policy.copy_(v.action)
+        fn(k, v.obs, policy, weight, v.action, info, tol, iters_cap)
+        if fallback == "policy":                                 # a select on the device: no host decision
+            v.action.copy_(torch.where(info[:, 3:4] > 0.5, v.action, policy))
+        iters.copy_(info[:, 2])
+        log[step].copy_(info)
+        return policy.index_select(1, idx) if R else None        # (the proposal is read by the record alone)
+
+    with torch.no_grad():
+        _run_stepwise(tr, v, acc, H, trace=trace, con=con, producer=producer)
+    res = EvalResult(acc.cpu().numpy(), "filtered", H, seed)
+    res.days = days
+    live = np.arange(H)[None, :] < res.length[:, None]           # filled while the episode is live
+    log = log.cpu().numpy().transpose(1, 0, 2)
+    res.filter_iters = np.where(live, log[:, :, 2], 0).astype(np.int32)
+    res.filter_converged = live & (log[:, :, 3] > 0.5)
+    res.filter_distance = np.where(live, log[:, :, 0], 0).astype(np.float32)
     if want_con:
         res.constraints = _constraint_report(tr, con.cpu().numpy(), res.length, v.viol_thresh)
     if R:

@@ -1668,6 +1668,26 @@ class RPOTrainerBase(object):
         return evaluate_opf(self, episodes=episodes, seed=seed, horizon=horizon, init_states=init_states, record=record,
                             constraints=constraints, pe=pe, pe_cost=pe_cost, tol=tol, max_iters=max_iters)
 
+    def evaluate_filtered(self, episodes=10, seed=None, horizon=None, init_states=None, record=False, constraints=False,
+                          weight=None, tol=1e-4, max_iters=40, fallback="policy", eval_steps=None, eval_lr=None, scenarios=None):
+        """The policy behind the safety filter on ``evaluate()``'s episodes -> ``EvalResult`` with ``path == "filtered"``: at every
+        step the trainer's own evaluation action (deterministic actor + GRG projection, ``eval_steps`` / ``eval_lr`` as in
+        ``evaluate()``) is replaced by the feasible dispatch nearest to it (``EVOPFEnv.nearest_feasible``: one launch of
+        rpo_evopf_nearest into the env's action rows; ``weight``, ``tol``, ``max_iters`` are its).  EVOPF-v0 on a GPU only
+        (NotImplementedError elsewhere, with the reason).  ``episodes``, ``seed``, ``horizon``, ``init_states``, ``record``,
+        ``constraints`` and ``scenarios`` are ``evaluate()``'s: the same ``seed`` gives the same days and initial states of charge
+        as ``evaluate(seed=)`` and ``evaluate_opf(seed=)``, so "policy", "policy + filter" and "OPF" are paired per episode.  A step
+        whose solve did not converge (infeasible single-step problems exist) takes the policy's own action with
+        ``fallback="policy"`` -- a select on the device, not a host decision -- or the solver's last iterate with
+        ``fallback="last"``; there is no host synchronisation inside the loop.  ``result.filter_iters`` /
+        ``result.filter_converged`` / ``result.filter_distance`` [episode, step]; ``proj_iters`` sums the filter's iterations.  The
+        record's ``proposal`` is what the filter was given (the policy's action at ``env.partial_actions``), ``action`` what the
+        env stepped.  No trainer state changes."""
+        from .evaluation import evaluate_filtered
+        return evaluate_filtered(self, episodes=episodes, seed=seed, horizon=horizon, init_states=init_states, record=record,
+                                 constraints=constraints, weight=weight, tol=tol, max_iters=max_iters, fallback=fallback,
+                                 eval_steps=eval_steps, eval_lr=eval_lr, scenarios=scenarios)
+
     def pretrain(self, demos, steps=1000, batch_size=None, lr=None, seed=None, weights=None, clip=0.98, sync_targets=True,
                  idx=None):
         """Clone the actor from ``demos`` (``Demonstrations``: observations and the demonstrated basic actions, e.g.

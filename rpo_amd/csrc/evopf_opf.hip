@@ -58,6 +58,11 @@ struct OpfArgs {
     const float* consts;
     const float* state_in;    // [n, RPO_EVOPF_OPF_STATE] or NULL (the flat start)
     float* state_out;         // [n, RPO_EVOPF_OPF_STATE] or NULL
+    // the nearest-feasible instance alone (behind everything else: the other instances' arguments stay where they were)
+    const float* target;      // [n, >= 43] rows in the layout of an action; the 14 controlled components are read
+    int target_stride;
+    const float* weight;      // [14] (weight_stride 0), [n, 14] (weight_stride 14) or NULL (1 / half-width^2 of the variable's box)
+    int weight_stride;
 };
 // a row of the state: action[43] | lambda[28] | z_u[24] | z_l[24] | mu_u[24] | mu_l[24] | gamma, the bounded variables in the
 // order pg[5], qg[5], vm[14]
@@ -71,6 +76,9 @@ __device__ __forceinline__ int bus_of_battery(int j) {
     return j == 4 ? 7 : (j == 3 ? 5 : j);
 }
 
+// bus -> its generator, -1 at a load bus; literals for the same reason
+__device__ __forceinline__ int gen_of_bus(int b) { return b == 7 ? 4 : (b == 5 ? 3 : (b <= 2 ? b : -1)); }
+
 // FREE_PE: the battery power is a variable too (rpo_evopf_opf_free).  pe_j enters g like pg_j -- linearly, in the real-power
 // equation of bus kSpv[j] alone, with d g / d pe = +1 (eq_resid adds pg + pe; NOT jac_entry's -1, the reference's eq_jac sign,
 // DESIGN hazard E1) -- has no Hessian and a box, battery_bounds(soc) of the row's observation: it is eliminated by hand like the
@@ -80,7 +88,16 @@ __device__ __forceinline__ int bus_of_battery(int j) {
 // - g_e; after the solve lane NK + j reads dlambda_e from w.vec and forms dpe = (-N_pe - dlambda_e) / D_pe.  58 inequalities.
 // No state seam (state_in / state_out are not read).  The FREE_PE = false instance is the kernel as it stood, instruction for
 // instruction: every addition below folds away on a compile-time false.
-template <bool FREE_PE>
+//
+// NEAREST (with FREE_PE: its variables and its 58 bounds, unchanged): the safety filter, rpo_evopf_nearest.  The objective is
+// 0.5 sum_k w_k (y_k - t_k)^2 over the 14 components the actor controls (pg of generators 1..4, vm at the five generator buses,
+// pe[5]) in place of the generation cost -- every one of them a bounded variable a lane already owns.  pg and pe are eliminated by
+// hand, so the objective enters through their c2 = w (D = w + Sigma) and L_x = w (x - t) + lambda_e + (mu_u - mu_l); a vm lane of
+// a generator bus adds w to its diagonal entry and w (x - t) to its L_x.  w: the row of the weight table, or 1 / s^2 with s the
+// half-width of the lane's own box (hi, lo above; per row for pe), 0 where s <= 1e-6.  A weight that is not a finite number > 0
+// becomes a NaN, which ends its row "not converged" like a NaN in the target or the observation.  The start stays the flat one.
+// info[0] is the objective at exit.  The other two instances fold every line of it away.
+template <bool FREE_PE, bool NEAREST = false>
 __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs p) {
     __shared__ Ws wss[kOpfWaves];
     Ws& w = wss[threadIdx.x / RPO_WAVE];
@@ -116,11 +133,29 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
     else if (is_pg) { hi = w.c[RPO_EVOPF_C_PMAX + gen]; lo = w.c[RPO_EVOPF_C_PMIN + gen]; }
     else if (has_u) { hi = w.c[RPO_EVOPF_C_QMAX + gen]; lo = w.c[RPO_EVOPF_C_QMIN + gen]; }
     else if (is_pe) battery_bounds(w.s[2 * NB + bat], hi, lo);
+    // nearest: the lane's place among the 14 controlled components (the env's partial_actions order), its target and weight
+    float tk = 0.0f, wq = 0.0f;
+    bool ctrl = false;
+    if constexpr (NEAREST) {
+        const int vgen = gen_of_bus(vbus);
+        const int k = (is_pg && gen >= 1) ? gen - 1 : ((is_vm && vgen >= 0) ? NG - 1 + vgen : (is_pe ? 2 * NG - 1 + bat : -1));
+        ctrl = k >= 0;
+        if (ctrl) {
+            tk = p.target[(size_t)i * p.target_stride + xidx];
+            if (p.weight) {
+                const float v = p.weight[(size_t)i * p.weight_stride + k];
+                wq = (v > 0.0f && v < __builtin_inff()) ? v : __builtin_nanf("");
+            } else {
+                const float half = 0.5f * (hi - lo);
+                wq = half > 1e-6f ? 1.0f / (half * half) : 0.0f;
+            }
+        }
+    }
     const int bidx = is_vm ? 2 * NG + vbus : (is_pg ? gen : NG + gen);    // the lane's bounded variable in the state row's order
-    const float c2 = is_pg ? 2.0f * w.c[RPO_EVOPF_C_QUAD + gen] : 0.0f;
+    const float c2 = NEAREST ? (elim ? wq : 0.0f) : (is_pg ? 2.0f * w.c[RPO_EVOPF_C_QUAD + gen] : 0.0f);
     // linear cost: pe_cost_j of the battery lanes, by default what the env's reward charges for a unit of pe in units of obj_fn
-    const float c1 = is_pg ? w.c[RPO_EVOPF_C_LIN + gen]
-                           : (is_pe ? (p.pe ? p.pe[(size_t)i * NE + bat] : (kWe / kWg) * w.s[2 * NB + NE]) : 0.0f);
+    const float c1 = NEAREST ? 0.0f : (is_pg ? w.c[RPO_EVOPF_C_LIN + gen]
+                           : (is_pe ? (p.pe ? p.pe[(size_t)i * NE + bat] : (kWe / kWg) * w.s[2 * NB + NE]) : 0.0f));
 
     // ---- flat start
     {
@@ -161,7 +196,7 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         const float dmu = mu_u - mu_l;
         // generator variable of an equation lane: L_x, D, N of that variable; its column is eliminated into the lane's diagonal
         const float lam_e = w.dir[e], g_e = is_eq ? w.eq[e] : 0.0f;
-        const float lxu = elim ? (c2 * x + c1) + lam_e + dmu : 0.0f;
+        const float lxu = elim ? (NEAREST ? c2 * (x - tk) : c2 * x + c1) + lam_e + dmu : 0.0f;   // (nearest: the difference first, it is small)
         const float du = elim ? c2 + sig : 1.0f;
         const float nu = lxu + nbar;
         const float kdiag = has_u ? -1.0f / du : 0.0f;
@@ -202,7 +237,7 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
                 const bool same = vbus == n;
                 if (is_vm) v = col_vm ? -csn[n] : (same ? -dv : vmag[n] * ddn[n]);
                 else v = col_vm ? -((same ? dv : 0.0f) + vm_m * ddn[n]) : (same ? vm_m * csv : 0.0f) - vm_m * vmag[n] * csn[n];
-                if (is_vm && tid == c) v += sig;
+                if (is_vm && tid == c) v += NEAREST ? sig + wq : sig;
             } else if (is_eq) {
                 v = jac_entry(w, e, var);
             }
@@ -220,7 +255,7 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
             }
             row[c] = v;
         }
-        const float lxv = is_var ? jtl + (is_vm ? dmu : 0.0f) : 0.0f;          // L_x of the voltage unknown
+        const float lxv = is_var ? jtl + (is_vm ? (NEAREST ? dmu + wq * (x - tk) : dmu) : 0.0f) : 0.0f;   // L_x of the voltage unknown
         const float nv = lxv + (is_vm ? nbar : 0.0f);
         row[NK] = is_var ? -nv : (is_eq ? (has_u ? nu / du - g_e : -g_e) : 0.0f);
         if constexpr (FREE_PE) {
@@ -280,7 +315,11 @@ __global__ __launch_bounds__(RPO_WAVE * kOpfWaves) void evopf_opf_kernel(OpfArgs
         const float pg = w.a[PG0 + tid];
         part = w.c[RPO_EVOPF_C_QUAD + tid] * pg * pg + w.c[RPO_EVOPF_C_LIN + tid] * pg;
     }
-    const float cost = rpo_wave_sum_rows(part) + w.c[RPO_EVOPF_C_CONST];
+    float cost = rpo_wave_sum_rows(part) + w.c[RPO_EVOPF_C_CONST];
+    if constexpr (NEAREST) {
+        const float d = w.a[xidx] - tk;
+        cost = rpo_wave_sum_rows(ctrl ? 0.5f * wq * d * d : 0.0f);
+    }
     if (tid < NY) p.action[(size_t)i * NY + tid] = w.a[tid];
     if (tid < 4) p.info[(size_t)i * 4 + tid] = tid == 0 ? cost : (tid == 1 ? resid : (tid == 2 ? (float)it : (converged ? 1.0f : 0.0f)));
     if (!FREE_PE && p.state_out) {                                     // the state the stop test was last evaluated on
@@ -307,7 +346,7 @@ extern "C" int rpo_evopf_opf_state(int n, const float* obs, int obs_stride, cons
                                    void* stream) {
     if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < 2 * NB || (state_in && pe)) return RPO_ERR_ARG;
     if (!obs || !action_out || !info_out || !consts_dev) return RPO_ERR_NULL;
-    const OpfArgs args{n, obs, obs_stride, pe, action_out, info_out, tol, max_iters, consts_dev, state_in, state_out};
+    const OpfArgs args{n, obs, obs_stride, pe, action_out, info_out, tol, max_iters, consts_dev, state_in, state_out, nullptr, 0, nullptr, 0};
     return launch(evopf_opf_kernel<false>, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
 }
 
@@ -315,6 +354,17 @@ extern "C" int rpo_evopf_opf_free(int n, const float* obs, int obs_stride, const
                                   float tol, int max_iters, const float* consts_dev, void* stream) {
     if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < NS) return RPO_ERR_ARG;
     if (!obs || !action_out || !info_out || !consts_dev) return RPO_ERR_NULL;
-    const OpfArgs args{n, obs, obs_stride, pe_cost, action_out, info_out, tol, max_iters, consts_dev, nullptr, nullptr};
+    const OpfArgs args{n, obs, obs_stride, pe_cost, action_out, info_out, tol, max_iters, consts_dev, nullptr, nullptr, nullptr, 0, nullptr, 0};
     return launch(evopf_opf_kernel<true>, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
+}
+
+extern "C" int rpo_evopf_nearest(int n, const float* obs, int obs_stride, const float* target, int target_stride, const float* weight,
+                                 int weight_stride, float* action_out, float* info_out, float tol, int max_iters,
+                                 const float* consts_dev, void* stream) {
+    if (n <= 0 || max_iters < 0 || !(tol > 0.0f) || obs_stride < NS || target_stride < NY || (weight_stride != 0 && weight_stride != NP))
+        return RPO_ERR_ARG;
+    if (!obs || !target || !action_out || !info_out || !consts_dev) return RPO_ERR_NULL;
+    const OpfArgs args{n, obs, obs_stride, nullptr, action_out, info_out, tol, max_iters, consts_dev, nullptr, nullptr, target, target_stride,
+                       weight, weight_stride};
+    return launch(evopf_opf_kernel<true, true>, dim3((n + kOpfWaves - 1) / kOpfWaves), RPO_WAVE * kOpfWaves, 0, stream, args);
 }

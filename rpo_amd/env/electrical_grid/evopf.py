@@ -18,8 +18,10 @@ the reference's method of that name (there: pypower's interior-point OPF, one st
 ``EvalTrajectory.opf_gap(env)`` (rpo_amd/algo/evaluation.py) the optimality gap of a recorded evaluation.  ``opf(state,
 pe="free")`` dispatches the batteries too: it minimises ``obj_fn + pe_cost . pe`` over all 43 components with the battery box of
 the row's state of charge, by default at the price that makes the optimum the best one-step reward (``reward_fn``); it is the
-controller of ``trainer.evaluate_opf`` and the reference of ``opf_gap(pe="free")``.  There is no CPU path: on the oracle backend or
-a CPU device all of these raise NotImplementedError with that reason.
+controller of ``trainer.evaluate_opf`` and the reference of ``opf_gap(pe="free")``.  ``nearest_feasible(obs, action)`` is the safety
+filter: the dispatch nearest to a policy's action, in its 14 controlled components, that meets the same equations and bounds (a
+third instance of that kernel; ``NearestResult``; ``trainer.evaluate_filtered`` plays whole episodes through it).  There is no CPU
+path: on the oracle backend or a CPU device all of these raise NotImplementedError with that reason.
 """
 import numpy as np
 import torch
@@ -306,6 +308,15 @@ class EVOPFEnv(HardConstraintEnv):
                                       "kernel rpo_evopf_opf_free only")
         return fn
 
+    def _nearest_kernel(self):
+        """The backend's nearest-feasible kernel (the safety filter), or NotImplementedError with the reason there is none."""
+        self._opf_kernel()
+        fn = getattr(self._backend, "evopf_nearest", None)
+        if fn is None:
+            raise NotImplementedError("this backend has no evopf_nearest kernel: the safety filter exists as the HIP kernel "
+                                      "rpo_evopf_nearest only")
+        return fn
+
     # ------------------------------------------------------------------------------------------ scenarios
     def scenarios(self, n, seed=0, env_id_base=0, episode=0):
         """The ``Scenarios`` (scenarios.py) that lanes ``env_id_base .. env_id_base + n - 1`` are dealt under ``seed`` in episode
@@ -452,6 +463,85 @@ class EVOPFEnv(HardConstraintEnv):
         Y[~res["converged"]] = np.nan
         return Y, total, total / X.shape[0]
 
+    # ------------------------------------------------------------------------------------------ safety filter
+    def _check_weight(self, weight, n, what):
+        """``weight`` of the safety filter -> None or a contiguous float32 device tensor [14] / [n, 14].  Values given on the
+        host are checked here (finite and > 0: ValueError); a device tensor's are not read -- the kernel ends a row whose
+        weights are not finite numbers > 0 as not converged."""
+        if weight is None:
+            return None
+        P = len(self._partial_actions)
+        on_device = isinstance(weight, torch.Tensor) and weight.device.type != "cpu"
+        if not on_device:
+            host = np.asarray(weight.detach().numpy() if isinstance(weight, torch.Tensor) else weight, dtype=np.float64)
+            if not (np.all(np.isfinite(host)) and np.all(host > 0)):
+                raise ValueError("%s: weight must hold finite numbers > 0" % what)
+        weight = self._t(weight).to(torch.float32)
+        if tuple(weight.shape) not in ((P,), (n, P)):
+            raise ValueError("%s: weight must be None, [%d] or [%d, %d], got %s" % (what, P, n, P, tuple(weight.shape)))
+        return weight.contiguous()
+
+    def nearest_feasible(self, obs, action, weight=None, tol=1e-4, max_iters=40, out=None):
+        """The safety filter: for every row the dispatch nearest to ``action`` that meets the power-flow equations and all 58
+        bounds, on the device (rpo_evopf_nearest, a third instance of the interior-point kernel of ``opf``).
+
+        ``obs`` [n, 57] observations; ``action`` [n, 43] actions, [n, 14] in ``partial_actions`` order, or an ``ActResult`` (its
+        ``action``).  Minimises ``0.5 * sum_k w_k (y_k - t_k)^2`` over the 14 components the actor controls (pg at the four
+        non-slack generators, vm at the five generator buses, pe) subject to ``eq_resid = 0`` and the bounds of ``ineq_resid``;
+        the equations fix every other component.  ``weight`` None: ``w_k = 1 / s_k^2`` with s_k the half-width of the variable's
+        box (per row for pe: ``battery_bounds``), the distance in box units that ``pretrain`` uses; else [14] or [n, 14], finite
+        and > 0.  Same method, flat start (not the target), ``tol`` and ``max_iters`` as ``opf``; an infeasible single-step problem
+        ends with ``converged`` False.  Returns a ``NearestResult`` of device tensors; nothing synchronises with the host.
+        ``out``: an earlier result of the same n, whose buffers are reused."""
+        fn = self._nearest_kernel()
+        tol, iters = float(tol), int(max_iters)
+        if not tol > 0.0 or iters != max_iters or iters < 0:
+            raise ValueError("nearest_feasible: tol must be > 0 and max_iters an integer >= 0, got %r and %r" % (tol, max_iters))
+        obs = self._t(obs)
+        if obs.dim() == 1:
+            obs = obs.view(1, -1)
+        if obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != self.state_dim:
+            raise ValueError("nearest_feasible: obs must be [n, %d] observations, got %s" % (self.state_dim, tuple(obs.shape)))
+        if obs.stride(1) != 1:
+            obs = obs.contiguous()
+        n, P = obs.shape[0], len(self._partial_actions)
+        if not isinstance(action, (torch.Tensor, np.ndarray, list, tuple)) and hasattr(action, "action"):
+            action = action.action                              # an ActResult
+        action = self._t(action)
+        if action.dim() == 1:
+            action = action.view(1, -1)
+        if action.dim() != 2 or action.shape[0] != n or action.shape[1] not in (self._ydim, P):
+            raise ValueError("nearest_feasible: action must be [%d, %d], [%d, %d] (partial_actions order) or an ActResult of %d "
+                             "rows, got %s" % (n, self._ydim, n, P, n, tuple(action.shape)))
+        weight = self._check_weight(weight, n, "nearest_feasible")
+        if out is None:
+            out = NearestResult(torch.empty(n, self._ydim, device=obs.device), torch.empty(n, 4, device=obs.device),
+                                torch.empty(n, P, device=obs.device), torch.empty(n, P, device=obs.device))
+        elif not isinstance(out, NearestResult) or tuple(out.action.shape) != (n, self._ydim) or tuple(out.info.shape) != (n, 4) \
+                or any(tuple(t.shape) != (n, P) for t in (out.target, out.moved)) \
+                or any(t.device != obs.device or t.dtype != torch.float32 or not t.is_contiguous()
+                       for t in (out.action, out.info, out.target, out.moved)):
+            raise ValueError("nearest_feasible: out must be a NearestResult of %d rows on %s" % (n, obs.device))
+        idx = self._partial_index(obs.device)
+        action = action.to(torch.float32)
+        if action.shape[1] == P:
+            out.target.copy_(action)
+            full = torch.zeros(n, self._ydim, device=obs.device)
+            full.index_copy_(1, idx, out.target)
+        else:
+            full = action if action.stride(1) == 1 else action.contiguous()
+            torch.index_select(full, 1, idx, out=out.target)
+        fn(self.kernels, obs, full, weight, out.action, out.info, tol, iters)
+        lo, hi = self.update(obs)                                # the box of the 14 controlled components, per row
+        torch.div((out.action.index_select(1, idx) - out.target).abs_(), 0.5 * (hi - lo), out=out.moved)
+        return out
+
+    def _partial_index(self, device):
+        key = ("partial_index", device)
+        if key not in self._box_cache:
+            self._box_cache[key] = torch.as_tensor(np.asarray(self._partial_actions), dtype=torch.int64, device=device)
+        return self._box_cache[key]
+
 
 class OpfResult(object):
     """What ``EVOPFEnv.opf`` returns: device tensors, row i for state i.  ``action`` [n, 43]: the full action vector (va at the
@@ -490,3 +580,33 @@ class OpfResult(object):
 
     def __repr__(self):
         return "OpfResult(n=%d)" % self.action.shape[0]
+
+
+class NearestResult(object):
+    """What ``EVOPFEnv.nearest_feasible`` returns: device tensors, row i for observation i.  ``action`` [n, 43]: the feasible
+    dispatch nearest to the target (the solver's last iterate where ``converged`` is False); ``target`` [n, 14]: what was asked
+    for, in ``partial_actions`` order; ``moved`` [n, 14] = |action - target| / half-width of the variable's box, in box units;
+    ``distance`` [n] = ``0.5 * sum w (y - t)^2``, what was minimised; ``residual`` [n]: the largest of the three stop quantities
+    at exit (NaN if one of them was); ``iters`` [n] int32; ``converged`` [n] bool.  The last four are views of / elementwise ops
+    on ``info`` [n, 4], the kernel's own output."""
+
+    def __init__(self, action, info, target, moved):
+        self.action, self.info, self.target, self.moved = action, info, target, moved
+
+    distance = property(lambda self: self.info[:, 0])
+    residual = property(lambda self: self.info[:, 1])
+    iters = property(lambda self: self.info[:, 2].to(torch.int32))
+    converged = property(lambda self: self.info[:, 3] > 0.5)
+
+    def numpy(self):
+        """dict of numpy arrays (one device-to-host copy per buffer; this synchronises)."""
+        info = self.info.detach().cpu().numpy()
+        return dict(action=self.action.detach().cpu().numpy(), distance=info[:, 0].copy(), residual=info[:, 1].copy(),
+                    iters=info[:, 2].astype(np.int32), converged=info[:, 3] > 0.5, target=self.target.detach().cpu().numpy(),
+                    moved=self.moved.detach().cpu().numpy())
+
+    def converged_rate(self):
+        return float((self.info[:, 3] > 0.5).float().mean())
+
+    def __repr__(self):
+        return "NearestResult(n=%d)" % self.action.shape[0]

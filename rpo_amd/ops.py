@@ -866,6 +866,38 @@ def evopf_opf_free(kernels, obs, pe_cost, action, info, tol, max_iters):
                                          float(tol), int(max_iters), kernels._c(action), _stream()), "rpo_evopf_opf_free")
 
 
+NEAREST_CONTROLLED = 14              # components of an action the safety filter measures its distance in: the env's partial_actions
+
+
+def evopf_nearest(kernels, obs, target, weight, action, info, tol, max_iters):
+    """The feasible dispatch nearest to ``target`` for every row (rpo_evopf_nearest, the safety filter): obs [n, >= 57] float32
+    observation rows with unit column stride, target [n, >= 43] float32 rows in the layout of an action with unit column stride
+    (its 14 controlled components are read), weight None (1 / half-width^2 of every controlled variable's box), [14] or [n, 14]
+    contiguous -> action [n, 43], info [n, 4] = (0.5 sum w (y - t)^2 at exit, largest stop quantity at exit, iterations, converged).
+    A function of the backend like ``evopf_opf_free``."""
+    if action is None or action.dim() != 2 or action.shape[1] != kernels.action_dim or action.shape[0] < 1:
+        raise RpoHipError("evopf_nearest: action must be [n >= 1, %d], got %s"
+                          % (kernels.action_dim, None if action is None else tuple(action.shape)))
+    n = action.shape[0]
+    if obs is None or obs.dim() != 2 or obs.shape[0] != n or obs.shape[1] < OPF_OBS or obs.stride(1) != 1:
+        raise RpoHipError("evopf_nearest: obs must be [%d, >= %d] rows with unit column stride, got %s"
+                          % (n, OPF_OBS, None if obs is None else (tuple(obs.shape), obs.stride())))
+    if target is None or target.dim() != 2 or target.shape[0] != n or target.shape[1] < kernels.action_dim or target.stride(1) != 1:
+        raise RpoHipError("evopf_nearest: target must be [%d, >= %d] rows with unit column stride, got %s"
+                          % (n, kernels.action_dim, None if target is None else (tuple(target.shape), target.stride())))
+    if info is None or tuple(info.shape) != (n, 4):
+        raise RpoHipError("evopf_nearest: info must be [%d, 4]" % n)
+    if weight is not None and (tuple(weight.shape) not in ((NEAREST_CONTROLLED,), (n, NEAREST_CONTROLLED)) or not weight.is_contiguous()):
+        raise RpoHipError("evopf_nearest: weight must be None or a contiguous [%d] or [%d, %d], got %s"
+                          % (NEAREST_CONTROLLED, n, NEAREST_CONTROLLED, tuple(weight.shape)))
+    stride = int(obs.stride(0)) if n > 1 else int(obs.shape[1])
+    tstride = int(target.stride(0)) if n > 1 else int(target.shape[1])
+    wstride = NEAREST_CONTROLLED if weight is not None and weight.dim() == 2 else 0
+    check(_lib.load().rpo_evopf_nearest(n, _p(obs, contiguous=False), stride, _p(target, contiguous=False), tstride,
+                                        _p(weight, allow_none=True), wstride, _p(action), _p(info), float(tol), int(max_iters),
+                                        kernels._c(action), _stream()), "rpo_evopf_nearest")
+
+
 SCEN_DAY = CONST["RPO_EVOPF_SCEN_DAY"]    # floats per day of a scenario table: price[48] | 24 x (pd[14], qd[14])
 
 
